@@ -7,11 +7,14 @@ pyramid, then the per-client slice -> inverse DFT -> demodulation for every audi
 and the byte gather for every waterfall client.  N=1 workload = BASELINE.json configs[1]:
 35 MSPS-shape IQ cs16, 2^20-point FFT, 16 SSB audio clients + 4 waterfall clients.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 Rank 0 prints ONE JSON line.  `value` is whole-job ingest in MSamples/s (new complex
-samples per second = frames/s * N/2) with the ring already resident in HBM.
+samples per second = frames/s * N/2) with the ring already resident in HBM, over ONE block
+of exactly K timed steps after W warm-up steps; `ms_per_step` is that block's time / K.
+A plain run does only that; --full adds everything else the line can carry (per-kernel
+figures, post chain, served end, other workloads and shardings, the CPU baseline).
 """
 import argparse
 import json
@@ -55,6 +58,12 @@ WORKLOADS = {
 # ~60-80 us of fixed cost (ramp, prologue, tail, the gaps between the kernels) whatever F is: 96.5 GS/s at F = 256, 99.9 at 512, 100.5
 # at 1024 on one box.  512 frames of cfg2 are 7.7 s of a 35 MSPS stream and 13 GB of the 288 GB of HBM.
 DEFAULT_BATCH = 512
+# --dump-outputs: frames of the last step whose spectrum and pyramid are written, the seed that draws them (and the samples of
+# arrays above their cap), and each array's cap in float32 entries (50 MiB in all)
+DUMP_FRAMES = 2
+DUMP_SEED = 0x5D5D0003
+DUMP_CAPS = {"spectrum": 4 << 20, "pyramid": 2 << 20, "audio": 4 << 20, "audio_power": 1 << 18, "audio_nan": 1 << 18,
+             "waterfall": 2 << 20}
 SAMPLE_BYTES = {"u8": 1, "s8": 1, "u16": 2, "s16": 2, "f32": 4, "f64": 8}
 
 
@@ -835,13 +844,16 @@ def run_sharded_bench(args, torch, rank, world, local_rank):
         frames = steps * F * (world if time_mode else 1)
         msps = frames * (N // 2) / dt / 1e6
         # (the root GPU's: rank 0 reads the ring, transforms, and serves its share of the clients; time sharding: every rank its own frames)
-        roofline, kernels, _ = kernel_roofline(eng.ctx, step, warmup + steps, min(steps, 20), wl, wl_name, params,
-                                               clients, waterfalls, F + warm, ms_per_step=dt / steps * 1e3,
-                                               frames_per_s=frames / dt / (world if time_mode else 1))
+        ab = algorithmic_bytes_per_frame(wl, params, clients, waterfalls)
+        if args.full:
+            roofline, kernels, _ = kernel_roofline(eng.ctx, step, warmup + steps, min(steps, 20), wl, wl_name, params,
+                                                   clients, waterfalls, F + warm, ms_per_step=dt / steps * 1e3,
+                                                   frames_per_s=frames / dt / (world if time_mode else 1))
+        else:  # (the per-kernel replay is --full's)
+            roofline, kernels = path_roofline(ab["total"], frames / dt / (world if time_mode else 1)), None
         if roofline:
             roofline["gpu"] = "rank 0 (root: raw ring, forward FFT, waterfalls, its share of the clients)"
         fence()
-        ab = algorithmic_bytes_per_frame(wl, params, clients, waterfalls)
         res = {"value": round(msps, 2), "ms_per_step": round(dt / steps * 1e3, 4), "steps": steps,
                "workload": wl_name + ": " + wl["desc"], "frames_per_step": F, "fft_size": N,
                "audio_clients": nclients_total, "waterfall_clients": len(waterfalls), "parallelism": par,
@@ -865,7 +877,8 @@ def run_sharded_bench(args, torch, rank, world, local_rank):
     # are measured in the same run and reported under `sharding`.
     main_mode = args.shard or "clients"
     results = {}
-    for m in (main_mode,) + tuple(x for x in ("clients", "clients_pipelined", "raw", "band", "time") if x != main_mode):
+    others = tuple(x for x in ("clients", "clients_pipelined", "raw", "band", "time") if x != main_mode) if args.full else ()
+    for m in (main_mode,) + others:
         try:
             results[m] = measure(m, args.steps if m == main_mode else min(args.steps, 30),
                                  args.warmup if m == main_mode else min(args.warmup, 5))
@@ -888,7 +901,9 @@ def run_sharded_bench(args, torch, rank, world, local_rank):
     c_group = None
     try:
         store = dist.distributed_c10d._get_default_store()
-        if rank == 0:
+        if not args.full:
+            pass
+        elif rank == 0:
             import subprocess
             try:
                 env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT",
@@ -910,7 +925,7 @@ def run_sharded_bench(args, torch, rank, world, local_rank):
     try:
         store = dist.distributed_c10d._get_default_store()
         if rank == 0:
-            if not args.no_cpu_baseline:
+            if args.full and not args.no_cpu_baseline:
                 r0 = results[main_mode]
                 cpu = cpu_baseline_subprocess((r0.get("workload") or "cfg4").split(":")[0], nclients=r0.get("audio_clients"))
             store.set("psdr_cpu_baseline_done", "1")
@@ -988,6 +1003,50 @@ class SingleGpuRun:
     def sync(self):
         self.eng.ctx.synchronize()
         self.torch.cuda.synchronize()
+
+    def timed_block(self, steps, warmup):
+        """The headline's timing: `warmup` untimed steps, then ONE block of exactly `steps` uninstrumented steps between two
+        full synchronisations.  Returns the block's wall time (seconds)."""
+        self.eng.ctx.set_profiling(0)
+        for i in range(warmup):
+            self.step(i)
+        self.sync()
+        t0 = time.perf_counter()
+        for i in range(steps):
+            self.step(warmup + i)
+        self.sync()
+        dt = time.perf_counter() - t0
+        self.next_step = warmup + steps
+        return dt
+
+    def dump_outputs(self, out_dir):
+        """--dump-outputs: what the last step handed its caller, as float32 DIR/<name>.npy - the spectrum and the int8 pyramid
+        of DUMP_FRAMES frames of the batch drawn with DUMP_SEED, every audio client's audio rows, power and NaN flags, every
+        waterfall client's rows (flattened, in client order).  An array longer than its DUMP_CAPS entry is replaced by the
+        entries at a sorted sample of its flat indices drawn with DUMP_SEED: the same for the same shape, run after run."""
+        ctx, F = self.eng.ctx, self.F
+        rng = np.random.default_rng(DUMP_SEED)
+        frames = np.sort(rng.choice(F, size=min(DUMP_FRAMES, F), replace=False))
+        out = {"spectrum": np.stack([ctx.read_spectrum(int(f)).view(np.float32) for f in frames]),
+               "pyramid": np.stack([ctx.read_quantized(int(f)) for f in frames])}
+        if self.eng.audio_clients:
+            got = [c.read_audio(F) for c in self.eng.audio_clients]
+            out["audio"] = np.stack([g[0] for g in got])
+            out["audio_power"] = np.stack([g[1] for g in got])
+            out["audio_nan"] = np.stack([g[2] for g in got])
+        if self.eng.waterfall_clients:
+            out["waterfall"] = np.concatenate([w.read_waterfall()[0].reshape(-1) for w in self.eng.waterfall_clients])
+        os.makedirs(out_dir, exist_ok=True)
+        total = 0
+        for name, a in out.items():
+            a = a.astype(np.float32)
+            if a.size > DUMP_CAPS[name]:
+                idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_CAPS[name], replace=False))
+                a = a.reshape(-1)[idx]
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+            total += a.nbytes
+        assert total <= 64 * 10 ** 6, total
+        return {"frames": [int(f) for f in frames], "arrays": sorted(out), "bytes": total}
 
     def timed(self, steps, warmup, min_reps=5, min_total_s=1.0, max_reps=40):
         """`warmup` untimed steps, then repetitions of EXACTLY `steps` steps, each bracketed by a full
@@ -1083,6 +1142,13 @@ def main():
                     help="frames per step (F); default 512 (DEFAULT_BATCH): a step of the two persistent passes has ~60 us of "
                          "fixed cost (ramp, prologue, tail, launch gaps) whatever F is (docs/history.md section 5, batch-size table)")
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the line can carry: repetitions with device-clock stamps, "
+                         "per-kernel replay, post chain, served end, the other workloads, client scaling, the C group leg, "
+                         "the CPU baseline (N > 1: every sharding); without it a run sets up, warms up, times --steps steps "
+                         "and prints the headline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32; N = 1 only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-post-chain", action="store_true",
                     help="skip the separate post-demodulation-chain measurement (used for the rocprofv3 kernel stats: "
@@ -1133,6 +1199,10 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.dump_outputs and (args.gpus > 1 or args.force_sharded):
+        raise SystemExit("--dump-outputs writes the one-GPU path's outputs: use it with --gpus 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: become N ranks (one process per GPU over RCCL) by re-executing
         # under torch.distributed.run, exactly the command line the driver would have written
@@ -1148,6 +1218,8 @@ def main():
                              f"{world}-GPU run as a {args.gpus}-GPU one")
     if args.batch <= 0:
         args.batch = DEFAULT_BATCH
+    if args.dump_outputs and world > 1:
+        raise SystemExit("--dump-outputs writes the one-GPU path's outputs: use it with --gpus 1")
 
     import torch
     if not torch.cuda.is_available():
@@ -1165,25 +1237,50 @@ def main():
     F = args.batch
     run = SingleGpuRun(torch, device, local_rank, wl_name, wl, F, args.ring_mib)
     eng, params, clients, waterfalls, N = run.eng, run.params, run.clients, run.waterfalls, run.N
-    # >= 3 s of timed steps (a 5-second utilisation sampler around the run should see the GPU busy at least once;
-    # the value is still the median repetition of exactly K steps)
+    # `value` and `ms_per_step`: ONE uninstrumented block of exactly --steps steps after --warmup
+    head = run.summary([run.timed_block(args.steps, args.warmup)], args.steps)
+    dumped = run.dump_outputs(args.dump_outputs) if args.dump_outputs else None
+    timing = (f"one uninstrumented block of exactly {args.steps} steps after {args.warmup} warm-up steps, bracketed by full "
+              "synchronisations; inputs resident in HBM before, results (spectrum, pyramid, audio, waterfall rows) resident in "
+              "HBM after: the device-to-host copy of the results is NOT in the timed region")
+    if not args.full:
+        out = {
+            "metric": "ingest MSamples/s + concurrent audio clients at 2^20-pt FFT",
+            "value": head["value"], "unit": "MSamples/s", "n_gpus": 1, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": head["ms_per_step"], "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": wl_name + ": " + wl["desc"], "frames_per_step": F,
+                       "fft_size": N, "audio_clients": len(clients), "waterfall_clients": len(waterfalls),
+                       "audio_fft_size": params["audio_fft_size"], "ring_MiB": round(run.nhalves * run.hb / 2 ** 20, 1),
+                       "realtime_factor": round(head["value"] * 1e6 / wl["sps"], 1), "timing": timing},
+            "roofline": head["roofline"],
+            "path": {"algorithmic_bytes_per_frame": head["algorithmic_bytes_per_frame"], "frames_per_s": head["frames_per_s"],
+                     "frac_of_hbm_peak": head["frac_of_hbm_peak"], "two_pass_model": head.get("two_pass_model")},
+            "dumped_outputs": dumped,
+        }
+        run.close()
+        emit(out)
+        return
+
+    # --full: repetitions of exactly K steps, >= 3 s of them (a 5-second utilisation sampler around the run should see the
+    # GPU busy at least once); every third carries the passes' device-clock stamps
     times = run.timed(args.steps, args.warmup, min_total_s=3.0, max_reps=400)
-    head = run.summary(times, args.steps)
+    reps = run.summary(times, args.steps)
 
     # per-kernel durations: profiled replay of the same steps (the events do not perturb `value`)
     roofline, kernels, ab = kernel_roofline(eng.ctx, run.step, run.next_step, 50, wl, wl_name, params,
-                                            clients, waterfalls, F, clock_us=run.clock_us, ms_per_step=head["ms_per_step"],
-                                            ms_per_step_stamped=(head.get("instrumentation") or {}).get("ms_per_step_with_device_clock_stamps"),
+                                            clients, waterfalls, F, clock_us=run.clock_us, ms_per_step=reps["ms_per_step"],
+                                            ms_per_step_stamped=(reps.get("instrumentation") or {}).get("ms_per_step_with_device_clock_stamps"),
                                             frames_per_s=head["frames_per_s"])
 
     # SURVEY 8f-2 (widened row): the optional post-demodulation chain (DC blocker + AGC + int16),
     # measured separately - it is NOT part of `value` (the metric's clients end at float audio)
     post = None
     if clients and not args.no_post_chain:
-        post = post_chain_measure(run, eng, params, wl, F, N, len(clients), head["ms_per_step"])
+        post = post_chain_measure(run, eng, params, wl, F, N, len(clients), reps["ms_per_step"])
     served = None
     if clients and not args.no_extra:
-        served = with_fetch_measure(run, eng, params, wl, F, N, len(clients), head["ms_per_step"], post)
+        served = with_fetch_measure(run, eng, params, wl, F, N, len(clients), reps["ms_per_step"], post)
     nhalves, hb = run.nhalves, run.hb
     run.close()
     del run
@@ -1264,18 +1361,19 @@ def main():
                    "fft_size": N, "audio_clients": len(clients), "waterfall_clients": len(waterfalls),
                    "audio_fft_size": params["audio_fft_size"], "ring_MiB": round(nhalves * hb / 2 ** 20, 1),
                    "realtime_factor": round(head["value"] * 1e6 / wl["sps"], 1),
-                   "timing": f"median of {head['repetitions']} UNINSTRUMENTED repetitions (psdr_set_profiling(0)) of exactly {args.steps} steps "
-                             f"({head['timed_s']} s timed), each bracketed by a full synchronisation; every third repetition "
-                             "of the loop carries the passes' device-clock stamps instead (mode 2) and is NOT part of `value` "
-                             "(path.instrumentation has both medians); inputs resident in "
-                             "HBM before, results (spectrum, pyramid, audio, waterfall rows) resident in HBM after: "
-                             "the device-to-host copy of the results is NOT in the timed region - `with_fetch` (and "
-                             "clients256.with_fetch) time the same step WITH it, overlapped with the next step"},
+                   "timing": timing + " - `with_fetch` (and clients256.with_fetch) time the same step WITH it, overlapped "
+                             "with the next step; path.repetitions: the same step in repetitions of exactly that many steps "
+                             f"({reps['repetitions']} UNINSTRUMENTED ones, {reps['timed_s']} s timed), every third repetition of "
+                             "that loop carrying the passes' device-clock stamps instead (mode 2; path.instrumentation has both "
+                             "medians)"},
         "roofline": roofline,
         "path": {"algorithmic_bytes_per_frame": head["algorithmic_bytes_per_frame"], "frames_per_s": head["frames_per_s"],
                  "frac_of_hbm_peak": head["frac_of_hbm_peak"], "two_pass_model": head.get("two_pass_model"),
-                 "ms_per_step_min_max": head["ms_per_step_min_max"],
-                 "instrumentation": head.get("instrumentation"), "kernels": kernels},
+                 "repetitions": {"ms_per_step_median": reps["ms_per_step"], "count": reps["repetitions"],
+                                 "timed_s": reps["timed_s"], "value": reps["value"]},
+                 "ms_per_step_min_max": reps["ms_per_step_min_max"],
+                 "instrumentation": reps.get("instrumentation"), "kernels": kernels},
+        "dumped_outputs": dumped,
         "clients256": extra.get("clients256"),
         "cfg3": extra.get("cfg3"),
         "cfg5_share": extra.get("cfg5_share"),

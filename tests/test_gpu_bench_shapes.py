@@ -193,8 +193,44 @@ def test_bench_launch_256_frames_vs_oracle(wl_name, post):
         run.close()
 
 
+def test_plain_bench_times_exactly_k_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """a plain `python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` (small batch and ring): the headline line with
+    `steps` = K and `ms_per_step` = value's own step, none of --full's blocks, and float32 outputs that two runs with the same
+    arguments write bit for bit alike"""
+    import json
+    import subprocess
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--batch", "8", "--ring-mib", "64", "--dump-outputs", str(d)], capture_output=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["unit"] == "MSamples/s"
+        assert line["higher_is_better"] is True and line["dtype"] == "f32" and line["ms_per_step"] > 0
+        # value and ms_per_step describe the same timed block: frames / s x N/2
+        F, N = line["config"]["frames_per_step"], line["config"]["fft_size"]
+        # (ms_per_step carries four decimals)
+        assert abs(line["value"] - F * (N // 2) / (line["ms_per_step"] * 1e-3) / 1e6) <= line["value"] * (1e-4 + 6e-5 / line["ms_per_step"]) + 0.02
+        for key in ("cpu_baseline", "post_chain", "with_fetch", "clients256", "cfg3"):
+            assert key not in line, key
+        files = sorted(os.listdir(d))
+        assert files == sorted(n + ".npy" for n in line["dumped_outputs"]["arrays"])
+        arrays = {f: np.load(d / f) for f in files}
+        assert all(a.dtype == np.float32 for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 * 10 ** 6
+        assert {"spectrum.npy", "pyramid.npy", "audio.npy", "waterfall.npy"} <= set(files)
+        assert arrays["audio.npy"].shape == (16, F, line["config"]["audio_fft_size"] // 2)
+        assert np.isfinite(arrays["spectrum.npy"]).all() and np.abs(arrays["spectrum.npy"]).max() > 0
+        dumps.append(arrays)
+    for f, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][f]), f
+
+
 def test_bench_gpus_2_runs_every_sharding_as_two_processes():
-    """`python bench.py --gpus 2` with no launcher around it: the self-launch, two ranks, all five shardings with the
+    """`python bench.py --gpus 2 --full` with no launcher around it: the self-launch, two ranks, all five shardings with the
     HIP back-ends.  A one-GPU box cannot run RCCL with two ranks, so PSDR_BENCH_ONE_DEVICE=1 puts both ranks on cuda:0
     over gloo: an orchestration test (it found int16 tensors handed to a collective), not a measurement."""
     import json
@@ -203,7 +239,7 @@ def test_bench_gpus_2_runs_every_sharding_as_two_processes():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--batch", "8", "--ring-mib", "64"], capture_output=True, timeout=900, env=env, cwd=ROOT)
+                        "--batch", "8", "--ring-mib", "64", "--full"], capture_output=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, "rank 0 prints ONE line"

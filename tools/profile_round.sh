@@ -6,9 +6,9 @@
 set -u
 TAG=${1:-r01}; WL=${2:-cfg2}; shift; shift
 R=$(pwd); O=$R/gpurun_out/$TAG; mkdir -p $O/profiles
-python bench.py --workload $WL --no-extra "$@" 2> $O/bench.err | tail -1 > $O/profiles/${TAG}_${WL}_bench.json
+python bench.py --full --workload $WL --no-extra "$@" 2> $O/bench.err | tail -1 > $O/profiles/${TAG}_${WL}_bench.json
 cd /tmp; export TMPDIR=/tmp
-B="python $R/bench.py --workload $WL --steps 30 --warmup 10 --no-cpu-baseline --no-post-chain --no-extra $*"
+B="python $R/bench.py --full --workload $WL --steps 30 --warmup 10 --no-cpu-baseline --no-post-chain --no-extra $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o p -- $B > $O/stats.log 2>&1
 # counter passes: the torch-free driver of the same library calls (rocprofv3's counter
 # collection crashes on torch's own ring-generation kernels), same N / F / clients as the bench

@@ -4,7 +4,7 @@ set -u
 O=gpurun_out/r06a; mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -q -x > $O/pytest.log 2>&1; echo "pytest rc=$?"
 grep -E "passed|failed" $O/pytest.log | tail -2
-timeout 900 python bench.py 2> $O/bench.err | tail -1 > $O/bench_default.json; echo "bench rc=$?"
+timeout 900 python bench.py --full 2> $O/bench.err | tail -1 > $O/bench_default.json; echo "bench rc=$?"
 python - <<'PY'
 import json
 d=json.load(open('gpurun_out/r06a/bench_default.json'))

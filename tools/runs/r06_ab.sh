@@ -14,7 +14,7 @@ for rep in 1 2 3; do
         agc)    E="PSDR_BENCH_AGC_FORM=1 PSDR_LIB=$R/build/variants/libpsdr_agc.so";;
         five)   E="PSDR_BENCH_AGC_FORM=0";;
       esac
-      env $E timeout 300 python bench.py --workload $w --no-extra --no-cpu-baseline --steps 40 --warmup 5 2>/dev/null | tail -1 | python -c "
+      env $E timeout 300 python bench.py --full --workload $w --no-extra --no-cpu-baseline --steps 40 --warmup 5 2>/dev/null | tail -1 | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); p=d['post_chain']
 print(json.dumps({'workload':'$w','lib':'$v','rep':$rep,'plain_ms':d['ms_per_step'],'chain_ms':p['ms_per_step'],'chain50_ms':p['ms_per_step_50_step_repetitions'],'over_plain':p['over_plain']}))"

@@ -5,7 +5,7 @@ O=gpurun_out/r06ad; mkdir -p $O
 timeout 2400 python -m pytest tests -m gpu -q -x --durations=15 > $O/pytest.log 2>&1; echo "pytest rc=$?"
 grep -E "passed|failed" $O/pytest.log | tail -2
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
-timeout 1200 python bench.py 2> $O/bench.err | tail -1 > $O/bench_default.json; echo "bench rc=$?"
+timeout 1200 python bench.py --full 2> $O/bench.err | tail -1 > $O/bench_default.json; echo "bench rc=$?"
 python - <<'PY'
 import json
 d=json.load(open('gpurun_out/r06ad/bench_default.json'))

@@ -6,7 +6,7 @@ R=$(pwd); O=$R/gpurun_out/r06ah; mkdir -p $O
 timeout 1500 python -m pytest tests/test_gpu_parity.py tests/test_gpu_abi.py tests/test_gpu_level2.py -m gpu -q -x -k "post_chain or pcm or fetch or level2" > $O/pytest.log 2>&1; echo "pytest rc=$?"
 tail -5 $O/pytest.log
 for w in clients256 cfg2; do
-  timeout 600 python bench.py --workload $w --no-extra --no-cpu-baseline --steps 40 --warmup 5 2> $O/bench_$w.err | tail -1 > $O/bench_$w.json
+  timeout 600 python bench.py --full --workload $w --no-extra --no-cpu-baseline --steps 40 --warmup 5 2> $O/bench_$w.err | tail -1 > $O/bench_$w.json
   python - <<PY
 import json
 d=json.load(open('$O/bench_$w.json'))

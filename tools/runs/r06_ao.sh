@@ -8,7 +8,7 @@ for rep in 1 2; do
     for v in "0:" "255:" "255:0" "0:8"; do
       m=${v%%:*}; rs=${v##*:}
       E="PSDR_PC_SKIP=$m PSDR_LIB=$R/build/variants/libpsdr_tuning.so"; [ -n "$rs" ] && E="$E PSDR_PC_RESERVE=$rs PSDR_PC_OWN=1"
-      env $E timeout 300 python bench.py --workload $w --no-extra --no-cpu-baseline --steps 40 --warmup 5 2>/dev/null | tail -1 | python -c "
+      env $E timeout 300 python bench.py --full --workload $w --no-extra --no-cpu-baseline --steps 40 --warmup 5 2>/dev/null | tail -1 | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); p=d['post_chain']
 print(json.dumps({'workload':'$w','skip':$m,'reserve':'$rs','rep':$rep,'plain_ms':d['ms_per_step'],'chain_ms':p['ms_per_step'],'over_plain':p['over_plain']}))"

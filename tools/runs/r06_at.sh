@@ -5,7 +5,7 @@ set -u
 R=$(pwd); O=$R/gpurun_out/r06at; mkdir -p $O
 for rep in 1 2 3; do
   for rs in 8 4; do
-    PSDR_PC_RESERVE=$rs PSDR_PC_OWN=1 PSDR_LIB=$R/build/variants/libpsdr_tuning.so timeout 300 python bench.py --workload cfg2 --no-extra --no-cpu-baseline --steps 40 --warmup 5 2>/dev/null | tail -1 | python -c "
+    PSDR_PC_RESERVE=$rs PSDR_PC_OWN=1 PSDR_LIB=$R/build/variants/libpsdr_tuning.so timeout 300 python bench.py --full --workload cfg2 --no-extra --no-cpu-baseline --steps 40 --warmup 5 2>/dev/null | tail -1 | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); p=d['post_chain']
 print(json.dumps({'reserve':$rs,'rep':$rep,'plain_ms':d['ms_per_step'],'chain_ms':p['ms_per_step'],'over_plain':p['over_plain']}))"

@@ -2,7 +2,7 @@
 # default bench line of the round's build (with_fetch included)
 set -u
 O=gpurun_out/r06k; mkdir -p $O
-timeout 1200 python bench.py 2> $O/bench.err | tail -1 > $O/bench_default.json; echo "bench rc=$?"
+timeout 1200 python bench.py --full 2> $O/bench.err | tail -1 > $O/bench_default.json; echo "bench rc=$?"
 tail -5 $O/bench.err
 python - <<'PY'
 import json

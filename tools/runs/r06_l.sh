@@ -27,7 +27,7 @@ for l in open('gpurun_out/r06l/ab.jsonl'):
 for k,v in sorted(d.items()): print(k, v)
 PY
 tail -3 $O/ab.err
-timeout 1200 python bench.py 2> $O/bench.err | tail -1 > $O/bench_default.json; echo "bench rc=$?"
+timeout 1200 python bench.py --full 2> $O/bench.err | tail -1 > $O/bench_default.json; echo "bench rc=$?"
 python - <<'PY'
 import json
 d=json.load(open('gpurun_out/r06l/bench_default.json'))

@@ -6,7 +6,7 @@ R=$(pwd); O=$R/gpurun_out/r06n; mkdir -p $O
 L=$R/build/variants/libpsdr_tuning.so
 run() { # tag workload env...
   tag=$1; w=$2; shift; shift
-  env "$@" PSDR_LIB=$L timeout 300 python bench.py --workload $w --no-extra --no-cpu-baseline --no-post-chain --steps 40 --warmup 5 2>/dev/null | tail -1 | python -c "
+  env "$@" PSDR_LIB=$L timeout 300 python bench.py --full --workload $w --no-extra --no-cpu-baseline --no-post-chain --steps 40 --warmup 5 2>/dev/null | tail -1 | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); k=d['path']['kernels']
 print(json.dumps({'tag':'$tag','ms_per_step':d['ms_per_step'],'frac':d['roofline']['frac'],'p1':k.get('fft_pass1',{}).get('device_clock_us_median'),'p2':k.get('fft_pass2',{}).get('device_clock_us_median')}))"

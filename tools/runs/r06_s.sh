@@ -3,7 +3,7 @@
 set -u
 O=gpurun_out/r06s; mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_abi.py tests/test_gpu_level2.py -m gpu -q -x > $O/pytest.log 2>&1; echo "pytest rc=$?"; tail -3 $O/pytest.log
-timeout 1200 python bench.py --no-cpu-baseline 2> $O/bench.err | tail -1 > $O/bench_default.json; echo "bench rc=$?"
+timeout 1200 python bench.py --full --no-cpu-baseline 2> $O/bench.err | tail -1 > $O/bench_default.json; echo "bench rc=$?"
 python - <<'PY'
 import json
 d=json.load(open('gpurun_out/r06s/bench_default.json'))

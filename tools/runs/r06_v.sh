@@ -2,7 +2,7 @@
 # the committed default bench line of the round's final build (profiles/r06_bench_default.json)
 set -u
 O=gpurun_out/r06v; mkdir -p $O
-timeout 1500 python bench.py 2> $O/bench.err | tail -1 > $O/bench_default.json; echo "bench rc=$?"
+timeout 1500 python bench.py --full 2> $O/bench.err | tail -1 > $O/bench_default.json; echo "bench rc=$?"
 python - <<'PY'
 import json
 d=json.load(open('gpurun_out/r06v/bench_default.json'))

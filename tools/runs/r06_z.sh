@@ -8,7 +8,7 @@ tail -15 $O/pytest.log
 for rep in 1 2 3; do
   for form in 1 0; do
     for w in clients256 cfg2; do
-      PSDR_BENCH_AGC_FORM=$form timeout 300 python bench.py --workload $w --no-extra --no-cpu-baseline --steps 40 --warmup 5 2>/dev/null | tail -1 | python -c "
+      PSDR_BENCH_AGC_FORM=$form timeout 300 python bench.py --full --workload $w --no-extra --no-cpu-baseline --steps 40 --warmup 5 2>/dev/null | tail -1 | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); p=d['post_chain']
 print(json.dumps({'workload':'$w','form':$form,'rep':$rep,'plain_ms':d['ms_per_step'],'chain_ms':p['ms_per_step'],'chain50_ms':p['ms_per_step_50_step_repetitions'],'over_plain':p['over_plain']}))"
