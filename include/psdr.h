@@ -59,9 +59,9 @@ typedef enum psdr_mode { PSDR_USB = 0, PSDR_LSB = 1, PSDR_AM = 2, PSDR_FM = 3 } 
 
 typedef struct psdr_config {
     uint32_t struct_size;        /* = sizeof(psdr_config) */
-    uint32_t fft_size;           /* N, power of two (FFT::FFT size, src/fft_impl.cpp:63) */
+    uint32_t fft_size;           /* N, power of two (FFT::FFT size, src/fft_impl.cpp:63): IQ 2^12..2^22, real 2^13..2^23 */
     int32_t is_real;             /* plan_r2c vs plan_c2c (src/fft.cpp:25-29) */
-    int32_t downsample_levels;   /* src/spectrumserver.cpp:186-190 */
+    int32_t downsample_levels;   /* src/spectrumserver.cpp:186-190; 1..log2(R)+1 (R = N IQ, N/2 real) */
     int32_t brightness_offset;   /* src/fft_impl.cpp:69 */
     int32_t additional_size;     /* set_output_additional_size(), src/spectrumserver.cpp:214 */
     int32_t audio_fft_size;      /* n = ceil(audio_sps*N/sps/4)*4, src/websocket.cpp:133 */

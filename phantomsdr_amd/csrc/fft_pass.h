@@ -544,7 +544,9 @@ __device__ __forceinline__ constexpr float image_scale() {
 //     couple's other half at the same output index c2.
 // CP (PAIR): (row, mirror row) couples per pass-2 tile - 8 for 1024-point rows (tiles of 16 rows), 4 for 2048-point rows
 // (tiles of 8 rows: 2^22-point real frames split 1024 x 2048)
-template <int L, int T, int SB, bool PAIR = false, int CP = 8>
+// TBG: the second twiddle factor is read from L2 instead of LDS (a 2048-point tile of 8 columns, its stage table and 2048
+// entries of it are 160 KiB: more than a work-group gets beside the kernel's own LDS words)
+template <int L, int T, int SB, bool PAIR = false, int CP = 8, bool TBG = false>
 __device__ __forceinline__ void pass1_body(const Pass1Args &a, unsigned vb, unsigned vgrid) {
     static_assert(CP == 8 || CP == 4, "couples per pass-2 tile");
     constexpr int L2CP = CP == 8 ? 3 : 2;
@@ -576,12 +578,18 @@ __device__ __forceinline__ void pass1_body(const Pass1Args &a, unsigned vb, unsi
 
     // two-level W_M table with B = M2: W_M^e = W_M1^{e >> log2M2} * W_M^{e & (M2-1)}.  The
     // first factor IS the stage table Wl (in LDS); the second (M2 entries) is staged next
-    // to it, so a per-tile twiddle look-up costs two LDS reads, no L2 round trip.
+    // to it, so a per-tile twiddle look-up costs two LDS reads, no L2 round trip (TBG: one of them from L2).
     cf *ldsTB = Wl + L;
-    auto tw = [&](unsigned e) -> cf { return cmul(Wl[e >> a.log2M2], ldsTB[e & (unsigned)(M2 - 1)]); };
+    auto tb = [&](unsigned i) -> cf {
+        if constexpr (TBG)
+            return a.TB[i];
+        else
+            return ldsTB[i];
+    };
+    auto tw = [&](unsigned e) -> cf { return cmul(Wl[e >> a.log2M2], tb(e & (unsigned)(M2 - 1))); };
     auto tw2 = [&](unsigned eA, unsigned eB, cf &rA, cf &rB) {  // two look-ups, products interleaved
-        cmul_pair(rA, Wl[eA >> a.log2M2], ldsTB[eA & (unsigned)(M2 - 1)], rB, Wl[eB >> a.log2M2],
-                  ldsTB[eB & (unsigned)(M2 - 1)]);
+        cmul_pair(rA, Wl[eA >> a.log2M2], tb(eA & (unsigned)(M2 - 1)), rB, Wl[eB >> a.log2M2],
+                  tb(eB & (unsigned)(M2 - 1)));
     };
 
     // chunk i*NT + tid of the image = row (i*NT + tid)/LPR, byte (tid % LPR)*16 of that row.
@@ -631,7 +639,8 @@ __device__ __forceinline__ void pass1_body(const Pass1Args &a, unsigned vb, unsi
     }
     // table staging after the first tile's loads are in flight (one latency, not two)
     for (int i = tid; i < L; i += NT) Wl[i] = a.Wl[i];
-    for (int i = tid; i < M2; i += NT) ldsTB[i] = a.TB[i];
+    if constexpr (!TBG)
+        for (int i = tid; i < M2; i += NT) ldsTB[i] = a.TB[i];
     tq.draw_first();
     __syncthreads();  // Wl and the twiddle table are visible
     PSDR_WGTRACE(a.trace, 1);
@@ -851,6 +860,11 @@ __device__ __forceinline__ void pass1_body(const Pass1Args &a, unsigned vb, unsi
 template <int L, int T, int SB, bool PAIR = false, int CP = 8>
 __global__ __launch_bounds__(L *T / 32) void k_fft_pass1(Pass1Args a) {
     pass1_body<L, T, SB, PAIR, CP>(a, blockIdx.x, gridDim.x);
+}
+// the same with the second twiddle factor read from L2 (2048 x 2048: 2^22-point IQ, 2^23-point real frames)
+template <int L, int T, int SB>
+__global__ __launch_bounds__(L *T / 32) void k_fft_pass1_l2tb(Pass1Args a) {
+    pass1_body<L, T, SB, false, 8, true>(a, blockIdx.x, gridDim.x);
 }
 
 struct Pass2Args {

@@ -374,6 +374,19 @@ def test_error_paths():
         Context(1000, 0, 1)                                  # not a power of two
     with pytest.raises(PsdrError):
         Context(1 << 10, 0, 1)                               # below the supported range
+    # complex transform lengths 2^12..2^22: IQ 2^12..2^22, real 2^13..2^23 (PSDR_ERR_UNSUPPORTED outside)
+    for N, is_real in [(1 << 11, 0), (1 << 23, 0), (1 << 12, 1), (1 << 24, 1)]:
+        with pytest.raises(PsdrError) as e:
+            Context(N, is_real, 1)
+        assert e.value.code == -6, (N, is_real)
+    # downsample_levels 1..log2(R) + 1 (the last level is one bin)
+    for N, is_real in [(1 << 12, 0), (1 << 13, 1)]:
+        mx = 13
+        for bad in (0, mx + 1):
+            with pytest.raises(PsdrError) as e:
+                Context(N, is_real, bad)
+            assert e.value.code == -1, (N, is_real, bad)
+        Context(N, is_real, mx).close()
     ctx = Context(1 << 14, 0, 3, audio_fft_size=248, max_clients=2)
     try:
         a, b = AudioClient(ctx), AudioClient(ctx)
