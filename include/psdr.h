@@ -282,8 +282,11 @@ int psdr_set_post_chain(psdr_ctx *ctx, int enable);
  *   buffer the reference hands its encoder (dsp_float_to_int16's output, src/utils/dsp.cpp:152-165, holds 16-bit values):
  *   half the bytes for psdr_fetch_begin(PSDR_FETCH_PCM) to move - with hundreds of clients the copy to the host is what
  *   bounds the served path.  psdr_fetched_pcm16 hands the rows out; psdr_fetched_audio's pcm is NULL for
- *   such a batch; psdr_read_pcm still delivers int32 (widened on the host).  0 (default): int32 rows. */
+ *   such a batch; psdr_read_pcm still delivers int32 (widened on the host).  0 (default): int32 rows.
+ * PSDR_OPT_WATERFALL_DETECTOR (any time, any thread): the psdr_wf_detector a client gets at psdr_waterfall_add (clients that
+ *   exist keep theirs: psdr_waterfall_set_detector).  PSDR_WF_SAMPLE (default): the reference's waterfall. */
 enum { PSDR_OPT_POST_CHAIN_STREAMS = 1, PSDR_OPT_POST_CHAIN_AGC = 2, PSDR_OPT_POST_CHAIN_PCM16 = 3 };
+#define PSDR_OPT_WATERFALL_DETECTOR 4
 int psdr_set_option(psdr_ctx *ctx, int option, int value);
 /* pcm: [frames of the last demod_batch][audio_fft_size/2]; nframes = rows pcm holds (as psdr_read_audio) */
 int psdr_read_pcm(psdr_ctx *ctx, int id, int nframes, int32_t *pcm, int *nframes_out);
@@ -297,9 +300,38 @@ int psdr_waterfall_set_range(psdr_ctx *ctx, int id, int level, int l, int r);
 /* WaterfallClient::on_window_message (src/waterfall.cpp:53-94): picks the level */
 int psdr_waterfall_on_window_message(psdr_ctx *ctx, int id, int l, int r, int *level_out,
                                      int *l_out, int *r_out);
+/* What a sent row shows of the frames BETWEEN two sent frames - the detector of a spectrum display.  The reference sends
+ * frame s (s % skip_num == 0) and drops the skip_num - 1 frames before it (src/fft.cpp:33,102-104), although the int8
+ * pyramid exists for every frame: a burst shorter than skip_num frames is seen only if it falls on a sent one.
+ *   PSDR_WF_SAMPLE  row[j] = q_s[j]: the reference's waterfall, bit for bit (the default; k_waterfall_gather alone runs)
+ *   PSDR_WF_PEAK    row[j] = max over t in W(s) of q_t[j] (signed int8): max-hold
+ *   PSDR_WF_MEAN    row[j] = floor((2 S + n) / (2 n)), S = sum over W(s) of q_t[j], n = |W(s)|: the mean of the dB values
+ *                   (video averaging, round half up) - not of linear power, which is never stored per frame
+ * q_t = frame t's values at the client's level, indices [l, r), as psdr_read_quantized delivers them.  W(s) is the WINDOW of
+ * frame s: the frames t with s - skip_num < t <= s that belong to the current RUN (psdr_waterfall_batch below).  A detector
+ * changes the bytes of a row and nothing else: number and length of the rows, labels, psdr_read_waterfall,
+ * psdr_fetch_begin(PSDR_FETCH_WATERFALL) / psdr_fetched_waterfall are the same, and clients with different detectors share
+ * a call.  psdr_waterfall_set_detector: any thread; PSDR_ERR_INVALID for an unknown id or value; PSDR_ERR_UNSUPPORTED for
+ * PSDR_WF_MEAN on a context with skip_num > 2^24 (the sums are 32 bits wide: 255 * 2^24 fits); in force from the next
+ * psdr_waterfall_batch on. */
+typedef enum psdr_wf_detector { PSDR_WF_SAMPLE = 0, PSDR_WF_PEAK = 1, PSDR_WF_MEAN = 2 } psdr_wf_detector;
+int psdr_waterfall_set_detector(psdr_ctx *ctx, int id, int detector);
 /* waterfall_loop + send_waterfall (src/websocket.cpp:207-236, src/waterfall.cpp:44-51):
  * gathers q_level[l..r) of every waterfall client for every frame f of the last batch
- * with (first_frame_num+f) % skip_num == 0. */
+ * with (first_frame_num+f) % skip_num == 0.
+ * Detectors - runs and windows.  Each call speaks for the batch processed just before it.  A call whose first_frame_num
+ * equals the previous call's first_frame_num + its number of frames CONTINUES the run; any other call (the first one, a
+ * gap, a repeated first_frame_num) starts a new run, and so does the first call with a non-sample client among the active
+ * ones after calls without any (the library keeps no history while nobody asks for it).  Frames before the run's start
+ * never contribute: the first row of a run may stand for fewer than skip_num frames, frame 0 stands for itself.  Inside a
+ * run a window reaches back across as many earlier batches as it needs (skip_num larger than the batch; one-frame
+ * batches), through a context-wide carry over the raw pyramid records - element-wise maximum and sum of the run's frames
+ * behind its last sent frame, updated by every call while some active client has a detector.  The client's window
+ * [level, l, r) and detector AT THE CALL are applied to all frames of W(s): a client that retunes, zooms, changes its
+ * detector or attaches in the middle of a window gets a complete row at the next sent frame.  A caller whose clients use
+ * a detector therefore calls this for EVERY batch, also one without a sent frame (it gathers nothing, nsent = 0, and
+ * feeds the carry).  psdr_group_step / _step_ring do: they call it on the root at every step, so the group path needs
+ * nothing further. */
 int psdr_waterfall_batch(psdr_ctx *ctx, uint64_t first_frame_num);
 /* bytes [nsent][r-l] for one client, with the range the rows were GATHERED with: the window may
  * have been changed by another thread since psdr_waterfall_batch, so level/l/r of that batch are

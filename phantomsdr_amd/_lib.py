@@ -83,6 +83,7 @@ SYMBOLS = [
     ("psdr_waterfall_set_range", _i, [_vp, _i, _i, _i, _i]),
     ("psdr_waterfall_on_window_message", _i,
      [_vp, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    ("psdr_waterfall_set_detector", _i, [_vp, _i, _i]),
     ("psdr_waterfall_batch", _i, [_vp, _u64]),
     ("psdr_read_waterfall", _i, [_vp, _i, _vp, _sz, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     ("psdr_spectrum_device_ptr", _i, [_vp, _i, _pp, C.POINTER(_sz)]),

@@ -23,6 +23,9 @@ FORMAT_DTYPES = {"u8": np.uint8, "s8": np.int8, "u16": np.uint16, "s16": np.int1
                  "f32": np.float32, "f64": np.float64}
 USB, LSB, AM, FM = 0, 1, 2, 3
 MODES = {"USB": USB, "LSB": LSB, "AM": AM, "FM": FM}
+# psdr_wf_detector (include/psdr.h): what a sent waterfall row shows of the frames since the previous one
+WF_SAMPLE, WF_PEAK, WF_MEAN = 0, 1, 2
+WF_DETECTORS = {"sample": WF_SAMPLE, "peak": WF_PEAK, "mean": WF_MEAN}
 
 FFTW_MEASURE, FFTW_DESTROY_INPUT, FFTW_ESTIMATE = 0, 1, 1 << 6  # accepted and ignored
 
@@ -153,6 +156,7 @@ class Context:
     OPT_POST_CHAIN_STREAMS = 1
     OPT_POST_CHAIN_PCM16 = 3  # 1: the chain's PCM as int16 rows (half the bytes to the host; fetched_pcm16), 0 (default): int32 rows
     OPT_POST_CHAIN_AGC = 2  # 1 (default): chunk maxima + one kernel for the AGC where the rate allows it; 0: the five-kernel form
+    OPT_WATERFALL_DETECTOR = 4  # WF_SAMPLE (default) / WF_PEAK / WF_MEAN: the detector of waterfall clients added from now on
 
     def set_option(self, option, value):
         check(self.lib.psdr_set_option(self.h, int(option), int(value)))
@@ -465,6 +469,13 @@ class WaterfallClient:
         self.level, self.l = int(level), max(0, int(l))
         self.r = min(int(r), self.ctx.R >> self.level)
 
+    def set_detector(self, detector):
+        """"sample" (the reference's waterfall, the default), "peak" (max-hold) or "mean" (mean of the dB values) over the
+        frames a sent row stands for (psdr.h: psdr_wf_detector); in force from the next waterfall_batch on"""
+        det = WF_DETECTORS[detector] if isinstance(detector, str) else int(detector)
+        check(self.ctx.lib.psdr_waterfall_set_detector(self.ctx.h, self.id, det))
+        self.detector = det
+
     def on_window_message(self, l, r):
         lv, nl, nr = C.c_int(), C.c_int(), C.c_int()
         rc = self.ctx.lib.psdr_waterfall_on_window_message(self.ctx.h, self.id, int(l), int(r),
@@ -606,10 +617,12 @@ class SpectrumEngine:
         self.audio_clients.append(c)
         return c
 
-    def add_waterfall_client(self, level=None, l=None, r=None):
+    def add_waterfall_client(self, level=None, l=None, r=None, detector=None):
         w = WaterfallClient(self.ctx)
         if level is not None:
             w.set_waterfall_range(level, l, r)
+        if detector is not None:
+            w.set_detector(detector)
         self.waterfall_clients.append(w)
         return w
 

@@ -25,7 +25,7 @@ extern "C" const char *psdr_version(void) {
 namespace psdr {
 const char *kKernelNames[K_COUNT] = {"fft_pass1",  "fft_pass2", "untangle_real", "pyramid_tail",
                                      "demod_idft", "demod_ola", "waterfall_gather", "post_chain",
-                                     "real_seam",  "band_pack"};
+                                     "real_seam",  "band_pack",  "waterfall_hold", "waterfall_carry"};
 
 void resolve_pending(psdr_ctx *c) {
     if (c->pending.empty()) return;
@@ -172,6 +172,8 @@ void free_all(psdr_ctx *c) {
     c->client_ring.destroy();
     c->wf_ring.destroy();
     F(c->d_wfout);
+    F(c->d_wf_peak);
+    F(c->d_wf_sum);
     auto H = [](void *p) {
         if (p) hipHostFree(p);
     };

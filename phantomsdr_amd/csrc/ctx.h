@@ -47,7 +47,7 @@ inline const char *psdr_tuning_env(const char *name) {
 
 namespace psdr {
 
-enum KernelId { K_PASS1, K_PASS2, K_UNTANGLE, K_TAIL, K_IDFT, K_OLA, K_WFALL, K_POST, K_SEAM, K_BAND, K_COUNT };
+enum KernelId { K_PASS1, K_PASS2, K_UNTANGLE, K_TAIL, K_IDFT, K_OLA, K_WFALL, K_POST, K_SEAM, K_BAND, K_WFHOLD, K_WFCARRY, K_COUNT };
 extern const char *kKernelNames[K_COUNT];
 
 struct PendingEvent {
@@ -70,11 +70,13 @@ struct AudioSlot {
 struct WfSlot {
     bool active = false;
     int level = 0, l = 0, r = 0;
+    int det = PSDR_WF_SAMPLE;  // psdr_waterfall_set_detector
     // the last psdr_waterfall_batch: what was gathered, and with which window (set_range may run
     // on another thread between the batch and psdr_read_waterfall)
     size_t out_off = 0;
     int nsent = 0;
     int b_level = 0, b_l = 0, b_r = 0;
+    int b_det = PSDR_WF_SAMPLE;
 };
 
 // Small host->device parameter blocks (client lists) are double-buffered K deep so a new
@@ -321,6 +323,16 @@ struct psdr_ctx {
     size_t wf_sent_off = 0;
     int8_t *d_wfout = nullptr;
     size_t wfout_cap = 0;
+    // waterfall detectors (psdr_waterfall_set_detector): the carry is the reduction of the frames of the current RUN of
+    // psdr_waterfall_batch calls that lie behind the run's last sent frame - what the next sent row's window holds of
+    // earlier batches.  Allocated by the first batch with a non-sample client; touched on `side` only.
+    int opt_wf_det = PSDR_WF_SAMPLE;   // PSDR_OPT_WATERFALL_DETECTOR: what psdr_waterfall_add hands a new client
+    int8_t *d_wf_peak = nullptr;
+    uint32_t *d_wf_sum = nullptr;
+    size_t wf_lenA = 0, wf_qB0 = 0, wf_lenB = 0;
+    bool wf_run = false;               // the last psdr_waterfall_batch kept the carry (some client had a detector)
+    uint64_t wf_next = 0;              // ... and the first_frame_num that continues it
+    int wf_carry_n = 0;                // frames the carry stands for
 
     // streaming ingest ring (psdr_ring_*)
     struct IngestRing {
@@ -419,6 +431,7 @@ int real_seg_len(const psdr_ctx *c, int nframes);
 void seg_plan_counts(const psdr_ctx *c, int nframes, unsigned *nsegs, unsigned *nseam, bool *handoff);
 int seg_plan(psdr_ctx *c, int nframes, const psdr_ctx::SegPlan **out);  // (built and uploaded on first use of a batch size)
 int process_frames(psdr_ctx *c, const void *d_halves, int nframes, int fmt, hipEvent_t ev_raw_consumed = nullptr);
+int set_wf_default_detector(psdr_ctx *c, int detector);  // PSDR_OPT_WATERFALL_DETECTOR
 // pass1.hip / pass2.hip (Pass1Args / Pass2Args: fft_pass.h)
 struct Pass1Args;
 struct Pass2Args;

@@ -475,6 +475,144 @@ __global__ __launch_bounds__(256) void k_waterfall_gather(const int8_t *Q, size_
     }
 }
 
+// ---- waterfall detectors (psdr_waterfall_set_detector): peak-hold and mean over the frames a sent row stands for ----
+// The int8 values are taken with the sign bit flipped (q + 128 as an unsigned byte): unsigned order is signed order, and
+// sums carry no sign.  gfx950 has no packed 8-bit maximum, so a dword's four bytes are extracted and reduced one by one.
+template <int W>
+__device__ __forceinline__ void wf_acc(unsigned x, unsigned (&mx)[W], unsigned (&sm)[W]) {
+    x ^= W == 4 ? 0x80808080u : 0x80u;
+#pragma unroll
+    for (int k = 0; k < W; k++) {
+        const unsigned b = (x >> (8 * k)) & 0xFFu;
+        mx[k] = mx[k] > b ? mx[k] : b;
+        sm[k] += b;
+    }
+}
+// floor((2 S + n) / (2 n)) of the signed sum S = s - 128 n: round half up (s <= 255 n, n <= 2^24)
+__device__ __forceinline__ unsigned wf_mean(unsigned s, unsigned n) {
+    if (n < (1u << 22)) return ((2u * s + n) / (2u * n)) ^ 0x80u;
+    return (unsigned)((2ull * s + n) / (2ull * n)) ^ 0x80u;
+}
+
+// one row of one client: W = 4 values per lane through dword loads (WfClient::vec), or 1.  Where a value sits inside a
+// frame (and inside the carry, which mirrors the frame) does not depend on the frame: computed once per lane.
+template <int DET, int W>
+__device__ __forceinline__ void wf_hold_row(const WfHoldArgs &a, const WfClient &c, int tiled_lt, int ch, const RecMap &map,
+                                            int f_lo, int f_hi, bool use_carry, unsigned n, int8_t *dst) {
+    const bool tiled = c.level <= tiled_lt;
+    const int per = ch >> c.level, loff = tiled_level_offset(ch, c.level);
+    const int8_t *base = tiled ? a.Qt : a.Q;
+    const size_t stride = tiled ? a.qt_stride : a.q_stride;
+    for (int j0 = (W == 4 ? (c.l & ~3) : c.l) + W * (int)threadIdx.x; j0 < c.r; j0 += W * (int)blockDim.x) {
+        size_t off, coff;
+        if (tiled) {
+            off = map.pos((size_t)j0 / per) * (2 * ch) + loff + ((size_t)j0 % per);
+            coff = off;
+        } else {
+            off = c.qoff + (size_t)j0;
+            coff = a.lenA + (off - a.qB0);
+        }
+        unsigned mx[W], sm[W];
+#pragma unroll
+        for (int k = 0; k < W; k++) mx[k] = sm[k] = 0;
+        if (use_carry) {
+            if (DET == PSDR_WF_PEAK) {
+                unsigned z[W];
+                wf_acc<W>(W == 4 ? *reinterpret_cast<const unsigned *>(a.peak + coff) : (unsigned)(uint8_t)a.peak[coff], mx, z);
+            } else {
+#pragma unroll
+                for (int k = 0; k < W; k++) sm[k] = a.sum[coff + k];
+            }
+        }
+        const int8_t *p = base + (size_t)f_lo * stride + off;
+        for (int f = f_lo; f <= f_hi; f++, p += stride)
+            wf_acc<W>(W == 4 ? *reinterpret_cast<const unsigned *>(p) : (unsigned)(uint8_t)*p, mx, sm);
+        unsigned v[W];
+#pragma unroll
+        for (int k = 0; k < W; k++) v[k] = DET == PSDR_WF_PEAK ? (mx[k] ^ 0x80u) : wf_mean(sm[k], n);
+        int8_t *d = dst + (j0 - c.l);
+        if (W == 4 && j0 >= c.l && j0 + 4 <= c.r && ((uintptr_t)d & 3) == 0) {
+            *reinterpret_cast<unsigned *>(d) = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
+        } else {
+#pragma unroll
+            for (int k = 0; k < W; k++)
+                if (j0 + k >= c.l && j0 + k < c.r) d[k] = (int8_t)v[k];
+        }
+    }
+}
+
+// beside k_waterfall_gather, for the clients with a detector: one work-group row per (client, sent frame).  The row of
+// sent frame f reduces q_level[l..r) over the frames (f - skip, f] of the batch and - the batch's first sent row alone
+// can reach back that far - over the carry, which holds the run's frames behind its last sent frame.
+__global__ __launch_bounds__(256) void k_waterfall_hold(WfHoldArgs a, int tiled_lt, int ch, RecMap map, const WfClient *cl,
+                                                        const int *sent_frames, int nsent, int8_t *out) {
+    const WfClient c = cl[blockIdx.x];
+    if (!c.active || c.det == PSDR_WF_SAMPLE) return;
+    const int si = blockIdx.y;
+    if (si >= nsent) return;
+    const int f = sent_frames[si];
+    const long long lo = (long long)f - ((long long)a.skip - 1);
+    const int f_lo = lo > 0 ? (int)lo : 0;
+    const bool use_carry = lo < 0 && a.carry_n > 0;
+    const unsigned n = (unsigned)(f - f_lo + 1) + (use_carry ? (unsigned)a.carry_n : 0u);
+    int8_t *dst = out + c.out_off + (size_t)si * (c.r - c.l);
+    if (c.det == PSDR_WF_PEAK) {
+        if (c.vec)
+            wf_hold_row<PSDR_WF_PEAK, 4>(a, c, tiled_lt, ch, map, f_lo, f, use_carry, n, dst);
+        else
+            wf_hold_row<PSDR_WF_PEAK, 1>(a, c, tiled_lt, ch, map, f_lo, f, use_carry, n, dst);
+    } else {
+        if (c.vec)
+            wf_hold_row<PSDR_WF_MEAN, 4>(a, c, tiled_lt, ch, map, f_lo, f, use_carry, n, dst);
+        else
+            wf_hold_row<PSDR_WF_MEAN, 1>(a, c, tiled_lt, ch, map, f_lo, f, use_carry, n, dst);
+    }
+}
+
+// the carry: element-wise maximum and sum of frames f0 .. nframes-1 of the batch over the raw record buffers, 16 bytes
+// per lane.  accumulate = 0: the batch held a sent frame (or starts a run) and the carry is replaced; 1: reduced onto it.
+__global__ __launch_bounds__(256) void k_waterfall_carry(WfHoldArgs a, int f0, int accumulate) {
+    const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 16;
+    if (i >= a.lenA + a.lenB) return;
+    const int8_t *src = i < a.lenA ? a.Qt + i : a.Q + a.qB0 + (i - a.lenA);
+    const size_t stride = i < a.lenA ? a.qt_stride : a.q_stride;
+    unsigned mx[4][4], sm[4][4];
+    uint4 *ps = reinterpret_cast<uint4 *>(a.sum + i);
+    if (accumulate) {
+        const uint4 m = *reinterpret_cast<const uint4 *>(a.peak + i);
+        const unsigned mw[4] = {m.x, m.y, m.z, m.w};
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            const uint4 s = ps[w];
+            unsigned z[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) mx[w][k] = 0;
+            wf_acc<4>(mw[w], mx[w], z);
+            sm[w][0] = s.x, sm[w][1] = s.y, sm[w][2] = s.z, sm[w][3] = s.w;
+        }
+    } else {
+#pragma unroll
+        for (int w = 0; w < 4; w++)
+#pragma unroll
+            for (int k = 0; k < 4; k++) mx[w][k] = sm[w][k] = 0;
+    }
+    src += (size_t)f0 * stride;
+    for (int f = f0; f < a.nframes; f++, src += stride) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(src);
+        wf_acc<4>(v.x, mx[0], sm[0]);
+        wf_acc<4>(v.y, mx[1], sm[1]);
+        wf_acc<4>(v.z, mx[2], sm[2]);
+        wf_acc<4>(v.w, mx[3], sm[3]);
+    }
+    unsigned mo[4];
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+        mo[w] = (mx[w][0] | (mx[w][1] << 8) | (mx[w][2] << 16) | (mx[w][3] << 24)) ^ 0x80808080u;
+        ps[w] = make_uint4(sm[w][0], sm[w][1], sm[w][2], sm[w][3]);
+    }
+    *reinterpret_cast<uint4 *>(a.peak + i) = make_uint4(mo[0], mo[1], mo[2], mo[3]);
+}
+
 // tiled records -> the reference's level-major layout (levels 0..tiled_lt of one frame)
 __global__ __launch_bounds__(256) void k_untile_q(const int8_t *Qt, int8_t *Q, size_t R, int ch, int tiled_lt,
                                                   int nlevels, RecMap map) {

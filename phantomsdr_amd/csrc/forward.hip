@@ -585,6 +585,7 @@ extern "C" int psdr_waterfall_add(psdr_ctx *c, int *id_out) {
             s.level = c->levels - 1;
             s.l = 0;
             s.r = std::min(c->min_waterfall_fft, (int)(c->R >> s.level));  // set_waterfall_range(levels-1, 0, min_waterfall_fft)
+            s.det = c->opt_wf_det;
             *id_out = (int)i;
             return PSDR_OK;
         }
@@ -596,6 +597,31 @@ extern "C" int psdr_waterfall_remove(psdr_ctx *c, int id) {
     int rc = check_wslot(c, id);
     if (rc) return rc;
     c->wslots[id].active = false;
+    return PSDR_OK;
+}
+// PSDR_WF_MEAN's sums are 32 bits wide: 255 per frame, at most skip_num frames in a window
+static int check_wf_detector(const psdr_ctx *c, int detector) {
+    if (detector != PSDR_WF_SAMPLE && detector != PSDR_WF_PEAK && detector != PSDR_WF_MEAN)
+        return fail(PSDR_ERR_INVALID, "waterfall detector %d: PSDR_WF_SAMPLE, PSDR_WF_PEAK or PSDR_WF_MEAN", detector);
+    if (detector == PSDR_WF_MEAN && c->cfg.skip_num > (1 << 24))
+        return fail(PSDR_ERR_UNSUPPORTED, "PSDR_WF_MEAN with skip_num %d > 2^24", c->cfg.skip_num);
+    return PSDR_OK;
+}
+int psdr::set_wf_default_detector(psdr_ctx *c, int detector) {
+    int rc = check_wf_detector(c, detector);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mtx);
+    c->opt_wf_det = detector;
+    return PSDR_OK;
+}
+extern "C" int psdr_waterfall_set_detector(psdr_ctx *c, int id, int detector) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mtx);
+    int rc = check_wslot(c, id);
+    if (rc) return rc;
+    rc = check_wf_detector(c, detector);
+    if (rc) return rc;
+    c->wslots[id].det = detector;
     return PSDR_OK;
 }
 extern "C" int psdr_waterfall_set_range(psdr_ctx *c, int id, int level, int l, int r) {
@@ -658,6 +684,9 @@ extern "C" int psdr_waterfall_batch(psdr_ctx *c, uint64_t first_frame_num) {
         if ((first_frame_num + (uint64_t)f) % (uint64_t)c->cfg.skip_num == 0) h_sent[nsent++] = f;
     size_t total = 0;
     int maxid = -1;
+    bool hold = false, any_sample = false;  // an active client with a detector / on PSDR_WF_SAMPLE
+    size_t q_up = 0;                        // byte offset of level tiled_lt + 1 in the level-major buffer
+    for (int t = 0; t <= c->tiled_lt && t < c->levels; t++) q_up += c->R >> t;
     for (size_t i = 0; i < c->wslots.size(); i++) {
         WfSlot &s = c->wslots[i];
         WfClient &w = h_wf[i];
@@ -668,41 +697,108 @@ extern "C" int psdr_waterfall_batch(psdr_ctx *c, uint64_t first_frame_num) {
         w.qoff = 0;
         for (int t = 0; t < s.level; t++) w.qoff += c->R >> t;
         w.out_off = total;
+        w.det = s.det;
+        // (k_waterfall_hold) tiled records hold ch >> level values of the level side by side, at a multiple of that many
+        // bytes; a level-major level starts at qoff and a dword must not reach past its end
+        w.vec = s.level <= c->tiled_lt ? ((c->tile_ch >> s.level) >= 4) : ((c->R >> s.level) % 4 == 0 && w.qoff % 4 == 0);
         s.out_off = total;
         s.nsent = s.active ? nsent : 0;
         s.b_level = s.level;
         s.b_l = s.l;
         s.b_r = s.r;
+        s.b_det = s.det;
         if (s.active) {
             total += (size_t)nsent * (size_t)(s.r - s.l);
             total = (total + 15) & ~(size_t)15;
             maxid = (int)i;
+            (s.det != PSDR_WF_SAMPLE ? hold : any_sample) = true;
         }
     }
-    if (maxid < 0 || nsent == 0 || total == 0) return PSDR_OK;
-    if (total > c->wfout_cap) {
-        if (c->d_wfout) HIPCHK(hipFree(c->d_wfout));
-        c->d_wfout = nullptr;
-        HIPCHK(hipMalloc((void **)&c->d_wfout, total));
-        c->wfout_cap = total;
+    // detectors: does this call continue the run the carry belongs to?  (header: psdr_waterfall_batch)
+    const int nf = c->last_nframes;
+    if (!(hold && c->wf_run && first_frame_num == c->wf_next)) c->wf_carry_n = 0;
+    c->wf_run = false;  // (true again once everything below is enqueued)
+    const bool gather = maxid >= 0 && nsent > 0 && total > 0;
+    if (!gather && !hold) return PSDR_OK;
+    WfHoldArgs ha{};
+    if (hold) {
+        if (!c->d_wf_peak) {  // first use: the carry mirrors one frame's records and upper levels
+            c->wf_lenA = c->tiled_lt >= 0 ? c->qt_stride : 0;
+            c->wf_qB0 = q_up & ~(size_t)15;
+            const size_t qB1 = (c->q_len + 15) & ~(size_t)15;  // <= q_stride, a multiple of 128
+            c->wf_lenB = qB1 > c->wf_qB0 ? qB1 - c->wf_qB0 : 0;
+            if ((c->wf_lenA & 15) || (c->qt_stride & 15) || qB1 > c->q_stride)
+                return fail(PSDR_ERR_UNSUPPORTED, "waterfall detectors: record buffers of %zu / %zu bytes per frame", c->qt_stride, c->q_stride);
+            const size_t len = c->wf_lenA + c->wf_lenB;
+            int8_t *pk = nullptr;
+            uint32_t *sm = nullptr;
+            if (hipMalloc((void **)&pk, len) != hipSuccess || hipMalloc((void **)&sm, len * sizeof(uint32_t)) != hipSuccess) {
+                (void)hipGetLastError();
+                if (pk) (void)hipFree(pk);
+                return fail(PSDR_ERR_NOMEM, "waterfall detectors: carry of %zu bytes", len * 5);
+            }
+            c->d_wf_peak = pk;
+            c->d_wf_sum = sm;
+        }
+        ha.Q = c->d_q;
+        ha.Qt = c->d_qt;
+        ha.q_stride = c->q_stride;
+        ha.qt_stride = c->qt_stride;
+        ha.lenA = c->wf_lenA;
+        ha.qB0 = c->wf_qB0;
+        ha.lenB = c->wf_lenB;
+        ha.peak = c->d_wf_peak;
+        ha.sum = c->d_wf_sum;
+        ha.carry_n = c->wf_carry_n;
+        ha.skip = c->cfg.skip_num;
+        ha.nframes = nf;
     }
-    {  // d_wfout exists once: a result fetch in flight (psdr_fetch_begin) reads it first
-        int rc = fetch_guard_wait(c, c->side, c->guard_wf);
-        if (rc) return rc;
-        c->guard_wf = nullptr;
+    if (gather) {
+        if (total > c->wfout_cap) {
+            if (c->d_wfout) HIPCHK(hipFree(c->d_wfout));
+            c->d_wfout = nullptr;
+            HIPCHK(hipMalloc((void **)&c->d_wfout, total));
+            c->wfout_cap = total;
+        }
+        {  // d_wfout exists once: a result fetch in flight (psdr_fetch_begin) reads it first
+            int rc = fetch_guard_wait(c, c->side, c->guard_wf);
+            if (rc) return rc;
+            c->guard_wf = nullptr;
+        }
+        HIPCHK(hipMemcpyAsync(d_wf, h_wf, (size_t)(maxid + 1) * sizeof(WfClient), hipMemcpyHostToDevice,
+                              c->side));
+        HIPCHK(hipMemcpyAsync(d_sent, h_sent, (size_t)nsent * sizeof(int), hipMemcpyHostToDevice,
+                              c->side));
+        if (any_sample || !hold) {
+            ProfScope ps(c, K_WFALL, c->side);
+            hipLaunchKernelGGL(k_waterfall_gather, dim3(maxid + 1, nsent), dim3(256), 0, c->side, c->d_q,
+                               c->q_stride, c->d_qt, c->qt_stride, c->tiled_lt, c->tile_ch, c->recmap, d_wf, d_sent, nsent,
+                               c->d_wfout);
+            HIPCHK(hipGetLastError());
+        }
+        if (hold) {  // behind the gather: it rewrites the rows of the clients with a detector
+            ProfScope ps(c, K_WFHOLD, c->side);
+            hipLaunchKernelGGL(k_waterfall_hold, dim3(maxid + 1, nsent), dim3(256), 0, c->side, ha, c->tiled_lt, c->tile_ch,
+                               c->recmap, d_wf, d_sent, nsent, c->d_wfout);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(c->wf_ring.release(ring, c->side));
     }
-    HIPCHK(hipMemcpyAsync(d_wf, h_wf, (size_t)(maxid + 1) * sizeof(WfClient), hipMemcpyHostToDevice,
-                          c->side));
-    HIPCHK(hipMemcpyAsync(d_sent, h_sent, (size_t)nsent * sizeof(int), hipMemcpyHostToDevice,
-                          c->side));
-    {
-        ProfScope ps(c, K_WFALL, c->side);
-        hipLaunchKernelGGL(k_waterfall_gather, dim3(maxid + 1, nsent), dim3(256), 0, c->side, c->d_q,
-                           c->q_stride, c->d_qt, c->qt_stride, c->tiled_lt, c->tile_ch, c->recmap, d_wf, d_sent, nsent,
-                           c->d_wfout);
-        HIPCHK(hipGetLastError());
+    if (hold) {
+        // the carry for the next call: the frames behind the batch's last sent frame replace it; a batch without a sent
+        // frame is reduced onto it (onto nothing, at the start of a run)
+        const int f0 = nsent > 0 ? h_sent[nsent - 1] + 1 : 0;
+        const int accumulate = nsent == 0 && c->wf_carry_n > 0;
+        if (f0 < nf) {
+            ProfScope ps(c, K_WFCARRY, c->side);
+            const size_t lanes = (ha.lenA + ha.lenB) / 16;
+            hipLaunchKernelGGL(k_waterfall_carry, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, c->side, ha, f0, accumulate);
+            HIPCHK(hipGetLastError());
+        }
+        c->wf_carry_n = (accumulate ? c->wf_carry_n : 0) + (nf - f0);
+        c->wf_next = first_frame_num + (uint64_t)nf;
+        c->wf_run = true;
     }
-    HIPCHK(c->wf_ring.release(ring, c->side));
     if (c->side != c->stream) {
         HIPCHK(hipEventRecord(c->ev_side_done, c->side));
         c->side_pending = true;

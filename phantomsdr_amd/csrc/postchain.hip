@@ -168,6 +168,8 @@ extern "C" int psdr_set_option(psdr_ctx *c, int option, int value) {
         c->opt_pc_agc = value;
         return PSDR_OK;
     }
+    case PSDR_OPT_WATERFALL_DETECTOR:
+        return set_wf_default_detector(c, value);
     default:
         return fail(PSDR_ERR_INVALID, "unknown option %d", option);
     }

@@ -68,6 +68,23 @@ struct WfClient {
     int active;
     size_t qoff;     // byte offset of `level` inside a frame's level-major int8 buffer
     size_t out_off;  // byte offset of this client's output block
+    int det;         // psdr_wf_detector of the batch: k_waterfall_hold writes the rows of the clients with det != 0
+    int vec;         // k_waterfall_hold: four consecutive values of the level, from a multiple of four on, are one aligned dword
+};
+
+// k_waterfall_hold / k_waterfall_carry (epilogue.h): the waterfall detectors' view of a batch and of the carry, the
+// reduction of the run's frames behind its last sent frame.  The carry mirrors a frame's raw record buffers byte for
+// byte: [0, lenA) the tiled records (Qt), behind them bytes [qB0, qB0 + lenB) of the level-major buffer (Q) - the levels
+// above tiled_lt, widened to whole 16-byte pieces.
+struct WfHoldArgs {
+    const int8_t *Q, *Qt;
+    size_t q_stride, qt_stride;
+    size_t lenA, qB0, lenB;
+    int8_t *peak;    // [lenA + lenB] element-wise maximum
+    uint32_t *sum;   // [lenA + lenB] element-wise sum of (q + 128): no sign to carry, 255 * 2^24 frames fit
+    int carry_n;     // frames the carry stands for when the kernel starts
+    int skip;        // skip_num
+    int nframes;     // frames of the batch
 };
 
 }  // namespace psdr

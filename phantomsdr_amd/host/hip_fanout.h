@@ -36,6 +36,10 @@ class HipFanout {
         std::vector<int> devices;
         int shard = PSDR_SHARD_CLIENTS;  // PSDR_SHARD_CLIENTS | _RAW | _BAND
         bool force_group = false;        // the group path (and RCCL) even with one device: testing
+        // input.waterfall_detector: what a sent waterfall row shows of the skip_num - 1 frames the reference drops before
+        // it (psdr.h: psdr_wf_detector) - PSDR_WF_SAMPLE: nothing (the reference), PSDR_WF_PEAK: max-hold, PSDR_WF_MEAN:
+        // mean of the dB values.  Every waterfall client gets it.  (The last member: older initialisers keep compiling.)
+        int waterfall_detector = PSDR_WF_SAMPLE;
     };
     // (the constructor and the frame loop's own calls throw std::runtime_error on failure: they run on the server's
     // main / fft_task threads, where the reference's own set-up throws too)
@@ -64,6 +68,7 @@ class HipFanout {
             chk(psdr_create(&cfg, &ctx));
         }
         chk(psdr_ring_create(ctx, p.ring_halves));
+        if (p.waterfall_detector != PSDR_WF_SAMPLE) chk(psdr_set_option(ctx, PSDR_OPT_WATERFALL_DETECTOR, p.waterfall_detector));
         if (p.post_chain)
             for (int r = 0; r < ranks(); r++) chk(psdr_set_post_chain(rank_ctx(r), 1));
     }
@@ -111,7 +116,10 @@ class HipFanout {
         }
         chk(psdr_process_ring(ctx, first, 1));
         chk(psdr_demod_batch(ctx, frame_num));                                         // signal_loop()
-        if (frame_num % (uint64_t)prm.skip_num == 0) chk(psdr_waterfall_batch(ctx, frame_num));  // waterfall_loop()
+        // waterfall_loop(): on the sent frames.  With a detector EVERY frame is reported: the calls between two sent frames
+        // gather nothing (fetch_waterfall stays false) and feed the carry the next sent row is reduced from.  (The group
+        // path above calls it on the root at every step anyway.)
+        if (prm.waterfall_detector != PSDR_WF_SAMPLE || frame_num % (uint64_t)prm.skip_num == 0) chk(psdr_waterfall_batch(ctx, frame_num));
         have_audio = psdr_fetch_batch(ctx) == PSDR_OK;  // (PSDR_ERR_STATE: no audio client yet)
         return true;
     }

@@ -107,6 +107,10 @@ def spectrumserver_cpp(L):
         '        hp.max_waterfall_clients = config["limits"]["waterfall"].value_or(1000);',
         '        hp.post_chain = config["input"]["hip_post_chain"].value_or(true);',
         "        hp.ring_halves = 8;",
+        '        // input.waterfall_detector = "sample" (default: the reference\'s waterfall) | "peak" | "mean": what a sent row shows of the',
+        '        // frames since the previous one (psdr.h: psdr_wf_detector); the packets on the wire are the same',
+        '        const std::string det = config["input"]["waterfall_detector"].value_or("sample");',
+        '        hp.waterfall_detector = det == "peak" ? PSDR_WF_PEAK : det == "mean" ? PSDR_WF_MEAN : PSDR_WF_SAMPLE;',
         "        // more than one GPU of the node: input.hip_devices = [0, 1, ...] (device 0 keeps the ring, the FFT and the waterfall",
         "        // clients, the audio clients are spread over all of them, the spectrum crosses xGMI once per frame: psdr_group_*)",
         '        if (auto *devs = config["input"]["hip_devices"].as_array())',
