@@ -29,7 +29,6 @@ const char *kKernelNames[K_COUNT] = {"fft_pass1",  "fft_pass2", "untangle_real",
 
 void resolve_pending(psdr_ctx *c) {
     if (c->pending.empty()) return;
-    hipStreamSynchronize(c->p1);
     hipStreamSynchronize(c->stream);
     hipStreamSynchronize(c->side);
     for (hipStream_t st : c->pc_s)
@@ -41,8 +40,8 @@ void resolve_pending(psdr_ctx *c) {
             c->k_n[p.kid] += 1;
             if (c->k_samples[p.kid].size() < 65536) c->k_samples[p.kid].push_back(ms * 1e3f);
         }
-        c->pool.push_back(p.a);
-        c->pool.push_back(p.b);
+        c->pool.push_back(std::move(p.a));
+        c->pool.push_back(std::move(p.b));
     }
     c->pending.clear();
 }
@@ -53,7 +52,6 @@ void resolve_kclock(psdr_ctx *c) {
     bool any = false;
     for (int w = 0; w < 2; w++) any = any || c->kclk_done[w] < std::min(c->kclk_pos[w], psdr_ctx::KCLK_SLOTS);
     if (!any) return;
-    hipStreamSynchronize(c->p1);
     hipStreamSynchronize(c->stream);
     std::vector<unsigned long long> h((size_t)2 * psdr_ctx::KCLK_SLOTS * 2);
     if (hipMemcpy(h.data(), c->d_kclk, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return;
@@ -92,9 +90,9 @@ std::vector<cf> make_twiddles(size_t count, size_t mult, size_t period, int sign
 }
 
 template <typename T>
-int upload(T **dst, const std::vector<T> &v) {
-    HIPCHK(hipMalloc((void **)dst, v.size() * sizeof(T)));
-    HIPCHK(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+int upload(DevBuf<T> &dst, const std::vector<T> &v) {
+    PSDRCHK(dst.alloc(v.size()));
+    HIPCHK(hipMemcpy(dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return PSDR_OK;
 }
 }  // namespace psdr
@@ -116,102 +114,6 @@ size_t fmt_bytes(int fmt) {
     }
 }
 
-
-void free_all(psdr_ctx *c) {
-    auto F = [](void *p) {
-        if (p) hipFree(p);
-    };
-    F(c->d_Wl1);
-    if (c->d_Wl2 != c->d_Wl1) F(c->d_Wl2);
-    F(c->d_TA);
-    F(c->d_trace);
-    F(c->d_kclk);
-    F(c->d_TB);
-    F(c->d_UA);
-    F(c->d_UB);
-    F(c->d_UG);
-    F(c->ring.d);
-    for (auto e : c->ring.ev_written)
-        if (e) hipEventDestroy(e);
-    for (auto e : c->ring.ev_read)
-        if (e) hipEventDestroy(e);
-    if (c->ring.copy) hipStreamDestroy(c->ring.copy);
-    for (int st = 0; st < 2; st++) {
-        F(c->seam_pool[st][0]);
-        F(c->seam_pool[st][1]);
-    }
-    F(c->d_segflag);
-    for (auto &sp : c->seg_plans) F(sp.d_tab);
-    F(c->d_tickets[0]);
-    F(c->d_tickets[1]);
-    F(c->d_Y);
-    F(c->d_Z);
-    for (int s = 0; s < 2; s++) {
-        F(c->spec_pool[s]);
-        F(c->q_pool[s]);
-        F(c->qt_pool[s]);
-        F(c->pscr_pool[s][0]);
-        F(c->pscr_pool[s][1]);
-        if (c->ev_set_done[s]) hipEventDestroy(c->ev_set_done[s]);
-    }
-    F(c->d_stage);
-    F(c->d_Wn);
-    F(c->d_stage_tab);
-    F(c->d_ypost);
-    F(c->d_gscratch);
-    F(c->d_bb_tail);
-    F(c->d_bb_last);
-    for (void *q : c->post_allocs) hipFree(q);
-    for (int k = 0; k < 2; k++) {
-        F(c->pwr_pool[k]);
-        F(c->audio_pool[k]);
-        F(c->nan_pool[k]);
-    }
-    F(c->d_real_prev);
-    F(c->d_ssb_mark);
-    c->client_ring.destroy();
-    c->wf_ring.destroy();
-    F(c->d_wfout);
-    F(c->d_wf_peak);
-    F(c->d_wf_sum);
-    auto H = [](void *p) {
-        if (p) hipHostFree(p);
-    };
-    H(c->h_out);
-    H(c->h_q);
-    for (auto &fs : c->fset) {
-        H(fs.audio);
-        H(fs.pwr);
-        H(fs.nan);
-        H(fs.pcm);
-        H(fs.wf);
-        if (fs.done) hipEventDestroy(fs.done);
-        if (fs.ev_wf) hipEventDestroy(fs.ev_wf);
-        if (fs.ev_pcm) hipEventDestroy(fs.ev_pcm);
-        if (fs.ev_audio) hipEventDestroy(fs.ev_audio);
-    }
-    if (c->ev_fetch_src) hipEventDestroy(c->ev_fetch_src);
-    if (c->fetch_stream) hipStreamDestroy(c->fetch_stream);
-    if (c->fetch_stream_pcm) hipStreamDestroy(c->fetch_stream_pcm);
-    for (auto &p : c->pending) {
-        hipEventDestroy(p.a);
-        hipEventDestroy(p.b);
-    }
-    for (auto e : c->pool) hipEventDestroy(e);
-    if (c->t0) hipEventDestroy(c->t0);
-    if (c->t1) hipEventDestroy(c->t1);
-    if (c->ev_fft_done) hipEventDestroy(c->ev_fft_done);
-    if (c->ev_side_done) hipEventDestroy(c->ev_side_done);
-    if (c->own_stream) hipStreamDestroy(c->own_stream);
-    if (c->ev_in) hipEventDestroy(c->ev_in);
-    if (c->own_side) hipStreamDestroy(c->own_side);
-    for (hipStream_t st : c->pc_s)
-        if (st) hipStreamDestroy(st);
-    for (auto &stage : c->ev_pc)
-        for (hipEvent_t e : stage)
-            if (e) hipEventDestroy(e);
-}
-
 int build(psdr_ctx *c) {
     const psdr_config &g = c->cfg;
     HIPCHK(hipSetDevice(c->device));
@@ -220,25 +122,24 @@ int build(psdr_ctx *c) {
         HIPCHK(hipGetDeviceProperties(&prop, c->device));
         c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }
-    HIPCHK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
+    PSDRCHK(c->own_stream.create());
     {
         // the consumers are short kernels that must squeeze in next to the persistent FFT
         // work-groups: give their stream the highest priority (the other way round, and the passes' stream at the
         // highest, measured within +-1 %: docs/history.md section 5)
         int lo = 0, hi = 0;
         HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        HIPCHK(hipStreamCreateWithPriority(&c->own_side, hipStreamNonBlocking, hi));
+        PSDRCHK(c->own_side.create(hi));
     }
     c->stream = c->own_stream;
     c->side = c->own_side;
     // (both passes run on `stream`; the first pass of batch b+1 on a stream of its own beside the second pass of batch b
     // was measured in rounds 1-3 - -12 % at F = 16, nothing from F = 32 on - and taken out in round 5)
-    c->p1 = c->own_stream;
-    HIPCHK(hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c->ev_fft_done, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c->ev_side_done, hipEventDisableTiming));
-    HIPCHK(hipEventCreate(&c->t0));
-    HIPCHK(hipEventCreate(&c->t1));
+    PSDRCHK(c->ev_in.create());
+    PSDRCHK(c->ev_fft_done.create());
+    PSDRCHK(c->ev_side_done.create());
+    PSDRCHK(c->t0.create_timing());
+    PSDRCHK(c->t1.create_timing());
 
     // The Hann window (build_hann_window, src/utils/dsp.cpp:6-11) is evaluated inside pass 1
     // from the twiddle tables; only W_N^1 (odd real samples) is needed on top of them.
@@ -248,47 +149,44 @@ int build(psdr_ctx *c) {
     }
     // ---- twiddles
     {
-        int rc = upload(&c->d_Wl1, make_twiddles((size_t)c->M1, 1, (size_t)c->M1, -1));
+        int rc = upload(c->d_Wl1, make_twiddles((size_t)c->M1, 1, (size_t)c->M1, -1));
         if (rc) return rc;
         if (c->M2 == c->M1) {
             c->d_Wl2 = c->d_Wl1;
         } else {
-            rc = upload(&c->d_Wl2, make_twiddles((size_t)c->M2, 1, (size_t)c->M2, -1));
+            rc = upload(c->own_Wl2, make_twiddles((size_t)c->M2, 1, (size_t)c->M2, -1));
             if (rc) return rc;
+            c->d_Wl2 = c->own_Wl2;
         }
         // inter-pass twiddle W_M^e = W_M1^{e >> log2M2} * W_M^{e & (M2-1)}: the first factor
         // is the pass-1 stage table, the second has M2 entries
-        rc = upload(&c->d_TB, make_twiddles((size_t)c->M2, 1, c->M, -1));
+        rc = upload(c->d_TB, make_twiddles((size_t)c->M2, 1, c->M, -1));
         if (rc) return rc;
         if (c->is_real) {
             c->log2UB = std::min(10, ilog2(c->N));
             const size_t UB = (size_t)1 << c->log2UB;
-            rc = upload(&c->d_UA, make_twiddles(c->N / UB + 1, UB, c->N, -1));
+            rc = upload(c->d_UA, make_twiddles(c->N / UB + 1, UB, c->N, -1));
             if (rc) return rc;
-            rc = upload(&c->d_UB, make_twiddles(UB, 1, c->N, -1));
+            rc = upload(c->d_UB, make_twiddles(UB, 1, c->N, -1));
             if (rc) return rc;
             if (c->real_fused) {
-                rc = upload(&c->d_UG, make_twiddles((size_t)(c->M1 / c->T2), (size_t)(c->T2 / 2), c->N, -1));  // W_N^{CP g}: the tile's factor
+                rc = upload(c->d_UG, make_twiddles((size_t)(c->M1 / c->T2), (size_t)(c->T2 / 2), c->N, -1));  // W_N^{CP g}: the tile's factor
                 if (rc) return rc;
             }
         }
     }
 #ifdef PSDR_TRACE_ON
-    HIPCHK(hipMalloc((void **)&c->d_trace, 4864 * sizeof(unsigned long long)));
-    HIPCHK(hipMemset(c->d_trace, 0, 4864 * sizeof(unsigned long long)));
+    PSDRCHK(c->d_trace.alloc(4864, true));
 #endif
     // ---- work buffers
     const size_t F = (size_t)c->max_batch;
-    for (int i = 0; i < 2; i++) {
-        HIPCHK(hipMalloc((void **)&c->d_tickets[i], TICKET_SLOTS * 8 * sizeof(unsigned)));
-        HIPCHK(hipMemset(c->d_tickets[i], 0, TICKET_SLOTS * 8 * sizeof(unsigned)));
-    }
-    HIPCHK(hipMalloc((void **)&c->d_Y, F * c->M * sizeof(cf)));
-    if (c->is_real && !c->real_fused) HIPCHK(hipMalloc((void **)&c->d_Z, F * c->M * sizeof(cf)));
-    if (!c->is_real && c->lay.mode) HIPCHK(hipMalloc((void **)&c->d_Z, (c->M + 2) * sizeof(cf)));  // k-order staging
+    for (auto &t : c->d_tickets) PSDRCHK(t.alloc(TICKET_SLOTS * 8, true));
+    PSDRCHK(c->d_Y.alloc(F * c->M));
+    if (c->is_real && !c->real_fused) PSDRCHK(c->d_Z.alloc(F * c->M));
+    if (!c->is_real && c->lay.mode) PSDRCHK(c->d_Z.alloc(c->M + 2));  // k-order staging
     if (c->real_fused) {
         // one frame of k-order staging for psdr_read_spectrum / psdr_get_output_buffer
-        HIPCHK(hipMalloc((void **)&c->d_Z, (c->M + 2) * sizeof(cf)));
+        PSDRCHK(c->d_Z.alloc(c->M + 2));
         if (const char *e = getenv("PSDR_SEG_LEN")) c->seg_len_env = atoi(e);
         size_t cap = 0, capc = 0;
         for (int nf = 1; nf <= c->max_batch; nf++) {
@@ -301,13 +199,12 @@ int build(psdr_ctx *c) {
         c->seam_cap = cap;
         c->seg_cap = capc;
         for (int st = 0; st < 2; st++) {  // part of the double-buffered result sets: k_real_seam is a consumer
-            HIPCHK(hipMalloc((void **)&c->seam_pool[st][0], cap * (size_t)c->M2 * (size_t)(c->T2 / 2) * sizeof(float)));  // [segment][M2][couples per tile]
-            HIPCHK(hipMalloc((void **)&c->seam_pool[st][1], capc * (size_t)c->M2 * sizeof(float)));
+            PSDRCHK(c->seam_pool[st][0].alloc(cap * (size_t)c->M2 * (size_t)(c->T2 / 2)));  // [segment][M2][couples per tile]
+            PSDRCHK(c->seam_pool[st][1].alloc(capc * (size_t)c->M2));
         }
         // flags (inside a launch only), then the fallback marks - ONE ARRAY PER RESULT SET: k_real_seam is a consumer, it may
         // run after the next batch's second pass has started writing its own marks
-        HIPCHK(hipMalloc((void **)&c->d_segflag, 3 * capc * sizeof(unsigned)));
-        HIPCHK(hipMemset(c->d_segflag, 0, 3 * capc * sizeof(unsigned)));
+        PSDRCHK(c->d_segflag.alloc(3 * capc, true));
         {  // the plans of the two batch sizes every caller uses, now rather than in the first batch (a synchronous upload)
             const psdr_ctx::SegPlan *sp;
             int rc = seg_plan(c, c->max_batch, &sp);
@@ -316,26 +213,21 @@ int build(psdr_ctx *c) {
         }
     }
     for (int s = 0; s < 2; s++) {
-        HIPCHK(hipMalloc((void **)&c->spec_pool[s], F * c->spec_stride * sizeof(cf)));
-        HIPCHK(hipMemset(c->spec_pool[s], 0, F * c->spec_stride * sizeof(cf)));
-        HIPCHK(hipMalloc((void **)&c->q_pool[s], F * c->q_stride));
-        HIPCHK(hipMemset(c->q_pool[s], 0, F * c->q_stride));
-        if (c->tiled_lt >= 0) {
-            HIPCHK(hipMalloc((void **)&c->qt_pool[s], F * c->qt_stride));
-            HIPCHK(hipMemset(c->qt_pool[s], 0, F * c->qt_stride));
-        }
-        HIPCHK(hipMalloc((void **)&c->pscr_pool[s][0], F * c->p_stride * sizeof(float)));
-        HIPCHK(hipMalloc((void **)&c->pscr_pool[s][1], F * c->p_stride * sizeof(float)));
-        HIPCHK(hipEventCreateWithFlags(&c->ev_set_done[s], hipEventDisableTiming));
+        PSDRCHK(c->spec_pool[s].alloc(F * c->spec_stride, true));
+        PSDRCHK(c->q_pool[s].alloc(F * c->q_stride, true));
+        if (c->tiled_lt >= 0) PSDRCHK(c->qt_pool[s].alloc(F * c->qt_stride, true));
+        PSDRCHK(c->pscr_pool[s][0].alloc(F * c->p_stride));
+        PSDRCHK(c->pscr_pool[s][1].alloc(F * c->p_stride));
+        PSDRCHK(c->ev_set_done[s].create());
     }
     select_set(c, 0);
     c->q_untiled.assign(F, 0);
     // ---- level-1 staging
-    HIPCHK(hipMalloc((void **)&c->d_stage, (c->is_real ? c->N : 2 * c->N) * sizeof(float)));
+    PSDRCHK(c->d_stage.alloc(c->is_real ? c->N : 2 * c->N));
     {
         const size_t nb = c->is_real ? (c->N / 2 + 1) : (c->N + (size_t)g.additional_size);
-        HIPCHK(hipHostMalloc((void **)&c->h_out, nb * sizeof(cf), hipHostMallocDefault));
-        HIPCHK(hipHostMalloc((void **)&c->h_q, std::max<size_t>(c->q_len, 16), hipHostMallocDefault));
+        PSDRCHK(c->h_out.alloc(nb));
+        PSDRCHK(c->h_q.alloc(c->q_len));
     }
     // ---- audio clients
     c->n = g.audio_fft_size;
@@ -376,7 +268,7 @@ int build(psdr_ctx *c) {
             c->lds_mode = 2;
             c->idft_lds = 0;
         }
-        int rc = upload(&c->d_Wn, make_twiddles((size_t)n, 1, (size_t)n, +1));
+        int rc = upload(c->d_Wn, make_twiddles((size_t)n, 1, (size_t)n, +1));
         if (rc) return rc;
         {
             // stage tables of the generic-radix Stockham: output o = s*(n/R) + i of a stage with
@@ -393,7 +285,7 @@ int build(psdr_ctx *c) {
                 }
                 pp *= R;
             }
-            rc = upload(&c->d_stage_tab, tab);
+            rc = upload(c->d_stage_tab, tab);
             if (rc) return rc;
             c->idft_threads = n <= 512 ? 128 : 256;
             if (const char *e = getenv("PSDR_DEMOD_CHAIN")) c->demod_chain = atoi(e) != 0;
@@ -401,25 +293,18 @@ int build(psdr_ctx *c) {
         }
         const size_t S = (size_t)std::max(1, g.max_clients);
         c->aslots.resize(S);
-        HIPCHK(hipMalloc((void **)&c->d_ypost, S * F * n * sizeof(cf)));
+        PSDRCHK(c->d_ypost.alloc(S * F * n));
         for (int k = 0; k < 2; k++) {
-            HIPCHK(hipMalloc((void **)&c->pwr_pool[k], S * F * sizeof(float)));
-            HIPCHK(hipMalloc((void **)&c->audio_pool[k], S * F * (n / 2) * sizeof(float)));
-            HIPCHK(hipMalloc((void **)&c->nan_pool[k], S * F * sizeof(int)));
-            HIPCHK(hipMemset(c->audio_pool[k], 0, S * F * (n / 2) * sizeof(float)));
-            HIPCHK(hipMemset(c->pwr_pool[k], 0, S * F * sizeof(float)));
-            HIPCHK(hipMemset(c->nan_pool[k], 0, S * F * sizeof(int)));
+            PSDRCHK(c->pwr_pool[k].alloc(S * F, true));
+            PSDRCHK(c->audio_pool[k].alloc(S * F * (n / 2), true));
+            PSDRCHK(c->nan_pool[k].alloc(S * F, true));
         }
         c->d_pwr = c->pwr_pool[0], c->d_audio = c->audio_pool[0], c->d_nan = c->nan_pool[0];
-        HIPCHK(hipMalloc((void **)&c->d_real_prev, 2 * S * (n / 2) * sizeof(float)));
-        HIPCHK(hipMalloc((void **)&c->d_bb_tail, 2 * S * (n / 2) * sizeof(cf)));
-        HIPCHK(hipMalloc((void **)&c->d_bb_last, 2 * S * sizeof(cf)));
-        HIPCHK(hipMemset(c->d_real_prev, 0, 2 * S * (n / 2) * sizeof(float)));
-        HIPCHK(hipMemset(c->d_bb_tail, 0, 2 * S * (n / 2) * sizeof(cf)));
-        HIPCHK(hipMemset(c->d_bb_last, 0, 2 * S * sizeof(cf)));
-        HIPCHK(hipMalloc((void **)&c->d_ssb_mark, S * sizeof(unsigned)));
-        HIPCHK(hipMemset(c->d_ssb_mark, 0, S * sizeof(unsigned)));
-        if (c->lds_mode == 2) HIPCHK(hipMalloc((void **)&c->d_gscratch, S * F * 2 * n * sizeof(cf)));
+        PSDRCHK(c->d_real_prev.alloc(2 * S * (n / 2), true));
+        PSDRCHK(c->d_bb_tail.alloc(2 * S * (n / 2), true));
+        PSDRCHK(c->d_bb_last.alloc(2 * S, true));
+        PSDRCHK(c->d_ssb_mark.alloc(S, true));
+        if (c->lds_mode == 2) PSDRCHK(c->d_gscratch.alloc(S * F * 2 * n));
         if (c->client_ring.init(S * (sizeof(ClientParams) + sizeof(int))))  // the batch's client list + the slot -> list index table
             return fail(PSDR_ERR_HIP, "client parameter ring allocation failed");
     }
@@ -544,7 +429,6 @@ extern "C" int psdr_create(const psdr_config *cfg, psdr_ctx **out) {
 
     int rc = build(c);
     if (rc) {
-        free_all(c);
         delete c;
         return rc;
     }
@@ -557,8 +441,7 @@ extern "C" void psdr_destroy(psdr_ctx *c) {
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
     if (c->side) hipStreamSynchronize(c->side);
-    free_all(c);
-    delete c;
+    delete c;  // (every buffer, event and stream goes with the member that owns it)
 }
 
 // ---- level 1 ---------------------------------------------------------------------------
@@ -662,17 +545,17 @@ extern "C" int psdr_ring_create(psdr_ctx *c, int nhalves) {
     if (nhalves < 2) return fail(PSDR_ERR_INVALID, "a ring needs at least 2 half-frames");
     if (c->ring.d) return fail(PSDR_ERR_STATE, "the context already has an ingest ring");
     HIPCHK(hipSetDevice(c->device));
-    auto &r = c->ring;
+    psdr_ctx::IngestRing r;  // built whole, then moved in: a failure leaves the context without a ring
     r.hb = psdr_half_frame_bytes(c);
     r.nhalves = nhalves;
-    HIPCHK(hipMalloc((void **)&r.d, (size_t)(nhalves + 1) * r.hb));
-    HIPCHK(hipMemset(r.d, 0, (size_t)(nhalves + 1) * r.hb));
-    HIPCHK(hipStreamCreateWithFlags(&r.copy, hipStreamNonBlocking));
-    r.ev_written.assign(nhalves, nullptr);
+    PSDRCHK(r.d.alloc((size_t)(nhalves + 1) * r.hb, true));
+    PSDRCHK(r.copy.create());
+    r.ev_written.resize(nhalves);
     r.ever_written.assign(nhalves, 0);
     r.reader_seq.assign(nhalves, 0);
-    for (auto &e : r.ev_written) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (auto &e : r.ev_read) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (auto &e : r.ev_written) PSDRCHK(e.create());
+    for (auto &e : r.ev_read) PSDRCHK(e.create());
+    c->ring = std::move(r);
     return PSDR_OK;
 }
 extern "C" int psdr_ring_write_async(psdr_ctx *c, uint64_t half_index, const void *host_half) {
@@ -720,7 +603,7 @@ extern "C" int psdr_process_ring(psdr_ctx *c, uint64_t first_half, int nframes) 
     for (int i = 0; i <= nframes; i++) {  // halves s0 .. s0+nframes (the last may be the mirror of slot 0)
         const int slot = (s0 + i) % r.nhalves;
         if (!r.ever_written[slot]) return fail(PSDR_ERR_STATE, "half-frame slot %d was never written", slot);
-        HIPCHK(hipStreamWaitEvent(c->p1, r.ev_written[slot], 0));
+        HIPCHK(hipStreamWaitEvent(c->stream, r.ev_written[slot], 0));
     }
     r.seq++;
     hipEvent_t ev = r.ev_read[r.seq % psdr_ctx::IngestRing::NEV];
@@ -733,7 +616,6 @@ extern "C" int psdr_process_ring(psdr_ctx *c, uint64_t first_half, int nframes) 
 
 int psdr::drain(psdr_ctx *c) {
     if (c->ring.copy) HIPCHK(hipStreamSynchronize(c->ring.copy));
-    if (c->p1 != c->stream) HIPCHK(hipStreamSynchronize(c->p1));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (c->side != c->stream) HIPCHK(hipStreamSynchronize(c->side));
     for (hipStream_t st : c->pc_s)
@@ -754,7 +636,7 @@ extern "C" int psdr_set_profiling(psdr_ctx *c, int mode) {
     if (mode == 2 && !c->d_kclk) {
         int khz = 0;
         if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device) == hipSuccess && khz > 0) c->wall_clock_khz = khz;
-        HIPCHK(hipMalloc((void **)&c->d_kclk, (size_t)2 * psdr_ctx::KCLK_SLOTS * 2 * sizeof(unsigned long long)));
+        PSDRCHK(c->d_kclk.alloc((size_t)2 * psdr_ctx::KCLK_SLOTS * 2));
         int rc = drain(c);
         if (rc) return rc;
         rc = reset_kclock(c);
@@ -816,7 +698,7 @@ extern "C" int psdr_timer_start(psdr_ctx *c) {
 extern "C" int psdr_timer_stop_ms(psdr_ctx *c, double *ms_out) {
     if (!c || !ms_out) return fail(PSDR_ERR_INVALID, "null argument");
     if (c->side_pending && c->side != c->stream) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_side_done, 0));
-    if (c->chain_pending && c->chain_seq > 0) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_pc[3][(c->chain_seq - 1) % psdr_ctx::PC_SETS], 0));
+    if (c->chain_pending && c->chain_seq > 0) HIPCHK(hipStreamWaitEvent(c->stream, c->pc.ev[3][(c->chain_seq - 1) % psdr_ctx::PC_SETS], 0));
     HIPCHK(hipEventRecord(c->t1, c->stream));
     HIPCHK(hipEventSynchronize(c->t1));
     float ms = 0;
@@ -869,11 +751,9 @@ extern "C" int psdr_set_stream(psdr_ctx *c, void *hip_stream) {
     if (hip_stream) {  // everything in order on the caller's stream
         c->stream = (hipStream_t)hip_stream;
         c->side = c->stream;
-        c->p1 = c->stream;
     } else {
         c->stream = c->own_stream;
         c->side = c->own_side;
-        c->p1 = c->own_stream;
     }
     return PSDR_OK;
 }

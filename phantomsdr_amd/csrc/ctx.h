@@ -18,6 +18,7 @@
 
 #include "../../include/psdr.h"
 #include "butterfly.h"
+#include "owned.h"
 #include "quantize.h"
 #include "types.h"
 
@@ -30,6 +31,12 @@ int psdr_fail(int code, const char *fmt, ...);
         if (e_ != hipSuccess)                                                               \
             return fail(PSDR_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
                         __FILE__, __LINE__);                                                \
+    } while (0)
+// ... for calls that return the library's own status (the owners of owned.h)
+#define PSDRCHK(expr)         \
+    do {                      \
+        int rc_ = (expr);     \
+        if (rc_) return rc_;  \
     } while (0)
 
 // Run-time knobs of the PRODUCT library (documented in DESIGN.md): PSDR_SEG_LEN (tiles per chain segment of the fused
@@ -51,7 +58,7 @@ enum KernelId { K_PASS1, K_PASS2, K_UNTANGLE, K_TAIL, K_IDFT, K_OLA, K_WFALL, K_
 extern const char *kKernelNames[K_COUNT];
 
 struct PendingEvent {
-    hipEvent_t a, b;
+    Event a, b;
     int kid;
 };
 struct AudioSlot {
@@ -83,25 +90,18 @@ struct WfSlot {
 // batch can be enqueued without waiting for the previous one to drain.
 struct ParamRing {
     static constexpr int K = 8;
-    unsigned char *h = nullptr, *d = nullptr;
+    HostBuf<unsigned char> h;
+    DevBuf<unsigned char> d;
     size_t slot_bytes = 0;
-    hipEvent_t ev[K] = {};
+    Event ev[K];
     bool used[K] = {};
     int idx = 0;
     int init(size_t bytes) {
         slot_bytes = (bytes + 255) & ~(size_t)255;
-        if (hipHostMalloc((void **)&h, slot_bytes * K, hipHostMallocDefault) != hipSuccess) return -1;
-        if (hipMalloc((void **)&d, slot_bytes * K) != hipSuccess) return -1;
-        for (int i = 0; i < K; i++)
-            if (hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) != hipSuccess) return -1;
-        return 0;
-    }
-    void destroy() {
-        if (h) hipHostFree(h);
-        if (d) hipFree(d);
-        for (int i = 0; i < K; i++)
-            if (ev[i]) hipEventDestroy(ev[i]);
-        h = d = nullptr;
+        PSDRCHK(h.alloc(slot_bytes * K));
+        PSDRCHK(d.alloc(slot_bytes * K));
+        for (Event &e : ev) PSDRCHK(e.create());
+        return PSDR_OK;
     }
     // returns the slot to fill (waits only if the ring wrapped onto a still-busy slot); -1: HIP error
     int acquire() {
@@ -142,18 +142,18 @@ struct psdr_ctx {
     SpecLayout lay{};                // device layout of the spectrum (natural unless real_fused)
     int nbands = 0, band_H = 0;      // psdr_set_band_layout: band regions (SpecLayout mode 3), halo columns per band
     int seg_len_env = 0;             // PSDR_SEG_LEN: tiles per chain segment (uniform segments, every one with a seam)
-    float *d_seamP = nullptr, *d_seamC = nullptr;  // of the current result set
-    float *seam_pool[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+    float *d_seamP = nullptr, *d_seamC = nullptr;  // views: seam_pool[cur_set][0 / 1]
+    DevBuf<float> seam_pool[2][2];
     size_t seam_cap = 0, seg_cap = 0;  // segments without a carry-in the seamP buffers hold; segments (seamC, flags)
     // chain segments of the fused real second pass for a batch of `nframes` frames (forward.hip: seg_plan)
     struct SegPlan {
         int nframes = 0;
         unsigned nsegs = 0, nseam = 0;  // the nseam segments without a carry-in come first
         bool handoff = false;           // the others get their carried row through memory inside the launch
-        uint4 *d_tab = nullptr;
+        DevBuf<uint4> d_tab;
     };
     std::vector<SegPlan> seg_plans;  // one per batch size seen
-    unsigned *d_segflag = nullptr;   // [seg_cap] epoch of the launch that last published the segment's carry-out; behind it
+    DevBuf<unsigned> d_segflag;      // [seg_cap] epoch of the launch that last published the segment's carry-out; behind it
                                      // [2][seg_cap] the fallback marks of the two result sets (fft_pass.h: segmark)
     unsigned seg_epoch = 0;
     int size_log2 = 0;
@@ -168,43 +168,41 @@ struct psdr_ctx {
     // Two streams: the FFT passes run on `stream`; everything that only consumes a finished
     // batch (pyramid tail, demodulation, waterfall gather) runs on `side`, so it overlaps
     // the next batch's pass 1 (its work-groups fit next to the persistent FFT work-groups).
-    hipStream_t stream = nullptr, side = nullptr;
-    hipStream_t own_stream = nullptr, own_side = nullptr;
-    // pass 1 runs on its own stream so that pass 1 of batch i+1 fills the CUs that pass 2 of
-    // batch i leaves one by one (persistent work-groups: launch ramp, prologue and tail of one
-    // kernel overlap with the other kernel's steady state); Y is double-buffered for that
-    hipStream_t p1 = nullptr;
-    cf *d_Y = nullptr;  // the inter-pass array, max_batch frames of M complex values
+    hipStream_t stream = nullptr, side = nullptr;  // views: own_stream / own_side, or the caller's (psdr_set_stream)
+    Stream own_stream, own_side;
+    DevBuf<cf> d_Y;  // the inter-pass array, max_batch frames of M complex values
     // TileQueue counters: a ring of TICKET_SLOTS launches x 8 counters per pass; half the ring is
     // re-zeroed (in stream order) whenever the other half starts being used
-    unsigned *d_tickets[2] = {nullptr, nullptr};
+    DevBuf<unsigned> d_tickets[2];
     unsigned ticket_pos[2] = {0, 0};
     bool input_on_main = false;  // level-1 H2D staging was enqueued on the main stream
-    hipEvent_t ev_in = nullptr;
-    hipEvent_t ev_fft_done = nullptr, ev_side_done = nullptr;
+    Event ev_in;
+    Event ev_fft_done, ev_side_done;
     bool side_pending = false;
     // Result buffers (spectrum, pyramid, level powers) exist twice: batch b+1 is produced
     // into the other set while the side stream still consumes batch b, so the FFT stream only
-    // ever waits for the consumers of batch b-1.  d_spec/d_q/d_qt/d_pscr point at the set of
-    // the LAST processed batch.
+    // ever waits for the consumers of batch b-1.  d_spec/d_q/d_qt/d_pscr are views of the set of
+    // the LAST processed batch (forward.hip: select_set).
     // (forward.hip: enqueue_tails - what the tail kernels of the batch just transformed need)
     bool tails_pending = false;
     const struct SegPlan *tails_plan = nullptr;
     int tails_nframes = 0;
     int cur_set = 0;
     bool alt_sets = false;  // alternate the sets also on a caller's stream (a group's root: the peers read batch b's spectrum while b + 1 is transformed)
-    cf *spec_pool[2] = {nullptr, nullptr};
-    int8_t *q_pool[2] = {nullptr, nullptr}, *qt_pool[2] = {nullptr, nullptr};
-    float *pscr_pool[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    hipEvent_t ev_set_done[2] = {nullptr, nullptr};
+    DevBuf<cf> spec_pool[2];
+    DevBuf<int8_t> q_pool[2], qt_pool[2];
+    DevBuf<float> pscr_pool[2][2];
+    Event ev_set_done[2];
     bool set_pending[2] = {false, false};
 
-    cf *d_Wl1 = nullptr, *d_Wl2 = nullptr, *d_TA = nullptr, *d_TB = nullptr;
-    cf *d_UA = nullptr, *d_UB = nullptr, *d_UG = nullptr;
+    DevBuf<cf> d_Wl1, own_Wl2, d_TB;
+    cf *d_Wl2 = nullptr;  // view: d_Wl1 when M2 == M1, else own_Wl2
+    DevBuf<cf> d_UA, d_UB, d_UG;
     cf wdelta = {1.f, 0.f};  // W_N^1
-    unsigned long long *d_trace = nullptr;  // PSDR_TRACE tuning builds: per pass [8][16] phase stamps + [256][8] work-group timeline
-    int log2B = 0, log2UB = 0;
-    cf *d_Z = nullptr, *d_spec = nullptr;
+    DevBuf<unsigned long long> d_trace;  // PSDR_TRACE tuning builds: per pass [8][16] phase stamps + [256][8] work-group timeline
+    int log2UB = 0;
+    DevBuf<cf> d_Z;
+    cf *d_spec = nullptr;
     int8_t *d_q = nullptr;   // level-major pyramid (the reference's layout)
     int8_t *d_qt = nullptr;  // tiled records of levels 0..LT (IQ fused epilogue), quantize.h
     size_t qt_stride = 0;
@@ -214,9 +212,9 @@ struct psdr_ctx {
     float *d_pscr[2] = {nullptr, nullptr};
 
     // level 1
-    float *d_stage = nullptr;
-    float *h_out = nullptr;
-    int8_t *h_q = nullptr;
+    DevBuf<float> d_stage;
+    HostBuf<cf> h_out;
+    HostBuf<int8_t> h_q;
     bool loaded = false, executed = false, out_valid = false, q_valid = false;
     int last_nframes = 0;
 
@@ -230,10 +228,9 @@ struct psdr_ctx {
     bool demod_chain = true;  // PSDR_DEMOD_CHAIN=0: the two-kernel path (k_demod_idft_fixed + k_demod_ola) for n = 360 / 720 too
     int demod_chain_k = 0;    // PSDR_DEMOD_K: frames per chain (0: 8, 4 when there are few clients)
     size_t idft_lds = 0;
-    int4 *d_stage_tab = nullptr;
+    DevBuf<int4> d_stage_tab;
     int idft_threads = 256;
-    cf *d_Wn = nullptr, *d_ypost = nullptr, *d_gscratch = nullptr, *d_bb_tail = nullptr,
-       *d_bb_last = nullptr;
+    DevBuf<cf> d_Wn, d_ypost, d_gscratch, d_bb_tail, d_bb_last;
     // post-demodulation chain (postchain.h), allocated by psdr_set_post_chain
     bool post_on = false;
     bool post_ready = false;   // the chain's buffers, events and streams exist (psdr_set_post_chain's one-time set-up went through)
@@ -241,7 +238,7 @@ struct psdr_ctx {
     int opt_pc_pcm16 = 0;      // PSDR_OPT_POST_CHAIN_PCM16: the chain's PCM as int16 rows (half the bytes to the host)
     bool pcm_is16 = false;     // ... of the last chain batch (what a fetch / psdr_read_pcm finds in the PCM buffer)
     int opt_pc_agc = 1;        // PSDR_OPT_POST_CHAIN_AGC: 1 = chunk maxima + k_pc_agc where it applies, 0 = the five-kernel form
-    PostArgs post{};
+    PostArgs post{};  // (passed to kernels by value: raw pointers, views of what `pc` owns)
     // The chain is a pipeline across batches (round 5), in the order of a batch's data:
     //   side     index, gather (behind the demodulation)
     //   pc_s[0]  moving averages (sequential), history
@@ -251,14 +248,21 @@ struct psdr_ctx {
     // one stream - longer than the step it hid behind (3.2 ms against 2.6).  What the stages hand on rotates over PC_SETS
     // sets, so a batch's chain may take up to two steps longer than a step.
     static constexpr int PC_SETS = 3;
-    hipStream_t pc_s[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev_pc[4][PC_SETS] = {};  // [stage][set]: the stage's kernels of the batch that used the set are done
-    float *post_x[PC_SETS] = {}, *post_m1[PC_SETS] = {}, *post_v1[PC_SETS] = {};
-    float *post_p[PC_SETS] = {}, *post_s[PC_SETS] = {}, *post_sm[PC_SETS] = {};  // prefix maxima then g_t / w_t / sub-block maxima
-    int *post_fstart[PC_SETS] = {}, *post_len[PC_SETS] = {};
-    // the AGC in one kernel behind chunk maxima (postchain.h k_pc_cm / k_pc_cscan / k_pc_agc): per set like P / S
-    float *post_cm[PC_SETS] = {}, *post_cp[PC_SETS] = {}, *post_cs[PC_SETS] = {};
-    int *post_falive[PC_SETS] = {};
+    Stream pc_s[3];
+    // what psdr_set_post_chain's one-time set-up creates: built whole, then moved in
+    struct PostChain {
+        Event ev[4][PC_SETS];  // [stage][set]: the stage's kernels of the batch that used the set are done
+        DevBuf<float> x[PC_SETS], m1[PC_SETS], v1[PC_SETS];
+        DevBuf<float> p[PC_SETS], s[PC_SETS], sm[PC_SETS];  // prefix maxima then g_t / w_t / sub-block maxima
+        DevBuf<int> fstart[PC_SETS], len[PC_SETS];
+        // the AGC in one kernel behind chunk maxima (postchain.h k_pc_cm / k_pc_cscan / k_pc_agc): per set like P / S
+        DevBuf<float> cm[PC_SETS], cp[PC_SETS], cs[PC_SETS];
+        DevBuf<int> falive[PC_SETS];
+        DevBuf<int32_t> pcm_pool[2];  // post.pcm is a view of the last batch's
+        DevBuf<int32_t> pcm_dump;     // PostArgs' pointers of the same names
+        DevBuf<float> dc_s1, dc_s2, agc_gain;
+        DevBuf<int> agc_n0;
+    } pc;
     bool post_direct = false;  // the last chain batch's moving averages read d_audio themselves (k_pc_ma2 DIRECT)
     bool post_agc_ok = false;  // the rate / audio size allow it (L % 16 == 0, h % 4 == 0, h >= 16, D % 4 == 0)
     uint64_t chain_seq = 0;
@@ -266,17 +270,16 @@ struct psdr_ctx {
     int post_reserve = 8;  // CUs the FFT passes leave free while the chain is on (a multiple of 8: one per XCD); 0: none
     int post_lanes = 32;   // slots per work-group of the chain's two recurrence kernels
     bool post_own = true;  // their waves allocate a whole SIMD's registers
-    std::vector<void *> post_allocs;
     // Results of the LAST demodulation batch: d_audio / d_pwr / d_nan point into one of TWO sets that alternate from batch to
     // batch, so that the copies of batch b to the host (psdr_fetch_begin) run beside the demodulation of batch b + 1 instead
     // of holding it up (256 clients: 96 MB per step, 1.7 ms on the link - longer than the demodulation it follows)
-    float *d_pwr = nullptr, *d_audio = nullptr, *d_real_prev = nullptr;
+    float *d_pwr = nullptr, *d_audio = nullptr;  // views: pwr_pool / audio_pool / nan_pool [out_set]
     int *d_nan = nullptr;
-    float *audio_pool[2] = {nullptr, nullptr}, *pwr_pool[2] = {nullptr, nullptr};
-    int *nan_pool[2] = {nullptr, nullptr};
-    int32_t *pcm_pool[2] = {nullptr, nullptr};  // post chain: post.pcm points at the last batch's
+    DevBuf<float> d_real_prev;
+    DevBuf<float> audio_pool[2], pwr_pool[2];
+    DevBuf<int> nan_pool[2];
     int out_set = 0, pcm_set = 0;
-    unsigned *d_ssb_mark = nullptr;  // [slots] DemodArgs::ssb_mark (demod.h): USB / LSB batches that need the frame-ordered NaN guard
+    DevBuf<unsigned> d_ssb_mark;  // [slots] DemodArgs::ssb_mark (demod.h): USB / LSB batches that need the frame-ordered NaN guard
     ParamRing client_ring;
     int last_demod_frames = 0;
     uint64_t demod_seq = 0;  // number of demodulation batches so far (AudioSlot::last_seq)
@@ -286,16 +289,16 @@ struct psdr_ctx {
     // the device buffers it reads exist once, so the next batch's WRITERS (demodulation, waterfall gather, the chain's
     // output kernel) wait for `done` of the newest fetch in stream order (fetch_guard).
     struct FetchSet {
-        float *audio = nullptr, *pwr = nullptr;
-        int32_t *nan = nullptr, *pcm = nullptr;
-        int8_t *wf = nullptr;
+        HostBuf<float> audio, pwr;
+        HostBuf<int32_t> nan, pcm;
+        HostBuf<int8_t> wf;
         size_t wf_cap = 0;
-        hipEvent_t done = nullptr;       // every copy of the fetch on the first copy stream has landed
-        hipEvent_t ev_pcm = nullptr;     // ... and the PCM (its own copy stream: it waits for the post chain, up to two steps late)
+        Event done;                      // every copy of the fetch on the first copy stream has landed
+        Event ev_pcm;                    // ... and the PCM (its own copy stream: it waits for the post chain, up to two steps late)
         bool has_pcm = false;
         bool pcm16 = false;              // its PCM rows are int16 (PSDR_OPT_POST_CHAIN_PCM16 at that batch)
-        hipEvent_t ev_wf = nullptr;      // ... the waterfall rows (first in the copy stream: d_wfout exists once)
-        hipEvent_t ev_audio = nullptr;   // ... pwr, NaN flags, float audio (what the demodulation of batch b + 2 overwrites)
+        Event ev_wf;                     // ... the waterfall rows (first in the copy stream: d_wfout exists once)
+        Event ev_audio;                  // ... pwr, NaN flags, float audio (what the demodulation of batch b + 2 overwrites)
         bool inflight = false;
         unsigned what = 0;     // PSDR_FETCH_* bits the copies covered
         int frames = 0;        // frames of the demodulation batch (0: none was fetched)
@@ -312,23 +315,24 @@ struct psdr_ctx {
     int fetch_fill = 0;            // the set the next psdr_fetch_begin fills (a ring: the oldest in flight is fetch_fill - fetch_inflight)
     int fetch_inflight = 0;        // fetches begun and not yet ended
     int fetch_cur = -1;            // the set psdr_fetched_* read: completed by the last psdr_fetch_end
-    hipStream_t fetch_stream = nullptr, fetch_stream_pcm = nullptr;
-    hipEvent_t ev_fetch_src = nullptr;
+    Stream fetch_stream, fetch_stream_pcm;
+    Event ev_fetch_src;
     // what the next WRITER of a device-side result buffer waits for (stream-ordered): the newest fetch that read it
+    // (views of a FetchSet's events)
     hipEvent_t guard_wf = nullptr, guard_audio[2] = {nullptr, nullptr}, guard_pcm[2] = {nullptr, nullptr};
 
     // waterfall clients
     std::vector<WfSlot> wslots;
     ParamRing wf_ring;  // [WfClient x W][int x F]
     size_t wf_sent_off = 0;
-    int8_t *d_wfout = nullptr;
+    DevBuf<int8_t> d_wfout;
     size_t wfout_cap = 0;
     // waterfall detectors (psdr_waterfall_set_detector): the carry is the reduction of the frames of the current RUN of
     // psdr_waterfall_batch calls that lie behind the run's last sent frame - what the next sent row's window holds of
     // earlier batches.  Allocated by the first batch with a non-sample client; touched on `side` only.
     int opt_wf_det = PSDR_WF_SAMPLE;   // PSDR_OPT_WATERFALL_DETECTOR: what psdr_waterfall_add hands a new client
-    int8_t *d_wf_peak = nullptr;
-    uint32_t *d_wf_sum = nullptr;
+    DevBuf<int8_t> d_wf_peak;
+    DevBuf<uint32_t> d_wf_sum;
     size_t wf_lenA = 0, wf_qB0 = 0, wf_lenB = 0;
     bool wf_run = false;               // the last psdr_waterfall_batch kept the carry (some client had a detector)
     uint64_t wf_next = 0;              // ... and the first_frame_num that continues it
@@ -337,14 +341,14 @@ struct psdr_ctx {
     // streaming ingest ring (psdr_ring_*)
     struct IngestRing {
         static constexpr int NEV = 16;
-        unsigned char *d = nullptr;  // nhalves + 1 slots (the last mirrors slot 0: a frame window may end there)
+        DevBuf<unsigned char> d;     // nhalves + 1 slots (the last mirrors slot 0: a frame window may end there)
         int nhalves = 0;
         size_t hb = 0;
-        hipStream_t copy = nullptr;
-        std::vector<hipEvent_t> ev_written;   // per slot: its last H2D copy
+        Stream copy;
+        std::vector<Event> ev_written;        // per slot: its last H2D copy
         std::vector<char> ever_written;
         std::vector<uint64_t> reader_seq;     // per slot: the last psdr_process_ring call that read it
-        hipEvent_t ev_read[NEV] = {};         // pass 1 of process call seq % NEV has consumed its halves
+        Event ev_read[NEV];                   // pass 1 of process call seq % NEV has consumed its halves
         uint64_t seq = 0;
     } ring;
 
@@ -352,15 +356,15 @@ struct psdr_ctx {
     bool profiling = false;   // psdr_set_profiling mode 1: hipEvent brackets around every launch
     bool kclock = false;      // mode 2: device-clock stamps inside the two FFT passes (fft_pass.h kclk_*)
     static constexpr unsigned KCLK_SLOTS = 8192;  // launches per pass that can be stamped between two resets
-    unsigned long long *d_kclk = nullptr;         // [2 passes][KCLK_SLOTS][begin, end]
+    DevBuf<unsigned long long> d_kclk;            // [2 passes][KCLK_SLOTS][begin, end]
     unsigned kclk_pos[2] = {0, 0}, kclk_done[2] = {0, 0};
     double wall_clock_khz = 100000.0;
     std::vector<PendingEvent> pending;
-    std::vector<hipEvent_t> pool;
+    std::vector<Event> pool;
     double k_ms[K_COUNT] = {0};
     int64_t k_n[K_COUNT] = {0};
     std::vector<float> k_samples[K_COUNT];  // per-launch durations in us since the last reset (bounded)
-    hipEvent_t t0 = nullptr, t1 = nullptr;
+    Event t0, t1;
 };
 
 namespace psdr {
@@ -368,36 +372,32 @@ namespace psdr {
 struct ProfScope {
     psdr_ctx *c;
     int kid;
-    hipEvent_t a = nullptr, b = nullptr;
+    Event a, b;
     hipStream_t st;
     ProfScope(psdr_ctx *c_, int kid_, hipStream_t st_ = nullptr) : c(c_), kid(kid_), st(st_ ? st_ : c_->stream) {
         if (!c->profiling) return;
-        auto get = [&]() {
-            hipEvent_t e;
+        auto get = [&](Event &e) {
             if (!c->pool.empty()) {
-                e = c->pool.back();
+                e = std::move(c->pool.back());
                 c->pool.pop_back();
-            } else if (hipEventCreate(&e) != hipSuccess) {
-                e = nullptr;
+            } else {
+                (void)e.create_timing();
             }
-            return e;
         };
-        a = get();
-        b = get();
-        if (!a || !b || hipEventRecord(a, st) != hipSuccess) {  // no timing for this launch
-            if (a) c->pool.push_back(a);
-            if (b) c->pool.push_back(b);
-            a = b = nullptr;
-        }
+        get(a);
+        get(b);
+        if (!a || !b || hipEventRecord(a, st) != hipSuccess) give_back();  // no timing for this launch
     }
     ~ProfScope() {
         if (!c->profiling || !a) return;
-        if (hipEventRecord(b, st) == hipSuccess) {
-            c->pending.push_back({a, b, kid});
-        } else {
-            c->pool.push_back(a);
-            c->pool.push_back(b);
-        }
+        if (hipEventRecord(b, st) == hipSuccess)
+            c->pending.push_back({std::move(a), std::move(b), kid});
+        else
+            give_back();
+    }
+    void give_back() {
+        if (a) c->pool.push_back(std::move(a));
+        if (b) c->pool.push_back(std::move(b));
     }
 };
 

@@ -171,7 +171,7 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
         // DIRECT) on a stream of their own, up to two steps behind the passes (psdr_set_post_chain drains: the chain has
         // been on for every batch since chain_seq started to count)
         if (c->post_on && c->post_direct && c->chain_seq >= 2 && c->pc_s[0] && c->side != c->stream)
-            HIPCHK(hipStreamWaitEvent(c->side, c->ev_pc[1][(c->chain_seq - 2) % psdr_ctx::PC_SETS], 0));
+            HIPCHK(hipStreamWaitEvent(c->side, c->pc.ev[1][(c->chain_seq - 2) % psdr_ctx::PC_SETS], 0));
     }
     HIPCHK(hipMemcpyAsync(d_clients, h_clients, c->post_on ? S * (sizeof(ClientParams) + sizeof(int)) : (size_t)nact * sizeof(ClientParams),
                           hipMemcpyHostToDevice, c->side));
@@ -335,9 +335,9 @@ extern "C" int psdr_fetch_begin(psdr_ctx *c, unsigned what) {
     if (want_audio && (F == 0 || c->demod_seq == 0)) return fail(PSDR_ERR_STATE, "no demodulated batch to fetch");
     if ((what & PSDR_FETCH_PCM) && !c->post_on) return fail(PSDR_ERR_STATE, "PSDR_FETCH_PCM: post chain not enabled (psdr_set_post_chain)");
     HIPCHK(hipSetDevice(c->device));
-    if (!c->fetch_stream) HIPCHK(hipStreamCreateWithFlags(&c->fetch_stream, hipStreamNonBlocking));
-    if ((what & PSDR_FETCH_PCM) && !c->fetch_stream_pcm) HIPCHK(hipStreamCreateWithFlags(&c->fetch_stream_pcm, hipStreamNonBlocking));
-    if (!c->ev_fetch_src) HIPCHK(hipEventCreateWithFlags(&c->ev_fetch_src, hipEventDisableTiming));
+    if (!c->fetch_stream) PSDRCHK(c->fetch_stream.create());
+    if ((what & PSDR_FETCH_PCM) && !c->fetch_stream_pcm) PSDRCHK(c->fetch_stream_pcm.create());
+    if (!c->ev_fetch_src) PSDRCHK(c->ev_fetch_src.create());
     psdr_ctx::FetchSet &fs = c->fset[c->fetch_fill];
     if (fs.inflight) {  // every set in flight: the oldest one has to land first (its results are given up: psdr_fetch_end was not called)
         HIPCHK(hipEventSynchronize(fs.done));
@@ -347,14 +347,12 @@ extern "C" int psdr_fetch_begin(psdr_ctx *c, unsigned what) {
     }
     if (c->fetch_cur == c->fetch_fill) c->fetch_cur = -1;  // its pointers die now
     // (each block on its own: a failed allocation leaves nothing half-initialised behind for the next call)
-    if (!fs.done) HIPCHK(hipEventCreateWithFlags(&fs.done, hipEventDisableTiming));
-    if (!fs.ev_wf) HIPCHK(hipEventCreateWithFlags(&fs.ev_wf, hipEventDisableTiming));
-    if (!fs.ev_audio) HIPCHK(hipEventCreateWithFlags(&fs.ev_audio, hipEventDisableTiming));
-    if (!fs.ev_pcm) HIPCHK(hipEventCreateWithFlags(&fs.ev_pcm, hipEventDisableTiming));
-    if (want_audio && !fs.pwr) HIPCHK(hipHostMalloc((void **)&fs.pwr, S * mb * sizeof(float), hipHostMallocDefault));
-    if (want_audio && !fs.nan) HIPCHK(hipHostMalloc((void **)&fs.nan, S * mb * sizeof(int32_t), hipHostMallocDefault));
-    if ((what & PSDR_FETCH_AUDIO) && !fs.audio) HIPCHK(hipHostMalloc((void **)&fs.audio, S * mb * h * sizeof(float), hipHostMallocDefault));
-    if ((what & PSDR_FETCH_PCM) && !fs.pcm) HIPCHK(hipHostMalloc((void **)&fs.pcm, S * mb * h * sizeof(int32_t), hipHostMallocDefault));
+    for (Event *e : {&fs.done, &fs.ev_wf, &fs.ev_audio, &fs.ev_pcm})
+        if (!*e) PSDRCHK(e->create());
+    if (want_audio && !fs.pwr) PSDRCHK(fs.pwr.alloc(S * mb));
+    if (want_audio && !fs.nan) PSDRCHK(fs.nan.alloc(S * mb));
+    if ((what & PSDR_FETCH_AUDIO) && !fs.audio) PSDRCHK(fs.audio.alloc(S * mb * h));
+    if ((what & PSDR_FETCH_PCM) && !fs.pcm) PSDRCHK(fs.pcm.alloc(S * mb * h));
     size_t wf_bytes = 0;
     {
         std::lock_guard<std::mutex> lk(c->mtx);
@@ -371,9 +369,7 @@ extern "C" int psdr_fetch_begin(psdr_ctx *c, unsigned what) {
                 if (w.active && w.nsent > 0) wf_bytes = std::max(wf_bytes, (w.out_off + (size_t)w.nsent * (size_t)(w.b_r - w.b_l) + 15) & ~(size_t)15);
     }
     if (wf_bytes > fs.wf_cap) {
-        if (fs.wf) HIPCHK(hipHostFree(fs.wf));
-        fs.wf = nullptr, fs.wf_cap = 0;
-        HIPCHK(hipHostMalloc((void **)&fs.wf, wf_bytes, hipHostMallocDefault));
+        PSDRCHK(fs.wf.alloc(wf_bytes));  // (the old rows are given up only once the new buffer exists)
         fs.wf_cap = wf_bytes;
     }
     hipStream_t fst = c->fetch_stream;
@@ -409,7 +405,7 @@ extern "C" int psdr_fetch_begin(psdr_ctx *c, unsigned what) {
         hipStream_t fsp = c->fetch_stream_pcm;
         HIPCHK(hipStreamWaitEvent(fsp, c->ev_fetch_src, 0));
         if (c->chain_seq > 0 && c->pc_s[0] && c->side != c->stream)
-            HIPCHK(hipStreamWaitEvent(fsp, c->ev_pc[3][(c->chain_seq - 1) % psdr_ctx::PC_SETS], 0));
+            HIPCHK(hipStreamWaitEvent(fsp, c->pc.ev[3][(c->chain_seq - 1) % psdr_ctx::PC_SETS], 0));
         // (PSDR_OPT_POST_CHAIN_PCM16: the rows are int16 - the same buffers, half the bytes)
         const size_t sb = c->pcm_is16 ? sizeof(int16_t) : sizeof(int32_t);
         fs.pcm16 = c->pcm_is16;
@@ -448,8 +444,6 @@ extern "C" int psdr_fetch_end(psdr_ctx *c) {
         if (c->guard_pcm[i] == fs.ev_pcm) c->guard_pcm[i] = nullptr;
     }
     c->fetch_cur = k;
-    // one-launch transforms: a flow-control timeout of the batches since the last synchronisation is reported by drain();
-    // a fetch does not drain (that is its point) - psdr_synchronize still does
     return PSDR_OK;
 }
 extern "C" int psdr_fetch_batch(psdr_ctx *c) {
@@ -526,7 +520,7 @@ extern "C" int psdr_fetched_pcm16(psdr_ctx *c, int id, int frame, const int16_t 
     }
     if (frame < 0 || frame >= fs->frames) return fail(PSDR_ERR_INVALID, "frame %d not in the fetched batch of %d", frame, fs->frames);
     const size_t h = (size_t)c->n / 2, mb = (size_t)c->max_batch, row = (size_t)id * mb + (size_t)frame;
-    *pcm = reinterpret_cast<const int16_t *>(fs->pcm) + row * h;
+    *pcm = reinterpret_cast<const int16_t *>(fs->pcm.get()) + row * h;
     return PSDR_OK;
 }
 extern "C" int psdr_fetched_waterfall(psdr_ctx *c, int id, const int8_t **rows, int *nsent_out, int *level_out, int *l_out, int *r_out) {

@@ -137,9 +137,9 @@ int seg_plan(psdr_ctx *c, int nframes, const psdr_ctx::SegPlan **out) {
     }
     if (sp.nseam > c->seam_cap || sp.nsegs > c->seg_cap)
         return fail(PSDR_ERR_STATE, "seam buffers too small (%u + %u segments, %zu + %zu allocated)", sp.nseam, sp.nsegs, c->seam_cap, c->seg_cap);
-    HIPCHK(hipMalloc((void **)&sp.d_tab, tab.size() * sizeof(uint4)));
+    PSDRCHK(sp.d_tab.alloc(tab.size()));
     HIPCHK(hipMemcpy(sp.d_tab, tab.data(), tab.size() * sizeof(uint4), hipMemcpyHostToDevice));  // (once per batch size)
-    c->seg_plans.push_back(sp);
+    c->seg_plans.push_back(std::move(sp));
     *out = &c->seg_plans.back();
     return PSDR_OK;
 }
@@ -286,14 +286,14 @@ int process_frames(psdr_ctx *c, const void *d_halves, int nframes, int fmt, hipE
     // (tuning builds only: a timing-only experiment with WRONG results - all frames of a launch share a few frames of Y)
     if (const char *e = psdr_tuning_env("PSDR_Y_ALIAS")) a1.ymask = (unsigned)atoi(e) - 1u;
     {
-        int rc = next_tickets(c, 0, c->p1, &a1.tickets);
+        int rc = next_tickets(c, 0, c->stream, &a1.tickets);
         if (rc) return rc;
     }
     a1.tiles_per_frame = tiles1;
     a1.total_slots = tiles1 * (unsigned)nframes;
     int rc = launch_pass1(c, c->M1, c->T1, sb, a1, a1.total_slots, c->real_fused);
     if (rc) return rc;
-    if (ev_raw_consumed) HIPCHK(hipEventRecord(ev_raw_consumed, c->p1));  // pass 1 is the only reader of the raw halves
+    if (ev_raw_consumed) HIPCHK(hipEventRecord(ev_raw_consumed, c->stream));  // pass 1 is the only reader of the raw halves
 
     Pass2Args a2{};
     a2.Y = Y;
@@ -461,13 +461,13 @@ extern "C" int psdr_get_output_buffer(psdr_ctx *c, float **out) {
     if (!c || !out) return fail(PSDR_ERR_INVALID, "null argument");
     HIPCHK(hipSetDevice(c->device));
     if (c->last_nframes > 0 && !c->out_valid) {
-        int rc = copy_spectrum_k_order(c, 0, (cf *)c->h_out);
+        int rc = copy_spectrum_k_order(c, 0, c->h_out);
         if (rc) return rc;
         if (!c->is_real && c->cfg.additional_size > 0)  // wrap copy, src/fft.cpp:91-98
-            memcpy((cf *)c->h_out + c->N, c->h_out, sizeof(cf) * (size_t)c->cfg.additional_size);
+            memcpy(c->h_out + c->N, c->h_out, sizeof(cf) * (size_t)c->cfg.additional_size);
         c->out_valid = true;
     }
-    *out = c->h_out;
+    *out = (float *)c->h_out.get();
     return PSDR_OK;
 }
 extern "C" int psdr_get_quantized_buffer(psdr_ctx *c, int8_t **out) {
@@ -527,20 +527,13 @@ extern "C" int psdr_set_band_layout(psdr_ctx *c, int nbands, uint32_t halo_bins)
     HIPCHK(hipDeviceSynchronize());
     const size_t F = (size_t)c->max_batch, fs = (size_t)c->M1 * Lw;
     {  // the new buffers first: a failed allocation leaves the context as it was
-        cf *fresh[2] = {nullptr, nullptr};
-        for (int s = 0; s < 2; s++) {
-            if (hipMalloc((void **)&fresh[s], (size_t)nbands * F * fs * sizeof(cf)) != hipSuccess ||
-                hipMemset(fresh[s], 0, (size_t)nbands * F * fs * sizeof(cf)) != hipSuccess) {
+        DevBuf<cf> fresh[2];
+        for (auto &f : fresh)
+            if (f.alloc((size_t)nbands * F * fs, true)) {
                 (void)hipGetLastError();
-                for (int t = 0; t <= s; t++)
-                    if (fresh[t]) (void)hipFree(fresh[t]);
                 return fail(PSDR_ERR_NOMEM, "banded spectrum: %zu bytes per result set", (size_t)nbands * F * fs * sizeof(cf));
             }
-        }
-        for (int s = 0; s < 2; s++) {
-            if (c->spec_pool[s]) (void)hipFree(c->spec_pool[s]);
-            c->spec_pool[s] = fresh[s];
-        }
+        for (int s = 0; s < 2; s++) c->spec_pool[s] = std::move(fresh[s]);
     }
     c->nbands = nbands;
     c->band_H = H;
@@ -730,15 +723,14 @@ extern "C" int psdr_waterfall_batch(psdr_ctx *c, uint64_t first_frame_num) {
             if ((c->wf_lenA & 15) || (c->qt_stride & 15) || qB1 > c->q_stride)
                 return fail(PSDR_ERR_UNSUPPORTED, "waterfall detectors: record buffers of %zu / %zu bytes per frame", c->qt_stride, c->q_stride);
             const size_t len = c->wf_lenA + c->wf_lenB;
-            int8_t *pk = nullptr;
-            uint32_t *sm = nullptr;
-            if (hipMalloc((void **)&pk, len) != hipSuccess || hipMalloc((void **)&sm, len * sizeof(uint32_t)) != hipSuccess) {
+            DevBuf<int8_t> pk;
+            DevBuf<uint32_t> sm;
+            if (pk.alloc(len) || sm.alloc(len)) {
                 (void)hipGetLastError();
-                if (pk) (void)hipFree(pk);
                 return fail(PSDR_ERR_NOMEM, "waterfall detectors: carry of %zu bytes", len * 5);
             }
-            c->d_wf_peak = pk;
-            c->d_wf_sum = sm;
+            c->d_wf_peak = std::move(pk);
+            c->d_wf_sum = std::move(sm);
         }
         ha.Q = c->d_q;
         ha.Qt = c->d_qt;
@@ -755,9 +747,7 @@ extern "C" int psdr_waterfall_batch(psdr_ctx *c, uint64_t first_frame_num) {
     }
     if (gather) {
         if (total > c->wfout_cap) {
-            if (c->d_wfout) HIPCHK(hipFree(c->d_wfout));
-            c->d_wfout = nullptr;
-            HIPCHK(hipMalloc((void **)&c->d_wfout, total));
+            PSDRCHK(c->d_wfout.alloc(total));  // (the old rows are given up only once the new buffer exists)
             c->wfout_cap = total;
         }
         {  // d_wfout exists once: a result fetch in flight (psdr_fetch_begin) reads it first

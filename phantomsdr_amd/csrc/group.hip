@@ -80,26 +80,26 @@ struct psdr_group {
     bool peer_copy = false;         // PSDR_SHARD_PEER_COPY: peers pull with hipMemcpyPeerAsync instead
     std::mutex mtx;                 // the client table, next_rr, and every enqueue on the ranks' streams
     std::vector<GroupClient> clients;  // gid -> (rank, slot): the gid a caller holds never changes
-    std::vector<hipEvent_t> ev_rank;   // per rank, on its device: migration hand-over / peer copy done
-    std::vector<hipEvent_t> ev_t0, ev_t1;  // peer copy: the copy's own duration on the peer's stream
-    hipEvent_t ev_x = nullptr;         // the root's data of this step is ready (peer copy; overlapped exchange)
+    std::vector<Event> ev_rank;        // per rank, on its device: migration hand-over / peer copy done
+    std::vector<Event> ev_t0, ev_t1;   // peer copy: the copy's own duration on the peer's stream
+    Event ev_x;                        // the root's data of this step is ready (peer copy; overlapped exchange)
     bool copies_pending = false;       // peer copy: ev_rank[r] of the last step not yet waited for by the root
     // The exchange of batch b beside the root's transform of batch b + 1 (PSDR_SHARD_CLIENTS, banded PSDR_SHARD_BAND): the
     // root alternates its two result sets (psdr_ctx::alt_sets) and issues ITS side of the collective on a stream of its
     // own (`xs`), behind ev_x; what it waits for - before it overwrites a set two steps later - is that set's exchange
     // (ev_xdone[set]; peer copies: ev_pull[set][r], recorded by the peers).  PSDR_SHARD_SERIAL switches it off (A/B, tests).
     bool overlap = false;
-    hipStream_t xs = nullptr;
-    hipEvent_t ev_xdone[2] = {nullptr, nullptr};
+    Stream xs;
+    Event ev_xdone[2];
     bool xpending[2] = {false, false};
-    std::vector<hipEvent_t> ev_pull[2];
+    std::vector<Event> ev_pull[2];
     std::vector<int> dev;
     std::vector<psdr_ctx *> ctx;
-    std::vector<hipStream_t> st;    // the one stream per device everything of that rank is ordered on
+    std::vector<Stream> st;         // the one stream per device everything of that rank is ordered on
     std::vector<ncclComm_t> comm;
-    std::vector<void *> rbuf;       // per rank: receive buffer (raw halves / band region), nullptr where unused
+    std::vector<DevBuf<unsigned char>> rbuf;  // per rank: receive buffer (raw halves / band region), nullptr where unused
     size_t rbuf_bytes = 0;
-    std::vector<void *> sbuf;       // band sharding with the pack pass: the root's send buffers, one per band
+    std::vector<DevBuf<cf>> sbuf;   // band sharding with the pack pass: the root's send buffers, one per band
     // band sharding
     bool banded = false;            // the root writes band regions itself (no pack)
     uint32_t band_first[16] = {0}, band_bins[16] = {0};
@@ -107,7 +107,7 @@ struct psdr_group {
     int next_rr = 0;                // round-robin cursor of psdr_group_client_add
     // link accounting
     double link_bytes = 0;          // bytes that crossed ONE link (root -> one peer) in the last step
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Event ev0, ev1;
     bool timed = false;
     uint64_t steps = 0;
 };
@@ -143,24 +143,10 @@ extern "C" void psdr_group_destroy(psdr_group *g) {
             psdr_set_stream(g->ctx[r], nullptr);
         }
         if (r < (int)g->comm.size() && g->comm[r]) g_rccl.CommDestroy(g->comm[r]);
-        if (r < (int)g->rbuf.size() && g->rbuf[r]) hipFree(g->rbuf[r]);
-        if (r == 0)
-            for (void *p : g->sbuf)
-                if (p) hipFree(p);
-        if (r == 0 && g->ev0) hipEventDestroy(g->ev0), hipEventDestroy(g->ev1);
-        if (r == 0 && g->ev_x) hipEventDestroy(g->ev_x);
-        if (r == 0)
-            for (hipEvent_t e : g->ev_xdone)
-                if (e) hipEventDestroy(e);
-        for (auto &v : g->ev_pull)
-            if (r < (int)v.size() && v[r]) hipEventDestroy(v[r]);
-        if (r == 0 && g->xs) hipStreamDestroy(g->xs);
-        if (r < (int)g->ev_rank.size() && g->ev_rank[r]) hipEventDestroy(g->ev_rank[r]);
-        if (r < (int)g->ev_t0.size() && g->ev_t0[r]) hipEventDestroy(g->ev_t0[r]), hipEventDestroy(g->ev_t1[r]);
         if (g->ctx[r]) psdr_destroy(g->ctx[r]);
-        if (r < (int)g->st.size() && g->st[r]) hipStreamDestroy(g->st[r]);
+        if (r < (int)g->st.size()) g->st[r].reset();  // (behind the context that was ordered on it)
     }
-    delete g;
+    delete g;  // (the buffers, the events and the exchange stream go with their members)
 }
 
 extern "C" int psdr_group_create(const psdr_config *cfg, const int *devices, int ndevices, int shard, psdr_group **out) {
@@ -184,12 +170,12 @@ extern "C" int psdr_group_create(const psdr_config *cfg, const int *devices, int
     g->comm_on = !peer_copy && (ndevices > 1 || force_comm);
     g->dev.assign(devices, devices + ndevices);
     g->ctx.assign(ndevices, nullptr);
-    g->st.assign(ndevices, nullptr);
+    g->st.resize(ndevices);
     g->comm.assign(ndevices, nullptr);
-    g->rbuf.assign(ndevices, nullptr);
-    g->ev_rank.assign(ndevices, nullptr);
-    g->ev_t0.assign(ndevices, nullptr);
-    g->ev_t1.assign(ndevices, nullptr);
+    g->rbuf.resize(ndevices);
+    g->ev_rank.resize(ndevices);
+    g->ev_t0.resize(ndevices);
+    g->ev_t1.resize(ndevices);
     auto bail = [&](int rc) {
         const std::string msg = psdr_last_error();  // (the clean-up below must not overwrite it)
         psdr_group_destroy(g);
@@ -200,15 +186,14 @@ extern "C" int psdr_group_create(const psdr_config *cfg, const int *devices, int
         c.device = devices[r];
         int rc = psdr_create(&c, &g->ctx[r]);
         if (rc) return bail(rc);
-        if (hipSetDevice(devices[r]) != hipSuccess || hipStreamCreateWithFlags(&g->st[r], hipStreamNonBlocking) != hipSuccess) {
+        if (hipSetDevice(devices[r]) != hipSuccess || g->st[r].create()) {
             fail(PSDR_ERR_HIP, "stream creation on device %d failed", devices[r]);
             return bail(PSDR_ERR_HIP);
         }
         rc = psdr_set_stream(g->ctx[r], g->st[r]);
         if (rc) return bail(rc);
         // (events belong to the device that is current when they are created)
-        if (hipEventCreateWithFlags(&g->ev_rank[r], hipEventDisableTiming) != hipSuccess || hipEventCreate(&g->ev_t0[r]) != hipSuccess ||
-            hipEventCreate(&g->ev_t1[r]) != hipSuccess) {
+        if (g->ev_rank[r].create() || g->ev_t0[r].create_timing() || g->ev_t1[r].create_timing()) {
             fail(PSDR_ERR_HIP, "event creation on device %d failed", devices[r]);
             return bail(PSDR_ERR_HIP);
         }
@@ -232,7 +217,7 @@ extern "C" int psdr_group_create(const psdr_config *cfg, const int *devices, int
     if (shard == PSDR_SHARD_RAW) {
         g->rbuf_bytes = (F + 1) * psdr_half_frame_bytes(c0);
         for (int r = 1; r < ndevices; r++) {
-            if (hipSetDevice(devices[r]) != hipSuccess || hipMalloc(&g->rbuf[r], g->rbuf_bytes) != hipSuccess) {
+            if (hipSetDevice(devices[r]) != hipSuccess || g->rbuf[r].alloc(g->rbuf_bytes)) {
                 fail(PSDR_ERR_NOMEM, "raw receive buffer of %zu bytes on device %d", g->rbuf_bytes, devices[r]);
                 return bail(PSDR_ERR_NOMEM);
             }
@@ -255,12 +240,12 @@ extern "C" int psdr_group_create(const psdr_config *cfg, const int *devices, int
             const uint32_t cnt = (uint32_t)std::min(per + 1 + halo, R);
             g->band_stride = cnt;
             for (int b = 0; b < ndevices; b++) g->band_first[b] = (uint32_t)((size_t)b * (R / (size_t)ndevices)), g->band_bins[b] = cnt;
-            g->sbuf.assign(ndevices, nullptr);
+            g->sbuf.resize(ndevices);
             // (one device with the collectives forced: band 0 - the whole spectrum - is packed, sent to and received from
             // oneself and demodulated from the received buffer, so that the pack + ncclSend / ncclRecv + band demodulation
             // path runs on a single-GPU box)
             for (int b = (ndevices == 1 && g->comm_on) ? 0 : 1; b < ndevices; b++) {
-                if (hipSetDevice(devices[0]) != hipSuccess || hipMalloc(&g->sbuf[b], F * g->band_stride * sizeof(cf)) != hipSuccess) {
+                if (hipSetDevice(devices[0]) != hipSuccess || g->sbuf[b].alloc(F * g->band_stride)) {
                     fail(PSDR_ERR_NOMEM, "band send buffer of %zu bytes", F * g->band_stride * sizeof(cf));
                     return bail(PSDR_ERR_NOMEM);
                 }
@@ -268,14 +253,13 @@ extern "C" int psdr_group_create(const psdr_config *cfg, const int *devices, int
         }
         g->rbuf_bytes = F * g->band_stride * sizeof(cf);
         for (int r = (ndevices == 1 && g->comm_on) ? 0 : 1; r < ndevices; r++) {
-            if (hipSetDevice(devices[r]) != hipSuccess || hipMalloc(&g->rbuf[r], g->rbuf_bytes) != hipSuccess) {
+            if (hipSetDevice(devices[r]) != hipSuccess || g->rbuf[r].alloc(g->rbuf_bytes)) {
                 fail(PSDR_ERR_NOMEM, "band receive buffer of %zu bytes on device %d", g->rbuf_bytes, devices[r]);
                 return bail(PSDR_ERR_NOMEM);
             }
         }
     }
-    if (hipSetDevice(devices[0]) != hipSuccess || hipEventCreate(&g->ev0) != hipSuccess || hipEventCreate(&g->ev1) != hipSuccess ||
-        hipEventCreateWithFlags(&g->ev_x, hipEventDisableTiming) != hipSuccess) {
+    if (hipSetDevice(devices[0]) != hipSuccess || g->ev0.create_timing() || g->ev1.create_timing() || g->ev_x.create()) {
         fail(PSDR_ERR_HIP, "event creation failed");
         return bail(PSDR_ERR_HIP);
     }
@@ -283,11 +267,11 @@ extern "C" int psdr_group_create(const psdr_config *cfg, const int *devices, int
     g->overlap = !serial && (g->comm_on || g->peer_copy) && (shard == PSDR_SHARD_CLIENTS || (shard == PSDR_SHARD_BAND && g->banded));
     if (g->overlap) {
         c0->alt_sets = true;
-        bool ok = hipStreamCreateWithFlags(&g->xs, hipStreamNonBlocking) == hipSuccess;
-        for (hipEvent_t &e : g->ev_xdone) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+        bool ok = !g->xs.create();
+        for (Event &e : g->ev_xdone) ok = ok && !e.create();
         for (auto &v : g->ev_pull) {
-            v.assign(ndevices, nullptr);
-            for (int r = 1; r < ndevices && ok; r++) ok = hipSetDevice(devices[r]) == hipSuccess && hipEventCreateWithFlags(&v[r], hipEventDisableTiming) == hipSuccess;
+            v.resize(ndevices);
+            for (int r = 1; r < ndevices && ok; r++) ok = hipSetDevice(devices[r]) == hipSuccess && !v[r].create();
         }
         if (!ok) {
             fail(PSDR_ERR_HIP, "exchange stream / events could not be created");
@@ -438,7 +422,7 @@ static int group_step(psdr_group *g, const void *raw_root, uint64_t first_half, 
     };
     // ... and the pull itself: peer r copies `bytes` from the root's src[r] into dst[r] on ITS OWN stream, behind the
     // root's "data ready" event - n - 1 independent copies, one per root -> peer link
-    auto peers_pull = [&](const std::vector<const void *> &src, const std::vector<void *> &dst, size_t bytes) -> int {
+    auto peers_pull = [&](const std::vector<const void *> &src, const auto &dst, size_t bytes) -> int {
         HIPCHK(hipSetDevice(g->dev[0]));
         HIPCHK(hipEventRecord(g->ev_x, g->st[0]));
         for (int r = 1; r < g->n; r++) {
@@ -486,7 +470,7 @@ static int group_step(psdr_group *g, const void *raw_root, uint64_t first_half, 
         g->link_bytes = bytes;
         return PSDR_OK;
     };
-    auto peers_pull_set = [&](int set, const std::vector<const void *> &src, const std::vector<void *> &dst, size_t bytes) -> int {
+    auto peers_pull_set = [&](int set, const std::vector<const void *> &src, const auto &dst, size_t bytes) -> int {
         HIPCHK(hipSetDevice(g->dev[0]));
         HIPCHK(hipEventRecord(g->ev_x, g->st[0]));
         for (int r = 1; r < g->n; r++) {
@@ -606,16 +590,16 @@ static int group_step(psdr_group *g, const void *raw_root, uint64_t first_half, 
                 if (g->banded) {
                     rc = psdr_band_region(c0, b, &send[b], nullptr, nullptr, nullptr);  // the region of THIS batch (the sets alternate)
                 } else {
-                    rc = psdr_pack_band(c0, nframes, g->band_first[b], g->band_bins[b], (float *)g->sbuf[b], g->band_stride);
-                    send[b] = (const float *)g->sbuf[b];
+                    rc = psdr_pack_band(c0, nframes, g->band_first[b], g->band_bins[b], (float *)g->sbuf[b].get(), g->band_stride);
+                    send[b] = (const float *)g->sbuf[b].get();
                 }
                 if (rc) return rc;
             }
             const bool self_loop = g->comm_on && g->n == 1;  // forced on one device: band 0 goes through RCCL to oneself
             if (self_loop) {
-                rc = psdr_pack_band(c0, nframes, g->band_first[0], g->band_bins[0], (float *)g->sbuf[0], g->band_stride);
+                rc = psdr_pack_band(c0, nframes, g->band_first[0], g->band_bins[0], (float *)g->sbuf[0].get(), g->band_stride);
                 if (rc) return rc;
-                send[0] = (const float *)g->sbuf[0];
+                send[0] = (const float *)g->sbuf[0].get();
             }
             if (g->comm_on) {
                 hipStream_t s0 = g->overlap ? g->xs : g->st[0];  // (overlap: banded regions only - they alternate with the result sets)
@@ -650,12 +634,12 @@ static int group_step(psdr_group *g, const void *raw_root, uint64_t first_half, 
                 if (rc) return rc;
             }
             // the root's own clients read its spectrum through SpecLayout::pos (self_loop: the band buffer that came back)
-            rc = self_loop ? psdr_demod_batch_from_band(c0, (const float *)g->rbuf[0], g->band_stride, g->band_first[0], g->band_bins[0], nframes, first_frame_num)
+            rc = self_loop ? psdr_demod_batch_from_band(c0, (const float *)g->rbuf[0].get(), g->band_stride, g->band_first[0], g->band_bins[0], nframes, first_frame_num)
                            : psdr_demod_batch(c0, first_frame_num);
             if (rc) return rc;
             for (int b = 1; b < g->n; b++) {
-                rc = g->banded ? psdr_demod_batch_from_band_region(g->ctx[b], (const float *)g->rbuf[b], g->band_stride, g->band_first[b], g->band_bins[b], nframes, first_frame_num)
-                               : psdr_demod_batch_from_band(g->ctx[b], (const float *)g->rbuf[b], g->band_stride, g->band_first[b], g->band_bins[b], nframes, first_frame_num);
+                rc = g->banded ? psdr_demod_batch_from_band_region(g->ctx[b], (const float *)g->rbuf[b].get(), g->band_stride, g->band_first[b], g->band_bins[b], nframes, first_frame_num)
+                               : psdr_demod_batch_from_band(g->ctx[b], (const float *)g->rbuf[b].get(), g->band_stride, g->band_first[b], g->band_bins[b], nframes, first_frame_num);
                 if (rc) return rc;
             }
         }

@@ -13,10 +13,10 @@ static int launch_pass1_k(psdr_ctx *c, K kern, int L, int T, size_t lds, const P
     // (per context = per device: the attribute is a property of the function ON a device)
     if (c->lds_attr_done.insert((const void *)kern).second)
         HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P1_LDS_MAX));
-    ProfScope ps(c, K_PASS1, c->p1);
+    ProfScope ps(c, K_PASS1, c->stream);
     // persistent: as many work-groups per CU as their LDS admits (a 128 KiB tile: one)
     const unsigned grid = persistent_grid(c, blocks, lds);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(L * T / 32), lds, c->p1, a);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(L * T / 32), lds, c->stream, a);
     HIPCHK(hipGetLastError());
     return PSDR_OK;
 }

@@ -23,9 +23,9 @@ __global__ void k_pc_spin(unsigned long long ticks) {
 __global__ void k_pc_nop() {}
 
 int pc_launch_gap_us(psdr_ctx *c, hipStream_t cand, hipStream_t on, double *us) {
-    hipEvent_t a, b;
-    HIPCHK(hipEventCreate(&a));
-    HIPCHK(hipEventCreate(&b));
+    Event a, b;
+    PSDRCHK(a.create_timing());
+    PSDRCHK(b.create_timing());
     const unsigned long long ticks = (unsigned long long)(c->wall_clock_khz * 2.0);  // 2 ms
     hipLaunchKernelGGL(k_pc_spin, dim3(1), dim3(64), 0, cand, ticks);
     HIPCHK(hipEventRecord(a, on));
@@ -35,8 +35,6 @@ int pc_launch_gap_us(psdr_ctx *c, hipStream_t cand, hipStream_t on, double *us) 
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, a, b));
     HIPCHK(hipStreamSynchronize(cand));
-    hipEventDestroy(a);
-    hipEventDestroy(b);
     *us = ms * 1e3 / 16.0;
     return PSDR_OK;
 }
@@ -58,18 +56,9 @@ int pc_pick_streams(psdr_ctx *c) {
     constexpr int NC = 6;
     int lo = 0, hi = 0;
     HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    hipStream_t cand[NC] = {};
+    Stream cand[NC];  // (the three chosen are moved into the context at the end; the others, or all on an error path, die here)
     double gap[NC] = {};
-    struct Guard {  // an error path leaves no candidate stream behind
-        hipStream_t *c;
-        bool keep = false;
-        ~Guard() {
-            if (!keep)
-                for (int i = 0; i < NC; i++)
-                    if (c[i]) hipStreamDestroy(c[i]);
-        }
-    } guard{cand};
-    for (hipStream_t &st : cand) HIPCHK(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, hi));
+    for (Stream &st : cand) PSDRCHK(st.create(hi));
     hipLaunchKernelGGL(k_pc_nop, dim3(1), dim3(64), 0, c->stream);  // (code objects loaded, queues created)
     if (c->side != c->stream) hipLaunchKernelGGL(k_pc_nop, dim3(1), dim3(64), 0, c->side);
     for (hipStream_t st : cand) hipLaunchKernelGGL(k_pc_spin, dim3(1), dim3(64), 0, st, 1ull);
@@ -134,12 +123,9 @@ int pc_pick_streams(psdr_ctx *c) {
         for (int i = 0; i < NC; i++) fprintf(stderr, " %.1f/%.1f", gap[i], gside[i]);
         fprintf(stderr, " -> streams %d and %d\n", first, second);
     }
-    c->pc_s[0] = cand[first];
-    c->pc_s[2] = cand[second];
-    c->pc_s[1] = cand[third];
-    guard.keep = true;
-    for (int i = 0; i < NC; i++)
-        if (i != first && i != second && i != third) hipStreamDestroy(cand[i]);
+    c->pc_s[0] = std::move(cand[first]);
+    c->pc_s[2] = std::move(cand[second]);
+    c->pc_s[1] = std::move(cand[third]);
     return PSDR_OK;
 }
 }  // namespace
@@ -187,20 +173,12 @@ extern "C" int psdr_set_post_chain(psdr_ctx *c, int enable) {
         return PSDR_OK;
     }
     if (!c->post_ready) {
-        // (one-time set-up; `post_ready` is raised only when EVERY allocation and the stream choice went through - a failure
-        // half-way gives everything back, so a retry starts from scratch instead of running the chain on null pointers)
-        auto undo = [&]() {
-            for (void *q : c->post_allocs) hipFree(q);
-            c->post_allocs.clear();
-            c->post = PostArgs{};
-            c->pcm_pool[0] = c->pcm_pool[1] = nullptr;
-            for (int i = 0; i < psdr_ctx::PC_SETS; i++)
-                c->post_fstart[i] = c->post_len[i] = c->post_falive[i] = nullptr, c->post_x[i] = c->post_m1[i] = c->post_v1[i] = c->post_p[i] = c->post_s[i] = c->post_sm[i] = c->post_cm[i] = c->post_cp[i] = c->post_cs[i] = nullptr;
-            c->post_agc_ok = false;
-        };
+        // (one-time set-up, built in locals and moved into the context only when EVERY allocation and the stream choice went
+        // through: a failure half-way leaves the context as it was, and a retry starts from scratch)
         const int rate = c->cfg.audio_rate;
         if (rate < 750) return fail(PSDR_ERR_INVALID, "audio_rate %d too small for the DC blocker", rate);
-        PostArgs &a = c->post;
+        PostArgs a{};
+        psdr_ctx::PostChain pc;
         const size_t S = c->aslots.size(), h = (size_t)c->n / 2, Tm = (size_t)c->max_batch * h;
         a.max_batch = c->max_batch;
         a.h = (int)h;
@@ -217,12 +195,6 @@ extern "C" int psdr_set_post_chain(psdr_ctx *c, int enable) {
         // k_pc_prefix / k_pc_want walk it in 256-row pieces)
         if (a.D < 1 || a.L < 2 || a.D > 12288)
             return fail(PSDR_ERR_UNSUPPORTED, "audio_rate %d: DC delay %d / look-ahead %d unsupported", rate, a.D, a.L);
-        auto alloc = [&](void **ptr, size_t bytes) -> int {
-            HIPCHK(hipMalloc(ptr, std::max<size_t>(bytes, 16)));
-            c->post_allocs.push_back(*ptr);
-            HIPCHK(hipMemset(*ptr, 0, std::max<size_t>(bytes, 16)));
-            return PSDR_OK;
-        };
         // lane-interleaved streams (postchain.h): pitches are multiples of 4 floats per slot, + padding for the
         // blocked kernels' look-ahead; a block of 64 slots is allocated whole
         const size_t S64 = (S + 63) / 64 * 64;
@@ -236,41 +208,40 @@ extern "C" int psdr_set_post_chain(psdr_ctx *c, int enable) {
         const size_t nblk = (((size_t)a.L - 1 + Tm) + a.L - 1) / a.L;
         // the AGC in one kernel (postchain.h k_pc_agc): whole chunks of 16 floats must line up with sample 0's row and with the
         // row groups of a frame; stream position / h by one 32-bit multiplication
-        c->post_agc_ok = (a.L % 16) == 0 && a.L >= 32 && a.vo == 1 && (h % 4) == 0 && h >= 16 && (a.D % 4) == 0 && (Tm + 4096) * h < ((size_t)1 << 32);
+        const bool agc_ok = (a.L % 16) == 0 && a.L >= 32 && a.vo == 1 && (h % 4) == 0 && h >= 16 && (a.D % 4) == 0 && (Tm + 4096) * h < ((size_t)1 << 32);
         a.nch = (int)((size_t)a.L / 16 + (Tm + 15) / 16 + 8);
         a.h_magic = (unsigned)((((uint64_t)1 << 32) + h - 1) / h);
         int rc = 0;
         for (int i = 0; i < psdr_ctx::PC_SETS && !rc; i++) {
-            rc = alloc((void **)&c->post_fstart[i], S * c->max_batch * sizeof(int));
-            if (!rc) rc = alloc((void **)&c->post_len[i], S * sizeof(int));
-            if (!rc) rc = alloc((void **)&c->post_x[i], a.px * S64 * sizeof(float));
-            if (!rc) rc = alloc((void **)&c->post_m1[i], a.px * S64 * sizeof(float));
-            if (!rc) rc = alloc((void **)&c->post_v1[i], a.pv * S64 * sizeof(float));
-            if (!rc) rc = alloc((void **)&c->post_p[i], a.pv * S64 * sizeof(float));
-            if (!rc) rc = alloc((void **)&c->post_s[i], a.pv * S64 * sizeof(float));
-            if (!rc) rc = alloc((void **)&c->post_sm[i], S64 * nblk * a.nsub * sizeof(float));
-            if (c->post_agc_ok) {
-                if (!rc) rc = alloc((void **)&c->post_cm[i], S64 * a.nch * sizeof(float));
-                if (!rc) rc = alloc((void **)&c->post_cp[i], S64 * a.nch * sizeof(float));
-                if (!rc) rc = alloc((void **)&c->post_cs[i], S64 * a.nch * sizeof(float));
-                if (!rc) rc = alloc((void **)&c->post_falive[i], S64 * c->max_batch * sizeof(int));
+            rc = pc.fstart[i].alloc(S * c->max_batch, true);
+            if (!rc) rc = pc.len[i].alloc(S, true);
+            if (!rc) rc = pc.x[i].alloc(a.px * S64, true);
+            if (!rc) rc = pc.m1[i].alloc(a.px * S64, true);
+            if (!rc) rc = pc.v1[i].alloc(a.pv * S64, true);
+            if (!rc) rc = pc.p[i].alloc(a.pv * S64, true);
+            if (!rc) rc = pc.s[i].alloc(a.pv * S64, true);
+            if (!rc) rc = pc.sm[i].alloc(S64 * nblk * a.nsub, true);
+            if (agc_ok) {
+                if (!rc) rc = pc.cm[i].alloc(S64 * a.nch, true);
+                if (!rc) rc = pc.cp[i].alloc(S64 * a.nch, true);
+                if (!rc) rc = pc.cs[i].alloc(S64 * a.nch, true);
+                if (!rc) rc = pc.falive[i].alloc(S64 * c->max_batch, true);
             }
-            for (auto &stage : c->ev_pc)
-                if (!rc && !stage[i] && hipEventCreateWithFlags(&stage[i], hipEventDisableTiming) != hipSuccess)
-                    rc = fail(PSDR_ERR_HIP, "post chain: event creation failed");
+            for (auto &stage : pc.ev)
+                if (!rc) rc = stage[i].create();
         }
-        for (int k = 0; k < 2 && !rc; k++) rc = alloc((void **)&c->pcm_pool[k], S * Tm * sizeof(int32_t));
-        a.pcm = c->pcm_pool[0];
-        if (!rc) rc = alloc((void **)&a.pcm_dump, 64 * (1 + PC_AGC_NP) * 16);
-        if (!rc) rc = alloc((void **)&a.dc_s1, S * sizeof(float));
-        if (!rc) rc = alloc((void **)&a.dc_s2, S * sizeof(float));
-        if (!rc) rc = alloc((void **)&a.agc_gain, S * sizeof(float));
-        if (!rc) rc = alloc((void **)&a.agc_n0, S * sizeof(int));
+        for (int k = 0; k < 2 && !rc; k++) rc = pc.pcm_pool[k].alloc(S * Tm, true);
+        if (!rc) rc = pc.pcm_dump.alloc(64 * (1 + PC_AGC_NP) * 16 / sizeof(int32_t), true);
+        if (!rc) rc = pc.dc_s1.alloc(S, true);
+        if (!rc) rc = pc.dc_s2.alloc(S, true);
+        if (!rc) rc = pc.agc_gain.alloc(S, true);
+        if (!rc) rc = pc.agc_n0.alloc(S, true);
         if (rc) {
             const std::string msg = psdr_last_error();
-            undo();
             return fail(rc == PSDR_ERR_HIP ? PSDR_ERR_NOMEM : rc, "post chain set-up: %s", msg.c_str());
         }
+        a.pcm = pc.pcm_pool[0];
+        a.pcm_dump = pc.pcm_dump, a.dc_s1 = pc.dc_s1, a.dc_s2 = pc.dc_s2, a.agc_gain = pc.agc_gain, a.agc_n0 = pc.agc_n0;
         // The chain's streams (only a context that owns its side stream pipelines the chain: with a caller's stream - group
         // members - everything rides on that one stream and no chain stream is made).  PSDR_OPT_POST_CHAIN_STREAMS:
         //   0 (default)  three streams in creation order, the first and the third used: deterministic; the FIRST context of a
@@ -281,27 +252,18 @@ extern "C" int psdr_set_post_chain(psdr_ctx *c, int enable) {
         if (!c->pc_s[0] && c->side != c->stream) {
             int pick = c->opt_pc_streams;
             if (const char *e = psdr_tuning_env("PSDR_PC_PICK")) pick = atoi(e) != 0;  // (tuning build)
-            if (pick && pc_pick_streams(c) != PSDR_OK) {
-                for (hipStream_t &st : c->pc_s) {
-                    if (st) hipStreamDestroy(st);
-                    st = nullptr;
-                }
-            }
+            if (pick) (void)pc_pick_streams(c);  // (sets pc_s only when the whole measurement went through)
             if (!c->pc_s[0]) {
                 int lo = 0, hi = 0;
-                hipError_t e = hipDeviceGetStreamPriorityRange(&lo, &hi);
-                for (hipStream_t &st : c->pc_s)
-                    if (e == hipSuccess) e = hipStreamCreateWithPriority(&st, hipStreamNonBlocking, hi);
-                if (e != hipSuccess) {
-                    for (hipStream_t &st : c->pc_s) {
-                        if (st) hipStreamDestroy(st);
-                        st = nullptr;
-                    }
-                    undo();
-                    return fail(PSDR_ERR_HIP, "post chain: stream creation failed: %s", hipGetErrorString(e));
-                }
+                Stream s3[3];
+                if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess || s3[0].create(hi) || s3[1].create(hi) || s3[2].create(hi))
+                    return fail(PSDR_ERR_HIP, "post chain: stream creation failed");
+                for (int i = 0; i < 3; i++) c->pc_s[i] = std::move(s3[i]);
             }
         }
+        c->pc = std::move(pc);
+        c->post = a;
+        c->post_agc_ok = agc_ok;
         c->post_ready = true;
     }
     {
@@ -364,7 +326,7 @@ int psdr::post_chain_enqueue(psdr_ctx *c, const ClientParams *d_clients, const i
     bool ma_cmw = false;  // (set below, once the work-group count is known)
     // this batch's PCM goes to the other of two buffers (the copy of the last batch's to the host may still read its own)
     c->pcm_set ^= 1;
-    c->post.pcm = c->pcm_pool[c->pcm_set];
+    c->post.pcm = c->pc.pcm_pool[c->pcm_set];
     PostArgs pa = c->post;
     pa.pcm16 = c->opt_pc_pcm16;
     c->pcm_is16 = pa.pcm16 != 0;
@@ -374,16 +336,16 @@ int psdr::post_chain_enqueue(psdr_ctx *c, const ClientParams *d_clients, const i
     pa.slot_ci = d_slot_ci;
     pa.nact = nact + npaused;
     pa.nframes = nframes;
-    pa.X = c->post_x[set], pa.Xn = c->post_x[nxt];
-    pa.M1 = c->post_m1[set], pa.M1n = c->post_m1[nxt];
-    pa.V1 = c->post_v1[set], pa.V1n = c->post_v1[nxt];
-    pa.P = c->post_p[set];
-    pa.S = c->post_s[set];
-    pa.SM = c->post_sm[set];
-    pa.fstart = c->post_fstart[set];
-    pa.len = c->post_len[set];
-    pa.CM = c->post_cm[set], pa.CP = c->post_cp[set], pa.CS = c->post_cs[set];
-    pa.falive = c->post_falive[set];
+    pa.X = c->pc.x[set], pa.Xn = c->pc.x[nxt];
+    pa.M1 = c->pc.m1[set], pa.M1n = c->pc.m1[nxt];
+    pa.V1 = c->pc.v1[set], pa.V1n = c->pc.v1[nxt];
+    pa.P = c->pc.p[set];
+    pa.S = c->pc.s[set];
+    pa.SM = c->pc.sm[set];
+    pa.fstart = c->pc.fstart[set];
+    pa.len = c->pc.len[set];
+    pa.CM = c->pc.cm[set], pa.CP = c->pc.cp[set], pa.CS = c->pc.cs[set];
+    pa.falive = c->pc.falive[set];
     pa.ma_fused = pa.D == 32 ? 1 : 0;  // both averages in one loop (postchain.h)
     // ... which may read the demodulator's rows themselves instead of a gathered copy (k_pc_ma2 DIRECT; part of the round-6
     // form of the chain, PSDR_OPT_POST_CHAIN_AGC = 1; the demodulation two batches on waits for this batch's stage 1: demod.hip)
@@ -409,11 +371,11 @@ int psdr::post_chain_enqueue(psdr_ctx *c, const ClientParams *d_clients, const i
     //   d_audio[b mod 2] (DIRECT)             demodulation(b) <- averages / history of batch b - 2 (the wait is in demod.hip)
     // i.e. a stage waits for its predecessor of THIS batch and for the output stage of the batch that had the set.
     auto wait = [&](hipStream_t st, int stage, int which) -> int {
-        if (piped) HIPCHK(hipStreamWaitEvent(st, c->ev_pc[stage][which], 0));
+        if (piped) HIPCHK(hipStreamWaitEvent(st, c->pc.ev[stage][which], 0));
         return PSDR_OK;
     };
     auto done = [&](hipStream_t st, int stage) -> int {
-        if (piped) HIPCHK(hipEventRecord(c->ev_pc[stage][set], st));
+        if (piped) HIPCHK(hipEventRecord(c->pc.ev[stage][set], st));
         return PSDR_OK;
     };
     int rc = 0;
