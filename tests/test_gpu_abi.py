@@ -109,18 +109,17 @@ def test_waterfall_size_is_min_waterfall_fft(ws):
         ctx.close()
 
 
-@pytest.mark.parametrize("N,is_real", [(1 << 16, 0), (1 << 21, 1)])
-def test_ring_ingest_matches_flat_upload(N, is_real):
-    """psdr_ring_write_async + psdr_process_ring (pinned host halves -> HBM ring on a copy stream, writes
-    running ahead of the transforms, the ring wrapping several times) give bit-identical spectra, int8
-    pyramids and audio to psdr_process_batch over a flat upload of the same stream."""
+def ring_ingest_against_flat_upload(N, is_real, fmt):
+    """the body of test_ring_ingest_matches_flat_upload for one input format (tests/test_gpu_format_invariance.py runs
+    the formats whose half-frames are a quarter and four times the size of s16's)"""
     from phantomsdr_amd import AudioClient, Context
     from phantomsdr_amd._lib import PsdrError
     R = N // 2 if is_real else N
     n, F, nb, nh = 360, 4, 7, 8                     # 7 batches of 4 frames through an 8-half ring
     total = nb * F
-    raw = quantize_raw(synth_stream((total + 1) * (N // 2), bool(is_real), seed=9, fft_size=N), "s16", bool(is_real))
-    mk = lambda: Context(N, is_real, _levels(R), additional_size=n, audio_fft_size=n, input_format="s16",
+    sigma = 2.0 ** -5 if fmt in ("u8", "s8") else 2.0 ** -9   # (8-bit samples need a signal above their step)
+    raw = quantize_raw(synth_stream((total + 1) * (N // 2), bool(is_real), seed=9, sigma=sigma, fft_size=N), fmt, bool(is_real))
+    mk = lambda: Context(N, is_real, _levels(R), additional_size=n, audio_fft_size=n, input_format=fmt,
                          max_batch=F, max_clients=2)
     a, b = mk(), mk()
     try:
@@ -168,6 +167,14 @@ def test_ring_ingest_matches_flat_upload(N, is_real):
     finally:
         a.close()
         b.close()
+
+
+@pytest.mark.parametrize("N,is_real", [(1 << 16, 0), (1 << 21, 1)])
+def test_ring_ingest_matches_flat_upload(N, is_real):
+    """psdr_ring_write_async + psdr_process_ring (pinned host halves -> HBM ring on a copy stream, writes
+    running ahead of the transforms, the ring wrapping several times) give bit-identical spectra, int8
+    pyramids and audio to psdr_process_batch over a flat upload of the same stream."""
+    ring_ingest_against_flat_upload(N, is_real, "s16")
 
 
 def test_band_calls_refuse_bad_arguments():

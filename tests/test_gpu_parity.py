@@ -43,6 +43,7 @@ def check_pyramid(q_gpu, spec_gpu_k, q_orc, N, is_real, levels):
     (1 << 18, 0), (1 << 19, 0), (1 << 20, 0), (1 << 21, 0),
     (1 << 13, 1), (1 << 14, 1), (1 << 15, 1), (1 << 16, 1), (1 << 17, 1), (1 << 19, 1),
     (1 << 21, 1), (1 << 22, 1),
+    (1 << 22, 0), (1 << 18, 1), (1 << 20, 1), (1 << 23, 1),   # with these, every shape psdr_create accepts
 ])
 def test_fft_plugin_level1(N, is_real):
     """HipFFT driven exactly like the reference drives class FFT (src/fft.cpp:17-30,61-98)."""
