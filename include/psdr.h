@@ -55,7 +55,10 @@ typedef enum psdr_format {
 } psdr_format;
 
 /* demodulation_mode, src/client.h:43 */
-typedef enum psdr_mode { PSDR_USB = 0, PSDR_LSB = 1, PSDR_AM = 2, PSDR_FM = 3 } psdr_mode;
+/* PSDR_IQ (no counterpart in the reference's enum: its raw SIGNAL shortcut and its PLL over this baseband,
+ * src/signal.cpp:110-115, 242-252, are disabled there): the client's output is the complex baseband itself, see
+ * psdr_read_iq below */
+typedef enum psdr_mode { PSDR_USB = 0, PSDR_LSB = 1, PSDR_AM = 2, PSDR_FM = 3, PSDR_IQ = 4 } psdr_mode;
 
 typedef struct psdr_config {
     uint32_t struct_size;        /* = sizeof(psdr_config) */
@@ -154,7 +157,10 @@ int psdr_client_set_audio_range(psdr_ctx *ctx, int id, int l, double audio_mid, 
 /* AudioClient::on_window_message (src/signal.cpp:300-314): validated; PSDR_ERR_INVALID
  * (and no change) when the reference would silently return */
 int psdr_client_on_window_message(psdr_ctx *ctx, int id, int l, double audio_mid, int r);
-/* AudioClient::set_audio_demodulation / on_demodulation_message (src/signal.cpp:95-97,316-328) */
+/* AudioClient::set_audio_demodulation / on_demodulation_message (src/signal.cpp:95-97,316-328).
+ * The first PSDR_IQ of a context allocates the IQ rows: two sets of 8 * (audio_fft_size/2) bytes per client slot and
+ * batch frame, i.e. 16 * (audio_fft_size/2) * max_clients * max_batch bytes in all (a context that never sees an IQ client
+ * allocates none); PSDR_ERR_NOMEM, and the mode unchanged, if that fails. */
 int psdr_client_set_audio_demodulation(psdr_ctx *ctx, int id, int mode);
 /* signal_loop's slow-client rule (src/websocket.cpp:170-176): the reference does not call send_audio at all for a
  * client with more than 50 kB queued on its socket, so NOTHING of that client moves for the frame - overlap-add tails and
@@ -208,12 +214,29 @@ int psdr_demod_batch_from_band_region(psdr_ctx *ctx, const float *d_region, size
  * (PSDR_ERR_INVALID otherwise, nothing is written); *nframes_out (may be NULL) = rows written. */
 int psdr_read_audio(psdr_ctx *ctx, int id, int nframes, float *audio, float *pwr, int32_t *nan_flags,
                     int *nframes_out);
+/* PSDR_IQ - the overlap-added complex baseband at the audio rate as the client's output (external decoders, client-side
+ * synchronous AM, stereo / RDS).  With n = audio_fft_size, h = n/2, frame f of an IQ client is h complex samples
+ *   IQ_f[j] = s_f y_f[j] + s_{f-1} y_{f-1}[h + j],  j < h
+ * y_f: the UN-NORMALISED n-point backward DFT of the AM / FM bin placement (src/signal.cpp:175-198, 214), s_f: the flip sign
+ * of :223-234 - exactly what AM and FM detect (audio_complex_baseband after :235-237), interleaved re, im.  pwr is the
+ * usual sum over [l, r); the NaN flag of a frame is 1 if any component of IQ_f is NaN; the state always moves and is AM's
+ * and FM's (the tail, the last sample; the USB / LSB tail is kept), so a client may change between USB, LSB, AM, FM and IQ
+ * at any batch boundary and every mode continues as if it had run all along (never reset, src/signal.cpp:81-94, 316-328).
+ * A batch demodulated as IQ has NO audio and NO PCM: psdr_read_audio / psdr_read_pcm / psdr_fetched_audio /
+ * psdr_fetched_pcm16 answer PSDR_ERR_NO_DATA for such a slot, and the IQ calls answer PSDR_ERR_NO_DATA for a slot whose
+ * batch was not IQ.  To the post chain an IQ client is a paused one: its DC blocker and AGC stand still, and the AGC reset
+ * of the mode command takes effect at its next audio batch.  Other clients are not affected by a bit.
+ * psdr_read_iq: iq [nframes][n/2][2] floats (nframes * n in all), otherwise the contract of psdr_read_audio.
+ * psdr_iq_device_ptr: the rows [frames][n/2][2] of slot `id` in the LAST batch's set of IQ rows (two sets alternate from
+ * batch to batch: the pointer is good for that batch only; PSDR_ERR_NO_DATA before the context's first IQ client). */
+int psdr_read_iq(psdr_ctx *ctx, int id, int nframes, float *iq, float *pwr, int32_t *nan_flags, int *nframes_out);
+int psdr_iq_device_ptr(psdr_ctx *ctx, int id, const float **d_iq, const float **d_pwr);
 /* A client added after the last psdr_demod_batch has no results in it (the reference's frame loop would not
  * have posted a task for it either, src/websocket.cpp:156-185): psdr_read_audio / psdr_read_pcm / psdr_fetched_audio
  * return PSDR_ERR_NO_DATA for such a slot instead of the previous occupant's samples.
  *
  * Batched read-back - what a per-frame fan-out should use: psdr_fetch_batch copies the last demod batch's audio,
- * pwr, NaN flags (and PCM with the post chain on) of ALL client slots into pinned host memory owned by the
+ * pwr, NaN flags (and PCM with the post chain on; the IQ rows of PSDR_IQ clients) of ALL client slots into pinned host memory owned by the
  * context with ONE synchronisation and at most four strided copies; psdr_fetched_audio then hands out pointers
  * into that block (valid until the next psdr_fetch_batch) without touching the device.  frame: index inside the
  * batch.  audio / pcm: audio_fft_size/2 values.  Any output pointer may be NULL. */
@@ -238,8 +261,18 @@ int psdr_fetched_audio(psdr_ctx *ctx, int id, int frame, const float **audio, fl
 #define PSDR_FETCH_AUDIO 1u
 #define PSDR_FETCH_PCM 2u
 #define PSDR_FETCH_WATERFALL 4u
+/* the IQ rows of the batch's PSDR_IQ clients (with pwr and NaN flags, as always): ONE copy of the span from the lowest to
+ * the highest slot that was IQ in the batch, not of all max_clients slots - keep IQ clients in neighbouring slots. */
+#define PSDR_FETCH_IQ 8u
 int psdr_fetch_begin(psdr_ctx *ctx, unsigned what);
 int psdr_fetch_end(psdr_ctx *ctx);
+/* one frame of an IQ client in the fetched set: iq = n/2 (re, im) pairs in pinned host memory (NULL if the set was fetched
+ * without PSDR_FETCH_IQ), valid like psdr_fetched_audio's pointers: until PSDR_FETCH_SETS - 1 further psdr_fetch_begin calls
+ * have been made.  PSDR_ERR_NO_DATA: the client was not part of the fetched batch, or not as PSDR_IQ.  Any output pointer
+ * may be NULL.  psdr_fetched_iq_span: what the fetch's IQ copy covered - the first slot, the number of slots (0: no IQ
+ * client in the batch) and the bytes it moved (slots * frames * n/2 * 8); PSDR_ERR_STATE without PSDR_FETCH_IQ. */
+int psdr_fetched_iq(psdr_ctx *ctx, int id, int frame, const float **iq, float *pwr, int32_t *nan_flag);
+int psdr_fetched_iq_span(psdr_ctx *ctx, int *first_slot, int *nslots, size_t *bytes);
 /* one frame's PCM row (audio_fft_size/2 int16) of client `id` in the fetched set when the batch was produced with
  * PSDR_OPT_POST_CHAIN_PCM16 = 1 (PSDR_ERR_STATE otherwise); pointer into pinned host memory, valid like psdr_fetched_audio's */
 int psdr_fetched_pcm16(psdr_ctx *ctx, int id, int frame, const int16_t **pcm);
@@ -403,6 +436,8 @@ psdr_ctx *psdr_group_ctx(psdr_group *g, int rank);
  * (DC sums, AGC gain and look-ahead) does not: the client starts there like a fresh one (an AGC transient the reference
  * does not have); and psdr_group_fetched_audio answers PSDR_ERR_NO_DATA until the new device has demodulated a batch.
  * psdr_group_client_rank: the rank (index into `devices`) a client lives on now, -1 for an unknown gid. */
+/* PSDR_IQ is not served through a group (its rows are neither migrated nor fetched by gid): psdr_group_client_add and
+ * psdr_group_client_set_audio_demodulation answer PSDR_ERR_UNSUPPORTED for it. */
 int psdr_group_client_add(psdr_group *g, int l, double audio_mid, int r, int mode, int *gid_out);
 int psdr_group_client_remove(psdr_group *g, int gid);
 int psdr_group_client_set_audio_range(psdr_group *g, int gid, int l, double audio_mid, int r);

@@ -75,6 +75,10 @@ SYMBOLS = [
     ("psdr_demod_batch_from_band_region", _i, [_vp, _vp, _sz, C.c_uint32, C.c_uint32, _i, _u64]),
     ("psdr_read_audio", _i, [_vp, _i, _i, _vp, _vp, _vp, C.POINTER(_i)]),
     ("psdr_audio_device_ptr", _i, [_vp, _i, _pp, _pp]),
+    ("psdr_read_iq", _i, [_vp, _i, _i, _vp, _vp, _vp, C.POINTER(_i)]),
+    ("psdr_iq_device_ptr", _i, [_vp, _i, _pp, _pp]),
+    ("psdr_fetched_iq", _i, [_vp, _i, _i, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
+    ("psdr_fetched_iq_span", _i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_sz)]),
     ("psdr_set_post_chain", _i, [_vp, _i]),
     ("psdr_set_option", _i, [_vp, _i, _i]),
     ("psdr_read_pcm", _i, [_vp, _i, _i, _vp, C.POINTER(_i)]),

@@ -22,7 +22,8 @@ FORMATS = {"u8": 0, "s8": 1, "u16": 2, "s16": 3, "f32": 4, "f64": 5}
 FORMAT_DTYPES = {"u8": np.uint8, "s8": np.int8, "u16": np.uint16, "s16": np.int16,
                  "f32": np.float32, "f64": np.float64}
 USB, LSB, AM, FM = 0, 1, 2, 3
-MODES = {"USB": USB, "LSB": LSB, "AM": AM, "FM": FM}
+IQ = 4  # PSDR_IQ (include/psdr.h): the overlap-added complex baseband itself as the client's output
+MODES = {"USB": USB, "LSB": LSB, "AM": AM, "FM": FM, "IQ": IQ}
 # psdr_wf_detector (include/psdr.h): what a sent waterfall row shows of the frames since the previous one
 WF_SAMPLE, WF_PEAK, WF_MEAN = 0, 1, 2
 WF_DETECTORS = {"sample": WF_SAMPLE, "peak": WF_PEAK, "mean": WF_MEAN}
@@ -177,6 +178,7 @@ class Context:
 
     # --- the served end: results to pinned host memory (psdr_fetch_*) ------------------
     FETCH_AUDIO, FETCH_PCM, FETCH_WATERFALL = 1, 2, 4
+    FETCH_IQ = 8  # the IQ rows of the batch's PSDR_IQ clients: one copy of the span of slots that hold them
 
     def fetch_batch(self):
         check(self.lib.psdr_fetch_batch(self.h))
@@ -205,6 +207,20 @@ class Context:
         pc = C.POINTER(C.c_int16)()
         check(self.lib.psdr_fetched_pcm16(self.h, int(cid), int(frame), C.byref(pc)))
         return np.ctypeslib.as_array(pc, shape=(self.cfg.audio_fft_size // 2,)).copy()
+
+    def fetched_iq(self, cid, frame):
+        """(iq complex64[n/2] copy or None, pwr, nan flag) of one frame of an IQ client in the fetched batch"""
+        p = C.POINTER(C.c_float)()
+        pw, nan = C.c_float(0), C.c_int32(0)
+        check(self.lib.psdr_fetched_iq(self.h, int(cid), int(frame), C.byref(p), C.byref(pw), C.byref(nan)))
+        iq = np.ctypeslib.as_array(p, shape=(self.cfg.audio_fft_size,)).copy().view(np.complex64) if p else None
+        return iq, pw.value, nan.value
+
+    def fetched_iq_span(self):
+        """(first slot, slots, bytes) the fetched batch's IQ copy covered (psdr.h: psdr_fetched_iq_span)"""
+        lo, ns, nb = C.c_int(0), C.c_int(0), C.c_size_t(0)
+        check(self.lib.psdr_fetched_iq_span(self.h, C.byref(lo), C.byref(ns), C.byref(nb)))
+        return lo.value, ns.value, nb.value
 
     def fetched_waterfall(self, wid):
         """(rows [nsent][r - l] copy, level, l, r) of a waterfall client in the fetched batch"""
@@ -435,6 +451,16 @@ class AudioClient:
         got = C.c_int(0)
         check(self.ctx.lib.psdr_read_audio(self.ctx.h, self.id, F, _ptr(audio), _ptr(pwr), _ptr(nan), C.byref(got)))
         return audio[:got.value], pwr[:got.value], nan[:got.value]
+
+    def read_iq(self, nframes=None):
+        """(iq complex64[F][n/2], pwr[F], nan[F]) of the last demod batch of a client in IQ mode (psdr.h: psdr_read_iq)"""
+        F = nframes or self.ctx.last_demod_frames or self.ctx.last_nframes
+        iq = np.empty((F, self.ctx.n // 2), np.complex64)
+        pwr = np.empty(F, np.float32)
+        nan = np.empty(F, np.int32)
+        got = C.c_int(0)
+        check(self.ctx.lib.psdr_read_iq(self.ctx.h, self.id, F, _ptr(iq), _ptr(pwr), _ptr(nan), C.byref(got)))
+        return iq[:got.value], pwr[:got.value], nan[:got.value]
 
     def read_pcm(self, nframes=None):
         """int16 PCM (in int32, like the reference's buffer) of the last demod batch after the

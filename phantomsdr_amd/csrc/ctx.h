@@ -72,6 +72,7 @@ struct AudioSlot {
     uint64_t last_seq = 0;  // the demodulation batch (ctx->demod_seq) that last included this slot; 0: none yet
     int b_l = 0, b_r = 0;   // the window that batch was demodulated with (psdr_fetch_begin copies it into its FetchSet)
     double b_mid = 0;
+    int b_mode = PSDR_USB;  // ... and the mode: a batch demodulated as PSDR_IQ left complex rows (iq_pool) and no audio / PCM
     uint64_t born = 0;      // psdr_client_add's serial number: a fetched set answers only for the occupant it was filled with
 };
 struct WfSlot {
@@ -279,6 +280,10 @@ struct psdr_ctx {
     DevBuf<float> audio_pool[2], pwr_pool[2];
     DevBuf<int> nan_pool[2];
     int out_set = 0, pcm_set = 0;
+    // PSDR_IQ clients' rows [slot][max_batch][n/2] complex64: two pools that alternate with out_set like audio_pool, allocated
+    // when a client is first set to PSDR_IQ (psdr_client_set_audio_demodulation, under mtx) and kept; d_iq: the last batch's
+    DevBuf<cf> iq_pool[2];
+    cf *d_iq = nullptr;
     DevBuf<unsigned> d_ssb_mark;  // [slots] DemodArgs::ssb_mark (demod.h): USB / LSB batches that need the frame-ordered NaN guard
     ParamRing client_ring;
     int last_demod_frames = 0;
@@ -293,12 +298,16 @@ struct psdr_ctx {
         HostBuf<int32_t> nan, pcm;
         HostBuf<int8_t> wf;
         size_t wf_cap = 0;
+        // PSDR_FETCH_IQ: rows [slot - iq_lo][max_batch][n/2] of the iq_n slots from the lowest to the highest that were IQ
+        HostBuf<cf> iq;
+        size_t iq_cap = 0, iq_bytes = 0;  // slots the buffer holds; bytes the fetch's IQ copy moved
+        int iq_lo = 0, iq_n = 0;
         Event done;                      // every copy of the fetch on the first copy stream has landed
         Event ev_pcm;                    // ... and the PCM (its own copy stream: it waits for the post chain, up to two steps late)
         bool has_pcm = false;
         bool pcm16 = false;              // its PCM rows are int16 (PSDR_OPT_POST_CHAIN_PCM16 at that batch)
         Event ev_wf;                     // ... the waterfall rows (first in the copy stream: d_wfout exists once)
-        Event ev_audio;                  // ... pwr, NaN flags, float audio (what the demodulation of batch b + 2 overwrites)
+        Event ev_audio;                  // ... pwr, NaN flags, float audio, IQ rows (what the demodulation of batch b + 2 overwrites)
         bool inflight = false;
         unsigned what = 0;     // PSDR_FETCH_* bits the copies covered
         int frames = 0;        // frames of the demodulation batch (0: none was fetched)
@@ -307,6 +316,7 @@ struct psdr_ctx {
             uint64_t last_seq = 0, born = 0;
             int l = 0, r = 0;
             double mid = 0;
+            int mode = PSDR_USB;
         };
         std::vector<Win> win;      // per audio slot: the window the batch was demodulated with
         std::vector<WfSlot> wfm;   // per waterfall slot: what psdr_waterfall_batch gathered (out_off, nsent, b_*)

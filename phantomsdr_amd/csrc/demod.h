@@ -980,4 +980,137 @@ __global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) 
     if (ssb && !a.replay && __any(bad) && lane_ == 0) a.ssb_mark[srow] = a.mark_epoch;
 }
 
+// ---- PSDR_IQ: the overlap-added complex baseband itself as the client's output ------------------------------------
+// IQ_f[j] = s_f y_f[j] + s_{f-1} y_{f-1}[h + j], j < h: what AM and FM hold in `b` above before sqrtf / atan2f collapse it
+// (audio_complex_baseband after src/signal.cpp:235-237), stored as (re, im) rows iq[slot][max_batch][h].  IQ clients are
+// listed apart (a.clients = their list, nact = their number) and served by these two kernels alone; the transform is the
+// AM / FM one (every IDFT kernel above treats mode >= 2 as a complex transform into ypost).  The carried state is AM's
+// and FM's - bb_tail, bb_last = IQ_f[h-1], real_prev copied through - and always moves; the NaN flag of a frame is 1
+// if any component of IQ_f is NaN.
+
+// n = 360 / 720: k_demod_chain_fixed's walk for an IQ client - one wave per chain of K frames, the tail in registers,
+// ONE warm-up frame (no sample of IQ_f0 looks further back than y_{f0-1}), no detector, no NaN-guard replay, no
+// ssb_mark.  Same operations in the same order as k_demod_idft_fixed + k_demod_ola_iq (__fmul_rn / __fadd_rn: see
+// k_demod_chain_fixed): bit-identical outputs.  Grid and LDS as k_demod_chain_fixed.
+template <int N, int R0, int R1, int R2>
+__global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) void k_demod_chain_iq(DemodArgs a, int nact, int K, cf *iq) {
+    static_assert(R0 * R1 * R2 == N, "plan");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int h = N / 2, NH = (h + 63) / 64;
+    const int lane_ = threadIdx.x & 63, wv = threadIdx.x >> 6, W = blockDim.x >> 6;
+    cf *Wn = reinterpret_cast<cf *>(smem);
+    for (int i = threadIdx.x; i < N; i += blockDim.x) Wn[i] = a.Wn[i];
+    __syncthreads();
+    const int F = a.nframes, nch = (F + K - 1) / K;
+    const int item = __builtin_amdgcn_readfirstlane((int)blockIdx.x * W + wv);
+    if (item >= nact * nch) return;
+    const int ci = item / nch, f0 = (item - ci * nch) * K;
+    const int f1 = f0 + K < F ? f0 + K : F;
+    ClientParams cp = a.clients[ci];
+    cp.l = __builtin_amdgcn_readfirstlane(cp.l);
+    cp.r = __builtin_amdgcn_readfirstlane(cp.r);
+    cp.m_floor = __builtin_amdgcn_readfirstlane(cp.m_floor);
+    cp.mode = __builtin_amdgcn_readfirstlane(cp.mode);
+    cp.slot = __builtin_amdgcn_readfirstlane(cp.slot);
+    cp.state_cur = __builtin_amdgcn_readfirstlane(cp.state_cur);
+    cf *buf = Wn + N + (size_t)wv * N;
+    const size_t srow = (size_t)cp.slot;
+    const int cur = cp.state_cur, nxt = cur ^ 1;
+    const float *rp_old = a.real_prev + ((size_t)cur * a.slots + srow) * h;
+    float *rp_new = a.real_prev + ((size_t)nxt * a.slots + srow) * h;
+    const cf *bt_old = a.bb_tail + ((size_t)cur * a.slots + srow) * h;
+    cf *bt_new = a.bb_tail + ((size_t)nxt * a.slots + srow) * h;
+    const int fs = f0 == 0 ? 0 : f0 - 1;  // the warm-up frame: transformed, nothing written
+    cf tail[NH];                          // s_{f-1} y_{f-1}[h + j], j = lane + 64 u
+#pragma unroll
+    for (int u = 0; u < NH; u++) {
+        const int j = lane_ + 64 * u;
+        tail[u] = make_float2(0.f, 0.f);
+        if (fs == 0 && j < h) tail[u] = bt_old[j];  // the batch's first frame: the carried tail
+    }
+    constexpr int NR = (N + 63) / 64;
+    constexpr int HO = NR < 3 ? NR : (N <= 512 ? 3 : 6);
+    unsigned so[HO];
+    idft_slice_offsets<N, HO>(a, cp, lane_, so);
+    for (int f = fs; f < f1; f++) {
+        const bool emit = f >= f0;
+        int ln = lane_;  // (an opaque copy per iteration: k_demod_chain_fixed says why)
+        asm volatile("" : "+v"(ln));
+        const int lane = ln;
+        cf sv[NR];  // loads first, LDS after
+        idft_load_slice_at<N, HO>(a, cp, f, so, lane, sv);
+        const float pw = idft_slice_fixed<N, R0, R1, R2>(cp, sv, buf, Wn, lane);
+        if (emit && lane == 0) a.pwr[srow * a.max_batch + f] = pw;
+        const float sg = flip_frame(a.first_frame_num + (unsigned long long)f, cp.m_floor, a.is_real) ? -1.f : 1.f;
+        cf *out = iq + (srow * a.max_batch + f) * h;
+        const bool last = (f == F - 1);
+        int s_nan = 0;
+#pragma unroll
+        for (int u = 0; u < NH; u++) {
+            const int j = lane + 64 * u;
+            if (j < h) {
+                const cf v0 = buf[j], v1 = buf[h + j];
+                const cf y = make_float2(__fmul_rn(v0.x, sg), __fmul_rn(v0.y, sg));
+                const cf ynext = make_float2(__fmul_rn(v1.x, sg), __fmul_rn(v1.y, sg));
+                const cf b = make_float2(__fadd_rn(y.x, tail[u].x), __fadd_rn(y.y, tail[u].y));  // dsp_add_complex :235
+                if (isnan(b.x) || isnan(b.y)) s_nan = 1;
+                if (emit) {
+                    out[j] = b;
+                    if (last) {  // the state the next batch starts from (:200-203); USB / LSB's is kept
+                        bt_new[j] = ynext;
+                        rp_new[j] = rp_old[j];
+                        if (j == h - 1) a.bb_last[(size_t)nxt * a.slots + srow] = b;
+                    }
+                }
+                tail[u] = ynext;
+            }
+        }
+        const int any_nan = __any(s_nan);
+        if (emit && lane == 0) a.nan_flags[srow * a.max_batch + f] = any_nan ? 1 : 0;
+        wave_lds_sync();  // buf is read out: the next frame's transform may overwrite it
+    }
+}
+
+// any other n (and n = 360 / 720 with PSDR_DEMOD_CHAIN=0): the overlap-add of an IQ client's rows of ypost, beside
+// k_demod_ola and with its grid - one wave per (client, group of PSDR_OLA_FG frames)
+__global__ __launch_bounds__(256) void k_demod_ola_iq(DemodArgs a, int nact, cf *iq) {
+    constexpr int FG = PSDR_OLA_FG;
+    const int n = a.n, h = n / 2, tid = threadIdx.x & 63, NT = 64;
+    const int F = a.nframes, ngrp = (F + FG - 1) / FG;
+    const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= nact * ngrp) return;
+    const int ci = item / ngrp;
+    const ClientParams cp = a.clients[ci];
+    const int f0 = (item - ci * ngrp) * FG;
+    const size_t srow = (size_t)cp.slot;
+    const cf *yp = a.ypost + (srow * a.max_batch) * n;  // this client's frames
+    const int cur = cp.state_cur, nxt = cur ^ 1;
+    const float *rp_old = a.real_prev + ((size_t)cur * a.slots + srow) * h;
+    float *rp_new = a.real_prev + ((size_t)nxt * a.slots + srow) * h;
+    const cf *bt_old = a.bb_tail + ((size_t)cur * a.slots + srow) * h;
+    cf *bt_new = a.bb_tail + ((size_t)nxt * a.slots + srow) * h;
+#pragma unroll
+    for (int g = 0; g < FG; g++) {
+        const int f = f0 + g;
+        if (f >= F) break;
+        const cf *y = yp + (size_t)f * n;
+        cf *out = iq + (srow * a.max_batch + f) * h;
+        int s_nan = 0;
+        const bool last = (f == F - 1);
+        for (int j = tid; j < h; j += NT) {
+            const cf pv = (f == 0) ? bt_old[j] : yp[(size_t)(f - 1) * n + h + j];
+            const cf b = make_float2(y[j].x + pv.x, y[j].y + pv.y);  // dsp_add_complex :235
+            out[j] = b;
+            if (isnan(b.x) || isnan(b.y)) s_nan = 1;
+            if (last) {
+                bt_new[j] = y[h + j];  // :200-203 (second half kept for the next frame)
+                rp_new[j] = rp_old[j];
+                if (j == h - 1) a.bb_last[(size_t)nxt * a.slots + srow] = b;  // `prev` of :200
+            }
+        }
+        const int any_nan = __any(s_nan);
+        if (tid == 0) a.nan_flags[srow * a.max_batch + f] = any_nan ? 1 : 0;
+    }
+}
+
 }  // namespace psdr

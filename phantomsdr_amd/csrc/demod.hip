@@ -86,7 +86,20 @@ extern "C" int psdr_client_set_audio_demodulation(psdr_ctx *c, int id, int mode)
     std::lock_guard<std::mutex> lk(c->mtx);
     int rc = check_slot(c, id);
     if (rc) return rc;
-    if (mode < PSDR_USB || mode > PSDR_FM) return fail(PSDR_ERR_INVALID, "unknown mode %d", mode);
+    if (mode < PSDR_USB || mode > PSDR_IQ) return fail(PSDR_ERR_INVALID, "unknown mode %d", mode);
+    if (mode == PSDR_IQ && !c->iq_pool[1]) {
+        // the first IQ client of the context: its rows' two pools (a context that never sees one allocates nothing); both
+        // exist before either is kept, and the mode changes only then
+        HIPCHK(hipSetDevice(c->device));
+        const size_t rows = c->aslots.size() * (size_t)c->max_batch * ((size_t)c->n / 2);
+        DevBuf<cf> pool[2];
+        if (pool[0].alloc(rows) || pool[1].alloc(rows)) {
+            const std::string msg = psdr_last_error();
+            return fail(PSDR_ERR_NOMEM, "IQ rows (2 x %zu bytes): %s", rows * sizeof(cf), msg.c_str());
+        }
+        c->iq_pool[0] = std::move(pool[0]);
+        c->iq_pool[1] = std::move(pool[1]);
+    }
     c->aslots[id].mode = mode;
     if (c->aslots[id].agc_reset == 0) c->aslots[id].agc_reset = 1;  // src/signal.cpp:316-328: resets the AGC
     return PSDR_OK;
@@ -98,7 +111,7 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
                       const uint32_t *band = nullptr, bool band_tiled = false) {
     if (c->n <= 0) return fail(PSDR_ERR_STATE, "context created with audio_fft_size 0");
     HIPCHK(hipSetDevice(c->device));
-    int nact = 0, npaused = 0;
+    int nact = 0, npaused = 0, niq = 0, iq_off = 0;
     const int ring = c->client_ring.acquire();
     if (ring < 0) return fail(PSDR_ERR_HIP, "client parameter ring: event wait failed");
     ClientParams *h_clients = (ClientParams *)c->client_ring.host(ring);
@@ -106,6 +119,7 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     // behind the list, for the post chain: the list index of every slot's client (its kernels walk the SLOTS, lane = slot & 63)
     const size_t S = c->aslots.size();
     int *h_slot_ci = (int *)(h_clients + S), *d_slot_ci = (int *)(d_clients + S);
+    cf *iq_rows[2] = {nullptr, nullptr};
     {
         std::lock_guard<std::mutex> lk(c->mtx);
         if (band) {  // checked under the same lock that fixes the windows this batch is demodulated with
@@ -119,12 +133,17 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
                 }
             }
         }
+        iq_rows[0] = c->iq_pool[0], iq_rows[1] = c->iq_pool[1];  // (allocated under this lock, once)
         c->demod_seq++;
         for (size_t i = 0; i < c->aslots.size(); i++) {
             AudioSlot &s = c->aslots[i];
             if (!s.active || s.paused) continue;
             s.last_seq = c->demod_seq;
-            s.b_l = s.l, s.b_r = s.r, s.b_mid = s.mid;
+            s.b_l = s.l, s.b_r = s.r, s.b_mid = s.mid, s.b_mode = s.mode;
+            if (s.mode == PSDR_IQ) {  // listed apart, below
+                niq++;
+                continue;
+            }
             ClientParams &p = h_clients[nact++];
             p.l = s.l;
             p.r = s.r;
@@ -157,13 +176,41 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
                 p.paused = 1;
                 h_slot_ci[i] = nact + npaused - 1;
             }
+        // PSDR_IQ clients, behind both: the list of k_demod_chain_iq / k_demod_ola_iq.  To the post chain an IQ client IS a
+        // paused one - no audio of its own this batch, histories standing still, a pending AGC reset kept for its next
+        // audio batch - so those with a history come first and the chain's count of paused clients takes them in
+        if (niq > 0) {
+            iq_off = nact + npaused;
+            int k = iq_off;
+            for (int fresh = 0; fresh < 2; fresh++)
+                for (size_t i = 0; i < c->aslots.size(); i++) {
+                    AudioSlot &s = c->aslots[i];
+                    if (!s.active || s.paused || s.mode != PSDR_IQ || (s.agc_reset == 2) != (fresh == 1)) continue;
+                    ClientParams &p = h_clients[k];
+                    p = ClientParams{};
+                    p.l = s.l;
+                    p.r = s.r;
+                    p.m_floor = (int)std::floor(s.mid);
+                    p.mode = PSDR_IQ;
+                    p.slot = (int)i;
+                    p.state_cur = s.state_cur;
+                    s.state_cur ^= 1;
+                    p.paused = 1;
+                    if (!fresh && c->post_on && nact > 0) {
+                        h_slot_ci[i] = k;
+                        npaused++;
+                    }
+                    k++;
+                }
+        }
     }
     c->last_demod_frames = nframes;
-    if (nact == 0) return PSDR_OK;
+    if (nact + niq == 0) return PSDR_OK;
     {  // this batch's results go to the OTHER set (the copies of the last batch to the host may still be reading theirs); what
        // read this set two batches ago must have landed
         c->out_set ^= 1;
         c->d_audio = c->audio_pool[c->out_set], c->d_pwr = c->pwr_pool[c->out_set], c->d_nan = c->nan_pool[c->out_set];
+        c->d_iq = iq_rows[c->out_set];  // (null until the context's first IQ client)
         int rc = fetch_guard_wait(c, c->side, c->guard_audio[c->out_set]);
         if (rc) return rc;
         c->guard_audio[c->out_set] = nullptr;
@@ -173,7 +220,7 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
         if (c->post_on && c->post_direct && c->chain_seq >= 2 && c->pc_s[0] && c->side != c->stream)
             HIPCHK(hipStreamWaitEvent(c->side, c->pc.ev[1][(c->chain_seq - 2) % psdr_ctx::PC_SETS], 0));
     }
-    HIPCHK(hipMemcpyAsync(d_clients, h_clients, c->post_on ? S * (sizeof(ClientParams) + sizeof(int)) : (size_t)nact * sizeof(ClientParams),
+    HIPCHK(hipMemcpyAsync(d_clients, h_clients, c->post_on ? S * (sizeof(ClientParams) + sizeof(int)) : (size_t)(nact + niq) * sizeof(ClientParams),
                           hipMemcpyHostToDevice, c->side));
     DemodArgs a{};
     a.spec = spec;
@@ -219,20 +266,53 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     // non-finite values can arise: float input formats, or a spectrum that comes from the caller
     const bool can_be_nonfinite = c->cfg.input_format >= PSDR_FMT_F32 || spec != c->d_spec;
     bool ola_done = false;
-    {
+    const bool fixed_plan = c->n == 360 || c->n == 720;
+    // frames per chain of the one-kernel path for `cnt` clients (demod.h): long chains repeat fewer transforms (1 or 2 per
+    // chain), short ones give few clients enough waves
+    // (256 clients x 256 frames, same box: K = 4 / 8 / 16 / 32 -> 5.81 / 5.77 / 5.93 / 6.04 us per frame, the
+    // two-kernel path 5.99)
+    // (round 4, 512-frame launches: with 256 clients and more, chains of 16 still leave 8192 waves and repeat half as
+    // many warm-up transforms: 93.4 -> 94.6 GS/s on the 256-client shape, same box, interleaved twice)
+    auto chain_k = [&](int cnt) {
+        int K = c->demod_chain_k > 0 ? c->demod_chain_k : (cnt >= 256 && (unsigned)cnt * (unsigned)((nframes + 15) / 16) >= 8192u ? 16 : 8);
+        if (c->demod_chain_k <= 0)
+            while (K > 4 && (unsigned)cnt * (unsigned)((nframes + K - 1) / K) < 1024u) K >>= 1;
+        return K;
+    };
+    // the transform alone, into ypost, of the `cnt` clients listed in aa.clients (every path but the chain kernels')
+    auto launch_idft = [&](const DemodArgs &aa, int cnt) -> int {
+        if (fixed_plan) {
+            // compile-time plans (demod.h): 360 = 8*9*5, 720 = 8*9*10; W items per work-group in
+            // the 15 KiB of LDS an FFT pass leaves free on a CU
+            const unsigned items = (unsigned)cnt * (unsigned)nframes;
+            const unsigned W = c->n == 360 ? 4u : 1u;
+            const size_t lds = (size_t)(1 + W) * c->n * sizeof(cf);
+            if (c->n == 360)
+                hipLaunchKernelGGL((k_demod_idft_fixed<360, 8, 9, 5>), dim3((items + W - 1) / W), dim3(64 * W), lds,
+                                   c->side, aa, cnt);
+            else
+                hipLaunchKernelGGL((k_demod_idft_fixed<720, 8, 9, 10>), dim3((items + W - 1) / W), dim3(64 * W), lds,
+                                   c->side, aa, cnt);
+        } else if (c->n <= 512) {
+            // one wave per (client, frame), no work-group barriers (demod.h)
+            const unsigned items = (unsigned)cnt * (unsigned)nframes;
+            const size_t lds = (size_t)(2 * PSDR_IDFT_WAVES + 1) * c->n * sizeof(cf);
+            hipLaunchKernelGGL(k_demod_idft_wave, dim3((items + PSDR_IDFT_WAVES - 1) / PSDR_IDFT_WAVES),
+                               dim3(64 * PSDR_IDFT_WAVES), lds, c->side, aa, cnt);
+        } else {
+            if (c->idft_lds > 64 * 1024 && c->lds_attr_done.insert((const void *)k_demod_idft).second)
+                HIPCHK(hipFuncSetAttribute((const void *)k_demod_idft, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->idft_lds));
+            hipLaunchKernelGGL(k_demod_idft, dim3(cnt, nframes), dim3(c->idft_threads), c->idft_lds, c->side,
+                               aa);
+        }
+        return PSDR_OK;
+    };
+    if (nact > 0) {
         ProfScope ps(c, K_IDFT, c->side);
-        const bool fixed_plan = c->n == 360 || c->n == 720;
         if (fixed_plan && c->demod_chain) {
             // transform + overlap-add + demodulation in one kernel, one wave per chain of K consecutive frames of a
-            // client (demod.h): long chains repeat fewer transforms (1 or 2 per chain), short ones give few clients
-            // enough waves
-            // (256 clients x 256 frames, same box: K = 4 / 8 / 16 / 32 -> 5.81 / 5.77 / 5.93 / 6.04 us per frame, the
-            // two-kernel path 5.99)
-            // (round 4, 512-frame launches: with 256 clients and more, chains of 16 still leave 8192 waves and repeat half as
-            // many warm-up transforms: 93.4 -> 94.6 GS/s on the 256-client shape, same box, interleaved twice)
-            int K = c->demod_chain_k > 0 ? c->demod_chain_k : (nact >= 256 && (unsigned)nact * (unsigned)((nframes + 15) / 16) >= 8192u ? 16 : 8);
-            if (c->demod_chain_k <= 0)
-                while (K > 4 && (unsigned)nact * (unsigned)((nframes + K - 1) / K) < 1024u) K >>= 1;
+            // client (demod.h)
+            const int K = chain_k(nact);
             const unsigned items = (unsigned)nact * (unsigned)((nframes + K - 1) / K);
             const unsigned W = c->n == 360 ? 4u : 1u;
             const size_t lds = (size_t)(1 + W) * c->n * sizeof(cf);
@@ -254,38 +334,46 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
                                        c->side, ar, nact, KF);
             }
             ola_done = true;
-        } else if (fixed_plan) {
-            // compile-time plans (demod.h): 360 = 8*9*5, 720 = 8*9*10; W items per work-group in
-            // the 15 KiB of LDS an FFT pass leaves free on a CU
-            const unsigned items = (unsigned)nact * (unsigned)nframes;
-            const unsigned W = c->n == 360 ? 4u : 1u;
-            const size_t lds = (size_t)(1 + W) * c->n * sizeof(cf);
-            if (c->n == 360)
-                hipLaunchKernelGGL((k_demod_idft_fixed<360, 8, 9, 5>), dim3((items + W - 1) / W), dim3(64 * W), lds,
-                                   c->side, a, nact);
-            else
-                hipLaunchKernelGGL((k_demod_idft_fixed<720, 8, 9, 10>), dim3((items + W - 1) / W), dim3(64 * W), lds,
-                                   c->side, a, nact);
-        } else if (c->n <= 512) {
-            // one wave per (client, frame), no work-group barriers (demod.h)
-            const unsigned items = (unsigned)nact * (unsigned)nframes;
-            const size_t lds = (size_t)(2 * PSDR_IDFT_WAVES + 1) * c->n * sizeof(cf);
-            hipLaunchKernelGGL(k_demod_idft_wave, dim3((items + PSDR_IDFT_WAVES - 1) / PSDR_IDFT_WAVES),
-                               dim3(64 * PSDR_IDFT_WAVES), lds, c->side, a, nact);
         } else {
-            if (c->idft_lds > 64 * 1024 && c->lds_attr_done.insert((const void *)k_demod_idft).second)
-                HIPCHK(hipFuncSetAttribute((const void *)k_demod_idft, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->idft_lds));
-            hipLaunchKernelGGL(k_demod_idft, dim3(nact, nframes), dim3(c->idft_threads), c->idft_lds, c->side,
-                               a);
+            PSDRCHK(launch_idft(a, nact));
         }
         HIPCHK(hipGetLastError());
     }
-    if (!ola_done) {
+    if (nact > 0 && !ola_done) {
         ProfScope ps(c, K_OLA, c->side);
         const unsigned items = (unsigned)nact * (unsigned)((nframes + PSDR_OLA_FG - 1) / PSDR_OLA_FG);
         hipLaunchKernelGGL(k_demod_ola, dim3((items + 3) / 4), dim3(256), 0, c->side, a, nact);
         if (can_be_nonfinite) hipLaunchKernelGGL(k_demod_ola_seq, dim3(((unsigned)nact + 3) / 4), dim3(256), 0, c->side, a, nact);
         HIPCHK(hipGetLastError());
+    }
+    if (niq > 0) {
+        // the PSDR_IQ clients: launches of their own behind the others', on the same stream (demod.h)
+        DemodArgs ai = a;
+        ai.clients = d_clients + iq_off;
+        if (fixed_plan && c->demod_chain) {
+            ProfScope ps(c, K_IDFT, c->side);
+            const int K = chain_k(niq);
+            const unsigned items = (unsigned)niq * (unsigned)((nframes + K - 1) / K);
+            const unsigned W = c->n == 360 ? 4u : 1u;
+            const size_t lds = (size_t)(1 + W) * c->n * sizeof(cf);
+            if (c->n == 360)
+                hipLaunchKernelGGL((k_demod_chain_iq<360, 8, 9, 5>), dim3((items + W - 1) / W), dim3(64 * W), lds,
+                                   c->side, ai, niq, K, c->d_iq);
+            else
+                hipLaunchKernelGGL((k_demod_chain_iq<720, 8, 9, 10>), dim3((items + W - 1) / W), dim3(64 * W), lds,
+                                   c->side, ai, niq, K, c->d_iq);
+            HIPCHK(hipGetLastError());
+        } else {
+            {
+                ProfScope ps(c, K_IDFT, c->side);
+                PSDRCHK(launch_idft(ai, niq));
+                HIPCHK(hipGetLastError());
+            }
+            ProfScope ps(c, K_OLA, c->side);
+            const unsigned items = (unsigned)niq * (unsigned)((nframes + PSDR_OLA_FG - 1) / PSDR_OLA_FG);
+            hipLaunchKernelGGL(k_demod_ola_iq, dim3((items + 3) / 4), dim3(256), 0, c->side, ai, niq, c->d_iq);
+            HIPCHK(hipGetLastError());
+        }
     }
     hipStream_t last_user = c->side;
     if (c->post_on && nact > 0) {
@@ -305,10 +393,23 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
 // A slot whose client attached AFTER the last demodulation batch holds the previous occupant's results (or
 // nothing): the reference's per-client task would not exist for that frame either (src/websocket.cpp:156-185 walks
 // signal_slices at the time of the frame).  PSDR_ERR_NO_DATA, nothing is copied.
-static int slot_in_last_batch(psdr_ctx *c, int id) {
+// ... and a batch demodulated as PSDR_IQ holds complex rows and no audio / PCM, any other batch no IQ rows (want_iq:
+// the caller asks for IQ rows)
+static int slot_in_last_batch(psdr_ctx *c, int id, bool want_iq = false) {
     std::lock_guard<std::mutex> lk(c->mtx);
     if (c->demod_seq == 0 || c->aslots[id].last_seq != c->demod_seq)
         return fail(PSDR_ERR_NO_DATA, "client %d was not part of the last demodulation batch", id);
+    if ((c->aslots[id].b_mode == PSDR_IQ) != want_iq)
+        return fail(PSDR_ERR_NO_DATA, want_iq ? "client %d was not demodulated as PSDR_IQ in the last batch" : "client %d was demodulated as PSDR_IQ in the last batch: psdr_read_iq", id);
+    return PSDR_OK;
+}
+// the same for a fetched set
+static int slot_in_fetched_set(psdr_ctx *c, const psdr_ctx::FetchSet *fs, int id, bool want_iq) {
+    // (a slot handed to a new client since the batch was demodulated holds the previous occupant's rows: not this client's)
+    if ((size_t)id >= fs->win.size() || fs->win[id].last_seq != fs->seq || fs->win[id].born != c->aslots[id].born)
+        return fail(PSDR_ERR_NO_DATA, "client %d was not part of the fetched batch", id);
+    if ((fs->win[id].mode == PSDR_IQ) != want_iq)
+        return fail(PSDR_ERR_NO_DATA, want_iq ? "client %d was not demodulated as PSDR_IQ in the fetched batch" : "client %d was demodulated as PSDR_IQ in the fetched batch: psdr_fetched_iq", id);
     return PSDR_OK;
 }
 
@@ -328,8 +429,8 @@ int psdr::fetch_guard_wait(psdr_ctx *c, hipStream_t st, hipEvent_t ev) {
 }
 extern "C" int psdr_fetch_begin(psdr_ctx *c, unsigned what) {
     if (!c) return fail(PSDR_ERR_INVALID, "null argument");
-    if (what == 0 || (what & ~(PSDR_FETCH_AUDIO | PSDR_FETCH_PCM | PSDR_FETCH_WATERFALL))) return fail(PSDR_ERR_INVALID, "PSDR_FETCH_* bits 0x%x", what);
-    const bool want_audio = (what & (PSDR_FETCH_AUDIO | PSDR_FETCH_PCM)) != 0;
+    if (what == 0 || (what & ~(PSDR_FETCH_AUDIO | PSDR_FETCH_PCM | PSDR_FETCH_WATERFALL | PSDR_FETCH_IQ))) return fail(PSDR_ERR_INVALID, "PSDR_FETCH_* bits 0x%x", what);
+    const bool want_audio = (what & (PSDR_FETCH_AUDIO | PSDR_FETCH_PCM | PSDR_FETCH_IQ)) != 0;
     if (want_audio && c->n <= 0) return fail(PSDR_ERR_STATE, "context created with audio_fft_size 0");
     const size_t F = (size_t)c->last_demod_frames, h = (size_t)c->n / 2, mb = (size_t)c->max_batch, S = c->aslots.size();
     if (want_audio && (F == 0 || c->demod_seq == 0)) return fail(PSDR_ERR_STATE, "no demodulated batch to fetch");
@@ -354,6 +455,7 @@ extern "C" int psdr_fetch_begin(psdr_ctx *c, unsigned what) {
     if ((what & PSDR_FETCH_AUDIO) && !fs.audio) PSDRCHK(fs.audio.alloc(S * mb * h));
     if ((what & PSDR_FETCH_PCM) && !fs.pcm) PSDRCHK(fs.pcm.alloc(S * mb * h));
     size_t wf_bytes = 0;
+    int iq_lo = (int)S, iq_hi = -1;  // PSDR_FETCH_IQ: the span from the lowest to the highest slot that was IQ in the batch
     {
         std::lock_guard<std::mutex> lk(c->mtx);
         fs.win.resize(S);
@@ -361,12 +463,23 @@ extern "C" int psdr_fetch_begin(psdr_ctx *c, unsigned what) {
             const AudioSlot &sl = c->aslots[i];
             fs.win[i].last_seq = sl.active ? sl.last_seq : 0;
             fs.win[i].born = sl.born;
-            fs.win[i].l = sl.b_l, fs.win[i].r = sl.b_r, fs.win[i].mid = sl.b_mid;
+            fs.win[i].l = sl.b_l, fs.win[i].r = sl.b_r, fs.win[i].mid = sl.b_mid, fs.win[i].mode = sl.b_mode;
+            if ((what & PSDR_FETCH_IQ) && sl.active && sl.last_seq == c->demod_seq && sl.b_mode == PSDR_IQ) {
+                iq_lo = std::min(iq_lo, (int)i);
+                iq_hi = (int)i;
+            }
         }
         fs.wfm.assign(c->wslots.begin(), c->wslots.end());
         if (what & PSDR_FETCH_WATERFALL)
             for (const WfSlot &w : fs.wfm)
                 if (w.active && w.nsent > 0) wf_bytes = std::max(wf_bytes, (w.out_off + (size_t)w.nsent * (size_t)(w.b_r - w.b_l) + 15) & ~(size_t)15);
+    }
+    fs.iq_lo = iq_hi < 0 ? 0 : iq_lo;
+    fs.iq_n = iq_hi < 0 ? 0 : iq_hi - iq_lo + 1;
+    fs.iq_bytes = 0;
+    if ((size_t)fs.iq_n > fs.iq_cap) {
+        PSDRCHK(fs.iq.alloc((size_t)fs.iq_n * mb * h));
+        fs.iq_cap = (size_t)fs.iq_n;
     }
     if (wf_bytes > fs.wf_cap) {
         PSDRCHK(fs.wf.alloc(wf_bytes));  // (the old rows are given up only once the new buffer exists)
@@ -393,6 +506,16 @@ extern "C" int psdr_fetch_begin(psdr_ctx *c, unsigned what) {
         HIPCHK(rows_d2h(fs.pwr, c->d_pwr, sizeof(float)));
         HIPCHK(rows_d2h(fs.nan, c->d_nan, sizeof(int32_t)));
         if (what & PSDR_FETCH_AUDIO) HIPCHK(rows_d2h(fs.audio, c->d_audio, h * sizeof(float)));
+        if (fs.iq_n > 0) {
+            // the IQ rows of the span's slots only (the pools alternate with the audio's: ev_audio guards this set's too)
+            const size_t rb = h * sizeof(cf), nsl = (size_t)fs.iq_n;
+            const cf *src = c->d_iq + (size_t)fs.iq_lo * mb * h;
+            if (F == mb)
+                HIPCHK(hipMemcpyAsync(fs.iq, src, nsl * mb * rb, hipMemcpyDeviceToHost, fst));
+            else
+                HIPCHK(hipMemcpy2DAsync(fs.iq, mb * rb, src, mb * rb, F * rb, nsl, hipMemcpyDeviceToHost, fst));
+            fs.iq_bytes = nsl * F * rb;
+        }
         HIPCHK(hipEventRecord(fs.ev_audio, fst));
         c->guard_audio[c->out_set] = fs.ev_audio;
     }
@@ -459,7 +582,7 @@ extern "C" int psdr_fetch_batch(psdr_ctx *c) {
         int rc = drain(c);
         if (rc) return rc;
     }
-    int rc = psdr_fetch_begin(c, PSDR_FETCH_AUDIO | (c->post_on ? PSDR_FETCH_PCM : 0u) | PSDR_FETCH_WATERFALL);
+    int rc = psdr_fetch_begin(c, PSDR_FETCH_AUDIO | (c->post_on ? PSDR_FETCH_PCM : 0u) | PSDR_FETCH_WATERFALL | (c->d_iq ? PSDR_FETCH_IQ : 0u));
     if (rc) return rc;
     return psdr_fetch_end(c);
 }
@@ -493,9 +616,7 @@ extern "C" int psdr_fetched_audio(psdr_ctx *c, int id, int frame, const float **
         if (rc) return rc;
         if ((rc = fetched_set(c, &fs))) return rc;
         if (fs->seq == 0) return fail(PSDR_ERR_STATE, "the fetched batch carries no audio (PSDR_FETCH_AUDIO / _PCM)");
-        // (a slot handed to a new client since the batch was demodulated holds the previous occupant's rows: not this client's)
-        if ((size_t)id >= fs->win.size() || fs->win[id].last_seq != fs->seq || fs->win[id].born != c->aslots[id].born)
-            return fail(PSDR_ERR_NO_DATA, "client %d was not part of the fetched batch", id);
+        if ((rc = slot_in_fetched_set(c, fs, id, false))) return rc;
     }
     if (frame < 0 || frame >= fs->frames) return fail(PSDR_ERR_INVALID, "frame %d not in the fetched batch of %d", frame, fs->frames);
     const size_t h = (size_t)c->n / 2, mb = (size_t)c->max_batch, row = (size_t)id * mb + (size_t)frame;
@@ -515,12 +636,42 @@ extern "C" int psdr_fetched_pcm16(psdr_ctx *c, int id, int frame, const int16_t 
         if ((rc = fetched_set(c, &fs))) return rc;
         if (fs->seq == 0 || !(fs->what & PSDR_FETCH_PCM)) return fail(PSDR_ERR_STATE, "the fetched batch carries no PCM (PSDR_FETCH_PCM)");
         if (!fs->pcm16) return fail(PSDR_ERR_STATE, "the fetched PCM rows are int32 (PSDR_OPT_POST_CHAIN_PCM16 was 0 for that batch): psdr_fetched_audio");
-        if ((size_t)id >= fs->win.size() || fs->win[id].last_seq != fs->seq || fs->win[id].born != c->aslots[id].born)
-            return fail(PSDR_ERR_NO_DATA, "client %d was not part of the fetched batch", id);
+        if ((rc = slot_in_fetched_set(c, fs, id, false))) return rc;
     }
     if (frame < 0 || frame >= fs->frames) return fail(PSDR_ERR_INVALID, "frame %d not in the fetched batch of %d", frame, fs->frames);
     const size_t h = (size_t)c->n / 2, mb = (size_t)c->max_batch, row = (size_t)id * mb + (size_t)frame;
     *pcm = reinterpret_cast<const int16_t *>(fs->pcm.get()) + row * h;
+    return PSDR_OK;
+}
+extern "C" int psdr_fetched_iq(psdr_ctx *c, int id, int frame, const float **iq, float *pwr, int32_t *nan_flag) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    const psdr_ctx::FetchSet *fs = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);
+        int rc = check_slot(c, id);
+        if (rc) return rc;
+        if ((rc = fetched_set(c, &fs))) return rc;
+        if (fs->seq == 0) return fail(PSDR_ERR_STATE, "the fetched batch carries no audio (PSDR_FETCH_AUDIO / _PCM / _IQ)");
+        if ((rc = slot_in_fetched_set(c, fs, id, true))) return rc;
+    }
+    if (frame < 0 || frame >= fs->frames) return fail(PSDR_ERR_INVALID, "frame %d not in the fetched batch of %d", frame, fs->frames);
+    const size_t h = (size_t)c->n / 2, mb = (size_t)c->max_batch, row = (size_t)id * mb + (size_t)frame;
+    // (an IQ slot of a set fetched with PSDR_FETCH_IQ lies inside the span by construction)
+    const bool have = (fs->what & PSDR_FETCH_IQ) && id >= fs->iq_lo && id < fs->iq_lo + fs->iq_n;
+    if (iq) *iq = have ? reinterpret_cast<const float *>(fs->iq.get() + ((size_t)(id - fs->iq_lo) * mb + (size_t)frame) * h) : nullptr;
+    if (pwr) *pwr = fs->pwr[row];
+    if (nan_flag) *nan_flag = fs->nan[row];
+    return PSDR_OK;
+}
+extern "C" int psdr_fetched_iq_span(psdr_ctx *c, int *first_slot, int *nslots, size_t *bytes) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    const psdr_ctx::FetchSet *fs = nullptr;
+    int rc = fetched_set(c, &fs);
+    if (rc) return rc;
+    if (!(fs->what & PSDR_FETCH_IQ)) return fail(PSDR_ERR_STATE, "the fetched batch carries no IQ rows (PSDR_FETCH_IQ)");
+    if (first_slot) *first_slot = fs->iq_lo;
+    if (nslots) *nslots = fs->iq_n;
+    if (bytes) *bytes = fs->iq_bytes;
     return PSDR_OK;
 }
 extern "C" int psdr_fetched_waterfall(psdr_ctx *c, int id, const int8_t **rows, int *nsent_out, int *level_out, int *l_out, int *r_out) {
@@ -641,6 +792,42 @@ extern "C" int psdr_audio_device_ptr(psdr_ctx *c, int id, const float **d_audio,
     if (id < 0 || id >= (int)c->aslots.size()) return fail(PSDR_ERR_INVALID, "bad id %d", id);
     const size_t h = (size_t)c->n / 2, mb = (size_t)c->max_batch;
     if (d_audio) *d_audio = c->d_audio + (size_t)id * mb * h;
+    if (d_pwr) *d_pwr = c->d_pwr + (size_t)id * mb;
+    return PSDR_OK;
+}
+extern "C" int psdr_read_iq(psdr_ctx *c, int id, int nframes, float *iq, float *pwr, int32_t *nan_flags, int *nframes_out) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);
+        int rc = check_slot(c, id);
+        if (rc) return rc;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    const size_t F = (size_t)c->last_demod_frames, h = (size_t)c->n / 2, mb = (size_t)c->max_batch;
+    if (F == 0) return fail(PSDR_ERR_STATE, "no demodulated batch to read");
+    if (nframes < (int)F) return fail(PSDR_ERR_INVALID, "buffers hold %d frames, the last batch has %zu", nframes, F);
+    if (nframes_out) *nframes_out = (int)F;
+    {
+        int rc = slot_in_last_batch(c, id, true);
+        if (rc) return rc;
+        rc = drain(c);
+        if (rc) return rc;
+    }
+    if (iq)
+        HIPCHK(hipMemcpyAsync(iq, c->d_iq + (size_t)id * mb * h, F * h * sizeof(cf), hipMemcpyDeviceToHost, c->stream));
+    if (pwr)
+        HIPCHK(hipMemcpyAsync(pwr, c->d_pwr + (size_t)id * mb, F * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (nan_flags)
+        HIPCHK(hipMemcpyAsync(nan_flags, c->d_nan + (size_t)id * mb, F * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return PSDR_OK;
+}
+extern "C" int psdr_iq_device_ptr(psdr_ctx *c, int id, const float **d_iq, const float **d_pwr) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    if (id < 0 || id >= (int)c->aslots.size()) return fail(PSDR_ERR_INVALID, "bad id %d", id);
+    if (!c->d_iq) return fail(PSDR_ERR_NO_DATA, "no batch with a PSDR_IQ client has been demodulated");
+    const size_t h = (size_t)c->n / 2, mb = (size_t)c->max_batch;
+    if (d_iq) *d_iq = reinterpret_cast<const float *>(c->d_iq + (size_t)id * mb * h);
     if (d_pwr) *d_pwr = c->d_pwr + (size_t)id * mb;
     return PSDR_OK;
 }
