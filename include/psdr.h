@@ -57,8 +57,9 @@ typedef enum psdr_format {
 /* demodulation_mode, src/client.h:43 */
 /* PSDR_IQ (no counterpart in the reference's enum: its raw SIGNAL shortcut and its PLL over this baseband,
  * src/signal.cpp:110-115, 242-252, are disabled there): the client's output is the complex baseband itself, see
- * psdr_read_iq below */
-typedef enum psdr_mode { PSDR_USB = 0, PSDR_LSB = 1, PSDR_AM = 2, PSDR_FM = 3, PSDR_IQ = 4 } psdr_mode;
+ * psdr_read_iq below.  PSDR_SAM: synchronous AM - AM's baseband detected against the recovered carrier (the reference's
+ * HAS_LIQUID carrier transform, src/signal.cpp:205-222, without its PLL), see psdr_read_carrier below */
+typedef enum psdr_mode { PSDR_USB = 0, PSDR_LSB = 1, PSDR_AM = 2, PSDR_FM = 3, PSDR_IQ = 4, PSDR_SAM = 5 } psdr_mode;
 
 typedef struct psdr_config {
     uint32_t struct_size;        /* = sizeof(psdr_config) */
@@ -160,7 +161,9 @@ int psdr_client_on_window_message(psdr_ctx *ctx, int id, int l, double audio_mid
 /* AudioClient::set_audio_demodulation / on_demodulation_message (src/signal.cpp:95-97,316-328).
  * The first PSDR_IQ of a context allocates the IQ rows: two sets of 8 * (audio_fft_size/2) bytes per client slot and
  * batch frame, i.e. 16 * (audio_fft_size/2) * max_clients * max_batch bytes in all (a context that never sees an IQ client
- * allocates none); PSDR_ERR_NOMEM, and the mode unchanged, if that fails. */
+ * allocates none); PSDR_ERR_NOMEM, and the mode unchanged, if that fails.  The first PSDR_SAM allocates the carrier tails
+ * (16 * (audio_fft_size/2) bytes per client slot) and two sets of carrier records (8 bytes per client slot and batch
+ * frame each), all or none, with the same answer on failure; PSDR_ERR_STATE if the context's audio_rate is not positive. */
 int psdr_client_set_audio_demodulation(psdr_ctx *ctx, int id, int mode);
 /* signal_loop's slow-client rule (src/websocket.cpp:170-176): the reference does not call send_audio at all for a
  * client with more than 50 kB queued on its socket, so NOTHING of that client moves for the frame - overlap-add tails and
@@ -214,8 +217,8 @@ int psdr_demod_batch_from_band_region(psdr_ctx *ctx, const float *d_region, size
  * (PSDR_ERR_INVALID otherwise, nothing is written); *nframes_out (may be NULL) = rows written. */
 int psdr_read_audio(psdr_ctx *ctx, int id, int nframes, float *audio, float *pwr, int32_t *nan_flags,
                     int *nframes_out);
-/* PSDR_IQ - the overlap-added complex baseband at the audio rate as the client's output (external decoders, client-side
- * synchronous AM, stereo / RDS).  With n = audio_fft_size, h = n/2, frame f of an IQ client is h complex samples
+/* PSDR_IQ - the overlap-added complex baseband at the audio rate as the client's output (external decoders,
+ * stereo / RDS; synchronous AM is a mode of its own, PSDR_SAM).  With n = audio_fft_size, h = n/2, frame f of an IQ client is h complex samples
  *   IQ_f[j] = s_f y_f[j] + s_{f-1} y_{f-1}[h + j],  j < h
  * y_f: the UN-NORMALISED n-point backward DFT of the AM / FM bin placement (src/signal.cpp:175-198, 214), s_f: the flip sign
  * of :223-234 - exactly what AM and FM detect (audio_complex_baseband after :235-237), interleaved re, im.  pwr is the
@@ -231,6 +234,38 @@ int psdr_read_audio(psdr_ctx *ctx, int id, int nframes, float *audio, float *pwr
  * batch to batch: the pointer is good for that batch only; PSDR_ERR_NO_DATA before the context's first IQ client). */
 int psdr_read_iq(psdr_ctx *ctx, int id, int nframes, float *iq, float *pwr, int32_t *nan_flags, int *nframes_out);
 int psdr_iq_device_ptr(psdr_ctx *ctx, int id, const float **d_iq, const float **d_pwr);
+/* PSDR_SAM - synchronous AM: detection against the recovered carrier instead of the envelope (at modulation index 1.5 the
+ * envelope detector leaves a second harmonic at 0.23 of the fundamental, this one 1.3e-4).  A SAM client is an ordinary
+ * AUDIO client - audio rows, pwr, NaN flags, the post chain (DC blocker, AGC, PCM / PCM16), read and fetched like an AM
+ * client - only the detector differs.  With n = audio_fft_size, h = n/2, the AM / FM / IQ placement, flip sign s_f and
+ * state:
+ *   Baseband.  B_f[j] = s_f y_f[j] + s_{f-1} y_{f-1}[h + j] is the baseband AM detects, bit-identical to the PSDR_IQ rows of
+ *     a client on the same window (same transform code, same operation order).
+ *   Carrier transform.  c_f = the un-normalised n-point backward DFT of the same placed bins with indices
+ *     [cutoff, n - cutoff) zeroed, cutoff = 500 * n / audio_rate in integer division (src/signal.cpp:217-220).  If
+ *     2 * cutoff >= n nothing is zeroed (the reference's std::fill would be undefined there); if cutoff = 0 everything is.
+ *   Carrier baseband.  C_f[j] = s_f c_f[j] + s_{f-1} c_{f-1}[h + j].
+ *   Audio.  audio_f[j] = (B.re * C.re + B.im * C.im) / |C| at index j, |C| = sqrtf(C.re^2 + C.im^2); where |C| == 0,
+ *     audio_f[j] = B.re (the phase reference is 1).  Every operation is a correctly rounded f32 one (no fast division, no
+ *     fused product) in this order, and no batch split changes a bit.
+ *   NaN flag.  1 if any audio sample of the frame is NaN; the state moves before the guard, as for AM / FM.
+ *   State.  The AM / FM state (the tail, the last sample) moves exactly as in AM, the USB / LSB tail is copied through; the
+ *     one new piece is the carrier tail s_f c_f[h..n), [2][slots][h] complex.  A slot that was not demodulated as SAM in its
+ *     previous batch (a fresh slot; USB / LSB / AM / FM / IQ in between) starts from a ZERO carrier tail, not a stale one -
+ *     only the phase of C is used, so this warm-up of one frame is benign.  A paused slot keeps everything frozen.  Switching
+ *     among all six modes at batch boundaries leaves the other modes' streams continuous.
+ *   Carrier record.  Per frame two floats, what a front end needs for a lock indicator and auto-tune:
+ *     level = mean over j < h of |C_f[j]|;  offset_hz = audio_rate / (2 pi) * atan2f(Im S, Re S),
+ *     S = sum over j < h - 1 of C[j+1] * conj(C[j]): positive when the carrier sits above the centre of bin
+ *     floor(audio_mid), 0 when S = 0.
+ * n = 360 / 720 run the transform's compile-time plan twice per frame, any other n (and PSDR_DEMOD_CHAIN=0) sums the kept
+ * bins directly: the two paths may differ in the carrier's last bits, never in B.
+ * psdr_read_carrier: level / offset_hz [nframes] (either may be NULL), otherwise the contract of psdr_read_audio;
+ * PSDR_ERR_NO_DATA for a slot whose batch was not SAM.  psdr_fetched_carrier answers from the fetched set: a fetch that
+ * carries audio, PCM or IQ also copies the carrier records, ONE extra copy of the span from the lowest to the highest SAM
+ * slot of the batch. */
+int psdr_read_carrier(psdr_ctx *ctx, int id, int nframes, float *level, float *offset_hz, int *nframes_out);
+int psdr_fetched_carrier(psdr_ctx *ctx, int id, int frame, float *level, float *offset_hz);
 /* A client added after the last psdr_demod_batch has no results in it (the reference's frame loop would not
  * have posted a task for it either, src/websocket.cpp:156-185): psdr_read_audio / psdr_read_pcm / psdr_fetched_audio
  * return PSDR_ERR_NO_DATA for such a slot instead of the previous occupant's samples.
@@ -437,7 +472,8 @@ psdr_ctx *psdr_group_ctx(psdr_group *g, int rank);
  * does not have); and psdr_group_fetched_audio answers PSDR_ERR_NO_DATA until the new device has demodulated a batch.
  * psdr_group_client_rank: the rank (index into `devices`) a client lives on now, -1 for an unknown gid. */
 /* PSDR_IQ is not served through a group (its rows are neither migrated nor fetched by gid): psdr_group_client_add and
- * psdr_group_client_set_audio_demodulation answer PSDR_ERR_UNSUPPORTED for it. */
+ * psdr_group_client_set_audio_demodulation answer PSDR_ERR_UNSUPPORTED for it.  The same holds for PSDR_SAM: the carrier
+ * tail is not migrated and the carrier records are not fetched by gid. */
 int psdr_group_client_add(psdr_group *g, int l, double audio_mid, int r, int mode, int *gid_out);
 int psdr_group_client_remove(psdr_group *g, int gid);
 int psdr_group_client_set_audio_range(psdr_group *g, int gid, int l, double audio_mid, int r);

@@ -78,6 +78,8 @@ SYMBOLS = [
     ("psdr_read_iq", _i, [_vp, _i, _i, _vp, _vp, _vp, C.POINTER(_i)]),
     ("psdr_iq_device_ptr", _i, [_vp, _i, _pp, _pp]),
     ("psdr_fetched_iq", _i, [_vp, _i, _i, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
+    ("psdr_read_carrier", _i, [_vp, _i, _i, _vp, _vp, C.POINTER(_i)]),
+    ("psdr_fetched_carrier", _i, [_vp, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     ("psdr_fetched_iq_span", _i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_sz)]),
     ("psdr_set_post_chain", _i, [_vp, _i]),
     ("psdr_set_option", _i, [_vp, _i, _i]),

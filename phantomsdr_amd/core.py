@@ -23,7 +23,8 @@ FORMAT_DTYPES = {"u8": np.uint8, "s8": np.int8, "u16": np.uint16, "s16": np.int1
                  "f32": np.float32, "f64": np.float64}
 USB, LSB, AM, FM = 0, 1, 2, 3
 IQ = 4  # PSDR_IQ (include/psdr.h): the overlap-added complex baseband itself as the client's output
-MODES = {"USB": USB, "LSB": LSB, "AM": AM, "FM": FM, "IQ": IQ}
+SAM = 5  # PSDR_SAM: synchronous AM, detection against the recovered carrier (audio like AM, plus carrier records)
+MODES = {"USB": USB, "LSB": LSB, "AM": AM, "FM": FM, "IQ": IQ, "SAM": SAM}
 # psdr_wf_detector (include/psdr.h): what a sent waterfall row shows of the frames since the previous one
 WF_SAMPLE, WF_PEAK, WF_MEAN = 0, 1, 2
 WF_DETECTORS = {"sample": WF_SAMPLE, "peak": WF_PEAK, "mean": WF_MEAN}
@@ -215,6 +216,12 @@ class Context:
         check(self.lib.psdr_fetched_iq(self.h, int(cid), int(frame), C.byref(p), C.byref(pw), C.byref(nan)))
         iq = np.ctypeslib.as_array(p, shape=(self.cfg.audio_fft_size,)).copy().view(np.complex64) if p else None
         return iq, pw.value, nan.value
+
+    def fetched_carrier(self, cid, frame):
+        """(level, offset_hz) of one frame of a SAM client in the fetched batch (psdr.h: psdr_fetched_carrier)"""
+        lv, off = C.c_float(0), C.c_float(0)
+        check(self.lib.psdr_fetched_carrier(self.h, int(cid), int(frame), C.byref(lv), C.byref(off)))
+        return lv.value, off.value
 
     def fetched_iq_span(self):
         """(first slot, slots, bytes) the fetched batch's IQ copy covered (psdr.h: psdr_fetched_iq_span)"""
@@ -461,6 +468,15 @@ class AudioClient:
         got = C.c_int(0)
         check(self.ctx.lib.psdr_read_iq(self.ctx.h, self.id, F, _ptr(iq), _ptr(pwr), _ptr(nan), C.byref(got)))
         return iq[:got.value], pwr[:got.value], nan[:got.value]
+
+    def read_carrier(self, nframes=None):
+        """(level[F], offset_hz[F]) of the last demod batch of a client in SAM mode (psdr.h: psdr_read_carrier)"""
+        F = nframes or self.ctx.last_demod_frames or self.ctx.last_nframes
+        level = np.empty(F, np.float32)
+        off = np.empty(F, np.float32)
+        got = C.c_int(0)
+        check(self.ctx.lib.psdr_read_carrier(self.ctx.h, self.id, F, _ptr(level), _ptr(off), C.byref(got)))
+        return level[:got.value], off[:got.value]
 
     def read_pcm(self, nframes=None):
         """int16 PCM (in int32, like the reference's buffer) of the last demod batch after the

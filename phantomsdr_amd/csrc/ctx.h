@@ -72,7 +72,8 @@ struct AudioSlot {
     uint64_t last_seq = 0;  // the demodulation batch (ctx->demod_seq) that last included this slot; 0: none yet
     int b_l = 0, b_r = 0;   // the window that batch was demodulated with (psdr_fetch_begin copies it into its FetchSet)
     double b_mid = 0;
-    int b_mode = PSDR_USB;  // ... and the mode: a batch demodulated as PSDR_IQ left complex rows (iq_pool) and no audio / PCM
+    int b_mode = PSDR_USB;  // ... and the mode: a batch demodulated as PSDR_IQ left complex rows (iq_pool) and no audio / PCM; one
+                            // demodulated as PSDR_SAM left carrier records and a carrier tail the next SAM batch continues
     uint64_t born = 0;      // psdr_client_add's serial number: a fetched set answers only for the occupant it was filled with
 };
 struct WfSlot {
@@ -284,6 +285,11 @@ struct psdr_ctx {
     // when a client is first set to PSDR_IQ (psdr_client_set_audio_demodulation, under mtx) and kept; d_iq: the last batch's
     DevBuf<cf> iq_pool[2];
     cf *d_iq = nullptr;
+    // PSDR_SAM clients (demod.h): the carrier tail [2][slots][n/2] beside bb_tail, and the carrier records
+    // [slot][max_batch] (level, offset_hz) in two pools that alternate with out_set; allocated together when a client is
+    // first set to PSDR_SAM (under mtx) and kept.  d_car: the last batch's records
+    DevBuf<cf> d_car_tail, car_pool[2];
+    cf *d_car = nullptr;
     DevBuf<unsigned> d_ssb_mark;  // [slots] DemodArgs::ssb_mark (demod.h): USB / LSB batches that need the frame-ordered NaN guard
     ParamRing client_ring;
     int last_demod_frames = 0;
@@ -302,6 +308,10 @@ struct psdr_ctx {
         HostBuf<cf> iq;
         size_t iq_cap = 0, iq_bytes = 0;  // slots the buffer holds; bytes the fetch's IQ copy moved
         int iq_lo = 0, iq_n = 0;
+        // the carrier records [slot - car_lo][max_batch] of the car_n slots from the lowest to the highest that were SAM
+        HostBuf<cf> car;
+        size_t car_cap = 0;
+        int car_lo = 0, car_n = 0;
         Event done;                      // every copy of the fetch on the first copy stream has landed
         Event ev_pcm;                    // ... and the PCM (its own copy stream: it waits for the post chain, up to two steps late)
         bool has_pcm = false;

@@ -12,8 +12,9 @@
 //                 FM polar discriminator (src/utils/dsp.cpp:27-35), NaN guard (:266-271)
 //                 and the state carried to the next batch (:200-203, :273-275).
 // The AM "carrier" transform (:205-222,230-241) feeds only the liquid-dsp PLL branch
-// (:242-252), which is not part of the parity target; without liquid it has no
-// observable effect and is not computed.
+// (:242-252), which is not part of the parity target: USB / LSB / AM / FM / IQ clients do not
+// compute it.  PSDR_SAM clients do (k_demod_chain_sam / k_demod_ola_sam at the end of this
+// file): the carrier baseband is their phase reference, feed-forward, in place of the PLL.
 //
 // n = audio_fft_size is any multiple of 4 (248, 360, 720, 10068 ...): the transform is
 // a generic-radix Stockham, each radix-R butterfly a direct R-point DFT whose
@@ -1110,6 +1111,286 @@ __global__ __launch_bounds__(256) void k_demod_ola_iq(DemodArgs a, int nact, cf 
         }
         const int any_nan = __any(s_nan);
         if (tid == 0) a.nan_flags[srow * a.max_batch + f] = any_nan ? 1 : 0;
+    }
+}
+
+// ---- PSDR_SAM: synchronous AM, the baseband detected against the recovered carrier -------------------------------
+// The reference's HAS_LIQUID branch (src/signal.cpp:205-222, 230-233, 238-252) transforms the placed bins a second time
+// with the indices [cutoff, n - cutoff) zeroed (cutoff = 500 n / audio_rate: a +-500 Hz low-pass around bin
+// floor(audio_mid)), overlap-adds that "carrier" baseband C with a tail of its own and feeds B and C to liquid's PLL.  Here
+// C is the phase reference itself, feed-forward:
+//   audio_f[j] = (B.re C.re + B.im C.im) / |C|   (|C| == 0: B.re),  B = the PSDR_IQ row, C_f[j] = s_f c_f[j] + s_{f-1} c_{f-1}[h + j]
+// every operation correctly rounded and in a fixed order (sam_detect), so no batch split changes a bit.  SAM clients are
+// listed apart (a.clients = their list, nact = their number), like IQ clients.  State: bb_tail / bb_last / real_prev as
+// AM, plus the carrier tail s_f c_f[h..n) in SamArgs::car_tail [2][slots][h]; the host zeroes the current half for a slot
+// whose previous batch was not SAM.  Per frame one carrier record (level, offset_hz) in car_rec[slot][max_batch]:
+//   level = mean_j |C[j]|,  offset_hz = hz_per_rad * arg( sum_{1 <= j < h} C[j] conj(C[j-1]) )
+struct SamArgs {
+    cf *car_tail;      // [2][slots][n/2]
+    cf *car_rec;       // [slots][max_batch] (level, offset_hz)
+    int cutoff;        // placed indices [cutoff, n - cutoff) are zeroed: slice bin t is kept iff -cutoff <= t - m < cutoff
+    float hz_per_rad;  // audio_rate / (2 pi)
+};
+__device__ __forceinline__ float sam_detect(cf b, cf c, float &mag) {
+    mag = __fsqrt_rn(__fadd_rn(__fmul_rn(c.x, c.x), __fmul_rn(c.y, c.y)));
+    const float num = __fadd_rn(__fmul_rn(b.x, c.x), __fmul_rn(b.y, c.y));
+    return mag == 0.f ? b.x : __fdiv_rn(num, mag);
+}
+// one term of the offset sum: c conj(p)
+__device__ __forceinline__ cf sam_lag(cf c, cf p) {
+    return make_float2(fmaf(c.x, p.x, c.y * p.y), fmaf(c.y, p.x, -(c.x * p.y)));
+}
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+// n = 360 / 720: k_demod_chain_iq's walk - one wave per chain of K frames, ONE warm-up frame, both tails (B's and C's) in
+// registers.  Per frame the compile-time plan runs twice through ONE loop body (two inlined copies would double the code
+// and the address registers): pass 0 on the masked slice gives c_f, pass 1 on the whole slice gives y_f exactly as
+// k_demod_chain_iq computes it (B is bit-identical to the PSDR_IQ rows).  The second plan run instead of a direct sum over
+// the 2 cutoff kept bins: at n = 360 and 12 kHz the direct sum is 30 bins x 6 outputs per lane = 180 complex MACs (720 FMAs
+// and as many twiddle look-ups with an index product modulo n), the plan ~250 packed instructions with base + immediate
+// addressing; at n = 720 it is 2880 FMAs against ~600.  The slice is loaded again for pass 1 (L1 / L2 hits) instead of
+// being held in 2 NR registers across pass 0.  Grid as k_demod_chain_fixed; dynamic LDS = ((1 + W) * N + W * N/2) * 8 bytes.
+template <int N, int R0, int R1, int R2>
+__global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) void k_demod_chain_sam(DemodArgs a, int nact, int K, SamArgs sa) {
+    static_assert(R0 * R1 * R2 == N, "plan");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int h = N / 2, NH = (h + 63) / 64;
+    const int lane_ = threadIdx.x & 63, wv = threadIdx.x >> 6, W = blockDim.x >> 6;
+    cf *Wn = reinterpret_cast<cf *>(smem);
+    for (int i = threadIdx.x; i < N; i += blockDim.x) Wn[i] = a.Wn[i];
+    __syncthreads();
+    const int F = a.nframes, nch = (F + K - 1) / K;
+    const int item = __builtin_amdgcn_readfirstlane((int)blockIdx.x * W + wv);
+    if (item >= nact * nch) return;
+    const int ci = item / nch, f0 = (item - ci * nch) * K;
+    const int f1 = f0 + K < F ? f0 + K : F;
+    ClientParams cp = a.clients[ci];
+    cp.l = __builtin_amdgcn_readfirstlane(cp.l);
+    cp.r = __builtin_amdgcn_readfirstlane(cp.r);
+    cp.m_floor = __builtin_amdgcn_readfirstlane(cp.m_floor);
+    cp.mode = __builtin_amdgcn_readfirstlane(cp.mode);
+    cp.slot = __builtin_amdgcn_readfirstlane(cp.slot);
+    cp.state_cur = __builtin_amdgcn_readfirstlane(cp.state_cur);
+    cf *buf = Wn + N + (size_t)wv * N;
+    const size_t srow = (size_t)cp.slot;
+    const int cur = cp.state_cur, nxt = cur ^ 1;
+    const float *rp_old = a.real_prev + ((size_t)cur * a.slots + srow) * h;
+    float *rp_new = a.real_prev + ((size_t)nxt * a.slots + srow) * h;
+    const cf *bt_old = a.bb_tail + ((size_t)cur * a.slots + srow) * h;
+    cf *bt_new = a.bb_tail + ((size_t)nxt * a.slots + srow) * h;
+    const cf *ct_old = sa.car_tail + ((size_t)cur * a.slots + srow) * h;
+    cf *ct_new = sa.car_tail + ((size_t)nxt * a.slots + srow) * h;
+    const int fs = f0 == 0 ? 0 : f0 - 1;  // the warm-up frame: transformed, nothing written
+    cf tail[NH];                          // s_{f-1} y_{f-1}[h + j], j = lane + 64 u
+    // ... and s_{f-1} c_{f-1}[h + j] in h words of LDS of the wave's own behind the transform buffers: entry j is read and
+    // written by the lane that owns j alone (no wait between lanes), once per frame
+    cf *ctail = Wn + N + (size_t)W * N + (size_t)wv * h;
+#pragma unroll
+    for (int u = 0; u < NH; u++) {
+        const int j = lane_ + 64 * u;
+        tail[u] = make_float2(0.f, 0.f);
+        if (j < h) {
+            ctail[j] = make_float2(0.f, 0.f);
+            if (fs == 0) tail[u] = bt_old[j], ctail[j] = ct_old[j];  // the batch's first frame: the carried tails
+        }
+    }
+    constexpr int NR = (N + 63) / 64;
+    constexpr int HO = NR < 3 ? NR : (N <= 512 ? 3 : 2);  // (n = 720: the registers of four more offsets are the difference to scratch)
+    unsigned so[HO];
+    idft_slice_offsets<N, HO>(a, cp, lane_, so);
+    const int m = cp.m_floor - cp.l;
+    cf cC[NH];  // C_f[j], from pass 0 of a frame to its pass 1
+#pragma unroll
+    for (int u = 0; u < NH; u++) cC[u] = make_float2(0.f, 0.f);
+    // ONE loop over (frame, pass): a single copy of the transform in the kernel, as in k_demod_chain_iq
+    for (int it = 2 * fs; it < 2 * f1; it++) {
+        const int f = it >> 1, pass = it & 1;
+        const bool emit = f >= f0;
+        const float sg = flip_frame(a.first_frame_num + (unsigned long long)f, cp.m_floor, a.is_real) ? -1.f : 1.f;
+        float *out = a.audio + (srow * a.max_batch + f) * h;
+        const bool last = (f == F - 1);
+        {
+            int ln = lane_;  // (an opaque copy per iteration: k_demod_chain_fixed says why)
+            asm volatile("" : "+v"(ln));
+            const int lane = ln;
+            cf sv[NR];  // loads first, LDS after
+            idft_load_slice_at<N, HO>(a, cp, f, so, lane, sv);
+            if (pass == 0) {
+#pragma unroll
+                for (int u = 0; u < NR; u++) {
+                    const int d = lane + 64 * u - m;
+                    if (d < -sa.cutoff || d >= sa.cutoff) sv[u] = make_float2(0.f, 0.f);
+                }
+            }
+            const float pw = idft_slice_fixed<N, R0, R1, R2>(cp, sv, buf, Wn, lane);
+            if (pass == 0) {
+#pragma unroll
+                for (int u = 0; u < NH; u++) {
+                    const int j = lane + 64 * u;
+                    cC[u] = make_float2(0.f, 0.f);
+                    if (j < h) {
+                        const cf v0 = buf[j], v1 = buf[h + j];
+                        const cf ct = ctail[j];
+                        cC[u] = make_float2(__fadd_rn(__fmul_rn(v0.x, sg), ct.x), __fadd_rn(__fmul_rn(v0.y, sg), ct.y));
+                        ctail[j] = make_float2(__fmul_rn(v1.x, sg), __fmul_rn(v1.y, sg));
+                    }
+                }
+            } else {
+                if (emit && lane == 0) a.pwr[srow * a.max_batch + f] = pw;
+                int s_nan = 0;
+                float lvl = 0.f;
+                cf lag = make_float2(0.f, 0.f), ccarry = make_float2(0.f, 0.f);
+#pragma unroll
+                for (int u = 0; u < NH; u++) {
+                    const int j = lane + 64 * u;
+                    const cf c = cC[u];
+                    cf pr = make_float2(__shfl_up(c.x, 1, 64), __shfl_up(c.y, 1, 64));  // C[j-1]
+                    if (lane == 0) pr = ccarry;
+                    ccarry = make_float2(__shfl(c.x, 63, 64), __shfl(c.y, 63, 64));
+                    if (j < h) {
+                        const cf v0 = buf[j], v1 = buf[h + j];
+                        const cf y = make_float2(__fmul_rn(v0.x, sg), __fmul_rn(v0.y, sg));
+                        const cf ynext = make_float2(__fmul_rn(v1.x, sg), __fmul_rn(v1.y, sg));
+                        const cf b = make_float2(__fadd_rn(y.x, tail[u].x), __fadd_rn(y.y, tail[u].y));  // dsp_add_complex :235
+                        float mag;
+                        const float v = sam_detect(b, c, mag);
+                        if (isnan(v)) s_nan = 1;
+                        lvl += mag;
+                        if (j > 0) {
+                            const cf t = sam_lag(c, pr);
+                            lag.x += t.x, lag.y += t.y;
+                        }
+                        if (emit) {
+                            out[j] = v;
+                            if (last) {  // the state the next batch starts from (:200-203 precede the NaN guard); USB / LSB's is kept
+                                bt_new[j] = ynext;
+                                ct_new[j] = ctail[j];
+                                rp_new[j] = rp_old[j];
+                                if (j == h - 1) a.bb_last[(size_t)nxt * a.slots + srow] = b;
+                            }
+                        }
+                        tail[u] = ynext;
+                    }
+                }
+                const int any_nan = __any(s_nan);
+                lvl = wave_sum(lvl);
+                lag.x = wave_sum(lag.x), lag.y = wave_sum(lag.y);
+                if (emit && lane == 0) {
+                    a.nan_flags[srow * a.max_batch + f] = any_nan ? 1 : 0;
+                    sa.car_rec[srow * a.max_batch + f] = make_float2(lvl / (float)h, sa.hz_per_rad * atan2f(lag.y, lag.x));
+                }
+            }
+            wave_lds_sync();  // buf is read out: the next transform may overwrite it
+        }
+    }
+}
+
+// c_f[jout] of a SAM client by the direct sum over its kept bins d = t - m in [d0, d1), read from the spectrum:
+//   sum_d X[m_floor + d] W_n^{(d mod n) jout}
+__device__ __forceinline__ cf sam_carrier_dsum(const DemodArgs &a, const ClientParams &cp, const cf *S, int d0, int d1, int jout) {
+    const unsigned n = (unsigned)a.n;
+    float ar = 0.f, ai = 0.f;
+    for (int d = d0; d < d1; d++) {
+        const cf x = S[a.lay.pos(cp.m_floor + d)];
+        const cf w = a.Wn[((unsigned)(d < 0 ? (int)n + d : d) * (unsigned)jout) % n];  // (< n^2: audio sizes stay far below 2^16)
+        ar = fmaf(x.x, w.x, fmaf(-x.y, w.y, ar));
+        ai = fmaf(x.x, w.y, fmaf(x.y, w.x, ai));
+    }
+    return make_float2(ar, ai);
+}
+
+// any other n (and n = 360 / 720 with PSDR_DEMOD_CHAIN=0): behind the IDFT kernels, with k_demod_ola_iq's grid - one wave
+// per (client, group of PSDR_OLA_FG frames).  B from the client's rows of ypost exactly as k_demod_ola_iq adds them; the
+// carrier by the direct sum above (no second ypost): c_f[j], c_{f-1}[h + j] (the batch's first frame: the carried tail)
+// and, for the batch's last frame, c_f[h + j] for the tail.  The same function wherever a value is needed: the bits do
+// not depend on the batch split or on the frame's place in its group.
+__global__ __launch_bounds__(256) void k_demod_ola_sam(DemodArgs a, int nact, SamArgs sa) {
+    constexpr int FG = PSDR_OLA_FG;
+    const int n = a.n, h = n / 2, tid = threadIdx.x & 63, NT = 64;
+    const int F = a.nframes, ngrp = (F + FG - 1) / FG;
+    const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= nact * ngrp) return;
+    const int ci = item / ngrp;
+    const ClientParams cp = a.clients[ci];
+    const int f0 = (item - ci * ngrp) * FG;
+    const size_t srow = (size_t)cp.slot;
+    const cf *yp = a.ypost + (srow * a.max_batch) * n;  // this client's frames
+    const int cur = cp.state_cur, nxt = cur ^ 1;
+    const float *rp_old = a.real_prev + ((size_t)cur * a.slots + srow) * h;
+    float *rp_new = a.real_prev + ((size_t)nxt * a.slots + srow) * h;
+    const cf *bt_old = a.bb_tail + ((size_t)cur * a.slots + srow) * h;
+    cf *bt_new = a.bb_tail + ((size_t)nxt * a.slots + srow) * h;
+    const cf *ct_old = sa.car_tail + ((size_t)cur * a.slots + srow) * h;
+    cf *ct_new = sa.car_tail + ((size_t)nxt * a.slots + srow) * h;
+    // kept AND placed AND inside the slice: d = t - m with 0 <= t < r - l, -(h - 1) <= d < h, -cutoff <= d < cutoff
+    const int m = cp.m_floor - cp.l, len = cp.r - cp.l;
+    int d0 = -sa.cutoff, d1 = sa.cutoff;
+    if (d0 < -(h - 1)) d0 = -(h - 1);
+    if (d0 < -m) d0 = -m;
+    if (d1 > h) d1 = h;
+    if (d1 > len - m) d1 = len - m;
+    for (int g = 0; g < FG; g++) {
+        const int f = f0 + g;
+        if (f >= F) break;
+        const cf *y = yp + (size_t)f * n;
+        const cf *S = a.spec + (size_t)f * a.spec_stride;
+        const float sg = flip_frame(a.first_frame_num + (unsigned long long)f, cp.m_floor, a.is_real) ? -1.f : 1.f;
+        const float sgp = flip_frame(a.first_frame_num + (unsigned long long)f - 1ull, cp.m_floor, a.is_real) ? -1.f : 1.f;
+        float *out = a.audio + (srow * a.max_batch + f) * h;
+        int s_nan = 0;
+        const bool last = (f == F - 1);
+        float lvl = 0.f;
+        cf lag = make_float2(0.f, 0.f), ccarry = make_float2(0.f, 0.f);
+        for (int j0 = 0; j0 < h; j0 += NT) {  // (every lane walks every round: the shuffles below need the whole wave)
+            const int j = j0 + tid;
+            const bool ok = j < h;
+            cf c = make_float2(0.f, 0.f);
+            if (ok) {
+                const cf cy = sam_carrier_dsum(a, cp, S, d0, d1, j);
+                cf ct;
+                if (f == 0) {
+                    ct = ct_old[j];
+                } else {
+                    const cf cp1 = sam_carrier_dsum(a, cp, S - a.spec_stride, d0, d1, h + j);
+                    ct = make_float2(__fmul_rn(cp1.x, sgp), __fmul_rn(cp1.y, sgp));
+                }
+                c = make_float2(__fadd_rn(__fmul_rn(cy.x, sg), ct.x), __fadd_rn(__fmul_rn(cy.y, sg), ct.y));
+            }
+            cf pr = make_float2(__shfl_up(c.x, 1, 64), __shfl_up(c.y, 1, 64));  // C[j-1]
+            if (tid == 0) pr = ccarry;
+            ccarry = make_float2(__shfl(c.x, 63, 64), __shfl(c.y, 63, 64));
+            if (ok) {
+                const cf pv = (f == 0) ? bt_old[j] : yp[(size_t)(f - 1) * n + h + j];
+                const cf b = make_float2(y[j].x + pv.x, y[j].y + pv.y);  // dsp_add_complex :235
+                float mag;
+                const float v = sam_detect(b, c, mag);
+                out[j] = v;
+                if (isnan(v)) s_nan = 1;
+                lvl += mag;
+                if (j > 0) {
+                    const cf t = sam_lag(c, pr);
+                    lag.x += t.x, lag.y += t.y;
+                }
+                if (last) {
+                    bt_new[j] = y[h + j];  // :200-203 (second half kept for the next frame)
+                    const cf cn = sam_carrier_dsum(a, cp, S, d0, d1, h + j);
+                    ct_new[j] = make_float2(__fmul_rn(cn.x, sg), __fmul_rn(cn.y, sg));
+                    rp_new[j] = rp_old[j];
+                    if (j == h - 1) a.bb_last[(size_t)nxt * a.slots + srow] = b;  // `prev` of :200
+                }
+            }
+        }
+        const int any_nan = __any(s_nan);
+        lvl = wave_sum(lvl);
+        lag.x = wave_sum(lag.x), lag.y = wave_sum(lag.y);
+        if (tid == 0) {
+            a.nan_flags[srow * a.max_batch + f] = any_nan ? 1 : 0;
+            sa.car_rec[srow * a.max_batch + f] = make_float2(lvl / (float)h, sa.hz_per_rad * atan2f(lag.y, lag.x));
+        }
     }
 }
 

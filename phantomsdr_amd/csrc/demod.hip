@@ -86,7 +86,7 @@ extern "C" int psdr_client_set_audio_demodulation(psdr_ctx *c, int id, int mode)
     std::lock_guard<std::mutex> lk(c->mtx);
     int rc = check_slot(c, id);
     if (rc) return rc;
-    if (mode < PSDR_USB || mode > PSDR_IQ) return fail(PSDR_ERR_INVALID, "unknown mode %d", mode);
+    if (mode < PSDR_USB || mode > PSDR_SAM) return fail(PSDR_ERR_INVALID, "unknown mode %d", mode);
     if (mode == PSDR_IQ && !c->iq_pool[1]) {
         // the first IQ client of the context: its rows' two pools (a context that never sees one allocates nothing); both
         // exist before either is kept, and the mode changes only then
@@ -100,6 +100,20 @@ extern "C" int psdr_client_set_audio_demodulation(psdr_ctx *c, int id, int mode)
         c->iq_pool[0] = std::move(pool[0]);
         c->iq_pool[1] = std::move(pool[1]);
     }
+    if (mode == PSDR_SAM && !c->car_pool[1]) {
+        // the first SAM client of the context: the carrier tails and the two pools of carrier records, all three or none
+        if (c->cfg.audio_rate <= 0) return fail(PSDR_ERR_STATE, "PSDR_SAM needs audio_rate > 0 (the carrier low-pass is 500 Hz)");
+        HIPCHK(hipSetDevice(c->device));
+        const size_t S = c->aslots.size(), h = (size_t)c->n / 2, recs = S * (size_t)c->max_batch;
+        DevBuf<cf> tail, pool[2];
+        if (tail.alloc(2 * S * h, true) || pool[0].alloc(recs, true) || pool[1].alloc(recs, true)) {
+            const std::string msg = psdr_last_error();
+            return fail(PSDR_ERR_NOMEM, "carrier tails and records (%zu bytes): %s", (2 * S * h + 2 * recs) * sizeof(cf), msg.c_str());
+        }
+        c->d_car_tail = std::move(tail);
+        c->car_pool[0] = std::move(pool[0]);
+        c->car_pool[1] = std::move(pool[1]);
+    }
     c->aslots[id].mode = mode;
     if (c->aslots[id].agc_reset == 0) c->aslots[id].agc_reset = 1;  // src/signal.cpp:316-328: resets the AGC
     return PSDR_OK;
@@ -112,6 +126,8 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     if (c->n <= 0) return fail(PSDR_ERR_STATE, "context created with audio_fft_size 0");
     HIPCHK(hipSetDevice(c->device));
     int nact = 0, npaused = 0, niq = 0, iq_off = 0;
+    int nold = 0, nsam = 0;              // the active list: [0, nold) USB / LSB / AM / FM, [nold, nact) PSDR_SAM
+    std::vector<size_t> sam_zero;        // carrier tails (element offsets into d_car_tail) that start this batch from zero
     const int ring = c->client_ring.acquire();
     if (ring < 0) return fail(PSDR_ERR_HIP, "client parameter ring: event wait failed");
     ClientParams *h_clients = (ClientParams *)c->client_ring.host(ring);
@@ -119,7 +135,7 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     // behind the list, for the post chain: the list index of every slot's client (its kernels walk the SLOTS, lane = slot & 63)
     const size_t S = c->aslots.size();
     int *h_slot_ci = (int *)(h_clients + S), *d_slot_ci = (int *)(d_clients + S);
-    cf *iq_rows[2] = {nullptr, nullptr};
+    cf *iq_rows[2] = {nullptr, nullptr}, *car_rows[2] = {nullptr, nullptr};
     {
         std::lock_guard<std::mutex> lk(c->mtx);
         if (band) {  // checked under the same lock that fixes the windows this batch is demodulated with
@@ -134,14 +150,23 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
             }
         }
         iq_rows[0] = c->iq_pool[0], iq_rows[1] = c->iq_pool[1];  // (allocated under this lock, once)
+        car_rows[0] = c->car_pool[0], car_rows[1] = c->car_pool[1];
         c->demod_seq++;
         for (size_t i = 0; i < c->aslots.size(); i++) {
             AudioSlot &s = c->aslots[i];
             if (!s.active || s.paused) continue;
+            // PSDR_SAM: a slot whose previous batch was not SAM (a fresh slot, another mode in between) holds no carrier
+            // tail of its own - the other modes' kernels do not carry it along: it starts from zero
+            if (s.mode == PSDR_SAM && (s.last_seq == 0 || s.b_mode != PSDR_SAM))
+                sam_zero.push_back(((size_t)s.state_cur * S + i) * ((size_t)c->n / 2));
             s.last_seq = c->demod_seq;
             s.b_l = s.l, s.b_r = s.r, s.b_mid = s.mid, s.b_mode = s.mode;
             if (s.mode == PSDR_IQ) {  // listed apart, below
                 niq++;
+                continue;
+            }
+            if (s.mode == PSDR_SAM) {  // the tail of the active list, below
+                nsam++;
                 continue;
             }
             ClientParams &p = h_clients[nact++];
@@ -156,6 +181,25 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
             p.paused = 0;
             if (c->post_on) s.agc_reset = 0;
         }
+        nold = nact;
+        // PSDR_SAM clients: audio clients like the others (the post chain takes all nact, in any order: it walks the slots
+        // through h_slot_ci), listed behind them for launches of their own.  Without one the list is what it always was.
+        if (nsam > 0)
+            for (size_t i = 0; i < c->aslots.size(); i++) {
+                AudioSlot &s = c->aslots[i];
+                if (!s.active || s.paused || s.mode != PSDR_SAM) continue;
+                ClientParams &p = h_clients[nact++];
+                p.l = s.l;
+                p.r = s.r;
+                p.m_floor = (int)std::floor(s.mid);
+                p.mode = PSDR_SAM;
+                p.slot = (int)i;
+                p.state_cur = s.state_cur;
+                s.state_cur ^= 1;
+                p.agc_reset = c->post_on ? s.agc_reset : 0;
+                p.paused = 0;
+                if (c->post_on) s.agc_reset = 0;
+            }
         if (c->post_on) {
             for (size_t i = 0; i < S; i++) h_slot_ci[i] = -1;
             for (int i = 0; i < nact; i++) h_slot_ci[h_clients[i].slot] = i;
@@ -211,6 +255,7 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
         c->out_set ^= 1;
         c->d_audio = c->audio_pool[c->out_set], c->d_pwr = c->pwr_pool[c->out_set], c->d_nan = c->nan_pool[c->out_set];
         c->d_iq = iq_rows[c->out_set];  // (null until the context's first IQ client)
+        c->d_car = car_rows[c->out_set];  // (... first SAM client)
         int rc = fetch_guard_wait(c, c->side, c->guard_audio[c->out_set]);
         if (rc) return rc;
         c->guard_audio[c->out_set] = nullptr;
@@ -307,44 +352,81 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
         }
         return PSDR_OK;
     };
-    if (nact > 0) {
+    if (nold > 0) {
         ProfScope ps(c, K_IDFT, c->side);
         if (fixed_plan && c->demod_chain) {
             // transform + overlap-add + demodulation in one kernel, one wave per chain of K consecutive frames of a
             // client (demod.h)
-            const int K = chain_k(nact);
-            const unsigned items = (unsigned)nact * (unsigned)((nframes + K - 1) / K);
+            const int K = chain_k(nold);
+            const unsigned items = (unsigned)nold * (unsigned)((nframes + K - 1) / K);
             const unsigned W = c->n == 360 ? 4u : 1u;
             const size_t lds = (size_t)(1 + W) * c->n * sizeof(cf);
             if (c->n == 360)
                 hipLaunchKernelGGL((k_demod_chain_fixed<360, 8, 9, 5>), dim3((items + W - 1) / W), dim3(64 * W), lds,
-                                   c->side, a, nact, K);
+                                   c->side, a, nold, K);
             else
                 hipLaunchKernelGGL((k_demod_chain_fixed<720, 8, 9, 10>), dim3((items + W - 1) / W), dim3(64 * W), lds,
-                                   c->side, a, nact, K);
+                                   c->side, a, nold, K);
             if (can_be_nonfinite) {
                 DemodArgs ar = a;
                 ar.replay = 1;
                 const int KF = nframes;  // one chain = the whole batch
                 if (c->n == 360)
-                    hipLaunchKernelGGL((k_demod_chain_fixed<360, 8, 9, 5>), dim3(((unsigned)nact + W - 1) / W), dim3(64 * W), lds,
-                                       c->side, ar, nact, KF);
+                    hipLaunchKernelGGL((k_demod_chain_fixed<360, 8, 9, 5>), dim3(((unsigned)nold + W - 1) / W), dim3(64 * W), lds,
+                                       c->side, ar, nold, KF);
                 else
-                    hipLaunchKernelGGL((k_demod_chain_fixed<720, 8, 9, 10>), dim3(((unsigned)nact + W - 1) / W), dim3(64 * W), lds,
-                                       c->side, ar, nact, KF);
+                    hipLaunchKernelGGL((k_demod_chain_fixed<720, 8, 9, 10>), dim3(((unsigned)nold + W - 1) / W), dim3(64 * W), lds,
+                                       c->side, ar, nold, KF);
             }
             ola_done = true;
         } else {
-            PSDRCHK(launch_idft(a, nact));
+            PSDRCHK(launch_idft(a, nold));
         }
         HIPCHK(hipGetLastError());
     }
-    if (nact > 0 && !ola_done) {
+    if (nold > 0 && !ola_done) {
         ProfScope ps(c, K_OLA, c->side);
-        const unsigned items = (unsigned)nact * (unsigned)((nframes + PSDR_OLA_FG - 1) / PSDR_OLA_FG);
-        hipLaunchKernelGGL(k_demod_ola, dim3((items + 3) / 4), dim3(256), 0, c->side, a, nact);
-        if (can_be_nonfinite) hipLaunchKernelGGL(k_demod_ola_seq, dim3(((unsigned)nact + 3) / 4), dim3(256), 0, c->side, a, nact);
+        const unsigned items = (unsigned)nold * (unsigned)((nframes + PSDR_OLA_FG - 1) / PSDR_OLA_FG);
+        hipLaunchKernelGGL(k_demod_ola, dim3((items + 3) / 4), dim3(256), 0, c->side, a, nold);
+        if (can_be_nonfinite) hipLaunchKernelGGL(k_demod_ola_seq, dim3(((unsigned)nold + 3) / 4), dim3(256), 0, c->side, a, nold);
         HIPCHK(hipGetLastError());
+    }
+    if (nsam > 0) {
+        // the PSDR_SAM clients: the tail of the active list, launches of their own behind the others' (demod.h)
+        for (size_t off : sam_zero) HIPCHK(hipMemsetAsync(c->d_car_tail + off, 0, ((size_t)c->n / 2) * sizeof(cf), c->side));
+        DemodArgs as = a;
+        as.clients = d_clients + nold;
+        SamArgs sa{};
+        sa.car_tail = c->d_car_tail;
+        sa.car_rec = c->d_car;
+        sa.cutoff = (int)((int64_t)500 * c->n / c->cfg.audio_rate);  // src/signal.cpp:217-220
+        sa.hz_per_rad = (float)((double)c->cfg.audio_rate / (2.0 * M_PI));
+        if (fixed_plan && c->demod_chain) {
+            ProfScope ps(c, K_IDFT, c->side);
+            const int K = chain_k(nsam);
+            const unsigned items = (unsigned)nsam * (unsigned)((nframes + K - 1) / K);
+            // (a wave's carrier tail lives in n/2 words of LDS behind the transform buffers: two waves per work-group at
+            // n = 360, 11.25 KiB, and one at 720, 14.1 KiB - inside the 15 KiB an FFT pass leaves free on a CU)
+            const unsigned W = c->n == 360 ? 2u : 1u;
+            const size_t lds = ((size_t)(1 + W) * c->n + (size_t)W * (c->n / 2)) * sizeof(cf);
+            if (c->n == 360)
+                hipLaunchKernelGGL((k_demod_chain_sam<360, 8, 9, 5>), dim3((items + W - 1) / W), dim3(64 * W), lds,
+                                   c->side, as, nsam, K, sa);
+            else
+                hipLaunchKernelGGL((k_demod_chain_sam<720, 8, 9, 10>), dim3((items + W - 1) / W), dim3(64 * W), lds,
+                                   c->side, as, nsam, K, sa);
+            HIPCHK(hipGetLastError());
+        } else {
+            {
+                ProfScope ps(c, K_IDFT, c->side);
+                PSDRCHK(launch_idft(as, nsam));
+                HIPCHK(hipGetLastError());
+            }
+            ProfScope ps(c, K_OLA, c->side);
+            const unsigned items = (unsigned)nsam * (unsigned)((nframes + PSDR_OLA_FG - 1) / PSDR_OLA_FG);
+            hipLaunchKernelGGL(k_demod_ola_sam, dim3((items + 3) / 4), dim3(256), 0, c->side, as, nsam, sa);
+            HIPCHK(hipGetLastError());
+        }
     }
     if (niq > 0) {
         // the PSDR_IQ clients: launches of their own behind the others', on the same stream (demod.h)
@@ -456,6 +538,7 @@ extern "C" int psdr_fetch_begin(psdr_ctx *c, unsigned what) {
     if ((what & PSDR_FETCH_PCM) && !fs.pcm) PSDRCHK(fs.pcm.alloc(S * mb * h));
     size_t wf_bytes = 0;
     int iq_lo = (int)S, iq_hi = -1;  // PSDR_FETCH_IQ: the span from the lowest to the highest slot that was IQ in the batch
+    int car_lo = (int)S, car_hi = -1;  // the carrier records: ... that was SAM (with any of the audio bits)
     {
         std::lock_guard<std::mutex> lk(c->mtx);
         fs.win.resize(S);
@@ -467,6 +550,10 @@ extern "C" int psdr_fetch_begin(psdr_ctx *c, unsigned what) {
             if ((what & PSDR_FETCH_IQ) && sl.active && sl.last_seq == c->demod_seq && sl.b_mode == PSDR_IQ) {
                 iq_lo = std::min(iq_lo, (int)i);
                 iq_hi = (int)i;
+            }
+            if (want_audio && sl.active && sl.last_seq == c->demod_seq && sl.b_mode == PSDR_SAM) {
+                car_lo = std::min(car_lo, (int)i);
+                car_hi = (int)i;
             }
         }
         fs.wfm.assign(c->wslots.begin(), c->wslots.end());
@@ -480,6 +567,12 @@ extern "C" int psdr_fetch_begin(psdr_ctx *c, unsigned what) {
     if ((size_t)fs.iq_n > fs.iq_cap) {
         PSDRCHK(fs.iq.alloc((size_t)fs.iq_n * mb * h));
         fs.iq_cap = (size_t)fs.iq_n;
+    }
+    fs.car_lo = car_hi < 0 ? 0 : car_lo;
+    fs.car_n = car_hi < 0 ? 0 : car_hi - car_lo + 1;
+    if ((size_t)fs.car_n > fs.car_cap) {
+        PSDRCHK(fs.car.alloc((size_t)fs.car_n * mb));
+        fs.car_cap = (size_t)fs.car_n;
     }
     if (wf_bytes > fs.wf_cap) {
         PSDRCHK(fs.wf.alloc(wf_bytes));  // (the old rows are given up only once the new buffer exists)
@@ -515,6 +608,15 @@ extern "C" int psdr_fetch_begin(psdr_ctx *c, unsigned what) {
             else
                 HIPCHK(hipMemcpy2DAsync(fs.iq, mb * rb, src, mb * rb, F * rb, nsl, hipMemcpyDeviceToHost, fst));
             fs.iq_bytes = nsl * F * rb;
+        }
+        if (fs.car_n > 0) {
+            // the carrier records of the span's slots, one copy (their pools alternate with the audio's: ev_audio guards them)
+            const size_t rb = sizeof(cf), nsl = (size_t)fs.car_n;
+            const cf *src = c->d_car + (size_t)fs.car_lo * mb;
+            if (F == mb)
+                HIPCHK(hipMemcpyAsync(fs.car, src, nsl * mb * rb, hipMemcpyDeviceToHost, fst));
+            else
+                HIPCHK(hipMemcpy2DAsync(fs.car, mb * rb, src, mb * rb, F * rb, nsl, hipMemcpyDeviceToHost, fst));
         }
         HIPCHK(hipEventRecord(fs.ev_audio, fst));
         c->guard_audio[c->out_set] = fs.ev_audio;
@@ -661,6 +763,25 @@ extern "C" int psdr_fetched_iq(psdr_ctx *c, int id, int frame, const float **iq,
     if (iq) *iq = have ? reinterpret_cast<const float *>(fs->iq.get() + ((size_t)(id - fs->iq_lo) * mb + (size_t)frame) * h) : nullptr;
     if (pwr) *pwr = fs->pwr[row];
     if (nan_flag) *nan_flag = fs->nan[row];
+    return PSDR_OK;
+}
+extern "C" int psdr_fetched_carrier(psdr_ctx *c, int id, int frame, float *level, float *offset_hz) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    const psdr_ctx::FetchSet *fs = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);
+        int rc = check_slot(c, id);
+        if (rc) return rc;
+        if ((rc = fetched_set(c, &fs))) return rc;
+        if (fs->seq == 0) return fail(PSDR_ERR_STATE, "the fetched batch carries no audio (PSDR_FETCH_AUDIO / _PCM / _IQ)");
+        if ((rc = slot_in_fetched_set(c, fs, id, false))) return rc;
+        if (fs->win[id].mode != PSDR_SAM || id < fs->car_lo || id >= fs->car_lo + fs->car_n)
+            return fail(PSDR_ERR_NO_DATA, "client %d was not demodulated as PSDR_SAM in the fetched batch", id);
+    }
+    if (frame < 0 || frame >= fs->frames) return fail(PSDR_ERR_INVALID, "frame %d not in the fetched batch of %d", frame, fs->frames);
+    const cf rec = fs->car[(size_t)(id - fs->car_lo) * (size_t)c->max_batch + (size_t)frame];
+    if (level) *level = rec.x;
+    if (offset_hz) *offset_hz = rec.y;
     return PSDR_OK;
 }
 extern "C" int psdr_fetched_iq_span(psdr_ctx *c, int *first_slot, int *nslots, size_t *bytes) {
@@ -829,5 +950,37 @@ extern "C" int psdr_iq_device_ptr(psdr_ctx *c, int id, const float **d_iq, const
     const size_t h = (size_t)c->n / 2, mb = (size_t)c->max_batch;
     if (d_iq) *d_iq = reinterpret_cast<const float *>(c->d_iq + (size_t)id * mb * h);
     if (d_pwr) *d_pwr = c->d_pwr + (size_t)id * mb;
+    return PSDR_OK;
+}
+extern "C" int psdr_read_carrier(psdr_ctx *c, int id, int nframes, float *level, float *offset_hz, int *nframes_out) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);
+        int rc = check_slot(c, id);
+        if (rc) return rc;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    const size_t F = (size_t)c->last_demod_frames, mb = (size_t)c->max_batch;
+    if (F == 0) return fail(PSDR_ERR_STATE, "no demodulated batch to read");
+    if (nframes < (int)F) return fail(PSDR_ERR_INVALID, "buffers hold %d frames, the last batch has %zu", nframes, F);
+    if (nframes_out) *nframes_out = (int)F;
+    {
+        int rc = slot_in_last_batch(c, id);
+        if (rc) return rc;
+        {
+            std::lock_guard<std::mutex> lk(c->mtx);
+            if (c->aslots[id].b_mode != PSDR_SAM || !c->d_car)
+                return fail(PSDR_ERR_NO_DATA, "client %d was not demodulated as PSDR_SAM in the last batch", id);
+        }
+        rc = drain(c);
+        if (rc) return rc;
+    }
+    std::vector<cf> rec(F);
+    HIPCHK(hipMemcpyAsync(rec.data(), c->d_car + (size_t)id * mb, F * sizeof(cf), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (size_t f = 0; f < F; f++) {
+        if (level) level[f] = rec[f].x;
+        if (offset_hz) offset_hz[f] = rec[f].y;
+    }
     return PSDR_OK;
 }

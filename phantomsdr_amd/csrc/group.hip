@@ -290,6 +290,7 @@ extern "C" int psdr_group_client_add(psdr_group *g, int l, double audio_mid, int
     if (!g || !gid_out) return fail(PSDR_ERR_INVALID, "null argument");
     // (a group neither migrates nor fetches IQ rows: a context of its own serves such a client)
     if (mode == PSDR_IQ) return fail(PSDR_ERR_UNSUPPORTED, "PSDR_IQ clients are not served through a group");
+    if (mode == PSDR_SAM) return fail(PSDR_ERR_UNSUPPORTED, "PSDR_SAM clients are not served through a group (the carrier tail is not migrated)");
     std::lock_guard<std::mutex> lk(g->mtx);
     // clients / raw: round robin (client i on GPU i mod n, like assign_clients of distributed.py); band: the band the
     // window STARTS in (it may end in the halo)
@@ -319,6 +320,7 @@ extern "C" int psdr_group_client_remove(psdr_group *g, int gid) {
 extern "C" int psdr_group_client_set_audio_demodulation(psdr_group *g, int gid, int mode) {
     if (!g) return fail(PSDR_ERR_INVALID, "null argument");
     if (mode == PSDR_IQ) return fail(PSDR_ERR_UNSUPPORTED, "PSDR_IQ clients are not served through a group");
+    if (mode == PSDR_SAM) return fail(PSDR_ERR_UNSUPPORTED, "PSDR_SAM clients are not served through a group (the carrier tail is not migrated)");
     std::lock_guard<std::mutex> lk(g->mtx);
     int rank, id, rc = gid_split(g, gid, &rank, &id);
     return rc ? rc : psdr_client_set_audio_demodulation(g->ctx[rank], id, mode);
