@@ -76,6 +76,78 @@ __device__ __forceinline__ bool flip_frame(unsigned long long frame_num, int m_i
     // src/signal.cpp:160-162 with C++ remainder semantics for negative m_idx
     return (frame_num % 2 == 1) && ((m_idx % 2 == 0 && !is_real) || (m_idx % 2 == 1 && is_real));
 }
+// s_f: the sign frame f of the batch is multiplied with
+__device__ __forceinline__ float frame_sign(const DemodArgs &a, const ClientParams &cp, int f) {
+    return flip_frame(a.first_frame_num + (unsigned long long)f, cp.m_floor, a.is_real) ? -1.f : 1.f;
+}
+
+// ---- steps the kernels below share: ONE definition each -----------------------------------------------------------------
+// (The complex overlap-add step of the three chain kernels - y = s_f buf[j], b = y + tail, tail = s_f buf[h + j], the state on
+// the batch's last frame - stays written out in each: as one function k_demod_chain_fixed<360> took 83 VGPRs, <720> 44 bytes
+// of scratch and k_demod_chain_sam<360> 89 VGPRs, over their budgets beside a pass.  The kernels behind the IDFT share theirs:
+// ola_step.)
+__device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+// the twiddle table into the front of the work-group's LDS, behind the only work-group barrier of the wave-per-item kernels
+__device__ __forceinline__ cf *stage_twiddles(const DemodArgs &a, unsigned char *smem, int n) {
+    cf *Wn = reinterpret_cast<cf *>(smem);
+    for (int i = threadIdx.x; i < n; i += blockDim.x) Wn[i] = a.Wn[i];
+    __syncthreads();
+    return Wn;
+}
+// wave -> item: wave wv of work-group b takes item b W + wv of nact * ceil(F / K), the chain [f0, f1) of K consecutive frames
+// (the last one of a client may be shorter) of client ci; false: the grid's surplus.  Wave-uniform, in scalar registers.
+__device__ __forceinline__ bool wave_chain(int nact, int F, int K, int &ci, int &f0, int &f1) {
+    const int wv = threadIdx.x >> 6, W = blockDim.x >> 6, nch = (F + K - 1) / K;
+    const int item = __builtin_amdgcn_readfirstlane((int)blockIdx.x * W + wv);
+    if (item >= nact * nch) return false;
+    ci = item / nch, f0 = (item - ci * nch) * K;
+    f1 = f0 + K < F ? f0 + K : F;
+    return true;
+}
+// everything about a wave's client is wave-uniform: keep it in scalar registers (the mode branches become scalar
+// branches, the range tests compare against scalars)
+__device__ __forceinline__ ClientParams wave_uniform(ClientParams cp) {
+    cp.l = __builtin_amdgcn_readfirstlane(cp.l);
+    cp.r = __builtin_amdgcn_readfirstlane(cp.r);
+    cp.m_floor = __builtin_amdgcn_readfirstlane(cp.m_floor);
+    cp.mode = __builtin_amdgcn_readfirstlane(cp.mode);
+    cp.slot = __builtin_amdgcn_readfirstlane(cp.slot);
+    cp.state_cur = __builtin_amdgcn_readfirstlane(cp.state_cur);
+    return cp;
+}
+// a client's double-buffered state (src/signal.h:86-101): this batch reads half state_cur and writes the other one
+struct SlotState {
+    size_t row_old, row_new;  // [half][slot]: the element of bb_last, the row of real_prev / bb_tail / SamArgs::car_tail
+    const float *rp_old;
+    float *rp_new;
+    const cf *bt_old;
+    cf *bt_new;
+};
+__device__ __forceinline__ SlotState slot_state(const DemodArgs &a, const ClientParams &cp, int h) {
+    const size_t srow = (size_t)cp.slot;
+    const int cur = cp.state_cur, nxt = cur ^ 1;
+    SlotState st;
+    st.row_old = (size_t)cur * a.slots + srow;
+    st.row_new = (size_t)nxt * a.slots + srow;
+    st.rp_old = a.real_prev + ((size_t)cur * a.slots + srow) * h;
+    st.rp_new = a.real_prev + ((size_t)nxt * a.slots + srow) * h;
+    st.bt_old = a.bb_tail + ((size_t)cur * a.slots + srow) * h;
+    st.bt_new = a.bb_tail + ((size_t)nxt * a.slots + srow) * h;
+    return st;
+}
+// An opaque copy of the lane number for one iteration of a chain kernel's frame loop: with the loop-invariant lane the
+// compiler keeps every address of every stage in registers across the loop - 100 VGPRs more than the transform itself
+// needs, or 300-700 bytes of scratch
+__device__ __forceinline__ int opaque_lane(int lane) {
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+    return ln;
+}
 
 // one Stockham stage; RC > 0: radix known at compile time (all operand loads of a butterfly
 // are issued before the MAC chain), RC == 0: run-time radix (large prime factors)
@@ -127,39 +199,40 @@ __device__ __forceinline__ void idft_stage(const cf *src, cf *dst, const cf *Wn,
     }
 }
 
-// blockDim.x = 128 (n <= 512) or 256
-__global__ __launch_bounds__(256) void k_demod_idft(DemodArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int n = a.n, tid = threadIdx.x, NT = blockDim.x;
-    const ClientParams cp = a.clients[blockIdx.x];
-    const int f = blockIdx.y;
-    const unsigned long long frame_num = a.first_frame_num + (unsigned long long)f;
-
-    cf *bufA, *bufB;
-    const cf *Wn;
-    if (a.lds_mode == 0) {
-        bufA = reinterpret_cast<cf *>(smem);
-        bufB = bufA + n;
-        cf *w = bufB + n;
-        for (int i = tid; i < n; i += NT) w[i] = a.Wn[i];
-        Wn = w;
-    } else if (a.lds_mode == 1) {
-        bufA = reinterpret_cast<cf *>(smem);
-        bufB = bufA + n;
-        Wn = a.Wn;
-    } else {
-        bufA = a.gscratch + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 2) * n;
-        bufB = bufA + n;
-        Wn = a.Wn;
+// The transform of ONE (client, frame) item into its row of ypost by the NT threads that share bufA / bufB: slice power,
+// the mode-specific bin copy, the c2r extension, the stages, reversal (LSB) and sign.  `sy` is how these threads pass a
+// stage boundary together and sum the power: ItemGroup (a work-group: barriers) or ItemWave (one wave: its LDS
+// operations execute in order).
+struct ItemGroup {
+    float *red;  // [NT / 64] in LDS
+    __device__ __forceinline__ void sync() const { __syncthreads(); }
+    // the item's power from the waves' sums (in thread 0), behind a boundary
+    __device__ __forceinline__ float total(float pw, int tid, int NT) const {
+        if ((tid & 63) == 0) red[tid >> 6] = pw;
+        __syncthreads();
+        float tot = 0.f;
+        if (tid == 0)
+            for (int w = 0; w < NT / 64; w++) tot += red[w];
+        return tot;
     }
-    __shared__ float red[4];
-
+};
+struct ItemWave {
+    __device__ __forceinline__ void sync() const { wave_lds_sync(); }
+    __device__ __forceinline__ float total(float pw, int, int) const {
+        wave_lds_sync();
+        return pw;
+    }
+};
+template <class Sync>
+__device__ __forceinline__ void idft_item(const DemodArgs &a, const ClientParams &cp, int f, cf *bufA, cf *bufB, const cf *Wn,
+                                          int tid, int NT, Sync sy) {
+    const int n = a.n;
     const int len = cp.r - cp.l;
     const int m = cp.m_floor - cp.l;  // audio_m
     const cf *S = a.spec + (size_t)f * a.spec_stride;  // slice bin t at lay.pos(cp.l + t)
 
     for (int i = tid; i < n; i += NT) bufA[i] = make_float2(0.f, 0.f);
-    __syncthreads();
+    sy.sync();
 
     float pw = 0.f;
     for (int t = tid; t < len; t += NT) {
@@ -174,15 +247,8 @@ __global__ __launch_bounds__(256) void k_demod_idft(DemodArgs a) {
             if (t >= m - n / 2 + 1 && t < m) bufA[n - m + t] = v;
         }
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) pw += __shfl_xor(pw, d, 64);
-    if ((tid & 63) == 0) red[tid >> 6] = pw;
-    __syncthreads();
-    if (tid == 0) {
-        float tot = 0.f;
-        for (int w = 0; w < NT / 64; w++) tot += red[w];
-        a.pwr[(size_t)cp.slot * a.max_batch + f] = tot;
-    }
+    const float tot = sy.total(wave_sum(pw), tid, NT);
+    if (tid == 0) a.pwr[(size_t)cp.slot * a.max_batch + f] = tot;
 
     if (cp.mode < 2) {
         // c2r semantics: bins 0..n/2 only, Im of bin 0 and bin n/2 ignored; extend to the
@@ -195,7 +261,7 @@ __global__ __launch_bounds__(256) void k_demod_idft(DemodArgs a) {
             bufA[0].y = 0.f;
             bufA[n / 2].y = 0.f;
         }
-        __syncthreads();
+        sy.sync();
     }
 
     // generic-radix Stockham, backward; the index arithmetic of every (stage, output) pair is
@@ -215,11 +281,10 @@ __global__ __launch_bounds__(256) void k_demod_idft(DemodArgs a) {
         cf *tmp = src;
         src = dst;
         dst = tmp;
-        __syncthreads();
+        sy.sync();
     }
 
-    const bool flip = flip_frame(frame_num, cp.m_floor, a.is_real);
-    const float sg = flip ? -1.f : 1.f;
+    const float sg = frame_sign(a, cp, f);
     cf *yp = a.ypost + ((size_t)cp.slot * a.max_batch + f) * n;
     for (int jx = tid; jx < n; jx += NT) {
         cf v;
@@ -233,6 +298,31 @@ __global__ __launch_bounds__(256) void k_demod_idft(DemodArgs a) {
     }
 }
 
+// one work-group per (client, frame); blockDim.x = 128 (n <= 512) or 256
+__global__ __launch_bounds__(256) void k_demod_idft(DemodArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int n = a.n, tid = threadIdx.x, NT = blockDim.x;
+    cf *bufA, *bufB;
+    const cf *Wn;
+    if (a.lds_mode == 0) {
+        bufA = reinterpret_cast<cf *>(smem);
+        bufB = bufA + n;
+        cf *w = bufB + n;
+        for (int i = tid; i < n; i += NT) w[i] = a.Wn[i];  // (idft_item's first boundary covers it)
+        Wn = w;
+    } else if (a.lds_mode == 1) {
+        bufA = reinterpret_cast<cf *>(smem);
+        bufB = bufA + n;
+        Wn = a.Wn;
+    } else {
+        bufA = a.gscratch + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 2) * n;
+        bufB = bufA + n;
+        Wn = a.Wn;
+    }
+    __shared__ float red[4];
+    idft_item(a, a.clients[blockIdx.x], blockIdx.y, bufA, bufB, Wn, tid, NT, ItemGroup{red});
+}
+
 // The same transform with one WAVE per (client, frame) and no work-group barrier: the 64
 // lanes of a wave execute their LDS operations in order, so a stage boundary is just
 // "s_waitcnt lgkmcnt(0)".  With hundreds of clients the one-work-group-per-item kernel above
@@ -241,86 +331,17 @@ __global__ __launch_bounds__(256) void k_demod_idft(DemodArgs a) {
 // space an FFT pass leaves free on a CU).  n <= 512 (audio_fft_size 248, 360, ...).
 //   grid = ceil(nact * nframes / WAVES); dynamic LDS = (2 * WAVES + 1) * n * 8 bytes
 #define PSDR_IDFT_WAVES 2
-__device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
 __global__ __launch_bounds__(64 * PSDR_IDFT_WAVES) void k_demod_idft_wave(DemodArgs a, int nact) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int n = a.n, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    cf *Wn = reinterpret_cast<cf *>(smem);
-    for (int i = threadIdx.x; i < n; i += blockDim.x) Wn[i] = a.Wn[i];
-    __syncthreads();  // the only work-group barrier: the shared twiddle table
+    cf *Wn = stage_twiddles(a, smem, n);
     const int item = blockIdx.x * PSDR_IDFT_WAVES + wv;
     if (item >= nact * a.nframes) return;
     // consecutive items = consecutive frames of one client: the slice addresses of a
     // work-group's waves are F*8N bytes apart, their table look-ups identical
     const int ci = item / a.nframes, f = item - ci * a.nframes;
-    const ClientParams cp = a.clients[ci];
-    const unsigned long long frame_num = a.first_frame_num + (unsigned long long)f;
     cf *bufA = Wn + n + (size_t)wv * 2 * n, *bufB = bufA + n;
-
-    const int len = cp.r - cp.l;
-    const int m = cp.m_floor - cp.l;  // audio_m
-    const cf *S = a.spec + (size_t)f * a.spec_stride;  // slice bin t at lay.pos(cp.l + t)
-    for (int i = lane; i < n; i += 64) bufA[i] = make_float2(0.f, 0.f);
-    wave_lds_sync();
-    float pw = 0.f;
-    for (int t = lane; t < len; t += 64) {
-        const cf v = S[a.lay.pos(cp.l + t)];
-        pw += fmaf(v.x, v.x, v.y * v.y);
-        if (cp.mode == 0) {  // USB :125-137
-            if (t >= m && t < m + n) bufA[t - m] = v;
-        } else if (cp.mode == 1) {  // LSB :139-153
-            if (t >= m - n + 1 && t < m + 1) bufA[m - t] = v;
-        } else {  // AM/FM :175-198
-            if (t >= m && t < m + n / 2) bufA[t - m] = v;
-            if (t >= m - n / 2 + 1 && t < m) bufA[n - m + t] = v;
-        }
-    }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) pw += __shfl_xor(pw, d, 64);
-    if (lane == 0) a.pwr[(size_t)cp.slot * a.max_batch + f] = pw;
-    wave_lds_sync();
-    if (cp.mode < 2) {  // c2r semantics, see k_demod_idft
-        for (int k = lane + 1; k < n / 2; k += 64) {
-            const cf v = bufA[k];
-            bufA[n - k] = make_float2(v.x, -v.y);
-        }
-        if (lane == 0) {
-            bufA[0].y = 0.f;
-            bufA[n / 2].y = 0.f;
-        }
-        wave_lds_sync();
-    }
-    cf *src = bufA, *dst = bufB;
-    for (int st = 0; st < a.nstages; st++) {
-        const int R = a.radix[st];
-        const int4 *tab = a.stage_tab + (size_t)st * n;
-        switch (R) {
-#define PSDR_RCASE(r) case r: idft_stage<r>(src, dst, Wn, tab, n, r, lane, 64); break;
-            PSDR_RCASE(2) PSDR_RCASE(3) PSDR_RCASE(4) PSDR_RCASE(5) PSDR_RCASE(6) PSDR_RCASE(7)
-            PSDR_RCASE(8) PSDR_RCASE(9) PSDR_RCASE(10) PSDR_RCASE(12) PSDR_RCASE(14)
-            PSDR_RCASE(15) PSDR_RCASE(16)
-#undef PSDR_RCASE
-            default: idft_stage<0>(src, dst, Wn, tab, n, R, lane, 64); break;
-        }
-        cf *tmp = src;
-        src = dst;
-        dst = tmp;
-        wave_lds_sync();
-    }
-    const bool flip = flip_frame(frame_num, cp.m_floor, a.is_real);
-    const float sg = flip ? -1.f : 1.f;
-    cf *yp = a.ypost + ((size_t)cp.slot * a.max_batch + f) * n;
-    for (int jx = lane; jx < n; jx += 64) {
-        cf v;
-        if (cp.mode == 0)
-            v = make_float2(src[jx].x * sg, 0.f);
-        else if (cp.mode == 1)
-            v = make_float2(src[n - 1 - jx].x * sg, 0.f);  // std::reverse :155
-        else
-            v = make_float2(src[jx].x * sg, src[jx].y * sg);
-        yp[jx] = v;
-    }
+    idft_item(a, a.clients[ci], f, bufA, bufB, Wn, lane, 64, ItemWave{});
 }
 
 // ---- compile-time plans for the audio sizes the BASELINE configurations use (n = 360, 720)
@@ -548,8 +569,7 @@ __device__ __forceinline__ float idft_slice_fixed(const ClientParams &cp, const 
             }
         }
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) pw += __shfl_xor(pw, d, 64);
+    pw = wave_sum(pw);
     wave_lds_sync();
     idft_stage_fixed<N, R0, 1>(buf, Wn, lane);
     wave_lds_sync();
@@ -571,29 +591,17 @@ template <int N, int R0, int R1, int R2>
 __global__ __launch_bounds__(256, PSDR_IDFT_WPE) void k_demod_idft_fixed(DemodArgs a, int nact) {
     static_assert(R0 * R1 * R2 == N, "plan");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, W = blockDim.x >> 6;
-    cf *Wn = reinterpret_cast<cf *>(smem);
-    for (int i = threadIdx.x; i < N; i += blockDim.x) Wn[i] = a.Wn[i];
-    __syncthreads();  // the only work-group barrier: the shared twiddle table
-    // everything about the item is wave-uniform: keep it in scalar registers (the mode
-    // branches become scalar branches, the range tests compare against scalars)
-    const int item = __builtin_amdgcn_readfirstlane((int)blockIdx.x * W + wv);
-    if (item >= nact * a.nframes) return;
-    const int ci = item / a.nframes, f = item - ci * a.nframes;
-    ClientParams cp = a.clients[ci];
-    cp.l = __builtin_amdgcn_readfirstlane(cp.l);
-    cp.r = __builtin_amdgcn_readfirstlane(cp.r);
-    cp.m_floor = __builtin_amdgcn_readfirstlane(cp.m_floor);
-    cp.mode = __builtin_amdgcn_readfirstlane(cp.mode);
-    cp.slot = __builtin_amdgcn_readfirstlane(cp.slot);
-    const unsigned long long frame_num = a.first_frame_num + (unsigned long long)f;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    cf *Wn = stage_twiddles(a, smem, N);
+    int ci, f, f1;  // a chain of one frame
+    if (!wave_chain(nact, a.nframes, 1, ci, f, f1)) return;
+    const ClientParams cp = wave_uniform(a.clients[ci]);
     cf *buf = Wn + N + (size_t)wv * N;
 
     const float pw = idft_item_fixed<N, R0, R1, R2>(a, cp, f, buf, Wn, lane);
     if (lane == 0) a.pwr[(size_t)cp.slot * a.max_batch + f] = pw;
     constexpr int NR = (N + 63) / 64;
-    const bool flip = flip_frame(frame_num, cp.m_floor, a.is_real);
-    const float sg = flip ? -1.f : 1.f;
+    const float sg = frame_sign(a, cp, f);
     cf *yp = a.ypost + ((size_t)cp.slot * a.max_batch + f) * N;
     // (mode is a scalar: one plain loop per mode.  The single unrolled loop with the three-way
     // per-lane select inside was miscompiled by this toolchain - the real part of the last,
@@ -619,6 +627,24 @@ __global__ __launch_bounds__(256, PSDR_IDFT_WPE) void k_demod_idft_fixed(DemodAr
     }
 }
 
+// One complex overlap-add step behind the IDFT kernels (src/signal.cpp:235-237, 200-203), sample j < h of frame f of a
+// client whose rows of ypost start at yp: b = y_f[j] + y_{f-1}[h + j] (the batch's first frame: the carried tail) -> use(b);
+// on the batch's last frame the state the next batch starts from - the second half, B'_f[h-1] (`prev` of :200) - with
+// USB / LSB's copied through.
+template <class Use>
+__device__ __forceinline__ void ola_step(const DemodArgs &a, const SlotState &st, const cf *yp, int f, int j, Use use) {
+    const int n = a.n, h = n / 2;
+    const cf *y = yp + (size_t)f * n;
+    const cf pv = (f == 0) ? st.bt_old[j] : yp[(size_t)(f - 1) * n + h + j];
+    const cf b = make_float2(y[j].x + pv.x, y[j].y + pv.y);  // dsp_add_complex :235
+    use(b);
+    if (f == a.nframes - 1) {
+        st.bt_new[j] = y[h + j];  // :200-203 (second half kept for the next frame)
+        st.rp_new[j] = st.rp_old[j];
+        if (j == h - 1) a.bb_last[st.row_new] = b;  // `prev` of :200
+    }
+}
+
 // one WAVE per (client, group of PSDR_OLA_FG consecutive frames): no shared memory, no barrier (NaN flag by
 // wave vote).  A wave's life is three dependent round trips to memory (client parameters, then the two
 // halves it adds, then the stores) whatever it does in between - with one frame per wave 65 536 waves of
@@ -639,11 +665,7 @@ __global__ __launch_bounds__(256) void k_demod_ola(DemodArgs a, int nact) {
     const int f0 = (item - ci * ngrp) * FG;
     const size_t srow = (size_t)cp.slot;
     const cf *yp = a.ypost + (srow * a.max_batch) * n;  // this client's frames
-    const int cur = cp.state_cur, nxt = cur ^ 1;
-    const float *rp_old = a.real_prev + ((size_t)cur * a.slots + srow) * h;
-    float *rp_new = a.real_prev + ((size_t)nxt * a.slots + srow) * h;
-    const cf *bt_old = a.bb_tail + ((size_t)cur * a.slots + srow) * h;
-    cf *bt_new = a.bb_tail + ((size_t)nxt * a.slots + srow) * h;
+    const SlotState st = slot_state(a, cp, h);
 #pragma unroll
     for (int g = 0; g < FG; g++) {
         const int f = f0 + g;
@@ -662,7 +684,7 @@ __global__ __launch_bounds__(256) void k_demod_ola(DemodArgs a, int nact) {
                 int bad = 0;
                 for (int j = tid; j < n; j += NT) bad |= not_finite(y[j].x) ? 1 : 0;
                 if (f == 0)
-                    for (int j = tid; j < h; j += NT) bad |= not_finite(rp_old[j]) ? 1 : 0;
+                    for (int j = tid; j < h; j += NT) bad |= not_finite(st.rp_old[j]) ? 1 : 0;
                 if (__any(bad) && tid == 0) a.ssb_mark[srow] = a.mark_epoch;
             }
             int g = f - 1;
@@ -673,7 +695,7 @@ __global__ __launch_bounds__(256) void k_demod_ola(DemodArgs a, int nact) {
                 g--;
             }
             for (int j = tid; j < h; j += NT) {
-                const float prev = (g < 0) ? rp_old[j] : yp[(size_t)g * n + h + j].x;
+                const float prev = (g < 0) ? st.rp_old[j] : yp[(size_t)g * n + h + j].x;
                 const float v = y[j].x + prev;  // dsp_add_float :171
                 out[j] = v;
                 if (isnan(v)) s_nan = 1;
@@ -682,44 +704,38 @@ __global__ __launch_bounds__(256) void k_demod_ola(DemodArgs a, int nact) {
                 const int dropped = __any(s_nan);
                 for (int j = tid; j < h; j += NT) {
                     // :273-275, unless this frame was dropped: then the tail it would have added stays
-                    rp_new[j] = dropped ? ((g < 0) ? rp_old[j] : yp[(size_t)g * n + h + j].x) : y[h + j].x;
-                    bt_new[j] = bt_old[j];
+                    st.rp_new[j] = dropped ? ((g < 0) ? st.rp_old[j] : yp[(size_t)g * n + h + j].x) : y[h + j].x;
+                    st.bt_new[j] = st.bt_old[j];
                 }
-                if (tid == 0) a.bb_last[(size_t)nxt * a.slots + srow] = a.bb_last[(size_t)cur * a.slots + srow];
+                if (tid == 0) a.bb_last[st.row_new] = a.bb_last[st.row_old];
             }
         } else {
-            for (int j = tid; j < h; j += NT) {
-                const cf pv = (f == 0) ? bt_old[j] : yp[(size_t)(f - 1) * n + h + j];
-                const cf b = make_float2(y[j].x + pv.x, y[j].y + pv.y);  // dsp_add_complex :235
-                float v;
-                if (cp.mode == 2) {
-                    v = sqrtf(fmaf(b.x, b.x, b.y * b.y));  // dsp_am_demod
-                } else {
-                    cf pr;
-                    if (j > 0) {
-                        const cf pv1 = (f == 0) ? bt_old[j - 1] : yp[(size_t)(f - 1) * n + h + j - 1];
-                        pr = make_float2(y[j - 1].x + pv1.x, y[j - 1].y + pv1.y);
-                    } else if (f == 0) {
-                        pr = a.bb_last[(size_t)cur * a.slots + srow];
+            for (int j = tid; j < h; j += NT)
+                ola_step(a, st, yp, f, j, [&](cf b) {
+                    float v;
+                    if (cp.mode == 2) {
+                        v = sqrtf(fmaf(b.x, b.x, b.y * b.y));  // dsp_am_demod
                     } else {
-                        // B'_{f-1}[h-1] = y_{f-1}[h-1] + (tail of frame f-2, or the carried tail)
-                        const cf y1 = yp[(size_t)(f - 1) * n + h - 1];
-                        const cf t1 = (f == 1) ? bt_old[h - 1] : yp[(size_t)(f - 2) * n + n - 1];
-                        pr = make_float2(y1.x + t1.x, y1.y + t1.y);
+                        cf pr;
+                        if (j > 0) {
+                            const cf pv1 = (f == 0) ? st.bt_old[j - 1] : yp[(size_t)(f - 1) * n + h + j - 1];
+                            pr = make_float2(y[j - 1].x + pv1.x, y[j - 1].y + pv1.y);
+                        } else if (f == 0) {
+                            pr = a.bb_last[st.row_old];
+                        } else {
+                            // B'_{f-1}[h-1] = y_{f-1}[h-1] + (tail of frame f-2, or the carried tail)
+                            const cf y1 = yp[(size_t)(f - 1) * n + h - 1];
+                            const cf t1 = (f == 1) ? st.bt_old[h - 1] : yp[(size_t)(f - 2) * n + n - 1];
+                            pr = make_float2(y1.x + t1.x, y1.y + t1.y);
+                        }
+                        // arg(b * conj(pr)), src/utils/dsp.cpp:32
+                        const float re = fmaf(b.x, pr.x, b.y * pr.y);
+                        const float im = fmaf(b.x, -pr.y, b.y * pr.x);
+                        v = atan2f(im, re);
                     }
-                    // arg(b * conj(pr)), src/utils/dsp.cpp:32
-                    const float re = fmaf(b.x, pr.x, b.y * pr.y);
-                    const float im = fmaf(b.x, -pr.y, b.y * pr.x);
-                    v = atan2f(im, re);
-                }
-                out[j] = v;
-                if (isnan(v)) s_nan = 1;
-                if (last) {
-                    bt_new[j] = y[h + j];  // :200-203 (second half kept for the next frame)
-                    rp_new[j] = rp_old[j];
-                    if (j == h - 1) a.bb_last[(size_t)nxt * a.slots + srow] = b;  // `prev` of :200
-                }
-            }
+                    out[j] = v;
+                    if (isnan(v)) s_nan = 1;
+                });
         }
         const int any_nan = __any(s_nan);
         if (tid == 0) a.nan_flags[srow * a.max_batch + f] = any_nan ? 1 : 0;
@@ -737,16 +753,14 @@ __global__ __launch_bounds__(256) void k_demod_ola_seq(DemodArgs a, int nact) {
     const size_t srow = (size_t)cp.slot;
     if (cp.mode >= 2 || a.ssb_mark[srow] != a.mark_epoch) return;
     const cf *yp = a.ypost + (srow * a.max_batch) * n;
-    const int cur = cp.state_cur, nxt = cur ^ 1;
-    const float *rp_old = a.real_prev + ((size_t)cur * a.slots + srow) * h;
-    float *rp_new = a.real_prev + ((size_t)nxt * a.slots + srow) * h;
+    const SlotState st = slot_state(a, cp, h);
     int g = -1;  // the latest frame that survived (-1: the carried tail)
     for (int f = 0; f < a.nframes; f++) {
         const cf *y = yp + (size_t)f * n;
         float *out = a.audio + (srow * a.max_batch + f) * h;
         int s_nan = 0;
         for (int j = tid; j < h; j += NT) {
-            const float prev = (g < 0) ? rp_old[j] : yp[(size_t)g * n + h + j].x;
+            const float prev = (g < 0) ? st.rp_old[j] : yp[(size_t)g * n + h + j].x;
             const float v = y[j].x + prev;  // dsp_add_float :171
             out[j] = v;
             if (isnan(v)) s_nan = 1;
@@ -755,7 +769,7 @@ __global__ __launch_bounds__(256) void k_demod_ola_seq(DemodArgs a, int nact) {
         if (tid == 0) a.nan_flags[srow * a.max_batch + f] = dropped ? 1 : 0;
         if (!dropped) g = f;
     }
-    for (int j = tid; j < h; j += NT) rp_new[j] = (g < 0) ? rp_old[j] : yp[(size_t)g * n + h + j].x;  // :273-275
+    for (int j = tid; j < h; j += NT) st.rp_new[j] = (g < 0) ? st.rp_old[j] : yp[(size_t)g * n + h + j].x;  // :273-275
 }
 
 // ---- transform + overlap-add + demodulation in ONE kernel (compile-time plans) -------------------------------
@@ -768,39 +782,26 @@ __global__ __launch_bounds__(256) void k_demod_ola_seq(DemodArgs a, int nact) {
 // Same operations in the same order as the two-kernel path (explicit __fmul_rn / __fadd_rn where the fused form
 // would otherwise let the compiler contract what used to be split across two kernels): bit-identical outputs.
 //   grid = ceil(nact * ceil(nframes / K) / W), W = blockDim.x / 64; dynamic LDS = (1 + W) * N * 8 bytes
+
 template <int N, int R0, int R1, int R2>
 __global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) void k_demod_chain_fixed(DemodArgs a, int nact, int K) {
     static_assert(R0 * R1 * R2 == N, "plan");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int h = N / 2, NH = (h + 63) / 64;
-    const int lane_ = threadIdx.x & 63, wv = threadIdx.x >> 6, W = blockDim.x >> 6;
-    cf *Wn = reinterpret_cast<cf *>(smem);
-    for (int i = threadIdx.x; i < N; i += blockDim.x) Wn[i] = a.Wn[i];
-    __syncthreads();
-    const int F = a.nframes, nch = (F + K - 1) / K;
-    const int item = __builtin_amdgcn_readfirstlane((int)blockIdx.x * W + wv);
-    if (item >= nact * nch) return;
-    const int ci = item / nch, f0 = (item - ci * nch) * K;
-    const int f1 = f0 + K < F ? f0 + K : F;
+    const int lane_ = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    cf *Wn = stage_twiddles(a, smem, N);
+    const int F = a.nframes;
+    int ci, f0, f1;
+    if (!wave_chain(nact, F, K, ci, f0, f1)) return;
     ClientParams cp = a.clients[ci];
     // replay (DemodArgs::ssb_mark): the whole batch as ONE chain (K >= F: no warm-up frame, every decision in frame order),
     // for the USB / LSB slots the first launch marked
     if (a.replay && (cp.mode >= 2 || a.ssb_mark[cp.slot] != a.mark_epoch)) return;
-    cp.l = __builtin_amdgcn_readfirstlane(cp.l);
-    cp.r = __builtin_amdgcn_readfirstlane(cp.r);
-    cp.m_floor = __builtin_amdgcn_readfirstlane(cp.m_floor);
-    cp.mode = __builtin_amdgcn_readfirstlane(cp.mode);
-    cp.slot = __builtin_amdgcn_readfirstlane(cp.slot);
-    cp.state_cur = __builtin_amdgcn_readfirstlane(cp.state_cur);
+    cp = wave_uniform(cp);
     cf *buf = Wn + N + (size_t)wv * N;
     const size_t srow = (size_t)cp.slot;
-    const int cur = cp.state_cur, nxt = cur ^ 1;
-    const float *rp_old = a.real_prev + ((size_t)cur * a.slots + srow) * h;
-    float *rp_new = a.real_prev + ((size_t)nxt * a.slots + srow) * h;
-    const cf *bt_old = a.bb_tail + ((size_t)cur * a.slots + srow) * h;
-    cf *bt_new = a.bb_tail + ((size_t)nxt * a.slots + srow) * h;
+    const SlotState st = slot_state(a, cp, h);
     const bool ssb = cp.mode < 2;
-    auto sign_of = [&](int f) { return flip_frame(a.first_frame_num + (unsigned long long)f, cp.m_floor, a.is_real) ? -1.f : 1.f; };
     cf tail[NH];                         // y_{f-1}[h + j], j = lane + 64 u
     cf blast = make_float2(0.f, 0.f);    // FM: B'_{f-1}[h-1] (wave-uniform)
     // warm-up frames (transformed, nothing written): one before the chain, two for FM; ONE loop body for both kinds
@@ -811,9 +812,9 @@ __global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) 
         const int j = lane_ + 64 * u;
         tail[u] = make_float2(0.f, 0.f);
         // the batch's first frame: the carried state (src/signal.h:86-101)
-        if (fs == 0 && j < h) tail[u] = ssb ? make_float2(rp_old[j], 0.f) : bt_old[j];
+        if (fs == 0 && j < h) tail[u] = ssb ? make_float2(st.rp_old[j], 0.f) : st.bt_old[j];
     }
-    if (fs == 0 && cp.mode == 3) blast = a.bb_last[(size_t)cur * a.slots + srow];
+    if (fs == 0 && cp.mode == 3) blast = a.bb_last[st.row_old];
     int bad = 0;  // USB / LSB: a non-finite value seen (per lane)
     if (ssb) {
 #pragma unroll
@@ -836,11 +837,7 @@ __global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) 
     idft_slice_offsets<N, HO>(a, cp, lane_, so);
     while (f < f1) {
         const bool emit = f >= f0;
-        // (an opaque copy per iteration: with the loop-invariant lane the compiler keeps every address of every stage
-        // in registers across the loop - 100 VGPRs more than the transform itself needs, or 300-700 bytes of scratch)
-        int ln = lane_;
-        asm volatile("" : "+v"(ln));
-        const int lane = ln;
+        const int lane = opaque_lane(lane_);
         float pw;
         if (PSDR_DEMOD_PREFETCH && (N <= 512 || PSDR_DEMOD_PREFETCH > 1)) {  // (n = 720: 128 VGPRs + 48 bytes of scratch with it)
             cf sv[NR];
@@ -861,7 +858,7 @@ __global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) 
             pw = idft_slice_fixed<N, R0, R1, R2>(cp, sv, buf, Wn, lane);
         }
         if (emit && lane == 0) a.pwr[srow * a.max_batch + f] = pw;
-        const float sg = sign_of(f);
+        const float sg = frame_sign(a, cp, f);
         float *out = a.audio + (srow * a.max_batch + f) * h;
         const bool last = (f == F - 1);
         int s_nan = 0;
@@ -931,9 +928,9 @@ __global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) 
             if (ok && emit) {
                 out[j] = v;
                 if (last && !ssb) {  // the state the next batch starts from (:200-203); the other mode family's is kept
-                    bt_new[j] = ynext;
-                    rp_new[j] = rp_old[j];
-                    if (j == h - 1) a.bb_last[(size_t)nxt * a.slots + srow] = b;
+                    st.bt_new[j] = ynext;
+                    st.rp_new[j] = st.rp_old[j];
+                    if (j == h - 1) a.bb_last[st.row_new] = b;
                 }
             }
             if (!ssb) tail[u] = ynext;  // (:200-203 precede the NaN guard: the complex modes' state always moves)
@@ -957,7 +954,7 @@ __global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) 
                 for (int u = 0; u < NH; u++) {
                     const int j = lane + 64 * u;
                     tail[u] = yn[u];
-                    if (any_nan && j < h) tail[u] = make_float2(rp_old[j], 0.f);  // nothing survived before the chain: the carried tail
+                    if (any_nan && j < h) tail[u] = make_float2(st.rp_old[j], 0.f);  // nothing survived before the chain: the carried tail
                 }
                 f = f0;
                 wave_lds_sync();
@@ -968,11 +965,11 @@ __global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) 
                 const int j = lane + 64 * u;
                 if (!any_nan) tail[u] = yn[u];
                 if (last && j < h) {  // :273-275
-                    rp_new[j] = tail[u].x;
-                    bt_new[j] = bt_old[j];
+                    st.rp_new[j] = tail[u].x;
+                    st.bt_new[j] = st.bt_old[j];
                 }
             }
-            if (last && lane == 0) a.bb_last[(size_t)nxt * a.slots + srow] = a.bb_last[(size_t)cur * a.slots + srow];
+            if (last && lane == 0) a.bb_last[st.row_new] = a.bb_last[st.row_old];
         }
         if (emit && lane == 0) a.nan_flags[srow * a.max_batch + f] = any_nan ? 1 : 0;
         wave_lds_sync();  // buf is read out: the next frame's transform may overwrite it
@@ -989,7 +986,8 @@ __global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) 
 // and FM's - bb_tail, bb_last = IQ_f[h-1], real_prev copied through - and always moves; the NaN flag of a frame is 1
 // if any component of IQ_f is NaN.
 
-// n = 360 / 720: k_demod_chain_fixed's walk for an IQ client - one wave per chain of K frames, the tail in registers,
+// n = 360 / 720: one wave per chain of K frames of an IQ client, the tail in registers - the shared steps of
+// k_demod_chain_fixed (stage_twiddles, wave_chain, wave_uniform, slot_state, frame_sign, opaque_lane) around its own frame body:
 // ONE warm-up frame (no sample of IQ_f0 looks further back than y_{f0-1}), no detector, no NaN-guard replay, no
 // ssb_mark.  Same operations in the same order as k_demod_idft_fixed + k_demod_ola_iq (__fmul_rn / __fadd_rn: see
 // k_demod_chain_fixed): bit-identical outputs.  Grid and LDS as k_demod_chain_fixed.
@@ -998,36 +996,22 @@ __global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) 
     static_assert(R0 * R1 * R2 == N, "plan");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int h = N / 2, NH = (h + 63) / 64;
-    const int lane_ = threadIdx.x & 63, wv = threadIdx.x >> 6, W = blockDim.x >> 6;
-    cf *Wn = reinterpret_cast<cf *>(smem);
-    for (int i = threadIdx.x; i < N; i += blockDim.x) Wn[i] = a.Wn[i];
-    __syncthreads();
-    const int F = a.nframes, nch = (F + K - 1) / K;
-    const int item = __builtin_amdgcn_readfirstlane((int)blockIdx.x * W + wv);
-    if (item >= nact * nch) return;
-    const int ci = item / nch, f0 = (item - ci * nch) * K;
-    const int f1 = f0 + K < F ? f0 + K : F;
-    ClientParams cp = a.clients[ci];
-    cp.l = __builtin_amdgcn_readfirstlane(cp.l);
-    cp.r = __builtin_amdgcn_readfirstlane(cp.r);
-    cp.m_floor = __builtin_amdgcn_readfirstlane(cp.m_floor);
-    cp.mode = __builtin_amdgcn_readfirstlane(cp.mode);
-    cp.slot = __builtin_amdgcn_readfirstlane(cp.slot);
-    cp.state_cur = __builtin_amdgcn_readfirstlane(cp.state_cur);
+    const int lane_ = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    cf *Wn = stage_twiddles(a, smem, N);
+    const int F = a.nframes;
+    int ci, f0, f1;
+    if (!wave_chain(nact, F, K, ci, f0, f1)) return;
+    const ClientParams cp = wave_uniform(a.clients[ci]);
     cf *buf = Wn + N + (size_t)wv * N;
     const size_t srow = (size_t)cp.slot;
-    const int cur = cp.state_cur, nxt = cur ^ 1;
-    const float *rp_old = a.real_prev + ((size_t)cur * a.slots + srow) * h;
-    float *rp_new = a.real_prev + ((size_t)nxt * a.slots + srow) * h;
-    const cf *bt_old = a.bb_tail + ((size_t)cur * a.slots + srow) * h;
-    cf *bt_new = a.bb_tail + ((size_t)nxt * a.slots + srow) * h;
+    const SlotState st = slot_state(a, cp, h);
     const int fs = f0 == 0 ? 0 : f0 - 1;  // the warm-up frame: transformed, nothing written
     cf tail[NH];                          // s_{f-1} y_{f-1}[h + j], j = lane + 64 u
 #pragma unroll
     for (int u = 0; u < NH; u++) {
         const int j = lane_ + 64 * u;
         tail[u] = make_float2(0.f, 0.f);
-        if (fs == 0 && j < h) tail[u] = bt_old[j];  // the batch's first frame: the carried tail
+        if (fs == 0 && j < h) tail[u] = st.bt_old[j];  // the batch's first frame: the carried tail
     }
     constexpr int NR = (N + 63) / 64;
     constexpr int HO = NR < 3 ? NR : (N <= 512 ? 3 : 6);
@@ -1035,14 +1019,12 @@ __global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) 
     idft_slice_offsets<N, HO>(a, cp, lane_, so);
     for (int f = fs; f < f1; f++) {
         const bool emit = f >= f0;
-        int ln = lane_;  // (an opaque copy per iteration: k_demod_chain_fixed says why)
-        asm volatile("" : "+v"(ln));
-        const int lane = ln;
+        const int lane = opaque_lane(lane_);
         cf sv[NR];  // loads first, LDS after
         idft_load_slice_at<N, HO>(a, cp, f, so, lane, sv);
         const float pw = idft_slice_fixed<N, R0, R1, R2>(cp, sv, buf, Wn, lane);
         if (emit && lane == 0) a.pwr[srow * a.max_batch + f] = pw;
-        const float sg = flip_frame(a.first_frame_num + (unsigned long long)f, cp.m_floor, a.is_real) ? -1.f : 1.f;
+        const float sg = frame_sign(a, cp, f);
         cf *out = iq + (srow * a.max_batch + f) * h;
         const bool last = (f == F - 1);
         int s_nan = 0;
@@ -1058,9 +1040,9 @@ __global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) 
                 if (emit) {
                     out[j] = b;
                     if (last) {  // the state the next batch starts from (:200-203); USB / LSB's is kept
-                        bt_new[j] = ynext;
-                        rp_new[j] = rp_old[j];
-                        if (j == h - 1) a.bb_last[(size_t)nxt * a.slots + srow] = b;
+                        st.bt_new[j] = ynext;
+                        st.rp_new[j] = st.rp_old[j];
+                        if (j == h - 1) a.bb_last[st.row_new] = b;
                     }
                 }
                 tail[u] = ynext;
@@ -1085,30 +1067,18 @@ __global__ __launch_bounds__(256) void k_demod_ola_iq(DemodArgs a, int nact, cf 
     const int f0 = (item - ci * ngrp) * FG;
     const size_t srow = (size_t)cp.slot;
     const cf *yp = a.ypost + (srow * a.max_batch) * n;  // this client's frames
-    const int cur = cp.state_cur, nxt = cur ^ 1;
-    const float *rp_old = a.real_prev + ((size_t)cur * a.slots + srow) * h;
-    float *rp_new = a.real_prev + ((size_t)nxt * a.slots + srow) * h;
-    const cf *bt_old = a.bb_tail + ((size_t)cur * a.slots + srow) * h;
-    cf *bt_new = a.bb_tail + ((size_t)nxt * a.slots + srow) * h;
+    const SlotState st = slot_state(a, cp, h);
 #pragma unroll
     for (int g = 0; g < FG; g++) {
         const int f = f0 + g;
         if (f >= F) break;
-        const cf *y = yp + (size_t)f * n;
         cf *out = iq + (srow * a.max_batch + f) * h;
         int s_nan = 0;
-        const bool last = (f == F - 1);
-        for (int j = tid; j < h; j += NT) {
-            const cf pv = (f == 0) ? bt_old[j] : yp[(size_t)(f - 1) * n + h + j];
-            const cf b = make_float2(y[j].x + pv.x, y[j].y + pv.y);  // dsp_add_complex :235
-            out[j] = b;
-            if (isnan(b.x) || isnan(b.y)) s_nan = 1;
-            if (last) {
-                bt_new[j] = y[h + j];  // :200-203 (second half kept for the next frame)
-                rp_new[j] = rp_old[j];
-                if (j == h - 1) a.bb_last[(size_t)nxt * a.slots + srow] = b;  // `prev` of :200
-            }
-        }
+        for (int j = tid; j < h; j += NT)
+            ola_step(a, st, yp, f, j, [&](cf b) {
+                out[j] = b;
+                if (isnan(b.x) || isnan(b.y)) s_nan = 1;
+            });
         const int any_nan = __any(s_nan);
         if (tid == 0) a.nan_flags[srow * a.max_batch + f] = any_nan ? 1 : 0;
     }
@@ -1140,14 +1110,8 @@ __device__ __forceinline__ float sam_detect(cf b, cf c, float &mag) {
 __device__ __forceinline__ cf sam_lag(cf c, cf p) {
     return make_float2(fmaf(c.x, p.x, c.y * p.y), fmaf(c.y, p.x, -(c.x * p.y)));
 }
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-// n = 360 / 720: k_demod_chain_iq's walk - one wave per chain of K frames, ONE warm-up frame, both tails (B's and C's) in
-// registers.  Per frame the compile-time plan runs twice through ONE loop body (two inlined copies would double the code
+// n = 360 / 720: the same shared steps as k_demod_chain_iq - one wave per chain of K frames, ONE warm-up frame, both tails
+// (B's and C's) in registers.  Per frame the compile-time plan runs twice through ONE loop body (two inlined copies would double the code
 // and the address registers): pass 0 on the masked slice gives c_f, pass 1 on the whole slice gives y_f exactly as
 // k_demod_chain_iq computes it (B is bit-identical to the PSDR_IQ rows).  The second plan run instead of a direct sum over
 // the 2 cutoff kept bins: at n = 360 and 12 kHz the direct sum is 30 bins x 6 outputs per lane = 180 complex MACs (720 FMAs
@@ -1160,30 +1124,16 @@ __global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int h = N / 2, NH = (h + 63) / 64;
     const int lane_ = threadIdx.x & 63, wv = threadIdx.x >> 6, W = blockDim.x >> 6;
-    cf *Wn = reinterpret_cast<cf *>(smem);
-    for (int i = threadIdx.x; i < N; i += blockDim.x) Wn[i] = a.Wn[i];
-    __syncthreads();
-    const int F = a.nframes, nch = (F + K - 1) / K;
-    const int item = __builtin_amdgcn_readfirstlane((int)blockIdx.x * W + wv);
-    if (item >= nact * nch) return;
-    const int ci = item / nch, f0 = (item - ci * nch) * K;
-    const int f1 = f0 + K < F ? f0 + K : F;
-    ClientParams cp = a.clients[ci];
-    cp.l = __builtin_amdgcn_readfirstlane(cp.l);
-    cp.r = __builtin_amdgcn_readfirstlane(cp.r);
-    cp.m_floor = __builtin_amdgcn_readfirstlane(cp.m_floor);
-    cp.mode = __builtin_amdgcn_readfirstlane(cp.mode);
-    cp.slot = __builtin_amdgcn_readfirstlane(cp.slot);
-    cp.state_cur = __builtin_amdgcn_readfirstlane(cp.state_cur);
+    cf *Wn = stage_twiddles(a, smem, N);
+    const int F = a.nframes;
+    int ci, f0, f1;
+    if (!wave_chain(nact, F, K, ci, f0, f1)) return;
+    const ClientParams cp = wave_uniform(a.clients[ci]);
     cf *buf = Wn + N + (size_t)wv * N;
     const size_t srow = (size_t)cp.slot;
-    const int cur = cp.state_cur, nxt = cur ^ 1;
-    const float *rp_old = a.real_prev + ((size_t)cur * a.slots + srow) * h;
-    float *rp_new = a.real_prev + ((size_t)nxt * a.slots + srow) * h;
-    const cf *bt_old = a.bb_tail + ((size_t)cur * a.slots + srow) * h;
-    cf *bt_new = a.bb_tail + ((size_t)nxt * a.slots + srow) * h;
-    const cf *ct_old = sa.car_tail + ((size_t)cur * a.slots + srow) * h;
-    cf *ct_new = sa.car_tail + ((size_t)nxt * a.slots + srow) * h;
+    const SlotState st = slot_state(a, cp, h);
+    const cf *ct_old = sa.car_tail + st.row_old * h;
+    cf *ct_new = sa.car_tail + st.row_new * h;
     const int fs = f0 == 0 ? 0 : f0 - 1;  // the warm-up frame: transformed, nothing written
     cf tail[NH];                          // s_{f-1} y_{f-1}[h + j], j = lane + 64 u
     // ... and s_{f-1} c_{f-1}[h + j] in h words of LDS of the wave's own behind the transform buffers: entry j is read and
@@ -1195,7 +1145,7 @@ __global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) 
         tail[u] = make_float2(0.f, 0.f);
         if (j < h) {
             ctail[j] = make_float2(0.f, 0.f);
-            if (fs == 0) tail[u] = bt_old[j], ctail[j] = ct_old[j];  // the batch's first frame: the carried tails
+            if (fs == 0) tail[u] = st.bt_old[j], ctail[j] = ct_old[j];  // the batch's first frame: the carried tails
         }
     }
     constexpr int NR = (N + 63) / 64;
@@ -1210,13 +1160,11 @@ __global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) 
     for (int it = 2 * fs; it < 2 * f1; it++) {
         const int f = it >> 1, pass = it & 1;
         const bool emit = f >= f0;
-        const float sg = flip_frame(a.first_frame_num + (unsigned long long)f, cp.m_floor, a.is_real) ? -1.f : 1.f;
+        const float sg = frame_sign(a, cp, f);
         float *out = a.audio + (srow * a.max_batch + f) * h;
         const bool last = (f == F - 1);
         {
-            int ln = lane_;  // (an opaque copy per iteration: k_demod_chain_fixed says why)
-            asm volatile("" : "+v"(ln));
-            const int lane = ln;
+            const int lane = opaque_lane(lane_);
             cf sv[NR];  // loads first, LDS after
             idft_load_slice_at<N, HO>(a, cp, f, so, lane, sv);
             if (pass == 0) {
@@ -1267,10 +1215,10 @@ __global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) 
                         if (emit) {
                             out[j] = v;
                             if (last) {  // the state the next batch starts from (:200-203 precede the NaN guard); USB / LSB's is kept
-                                bt_new[j] = ynext;
+                                st.bt_new[j] = ynext;
                                 ct_new[j] = ctail[j];
-                                rp_new[j] = rp_old[j];
-                                if (j == h - 1) a.bb_last[(size_t)nxt * a.slots + srow] = b;
+                                st.rp_new[j] = st.rp_old[j];
+                                if (j == h - 1) a.bb_last[st.row_new] = b;
                             }
                         }
                         tail[u] = ynext;
@@ -1319,13 +1267,9 @@ __global__ __launch_bounds__(256) void k_demod_ola_sam(DemodArgs a, int nact, Sa
     const int f0 = (item - ci * ngrp) * FG;
     const size_t srow = (size_t)cp.slot;
     const cf *yp = a.ypost + (srow * a.max_batch) * n;  // this client's frames
-    const int cur = cp.state_cur, nxt = cur ^ 1;
-    const float *rp_old = a.real_prev + ((size_t)cur * a.slots + srow) * h;
-    float *rp_new = a.real_prev + ((size_t)nxt * a.slots + srow) * h;
-    const cf *bt_old = a.bb_tail + ((size_t)cur * a.slots + srow) * h;
-    cf *bt_new = a.bb_tail + ((size_t)nxt * a.slots + srow) * h;
-    const cf *ct_old = sa.car_tail + ((size_t)cur * a.slots + srow) * h;
-    cf *ct_new = sa.car_tail + ((size_t)nxt * a.slots + srow) * h;
+    const SlotState st = slot_state(a, cp, h);
+    const cf *ct_old = sa.car_tail + st.row_old * h;
+    cf *ct_new = sa.car_tail + st.row_new * h;
     // kept AND placed AND inside the slice: d = t - m with 0 <= t < r - l, -(h - 1) <= d < h, -cutoff <= d < cutoff
     const int m = cp.m_floor - cp.l, len = cp.r - cp.l;
     int d0 = -sa.cutoff, d1 = sa.cutoff;
@@ -1336,10 +1280,8 @@ __global__ __launch_bounds__(256) void k_demod_ola_sam(DemodArgs a, int nact, Sa
     for (int g = 0; g < FG; g++) {
         const int f = f0 + g;
         if (f >= F) break;
-        const cf *y = yp + (size_t)f * n;
         const cf *S = a.spec + (size_t)f * a.spec_stride;
-        const float sg = flip_frame(a.first_frame_num + (unsigned long long)f, cp.m_floor, a.is_real) ? -1.f : 1.f;
-        const float sgp = flip_frame(a.first_frame_num + (unsigned long long)f - 1ull, cp.m_floor, a.is_real) ? -1.f : 1.f;
+        const float sg = frame_sign(a, cp, f), sgp = frame_sign(a, cp, f - 1);
         float *out = a.audio + (srow * a.max_batch + f) * h;
         int s_nan = 0;
         const bool last = (f == F - 1);
@@ -1363,26 +1305,22 @@ __global__ __launch_bounds__(256) void k_demod_ola_sam(DemodArgs a, int nact, Sa
             cf pr = make_float2(__shfl_up(c.x, 1, 64), __shfl_up(c.y, 1, 64));  // C[j-1]
             if (tid == 0) pr = ccarry;
             ccarry = make_float2(__shfl(c.x, 63, 64), __shfl(c.y, 63, 64));
-            if (ok) {
-                const cf pv = (f == 0) ? bt_old[j] : yp[(size_t)(f - 1) * n + h + j];
-                const cf b = make_float2(y[j].x + pv.x, y[j].y + pv.y);  // dsp_add_complex :235
-                float mag;
-                const float v = sam_detect(b, c, mag);
-                out[j] = v;
-                if (isnan(v)) s_nan = 1;
-                lvl += mag;
-                if (j > 0) {
-                    const cf t = sam_lag(c, pr);
-                    lag.x += t.x, lag.y += t.y;
-                }
-                if (last) {
-                    bt_new[j] = y[h + j];  // :200-203 (second half kept for the next frame)
-                    const cf cn = sam_carrier_dsum(a, cp, S, d0, d1, h + j);
-                    ct_new[j] = make_float2(__fmul_rn(cn.x, sg), __fmul_rn(cn.y, sg));
-                    rp_new[j] = rp_old[j];
-                    if (j == h - 1) a.bb_last[(size_t)nxt * a.slots + srow] = b;  // `prev` of :200
-                }
-            }
+            if (ok)
+                ola_step(a, st, yp, f, j, [&](cf b) {
+                    float mag;
+                    const float v = sam_detect(b, c, mag);
+                    out[j] = v;
+                    if (isnan(v)) s_nan = 1;
+                    lvl += mag;
+                    if (j > 0) {
+                        const cf t = sam_lag(c, pr);
+                        lag.x += t.x, lag.y += t.y;
+                    }
+                    if (last) {  // the carrier's tail moves with the baseband's
+                        const cf cn = sam_carrier_dsum(a, cp, S, d0, d1, h + j);
+                        ct_new[j] = make_float2(__fmul_rn(cn.x, sg), __fmul_rn(cn.y, sg));
+                    }
+                });
         }
         const int any_nan = __any(s_nan);
         lvl = wave_sum(lvl);

@@ -119,6 +119,66 @@ extern "C" int psdr_client_set_audio_demodulation(psdr_ctx *c, int id, int mode)
     return PSDR_OK;
 }
 
+// One client of a batch's list: the window and the mode it is demodulated with; its double-buffered state flips.  To the
+// post chain a PSDR_IQ client is a paused one (no audio of its own this batch): a pending AGC reset stays with the slot.
+static void fill_params(ClientParams &p, AudioSlot &s, int slot, bool post_on) {
+    const bool audio = s.mode != PSDR_IQ;
+    p = ClientParams{};
+    p.l = s.l;
+    p.r = s.r;
+    p.m_floor = (int)std::floor(s.mid);
+    p.mode = s.mode;
+    p.slot = slot;
+    p.state_cur = s.state_cur;
+    s.state_cur ^= 1;
+    p.paused = audio ? 0 : 1;
+    if (audio && post_on) {
+        p.agc_reset = s.agc_reset;
+        s.agc_reset = 0;
+    }
+}
+
+// The one-kernel path (demod.h): a family of chain kernels is its two compile-time plans, 360 = 8*9*5 and 720 = 8*9*10
+template <class... X>
+struct ChainFamily {
+    void (*k360)(DemodArgs, int, int, X...);
+    void (*k720)(DemodArgs, int, int, X...);
+};
+static const ChainFamily<> CHAIN_FIXED{k_demod_chain_fixed<360, 8, 9, 5>, k_demod_chain_fixed<720, 8, 9, 10>};
+static const ChainFamily<cf *> CHAIN_IQ{k_demod_chain_iq<360, 8, 9, 5>, k_demod_chain_iq<720, 8, 9, 10>};
+static const ChainFamily<SamArgs> CHAIN_SAM{k_demod_chain_sam<360, 8, 9, 5>, k_demod_chain_sam<720, 8, 9, 10>};
+// frames per chain for `cnt` clients: long chains repeat fewer transforms (1 or 2 per chain), short ones give few
+// clients enough waves
+// (256 clients x 256 frames, same box: K = 4 / 8 / 16 / 32 -> 5.81 / 5.77 / 5.93 / 6.04 us per frame, the
+// two-kernel path 5.99)
+// (round 4, 512-frame launches: with 256 clients and more, chains of 16 still leave 8192 waves and repeat half as
+// many warm-up transforms: 93.4 -> 94.6 GS/s on the 256-client shape, same box, interleaved twice)
+static int chain_k(const psdr_ctx *c, int cnt, int nframes) {
+    if (c->demod_chain_k > 0) return c->demod_chain_k;
+    int K = cnt >= 256 && (unsigned)cnt * (unsigned)((nframes + 15) / 16) >= 8192u ? 16 : 8;
+    while (K > 4 && (unsigned)cnt * (unsigned)((nframes + K - 1) / K) < 1024u) K >>= 1;
+    return K;
+}
+// One wave per chain of K consecutive frames (K = 0: chain_k's choice) of each of the `cnt` clients listed in aa.clients.
+// W waves = items per work-group (W360 at n = 360, one at 720) share the twiddle table in LDS; each has a transform buffer
+// and `wave_lds` bytes more - inside the 15 KiB an FFT pass leaves free on a CU.
+template <class... X>
+static hipError_t launch_chain(psdr_ctx *c, const ChainFamily<X...> &fam, DemodArgs aa, int cnt, int K, unsigned W360, size_t wave_lds, X... extra) {
+    if (K <= 0) K = chain_k(c, cnt, aa.nframes);
+    const unsigned W = c->n == 360 ? W360 : 1u;
+    const unsigned items = (unsigned)cnt * (unsigned)((aa.nframes + K - 1) / K);
+    const size_t lds = (size_t)(1 + W) * c->n * sizeof(cf) + W * wave_lds;
+    void *args[] = {&aa, &cnt, &K, &extra...};
+    return hipLaunchKernel((const void *)(c->n == 360 ? fam.k360 : fam.k720), dim3((items + W - 1) / W), dim3(64 * W), args, lds, c->side);
+}
+// The overlap-add behind the IDFT kernels: one wave per (client, group of PSDR_OLA_FG frames)
+template <class... X>
+static hipError_t launch_ola(psdr_ctx *c, void (*k)(DemodArgs, int, X...), DemodArgs aa, int cnt, X... extra) {
+    const unsigned items = (unsigned)cnt * (unsigned)((aa.nframes + PSDR_OLA_FG - 1) / PSDR_OLA_FG);
+    void *args[] = {&aa, &cnt, &extra...};
+    return hipLaunchKernel((const void *)k, dim3((items + 3) / 4), dim3(256), args, 0, c->side);
+}
+
 // band != nullptr: `spec` is a window of bins [band[0], band[0] + band[1]) per frame - linear, or (band_tiled) one
 // band region of a banded spectrum (SpecLayout mode 4)
 static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nframes, uint64_t first_frame_num,
@@ -161,45 +221,20 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
                 sam_zero.push_back(((size_t)s.state_cur * S + i) * ((size_t)c->n / 2));
             s.last_seq = c->demod_seq;
             s.b_l = s.l, s.b_r = s.r, s.b_mid = s.mid, s.b_mode = s.mode;
-            if (s.mode == PSDR_IQ) {  // listed apart, below
-                niq++;
-                continue;
-            }
-            if (s.mode == PSDR_SAM) {  // the tail of the active list, below
-                nsam++;
-                continue;
-            }
-            ClientParams &p = h_clients[nact++];
-            p.l = s.l;
-            p.r = s.r;
-            p.m_floor = (int)std::floor(s.mid);
-            p.mode = s.mode;
-            p.slot = (int)i;
-            p.state_cur = s.state_cur;
-            s.state_cur ^= 1;
-            p.agc_reset = c->post_on ? s.agc_reset : 0;
-            p.paused = 0;
-            if (c->post_on) s.agc_reset = 0;
+            if (s.mode == PSDR_IQ) niq++;  // listed apart, below
         }
-        nold = nact;
-        // PSDR_SAM clients: audio clients like the others (the post chain takes all nact, in any order: it walks the slots
-        // through h_slot_ci), listed behind them for launches of their own.  Without one the list is what it always was.
-        if (nsam > 0)
+        // The active list: USB / LSB / AM / FM, then the PSDR_SAM clients - audio clients like the others (the post chain
+        // takes all nact, in any order: it walks the slots through h_slot_ci), listed behind them for launches of their own.
+        // Without one the list is what it always was.
+        for (int sam = 0; sam < 2; sam++) {
             for (size_t i = 0; i < c->aslots.size(); i++) {
                 AudioSlot &s = c->aslots[i];
-                if (!s.active || s.paused || s.mode != PSDR_SAM) continue;
-                ClientParams &p = h_clients[nact++];
-                p.l = s.l;
-                p.r = s.r;
-                p.m_floor = (int)std::floor(s.mid);
-                p.mode = PSDR_SAM;
-                p.slot = (int)i;
-                p.state_cur = s.state_cur;
-                s.state_cur ^= 1;
-                p.agc_reset = c->post_on ? s.agc_reset : 0;
-                p.paused = 0;
-                if (c->post_on) s.agc_reset = 0;
+                if (!s.active || s.paused || s.mode == PSDR_IQ || (s.mode == PSDR_SAM) != (sam == 1)) continue;
+                fill_params(h_clients[nact++], s, (int)i, c->post_on);
             }
+            if (!sam) nold = nact;
+        }
+        nsam = nact - nold;
         if (c->post_on) {
             for (size_t i = 0; i < S; i++) h_slot_ci[i] = -1;
             for (int i = 0; i < nact; i++) h_slot_ci[h_clients[i].slot] = i;
@@ -230,16 +265,7 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
                 for (size_t i = 0; i < c->aslots.size(); i++) {
                     AudioSlot &s = c->aslots[i];
                     if (!s.active || s.paused || s.mode != PSDR_IQ || (s.agc_reset == 2) != (fresh == 1)) continue;
-                    ClientParams &p = h_clients[k];
-                    p = ClientParams{};
-                    p.l = s.l;
-                    p.r = s.r;
-                    p.m_floor = (int)std::floor(s.mid);
-                    p.mode = PSDR_IQ;
-                    p.slot = (int)i;
-                    p.state_cur = s.state_cur;
-                    s.state_cur ^= 1;
-                    p.paused = 1;
+                    fill_params(h_clients[k], s, (int)i, c->post_on);
                     if (!fresh && c->post_on && nact > 0) {
                         h_slot_ci[i] = k;
                         npaused++;
@@ -312,18 +338,6 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     const bool can_be_nonfinite = c->cfg.input_format >= PSDR_FMT_F32 || spec != c->d_spec;
     bool ola_done = false;
     const bool fixed_plan = c->n == 360 || c->n == 720;
-    // frames per chain of the one-kernel path for `cnt` clients (demod.h): long chains repeat fewer transforms (1 or 2 per
-    // chain), short ones give few clients enough waves
-    // (256 clients x 256 frames, same box: K = 4 / 8 / 16 / 32 -> 5.81 / 5.77 / 5.93 / 6.04 us per frame, the
-    // two-kernel path 5.99)
-    // (round 4, 512-frame launches: with 256 clients and more, chains of 16 still leave 8192 waves and repeat half as
-    // many warm-up transforms: 93.4 -> 94.6 GS/s on the 256-client shape, same box, interleaved twice)
-    auto chain_k = [&](int cnt) {
-        int K = c->demod_chain_k > 0 ? c->demod_chain_k : (cnt >= 256 && (unsigned)cnt * (unsigned)((nframes + 15) / 16) >= 8192u ? 16 : 8);
-        if (c->demod_chain_k <= 0)
-            while (K > 4 && (unsigned)cnt * (unsigned)((nframes + K - 1) / K) < 1024u) K >>= 1;
-        return K;
-    };
     // the transform alone, into ypost, of the `cnt` clients listed in aa.clients (every path but the chain kernels')
     auto launch_idft = [&](const DemodArgs &aa, int cnt) -> int {
         if (fixed_plan) {
@@ -357,26 +371,11 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
         if (fixed_plan && c->demod_chain) {
             // transform + overlap-add + demodulation in one kernel, one wave per chain of K consecutive frames of a
             // client (demod.h)
-            const int K = chain_k(nold);
-            const unsigned items = (unsigned)nold * (unsigned)((nframes + K - 1) / K);
-            const unsigned W = c->n == 360 ? 4u : 1u;
-            const size_t lds = (size_t)(1 + W) * c->n * sizeof(cf);
-            if (c->n == 360)
-                hipLaunchKernelGGL((k_demod_chain_fixed<360, 8, 9, 5>), dim3((items + W - 1) / W), dim3(64 * W), lds,
-                                   c->side, a, nold, K);
-            else
-                hipLaunchKernelGGL((k_demod_chain_fixed<720, 8, 9, 10>), dim3((items + W - 1) / W), dim3(64 * W), lds,
-                                   c->side, a, nold, K);
+            HIPCHK(launch_chain(c, CHAIN_FIXED, a, nold, 0, 4u, 0));
             if (can_be_nonfinite) {
                 DemodArgs ar = a;
                 ar.replay = 1;
-                const int KF = nframes;  // one chain = the whole batch
-                if (c->n == 360)
-                    hipLaunchKernelGGL((k_demod_chain_fixed<360, 8, 9, 5>), dim3(((unsigned)nold + W - 1) / W), dim3(64 * W), lds,
-                                       c->side, ar, nold, KF);
-                else
-                    hipLaunchKernelGGL((k_demod_chain_fixed<720, 8, 9, 10>), dim3(((unsigned)nold + W - 1) / W), dim3(64 * W), lds,
-                                       c->side, ar, nold, KF);
+                HIPCHK(launch_chain(c, CHAIN_FIXED, ar, nold, nframes, 4u, 0));  // one chain = the whole batch
             }
             ola_done = true;
         } else {
@@ -386,11 +385,26 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     }
     if (nold > 0 && !ola_done) {
         ProfScope ps(c, K_OLA, c->side);
-        const unsigned items = (unsigned)nold * (unsigned)((nframes + PSDR_OLA_FG - 1) / PSDR_OLA_FG);
-        hipLaunchKernelGGL(k_demod_ola, dim3((items + 3) / 4), dim3(256), 0, c->side, a, nold);
+        HIPCHK(launch_ola(c, k_demod_ola, a, nold));
         if (can_be_nonfinite) hipLaunchKernelGGL(k_demod_ola_seq, dim3(((unsigned)nold + 3) / 4), dim3(256), 0, c->side, a, nold);
         HIPCHK(hipGetLastError());
     }
+    // a list with launches of its own (PSDR_SAM, PSDR_IQ): its chain kernel, or the transform and its overlap-add kernel
+    auto serve = [&](const auto &fam, auto ola, const DemodArgs &aa, int cnt, unsigned W360, size_t wave_lds, auto extra) -> int {
+        if (fixed_plan && c->demod_chain) {
+            ProfScope ps(c, K_IDFT, c->side);
+            HIPCHK(launch_chain(c, fam, aa, cnt, 0, W360, wave_lds, extra));
+            return PSDR_OK;
+        }
+        {
+            ProfScope ps(c, K_IDFT, c->side);
+            PSDRCHK(launch_idft(aa, cnt));
+            HIPCHK(hipGetLastError());
+        }
+        ProfScope ps(c, K_OLA, c->side);
+        HIPCHK(launch_ola(c, ola, aa, cnt, extra));
+        return PSDR_OK;
+    };
     if (nsam > 0) {
         // the PSDR_SAM clients: the tail of the active list, launches of their own behind the others' (demod.h)
         for (size_t off : sam_zero) HIPCHK(hipMemsetAsync(c->d_car_tail + off, 0, ((size_t)c->n / 2) * sizeof(cf), c->side));
@@ -401,61 +415,15 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
         sa.car_rec = c->d_car;
         sa.cutoff = (int)((int64_t)500 * c->n / c->cfg.audio_rate);  // src/signal.cpp:217-220
         sa.hz_per_rad = (float)((double)c->cfg.audio_rate / (2.0 * M_PI));
-        if (fixed_plan && c->demod_chain) {
-            ProfScope ps(c, K_IDFT, c->side);
-            const int K = chain_k(nsam);
-            const unsigned items = (unsigned)nsam * (unsigned)((nframes + K - 1) / K);
-            // (a wave's carrier tail lives in n/2 words of LDS behind the transform buffers: two waves per work-group at
-            // n = 360, 11.25 KiB, and one at 720, 14.1 KiB - inside the 15 KiB an FFT pass leaves free on a CU)
-            const unsigned W = c->n == 360 ? 2u : 1u;
-            const size_t lds = ((size_t)(1 + W) * c->n + (size_t)W * (c->n / 2)) * sizeof(cf);
-            if (c->n == 360)
-                hipLaunchKernelGGL((k_demod_chain_sam<360, 8, 9, 5>), dim3((items + W - 1) / W), dim3(64 * W), lds,
-                                   c->side, as, nsam, K, sa);
-            else
-                hipLaunchKernelGGL((k_demod_chain_sam<720, 8, 9, 10>), dim3((items + W - 1) / W), dim3(64 * W), lds,
-                                   c->side, as, nsam, K, sa);
-            HIPCHK(hipGetLastError());
-        } else {
-            {
-                ProfScope ps(c, K_IDFT, c->side);
-                PSDRCHK(launch_idft(as, nsam));
-                HIPCHK(hipGetLastError());
-            }
-            ProfScope ps(c, K_OLA, c->side);
-            const unsigned items = (unsigned)nsam * (unsigned)((nframes + PSDR_OLA_FG - 1) / PSDR_OLA_FG);
-            hipLaunchKernelGGL(k_demod_ola_sam, dim3((items + 3) / 4), dim3(256), 0, c->side, as, nsam, sa);
-            HIPCHK(hipGetLastError());
-        }
+        // (a wave's carrier tail lives in n/2 words of LDS behind the transform buffers: two waves per work-group at
+        // n = 360, 11.25 KiB, and one at 720, 14.1 KiB - inside the 15 KiB an FFT pass leaves free on a CU)
+        PSDRCHK(serve(CHAIN_SAM, k_demod_ola_sam, as, nsam, 2u, (size_t)(c->n / 2) * sizeof(cf), sa));
     }
     if (niq > 0) {
         // the PSDR_IQ clients: launches of their own behind the others', on the same stream (demod.h)
         DemodArgs ai = a;
         ai.clients = d_clients + iq_off;
-        if (fixed_plan && c->demod_chain) {
-            ProfScope ps(c, K_IDFT, c->side);
-            const int K = chain_k(niq);
-            const unsigned items = (unsigned)niq * (unsigned)((nframes + K - 1) / K);
-            const unsigned W = c->n == 360 ? 4u : 1u;
-            const size_t lds = (size_t)(1 + W) * c->n * sizeof(cf);
-            if (c->n == 360)
-                hipLaunchKernelGGL((k_demod_chain_iq<360, 8, 9, 5>), dim3((items + W - 1) / W), dim3(64 * W), lds,
-                                   c->side, ai, niq, K, c->d_iq);
-            else
-                hipLaunchKernelGGL((k_demod_chain_iq<720, 8, 9, 10>), dim3((items + W - 1) / W), dim3(64 * W), lds,
-                                   c->side, ai, niq, K, c->d_iq);
-            HIPCHK(hipGetLastError());
-        } else {
-            {
-                ProfScope ps(c, K_IDFT, c->side);
-                PSDRCHK(launch_idft(ai, niq));
-                HIPCHK(hipGetLastError());
-            }
-            ProfScope ps(c, K_OLA, c->side);
-            const unsigned items = (unsigned)niq * (unsigned)((nframes + PSDR_OLA_FG - 1) / PSDR_OLA_FG);
-            hipLaunchKernelGGL(k_demod_ola_iq, dim3((items + 3) / 4), dim3(256), 0, c->side, ai, niq, c->d_iq);
-            HIPCHK(hipGetLastError());
-        }
+        PSDRCHK(serve(CHAIN_IQ, k_demod_ola_iq, ai, niq, 4u, 0, c->d_iq));
     }
     hipStream_t last_user = c->side;
     if (c->post_on && nact > 0) {

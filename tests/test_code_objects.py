@@ -67,3 +67,10 @@ def test_demodulation_chain_kernels_fit_beside_a_pass(meta):
     # passes leave - allocated in eights, so 81 would be 88 and the kernel would wait for a CU without a pass
     for k, v in _find(meta, "psdr::k_demod_chain_fixed<360").items():
         assert v["vgpr"] <= 80, (k, v)
+    # the PSDR_IQ and PSDR_SAM chain kernels take the same wave slots: the same 128 registers, no scratch
+    for name in ("psdr::k_demod_chain_iq<", "psdr::k_demod_chain_sam<"):
+        for k, v in _find(meta, name).items():
+            assert v["vgpr"] <= 128 and v["scratch"] == 0, (k, v)
+    # ... and k_demod_chain_iq at n = 360 (62 registers) shares the 80-register budget of k_demod_chain_fixed<360>
+    for k, v in _find(meta, "psdr::k_demod_chain_iq<360").items():
+        assert v["vgpr"] <= 80, (k, v)
