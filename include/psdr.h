@@ -266,6 +266,41 @@ int psdr_iq_device_ptr(psdr_ctx *ctx, int id, const float **d_iq, const float **
  * slot of the batch. */
 int psdr_read_carrier(psdr_ctx *ctx, int id, int nframes, float *level, float *offset_hz, int *nframes_out);
 int psdr_fetched_carrier(psdr_ctx *ctx, int id, int frame, float *level, float *offset_hz);
+/* Fine tuning below one FFT bin.  The kernels place a client's bins around m = floor(audio_mid), as the reference does: the
+ * tuning grid is one bin of the main FFT (33 Hz at 35 MSPS and 2^20 points).  With the flag on, a client in mode USB, LSB or
+ * IQ is a TUNED client: the fraction delta = audio_mid - m is taken out at the audio rate by a rotator behind the
+ * overlap-add.  psdr_client_set_fine_tune may be called from any thread and takes force at the next batch; PSDR_ERR_INVALID
+ * for an unknown id.  The default is 0 - the reference's behaviour and the launches of a library without this call, bit
+ * for bit - or what psdr_set_option(ctx, PSDR_OPT_FINE_TUNE, 1) set before psdr_client_add (existing clients keep theirs).
+ * A tuned client takes the tuned path whatever the fraction is, delta = 0 included: the path follows the flag, not the
+ * value, so tuning across a bin boundary has no seam.  In AM, FM and SAM the flag is accepted and has NO effect - |B| and
+ * Re(B conj C) / |C| are invariant under a rotation, and the constant it would add to FM sits below the DC blocker: those
+ * clients' launches and bits are the untuned ones.  With n = audio_fft_size, h = n/2, s_f the flip sign:
+ *   Step.  step = (uint32) floor(delta * 2^32 / n + 0.5), in double, from the batch's snapshot of audio_mid: one unit is
+ *     2^-32 turn per audio sample (2.8e-6 Hz at 12 kHz); step < 2^30.
+ *   Phase.  One uint32 per client, 0 at psdr_client_add.  Sample j of frame f of a batch has phi = phi0 + (f * h + j) * step
+ *     in wrapping 32-bit arithmetic; a batch of F frames ends with phi0 += F * h * step.  The phase is continuous across
+ *     frames, batches and changes of delta (a retune by a fraction does not click); a paused client keeps it, and so does
+ *     a batch in which the client was not on the tuned path (flag off, or AM / FM / SAM).
+ *   Rotator.  w(phi) = exp(-2 pi i phi / 2^32) in f32: a pure function of a frame's phi and step, correctly rounded f32
+ *     operations in a fixed order (no fused contraction left to the compiler), the same device function in every kernel -
+ *     no batch split and no choice of path changes a bit.
+ *   Tuned IQ.  row_f[j] = B_f[j] * w(phi_{f,j}), B the PSDR_IQ row of the same window (bit-identical before the rotation).
+ *     State is IQ's (the tail, the UN-rotated last sample; the USB / LSB tail copied through); rows, NaN flag (of the
+ *     rotated row), psdr_read_iq, psdr_iq_device_ptr and PSDR_FETCH_IQ as for IQ; to the post chain a paused client.
+ *   Tuned USB / LSB.  B' is the same baseband built from the window clipped to the sideband - [max(l, m), r) for USB,
+ *     [l, min(r, m + 1)) for LSB - in the AM / FM placement (USB's bin m + k at index k, LSB's bin m - k at index n - k,
+ *     k < h; no Nyquist bin): bit-identical to the PSDR_IQ row of a client on the clipped window.
+ *     audio_f[j] = 2 Re(B'_f[j] w(phi_{f,j})): a bin at m + k comes out at k - delta bins of audio in USB, one at m - k at
+ *     k + delta in LSB.  pwr stays the sum over the whole [l, r).  The NaN flag is 1 if any audio sample is NaN; the state
+ *     moves before the guard (no frame is replayed).  State: a tail of its own, [2][slots][h] complex, allocated with the
+ *     context's first tuned USB / LSB client (16 * (audio_fft_size/2) bytes per client slot; PSDR_ERR_NOMEM and the flag - or,
+ *     from psdr_client_set_audio_demodulation, the mode - unchanged if that fails; a context that never sees one allocates
+ *     nothing).  A client whose previous batch was not tuned in the same mode starts from a ZERO tail: its first frame fades
+ *     in under the window's rising half.  The untuned USB / LSB tail, the AM / FM tail and last sample are copied through:
+ *     every other mode continues behind a tuned stretch as if it had run all along.  To the post chain a tuned USB / LSB
+ *     client is an ordinary audio client (DC blocker, AGC, PCM / PCM16), read and fetched like any other. */
+int psdr_client_set_fine_tune(psdr_ctx *ctx, int id, int on);
 /* A client added after the last psdr_demod_batch has no results in it (the reference's frame loop would not
  * have posted a task for it either, src/websocket.cpp:156-185): psdr_read_audio / psdr_read_pcm / psdr_fetched_audio
  * return PSDR_ERR_NO_DATA for such a slot instead of the previous occupant's samples.
@@ -352,9 +387,12 @@ int psdr_set_post_chain(psdr_ctx *ctx, int enable);
  *   bounds the served path.  psdr_fetched_pcm16 hands the rows out; psdr_fetched_audio's pcm is NULL for
  *   such a batch; psdr_read_pcm still delivers int32 (widened on the host).  0 (default): int32 rows.
  * PSDR_OPT_WATERFALL_DETECTOR (any time, any thread): the psdr_wf_detector a client gets at psdr_waterfall_add (clients that
- *   exist keep theirs: psdr_waterfall_set_detector).  PSDR_WF_SAMPLE (default): the reference's waterfall. */
+ *   exist keep theirs: psdr_waterfall_set_detector).  PSDR_WF_SAMPLE (default): the reference's waterfall.
+ * PSDR_OPT_FINE_TUNE (any time, any thread): 0 (default) or 1, the fine-tune flag a client gets at psdr_client_add (clients
+ *   that exist keep theirs: psdr_client_set_fine_tune).  PSDR_ERR_INVALID for any other value. */
 enum { PSDR_OPT_POST_CHAIN_STREAMS = 1, PSDR_OPT_POST_CHAIN_AGC = 2, PSDR_OPT_POST_CHAIN_PCM16 = 3 };
 #define PSDR_OPT_WATERFALL_DETECTOR 4
+#define PSDR_OPT_FINE_TUNE 5
 int psdr_set_option(psdr_ctx *ctx, int option, int value);
 /* pcm: [frames of the last demod_batch][audio_fft_size/2]; nframes = rows pcm holds (as psdr_read_audio) */
 int psdr_read_pcm(psdr_ctx *ctx, int id, int nframes, int32_t *pcm, int *nframes_out);
@@ -473,7 +511,8 @@ psdr_ctx *psdr_group_ctx(psdr_group *g, int rank);
  * psdr_group_client_rank: the rank (index into `devices`) a client lives on now, -1 for an unknown gid. */
 /* PSDR_IQ is not served through a group (its rows are neither migrated nor fetched by gid): psdr_group_client_add and
  * psdr_group_client_set_audio_demodulation answer PSDR_ERR_UNSUPPORTED for it.  The same holds for PSDR_SAM: the carrier
- * tail is not migrated and the carrier records are not fetched by gid. */
+ * tail is not migrated and the carrier records are not fetched by gid.  There is no psdr_group_* call for the fine-tune
+ * flag: a group's clients are untuned, and a band migration carries the flag's value 0. */
 int psdr_group_client_add(psdr_group *g, int l, double audio_mid, int r, int mode, int *gid_out);
 int psdr_group_client_remove(psdr_group *g, int gid);
 int psdr_group_client_set_audio_range(psdr_group *g, int gid, int l, double audio_mid, int r);

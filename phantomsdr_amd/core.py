@@ -159,6 +159,7 @@ class Context:
     OPT_POST_CHAIN_PCM16 = 3  # 1: the chain's PCM as int16 rows (half the bytes to the host; fetched_pcm16), 0 (default): int32 rows
     OPT_POST_CHAIN_AGC = 2  # 1 (default): chunk maxima + one kernel for the AGC where the rate allows it; 0: the five-kernel form
     OPT_WATERFALL_DETECTOR = 4  # WF_SAMPLE (default) / WF_PEAK / WF_MEAN: the detector of waterfall clients added from now on
+    OPT_FINE_TUNE = 5  # 0 (default) / 1: the fine-tune flag of audio clients added from now on (AudioClient.set_fine_tune)
 
     def set_option(self, option, value):
         check(self.lib.psdr_set_option(self.h, int(option), int(value)))
@@ -431,6 +432,11 @@ class AudioClient:
         """signal_loop's slow-client rule (src/websocket.cpp:170-176): a paused client gets no send_audio call -
         it sits out the demodulation batches with all of its state frozen."""
         check(self.ctx.lib.psdr_client_set_paused(self.ctx.h, self.id, 1 if paused else 0))
+
+    def set_fine_tune(self, on):
+        """tuning below one FFT bin (psdr_client_set_fine_tune): with the flag on, a USB / LSB / IQ client's fraction
+        audio_mid - floor(audio_mid) is taken out by a rotator at the audio rate; AM / FM / SAM are not affected."""
+        check(self.ctx.lib.psdr_client_set_fine_tune(self.ctx.h, self.id, 1 if on else 0))
 
     def on_window_message(self, l, m, r):
         """returns False where the reference silently returns (src/signal.cpp:302-311)."""

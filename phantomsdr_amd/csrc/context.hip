@@ -305,7 +305,8 @@ int build(psdr_ctx *c) {
         PSDRCHK(c->d_bb_last.alloc(2 * S, true));
         PSDRCHK(c->d_ssb_mark.alloc(S, true));
         if (c->lds_mode == 2) PSDRCHK(c->d_gscratch.alloc(S * F * 2 * n));
-        if (c->client_ring.init(S * (sizeof(ClientParams) + sizeof(int))))  // the batch's client list + the slot -> list index table
+        // the batch's client list + the slot -> list index table; behind them the tuned clients' list (ctx.h: ft_ring_off)
+        if (c->client_ring.init(ft_ring_off(S) + S * (sizeof(ClientParams) + sizeof(FtClient))))
             return fail(PSDR_ERR_HIP, "client parameter ring allocation failed");
     }
     // ---- waterfall clients

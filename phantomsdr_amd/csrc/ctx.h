@@ -75,6 +75,10 @@ struct AudioSlot {
     int b_mode = PSDR_USB;  // ... and the mode: a batch demodulated as PSDR_IQ left complex rows (iq_pool) and no audio / PCM; one
                             // demodulated as PSDR_SAM left carrier records and a carrier tail the next SAM batch continues
     uint64_t born = 0;      // psdr_client_add's serial number: a fetched set answers only for the occupant it was filled with
+    // psdr_client_set_fine_tune: with the flag on, a USB / LSB / IQ client is a TUNED client (demod.h: k_demod_chain_ft)
+    int fine = 0;
+    uint32_t ft_phi = 0;    // the rotator's phase at the next tuned batch's first sample (units of 2^-32 turn)
+    bool b_tuned = false;   // the last batch took the tuned path (with b_mode: whether the tuned USB / LSB tail continues)
 };
 struct WfSlot {
     bool active = false;
@@ -119,6 +123,10 @@ struct ParamRing {
         return e;
     }
 };
+
+// the client parameter ring's slot: [ClientParams x S][int x S], then from ft_ring_off(S) on the tuned clients' list,
+// [ClientParams x nt][FtClient x nt] with nt <= S
+inline size_t ft_ring_off(size_t S) { return (S * (sizeof(ClientParams) + sizeof(int)) + 15) & ~(size_t)15; }
 
 inline int ilog2(size_t v) {
     int l = 0;
@@ -290,6 +298,9 @@ struct psdr_ctx {
     // first set to PSDR_SAM (under mtx) and kept.  d_car: the last batch's records
     DevBuf<cf> d_car_tail, car_pool[2];
     cf *d_car = nullptr;
+    // tuned USB / LSB clients (demod.h): their own tail [2][slots][n/2], allocated with the context's first one (under mtx) and kept
+    DevBuf<cf> d_ft_tail;
+    int opt_fine_tune = 0;  // PSDR_OPT_FINE_TUNE: the flag psdr_client_add hands a new client
     DevBuf<unsigned> d_ssb_mark;  // [slots] DemodArgs::ssb_mark (demod.h): USB / LSB batches that need the frame-ordered NaN guard
     ParamRing client_ring;
     int last_demod_frames = 0;

@@ -1332,4 +1332,222 @@ __global__ __launch_bounds__(256) void k_demod_ola_sam(DemodArgs a, int nact, Sa
     }
 }
 
+// ---- fine tuning below one FFT bin: USB / LSB / IQ clients with the fine-tune flag (include/psdr.h) --------------------
+// The bins are placed around m = floor(audio_mid) as ever; the fraction delta = audio_mid - m is taken out behind the
+// overlap-add by a rotator at the audio rate, w(phi) = exp(-2 pi i phi / 2^32), phi_{f,j} = phi0 + (f h + j) step in wrapping
+// 32-bit arithmetic (step = round(delta 2^32 / n); the host carries phi0 from batch to batch):
+//   tuned IQ        row_f[j]   = B_f[j] w(phi_{f,j}),         B  = the PSDR_IQ row of the window
+//   tuned USB / LSB audio_f[j] = 2 Re(B'_f[j] w(phi_{f,j})),  B' = the PSDR_IQ row of the window CLIPPED to the sideband
+// Tuned clients are listed apart: a.clients[ci] carries the PLACED range [l, r) (the clipped window; the whole one for IQ)
+// with the AM / FM placement as its mode - the list every IDFT kernel above takes as it is - and FtArgs::ft[ci] (FtClient, types.h) the phase,
+// the step and the WHOLE window, over which pwr is summed.  One launch serves one family (SSB: float rows of `audio`, a tail
+// of its own in FtArgs::tail, every other piece of state copied through; IQ: complex rows of `iq`, IQ's state).
+struct FtArgs {
+    const FtClient *ft;  // [nact], beside a.clients
+    cf *tail;            // SSB: [2][slots][n/2], s_f y'_f[h..n) of the clipped transform
+    cf *iq;              // IQ: the rows [slots][max_batch][n/2]
+};
+__device__ __forceinline__ cf ft_cmul(cf a, cf b) {
+    return make_float2(__fmaf_rn(a.x, b.x, -__fmul_rn(a.y, b.y)), __fmaf_rn(a.x, b.y, __fmul_rn(a.y, b.x)));
+}
+// w(phi): the nearest quarter turn q comes off in integers, the rest r (|r| <= 2^29 units = an eighth of a turn) goes
+// through the degree-7 / degree-8 polynomials of sin and cos on [-pi/4, pi/4] (Cephes sinf / cosf: below 1 ulp of 1 there).
+// int -> float rounds r to 24 bits, 2^-28 turn.
+__device__ __forceinline__ cf ft_rot(unsigned phi) {
+    const unsigned q = (phi + 0x20000000u) >> 30;
+    const int r = (int)(phi - (q << 30));
+    const float x = __fmul_rn(__int2float_rn(r), 1.4629180792671596e-9f);  // 2 pi / 2^32
+    const float z = __fmul_rn(x, x);
+    const float ps = __fmaf_rn(__fmaf_rn(-1.9515295891e-4f, z, 8.3321608736e-3f), z, -1.6666654611e-1f);
+    const float pc = __fmaf_rn(__fmaf_rn(2.443315711809948e-5f, z, -1.388731625493765e-3f), z, 4.166664568298827e-2f);
+    const float s = __fmaf_rn(__fmul_rn(x, z), ps, x);
+    const float c = __fmaf_rn(__fmul_rn(z, z), pc, __fmaf_rn(z, -0.5f, 1.f));
+    // theta = q pi/2 + x: (cos, sin) = (c, s), (-s, c), (-c, -s), (s, -c) for q = 0 .. 3; w = (cos theta, -sin theta)
+    const float co = (q & 1u) ? s : c, si = (q & 1u) ? c : s;
+    return make_float2(((q + 1u) & 2u) ? -co : co, (q & 2u) ? si : -si);
+}
+// The rotators of a frame for the samples j0 + 64 u of one lane, phl = the phase of sample j0.  Two forms, both pure
+// functions of (phl, step, u): the direct one evaluates w at every sample's phase; the product one evaluates it at the
+// lane's first sample and multiplies with the wave-uniform constant w(64 u step), which a chain kernel computes once per
+// chain.  The same form in every kernel (DESIGN.md 3.9 has the instruction counts that chose it).
+#ifndef PSDR_FT_ROTATOR_DIRECT
+#define PSDR_FT_ROTATOR_DIRECT 0
+#endif
+__device__ __forceinline__ cf ft_w(unsigned phl, unsigned step, int u) {
+    if (PSDR_FT_ROTATOR_DIRECT || u == 0) return ft_rot(phl + 64u * (unsigned)u * step);
+    return ft_cmul(ft_rot(phl), ft_rot(64u * (unsigned)u * step));
+}
+
+// n = 360 / 720: the sibling of k_demod_chain_iq - one wave per chain of K frames, ONE warm-up frame, the tail in registers,
+// the same shared steps.  The slice is loaded over the whole window, summed for pwr exactly as idft_slice_fixed sums it, and
+// the bins outside the placed range are zeroed before the scatter: the buffer the stages see is the one a PSDR_IQ client on
+// the clipped window gives them, so B' is bit-identical to that client's rows.  SSB is a template flag: nothing in the frame
+// loop branches on the family.  Grid and LDS as k_demod_chain_iq.
+template <int N, int R0, int R1, int R2, bool SSB>
+__global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) void k_demod_chain_ft(DemodArgs a, int nact, int K, FtArgs fa) {
+    static_assert(R0 * R1 * R2 == N, "plan");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int h = N / 2, NH = (h + 63) / 64;
+    const int lane_ = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    cf *Wn = stage_twiddles(a, smem, N);
+    const int F = a.nframes;
+    int ci, f0, f1;
+    if (!wave_chain(nact, F, K, ci, f0, f1)) return;
+    const ClientParams cp = wave_uniform(a.clients[ci]);  // [l, r): the placed range
+    FtClient fc = fa.ft[ci];
+    fc.phi0 = __builtin_amdgcn_readfirstlane(fc.phi0);
+    fc.step = __builtin_amdgcn_readfirstlane(fc.step);
+    fc.l = __builtin_amdgcn_readfirstlane(fc.l);
+    fc.r = __builtin_amdgcn_readfirstlane(fc.r);
+    ClientParams cw = cp;  // the whole window: what is loaded and summed
+    cw.l = fc.l, cw.r = fc.r;
+    const int t0 = cp.l - fc.l, t1 = cp.r - fc.l;  // slice bins [t0, t1) are placed
+    cf *buf = Wn + N + (size_t)wv * N;
+    const size_t srow = (size_t)cp.slot;
+    const SlotState st = slot_state(a, cp, h);
+    const cf *tl_old = SSB ? fa.tail + st.row_old * h : st.bt_old;
+    cf *tl_new = SSB ? fa.tail + st.row_new * h : st.bt_new;
+    const int fs = f0 == 0 ? 0 : f0 - 1;  // the warm-up frame: transformed, nothing written
+    cf tail[NH];                          // s_{f-1} y_{f-1}[h + j], j = lane + 64 u
+#pragma unroll
+    for (int u = 0; u < NH; u++) {
+        const int j = lane_ + 64 * u;
+        tail[u] = make_float2(0.f, 0.f);
+        if (fs == 0 && j < h) tail[u] = tl_old[j];  // the batch's first frame: the carried tail
+    }
+#if !PSDR_FT_ROTATOR_DIRECT
+    cf wu[NH];  // w(64 u step): wave-uniform, in scalar registers (the bits are ft_w's)
+#pragma unroll
+    for (int u = 1; u < NH; u++) {
+        const cf t = ft_rot(64u * (unsigned)u * fc.step);
+        wu[u] = make_float2(__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t.x))),
+                            __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t.y))));
+    }
+#endif
+    constexpr int NR = (N + 63) / 64;
+    constexpr int HO = NR < 3 ? NR : (N <= 512 ? 3 : 6);
+    unsigned so[HO];
+    idft_slice_offsets<N, HO>(a, cw, lane_, so);
+    for (int f = fs; f < f1; f++) {
+        const bool emit = f >= f0;
+        const int lane = opaque_lane(lane_);
+        cf sv[NR];  // loads first, LDS after
+        idft_load_slice_at<N, HO>(a, cw, f, so, lane, sv);
+        float pw = 0.f;
+#pragma unroll
+        for (int u = 0; u < NR; u++) {
+            const int t = lane + 64 * u;
+            if (t < cw.r - cw.l) pw += fmaf(sv[u].x, sv[u].x, sv[u].y * sv[u].y);  // (idft_slice_fixed's sum, over the whole window)
+            if (t < t0 || t >= t1) sv[u] = make_float2(0.f, 0.f);
+        }
+        pw = wave_sum(pw);
+        idft_slice_fixed<N, R0, R1, R2>(cw, sv, buf, Wn, lane);
+        if (emit && lane == 0) a.pwr[srow * a.max_batch + f] = pw;
+        const float sg = frame_sign(a, cp, f);
+        const bool last = (f == F - 1);
+        const unsigned phl = fc.phi0 + ((unsigned)f * (unsigned)h + (unsigned)lane) * fc.step;
+        const cf w0 = ft_rot(phl);
+        int s_nan = 0;
+#pragma unroll
+        for (int u = 0; u < NH; u++) {
+            const int j = lane + 64 * u;
+            if (j < h) {
+                const cf v0 = buf[j], v1 = buf[h + j];
+                const cf y = make_float2(__fmul_rn(v0.x, sg), __fmul_rn(v0.y, sg));
+                const cf ynext = make_float2(__fmul_rn(v1.x, sg), __fmul_rn(v1.y, sg));
+                const cf b = make_float2(__fadd_rn(y.x, tail[u].x), __fadd_rn(y.y, tail[u].y));  // dsp_add_complex :235
+#if PSDR_FT_ROTATOR_DIRECT
+                const cf w = ft_w(phl, fc.step, u);
+#else
+                const cf w = u == 0 ? w0 : ft_cmul(w0, wu[u]);
+#endif
+                if constexpr (SSB) {
+                    const float v = __fmul_rn(2.f, __fmaf_rn(b.x, w.x, -__fmul_rn(b.y, w.y)));
+                    if (isnan(v)) s_nan = 1;
+                    if (emit) {
+                        a.audio[(srow * a.max_batch + f) * h + j] = v;
+                        if (last) {  // the client's own tail moves; every other mode's state is copied through
+                            tl_new[j] = ynext;
+                            st.bt_new[j] = st.bt_old[j];
+                            st.rp_new[j] = st.rp_old[j];
+                            if (j == h - 1) a.bb_last[st.row_new] = a.bb_last[st.row_old];
+                        }
+                    }
+                } else {
+                    const cf o = ft_cmul(b, w);
+                    if (isnan(o.x) || isnan(o.y)) s_nan = 1;
+                    if (emit) {
+                        fa.iq[(srow * a.max_batch + f) * h + j] = o;
+                        if (last) {  // IQ's state: the UN-rotated baseband's (:200-203); USB / LSB's is kept
+                            tl_new[j] = ynext;
+                            st.rp_new[j] = st.rp_old[j];
+                            if (j == h - 1) a.bb_last[st.row_new] = b;
+                        }
+                    }
+                }
+                tail[u] = ynext;
+            }
+        }
+        const int any_nan = __any(s_nan);
+        if (emit && lane == 0) a.nan_flags[srow * a.max_batch + f] = any_nan ? 1 : 0;
+        wave_lds_sync();  // buf is read out: the next frame's transform may overwrite it
+    }
+}
+
+// any other n (and n = 360 / 720 with PSDR_DEMOD_CHAIN=0): behind the IDFT kernels on the tuned list, with k_demod_ola_iq's
+// grid: ola_step, the shared rotator, a float or a float2 store.  The IDFT kernel summed pwr over the placed range: the
+// whole window's sum is written here, in idft_slice_fixed's order (bit-identical to the chain kernel's).
+template <bool SSB>
+__global__ __launch_bounds__(256) void k_demod_ola_ft(DemodArgs a, int nact, FtArgs fa) {
+    constexpr int FG = PSDR_OLA_FG;
+    const int n = a.n, h = n / 2, tid = threadIdx.x & 63, NT = 64;
+    const int F = a.nframes, ngrp = (F + FG - 1) / FG;
+    const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= nact * ngrp) return;
+    const int ci = item / ngrp;
+    const ClientParams cp = a.clients[ci];
+    const FtClient fc = fa.ft[ci];
+    const int f0 = (item - ci * ngrp) * FG;
+    const size_t srow = (size_t)cp.slot;
+    const cf *yp = a.ypost + (srow * a.max_batch) * n;  // this client's frames
+    const SlotState st = slot_state(a, cp, h);
+    SlotState sm = st;  // the tail ola_step adds and moves: the client's own for SSB
+    if (SSB) sm.bt_old = fa.tail + st.row_old * h, sm.bt_new = fa.tail + st.row_new * h;
+#pragma unroll
+    for (int g = 0; g < FG; g++) {
+        const int f = f0 + g;
+        if (f >= F) break;
+        const cf *S = a.spec + (size_t)f * a.spec_stride;
+        float pw = 0.f;
+        for (int t = tid; t < fc.r - fc.l; t += NT) {
+            const cf v = S[a.lay.pos(fc.l + t)];
+            pw += fmaf(v.x, v.x, v.y * v.y);
+        }
+        pw = wave_sum(pw);
+        if (tid == 0) a.pwr[srow * a.max_batch + f] = pw;
+        const unsigned phl = fc.phi0 + ((unsigned)f * (unsigned)h + (unsigned)tid) * fc.step;
+        int s_nan = 0, u = 0;
+        for (int j = tid; j < h; j += NT, u++) {
+            ola_step(a, sm, yp, f, j, [&](cf b) {
+                const cf w = ft_w(phl, fc.step, u);
+                if constexpr (SSB) {
+                    const float v = __fmul_rn(2.f, __fmaf_rn(b.x, w.x, -__fmul_rn(b.y, w.y)));
+                    a.audio[(srow * a.max_batch + f) * h + j] = v;
+                    if (isnan(v)) s_nan = 1;
+                } else {
+                    const cf o = ft_cmul(b, w);
+                    fa.iq[(srow * a.max_batch + f) * h + j] = o;
+                    if (isnan(o.x) || isnan(o.y)) s_nan = 1;
+                }
+            });
+            if (SSB && f == F - 1) {  // (ola_step moved the client's own tail as AM's: the AM / FM state is copied through instead)
+                st.bt_new[j] = st.bt_old[j];
+                if (j == h - 1) a.bb_last[st.row_new] = a.bb_last[st.row_old];
+            }
+        }
+        const int any_nan = __any(s_nan);
+        if (tid == 0) a.nan_flags[srow * a.max_batch + f] = any_nan ? 1 : 0;
+    }
+}
+
 }  // namespace psdr

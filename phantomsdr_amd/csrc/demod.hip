@@ -4,6 +4,21 @@
 #include "ctx.h"
 #include "demod.h"
 
+// a tuned client: the fine-tune flag in a mode the rotator means something in (AM, FM, SAM: the flag has no effect)
+static bool tuned_mode(int fine, int mode) { return fine && (mode == PSDR_USB || mode == PSDR_LSB || mode == PSDR_IQ); }
+// the context's first tuned USB / LSB client: its family's tails (a context that never sees one allocates nothing); under mtx
+static int ft_tail_alloc(psdr_ctx *c) {
+    if (c->d_ft_tail) return PSDR_OK;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t S = c->aslots.size(), h = (size_t)c->n / 2;
+    DevBuf<cf> tail;
+    if (tail.alloc(2 * S * h, true)) {
+        const std::string msg = psdr_last_error();
+        return fail(PSDR_ERR_NOMEM, "tuned USB / LSB tails (%zu bytes): %s", 2 * S * h * sizeof(cf), msg.c_str());
+    }
+    c->d_ft_tail = std::move(tail);
+    return PSDR_OK;
+}
 static int check_slot(psdr_ctx *c, int id) {
     if (id < 0 || id >= (int)c->aslots.size() || !c->aslots[id].active)
         return fail(PSDR_ERR_INVALID, "no audio client with id %d", id);
@@ -17,8 +32,10 @@ extern "C" int psdr_client_add(psdr_ctx *c, int *id_out) {
     for (size_t i = 0; i < c->aslots.size(); i++)
         if (!c->aslots[i].active) {
             AudioSlot &s = c->aslots[i];
+            if (c->opt_fine_tune) PSDRCHK(ft_tail_alloc(c));  // (a new client is a USB client: a tuned one under PSDR_OPT_FINE_TUNE)
             s = AudioSlot();
             s.active = true;
+            s.fine = c->opt_fine_tune;
             s.born = ++c->slot_births;
             // a fresh AudioClient starts from zeroed buffers (src/signal.h:42-51)
             const size_t S = c->aslots.size(), h = (size_t)c->n / 2;
@@ -114,8 +131,19 @@ extern "C" int psdr_client_set_audio_demodulation(psdr_ctx *c, int id, int mode)
         c->car_pool[0] = std::move(pool[0]);
         c->car_pool[1] = std::move(pool[1]);
     }
+    if (tuned_mode(c->aslots[id].fine, mode) && mode != PSDR_IQ) PSDRCHK(ft_tail_alloc(c));
     c->aslots[id].mode = mode;
     if (c->aslots[id].agc_reset == 0) c->aslots[id].agc_reset = 1;  // src/signal.cpp:316-328: resets the AGC
+    return PSDR_OK;
+}
+extern "C" int psdr_client_set_fine_tune(psdr_ctx *c, int id, int on) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mtx);
+    int rc = check_slot(c, id);
+    if (rc) return rc;
+    AudioSlot &s = c->aslots[id];
+    if (on && (s.mode == PSDR_USB || s.mode == PSDR_LSB)) PSDRCHK(ft_tail_alloc(c));
+    s.fine = on ? 1 : 0;
     return PSDR_OK;
 }
 
@@ -147,6 +175,8 @@ struct ChainFamily {
 static const ChainFamily<> CHAIN_FIXED{k_demod_chain_fixed<360, 8, 9, 5>, k_demod_chain_fixed<720, 8, 9, 10>};
 static const ChainFamily<cf *> CHAIN_IQ{k_demod_chain_iq<360, 8, 9, 5>, k_demod_chain_iq<720, 8, 9, 10>};
 static const ChainFamily<SamArgs> CHAIN_SAM{k_demod_chain_sam<360, 8, 9, 5>, k_demod_chain_sam<720, 8, 9, 10>};
+static const ChainFamily<FtArgs> CHAIN_FT_SSB{k_demod_chain_ft<360, 8, 9, 5, true>, k_demod_chain_ft<720, 8, 9, 10, true>};
+static const ChainFamily<FtArgs> CHAIN_FT_IQ{k_demod_chain_ft<360, 8, 9, 5, false>, k_demod_chain_ft<720, 8, 9, 10, false>};
 // frames per chain for `cnt` clients: long chains repeat fewer transforms (1 or 2 per chain), short ones give few
 // clients enough waves
 // (256 clients x 256 frames, same box: K = 4 / 8 / 16 / 32 -> 5.81 / 5.77 / 5.93 / 6.04 us per frame, the
@@ -188,6 +218,9 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     int nact = 0, npaused = 0, niq = 0, iq_off = 0;
     int nold = 0, nsam = 0;              // the active list: [0, nold) USB / LSB / AM / FM, [nold, nact) PSDR_SAM
     std::vector<size_t> sam_zero;        // carrier tails (element offsets into d_car_tail) that start this batch from zero
+    // tuned clients (demod.h: k_demod_chain_ft): listed apart, [0, ntssb) USB / LSB then [ntssb, ntssb + ntiq) IQ
+    int ntssb = 0, ntiq = 0;
+    std::vector<size_t> ft_zero;         // tuned USB / LSB tails (element offsets into d_ft_tail) that start from zero
     const int ring = c->client_ring.acquire();
     if (ring < 0) return fail(PSDR_ERR_HIP, "client parameter ring: event wait failed");
     ClientParams *h_clients = (ClientParams *)c->client_ring.host(ring);
@@ -195,6 +228,7 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     // behind the list, for the post chain: the list index of every slot's client (its kernels walk the SLOTS, lane = slot & 63)
     const size_t S = c->aslots.size();
     int *h_slot_ci = (int *)(h_clients + S), *d_slot_ci = (int *)(d_clients + S);
+    unsigned char *h_ft = (unsigned char *)h_clients + ft_ring_off(S), *d_ft = (unsigned char *)d_clients + ft_ring_off(S);
     cf *iq_rows[2] = {nullptr, nullptr}, *car_rows[2] = {nullptr, nullptr};
     {
         std::lock_guard<std::mutex> lk(c->mtx);
@@ -219,22 +253,56 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
             // tail of its own - the other modes' kernels do not carry it along: it starts from zero
             if (s.mode == PSDR_SAM && (s.last_seq == 0 || s.b_mode != PSDR_SAM))
                 sam_zero.push_back(((size_t)s.state_cur * S + i) * ((size_t)c->n / 2));
+            // a tuned USB / LSB client whose previous batch was not tuned in the same mode: likewise, its own tail from zero
+            const bool tuned = tuned_mode(s.fine, s.mode);
+            if (tuned && s.mode != PSDR_IQ && (s.last_seq == 0 || !s.b_tuned || s.b_mode != s.mode))
+                ft_zero.push_back(((size_t)s.state_cur * S + i) * ((size_t)c->n / 2));
             s.last_seq = c->demod_seq;
-            s.b_l = s.l, s.b_r = s.r, s.b_mid = s.mid, s.b_mode = s.mode;
-            if (s.mode == PSDR_IQ) niq++;  // listed apart, below
+            s.b_l = s.l, s.b_r = s.r, s.b_mid = s.mid, s.b_mode = s.mode, s.b_tuned = tuned;
+            if (tuned)
+                (s.mode == PSDR_IQ ? ntiq : ntssb)++;  // listed apart, below
+            else if (s.mode == PSDR_IQ)
+                niq++;  // listed apart, below
         }
+        // The tuned clients' list as the kernels see it: the placed range, the AM / FM placement; beside it phase, step and
+        // the whole window.  The phase moves on by the batch's samples here, from the snapshot.
+        ClientParams *h_ftc = (ClientParams *)h_ft;
+        FtClient *h_ftp = (FtClient *)(h_ftc + ntssb + ntiq);
+        int kt_ssb = 0, kt_iq = ntssb;
+        auto list_tuned = [&](AudioSlot &s, const ClientParams &p) {
+            const int k = s.mode == PSDR_IQ ? kt_iq++ : kt_ssb++;
+            ClientParams &q = h_ftc[k];
+            q = p;
+            q.mode = PSDR_AM;
+            if (s.mode == PSDR_USB) q.l = std::min(std::max(p.l, p.m_floor), p.r);  // [max(l, m), r)
+            if (s.mode == PSDR_LSB) q.r = p.m_floor < p.r ? std::max(p.m_floor + 1, p.l) : p.r;  // [l, min(r, m + 1))
+            const double delta = s.mid - std::floor(s.mid);
+            FtClient &t = h_ftp[k];
+            t.step = (uint32_t)std::floor(delta * 4294967296.0 / c->n + 0.5);
+            t.phi0 = s.ft_phi;
+            t.l = p.l, t.r = p.r;
+            s.ft_phi += (uint32_t)nframes * (uint32_t)(c->n / 2) * t.step;
+        };
         // The active list: USB / LSB / AM / FM, then the PSDR_SAM clients - audio clients like the others (the post chain
         // takes all nact, in any order: it walks the slots through h_slot_ci), listed behind them for launches of their own.
         // Without one the list is what it always was.
         for (int sam = 0; sam < 2; sam++) {
             for (size_t i = 0; i < c->aslots.size(); i++) {
                 AudioSlot &s = c->aslots[i];
-                if (!s.active || s.paused || s.mode == PSDR_IQ || (s.mode == PSDR_SAM) != (sam == 1)) continue;
+                if (!s.active || s.paused || s.mode == PSDR_IQ || (s.mode == PSDR_SAM) != (sam == 1) || tuned_mode(s.fine, s.mode)) continue;
                 fill_params(h_clients[nact++], s, (int)i, c->post_on);
             }
             if (!sam) nold = nact;
         }
         nsam = nact - nold;
+        // ... and behind SAM's tail the tuned USB / LSB clients: audio clients to the post chain, launches of their own
+        if (ntssb > 0)
+            for (size_t i = 0; i < c->aslots.size(); i++) {
+                AudioSlot &s = c->aslots[i];
+                if (!s.active || s.paused || s.mode == PSDR_IQ || !tuned_mode(s.fine, s.mode)) continue;
+                fill_params(h_clients[nact], s, (int)i, c->post_on);
+                list_tuned(s, h_clients[nact++]);
+            }
         if (c->post_on) {
             for (size_t i = 0; i < S; i++) h_slot_ci[i] = -1;
             for (int i = 0; i < nact; i++) h_slot_ci[h_clients[i].slot] = i;
@@ -258,13 +326,26 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
         // PSDR_IQ clients, behind both: the list of k_demod_chain_iq / k_demod_ola_iq.  To the post chain an IQ client IS a
         // paused one - no audio of its own this batch, histories standing still, a pending AGC reset kept for its next
         // audio batch - so those with a history come first and the chain's count of paused clients takes them in
+        // (tuned IQ clients: the kernels take them from the tuned list; this list names those with a history, as paused ones)
+        if (ntiq > 0)
+            for (size_t i = 0; i < c->aslots.size(); i++) {
+                AudioSlot &s = c->aslots[i];
+                if (!s.active || s.paused || s.mode != PSDR_IQ || !tuned_mode(s.fine, s.mode)) continue;
+                ClientParams p;
+                fill_params(p, s, (int)i, c->post_on);
+                list_tuned(s, p);
+                if (s.agc_reset != 2 && c->post_on && nact > 0) {
+                    h_clients[nact + npaused] = p;
+                    h_slot_ci[i] = nact + npaused++;
+                }
+            }
         if (niq > 0) {
             iq_off = nact + npaused;
             int k = iq_off;
             for (int fresh = 0; fresh < 2; fresh++)
                 for (size_t i = 0; i < c->aslots.size(); i++) {
                     AudioSlot &s = c->aslots[i];
-                    if (!s.active || s.paused || s.mode != PSDR_IQ || (s.agc_reset == 2) != (fresh == 1)) continue;
+                    if (!s.active || s.paused || s.mode != PSDR_IQ || (s.agc_reset == 2) != (fresh == 1) || tuned_mode(s.fine, s.mode)) continue;
                     fill_params(h_clients[k], s, (int)i, c->post_on);
                     if (!fresh && c->post_on && nact > 0) {
                         h_slot_ci[i] = k;
@@ -275,7 +356,7 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
         }
     }
     c->last_demod_frames = nframes;
-    if (nact + niq == 0) return PSDR_OK;
+    if (nact + niq + ntiq == 0) return PSDR_OK;
     {  // this batch's results go to the OTHER set (the copies of the last batch to the host may still be reading theirs); what
        // read this set two batches ago must have landed
         c->out_set ^= 1;
@@ -293,6 +374,8 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     }
     HIPCHK(hipMemcpyAsync(d_clients, h_clients, c->post_on ? S * (sizeof(ClientParams) + sizeof(int)) : (size_t)(nact + niq) * sizeof(ClientParams),
                           hipMemcpyHostToDevice, c->side));
+    if (ntssb + ntiq > 0)
+        HIPCHK(hipMemcpyAsync(d_ft, h_ft, (size_t)(ntssb + ntiq) * (sizeof(ClientParams) + sizeof(FtClient)), hipMemcpyHostToDevice, c->side));
     DemodArgs a{};
     a.spec = spec;
     a.spec_stride = spec_stride;
@@ -424,6 +507,25 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
         DemodArgs ai = a;
         ai.clients = d_clients + iq_off;
         PSDRCHK(serve(CHAIN_IQ, k_demod_ola_iq, ai, niq, 4u, 0, c->d_iq));
+    }
+    if (ntssb > 0 && !c->d_ft_tail) return fail(PSDR_ERR_STATE, "tuned USB / LSB clients without their tails");
+    if (ntssb + ntiq > 0) {
+        // the tuned clients: their own list, launches of their own behind the others' (demod.h)
+        for (size_t off : ft_zero) HIPCHK(hipMemsetAsync(c->d_ft_tail + off, 0, ((size_t)c->n / 2) * sizeof(cf), c->side));
+        DemodArgs at = a;
+        FtArgs fa{};
+        fa.tail = c->d_ft_tail;
+        fa.iq = c->d_iq;
+        if (ntssb > 0) {
+            at.clients = (const ClientParams *)d_ft;
+            fa.ft = (const FtClient *)(at.clients + ntssb + ntiq);
+            PSDRCHK(serve(CHAIN_FT_SSB, k_demod_ola_ft<true>, at, ntssb, 4u, 0, fa));
+        }
+        if (ntiq > 0) {
+            at.clients = (const ClientParams *)d_ft + ntssb;
+            fa.ft = (const FtClient *)((const ClientParams *)d_ft + ntssb + ntiq) + ntssb;
+            PSDRCHK(serve(CHAIN_FT_IQ, k_demod_ola_ft<false>, at, ntiq, 4u, 0, fa));
+        }
     }
     hipStream_t last_user = c->side;
     if (c->post_on && nact > 0) {

@@ -156,6 +156,12 @@ extern "C" int psdr_set_option(psdr_ctx *c, int option, int value) {
     }
     case PSDR_OPT_WATERFALL_DETECTOR:
         return set_wf_default_detector(c, value);
+    case PSDR_OPT_FINE_TUNE: {
+        if (value != 0 && value != 1) return fail(PSDR_ERR_INVALID, "PSDR_OPT_FINE_TUNE: 0 or 1, not %d", value);
+        std::lock_guard<std::mutex> lk(c->mtx);
+        c->opt_fine_tune = value;
+        return PSDR_OK;
+    }
     default:
         return fail(PSDR_ERR_INVALID, "unknown option %d", option);
     }

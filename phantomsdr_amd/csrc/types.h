@@ -20,6 +20,12 @@ struct ClientParams {
                     // double-buffered streams must carry the client's history across the batch it sits out)
 };
 
+// a tuned client (demod.h: k_demod_chain_ft / k_demod_ola_ft), beside its ClientParams in the tuned clients' list
+struct FtClient {
+    unsigned phi0, step;  // phase of sample 0 of the batch's frame 0; phase step per audio sample (units of 2^-32 turn)
+    int l, r;             // the whole window [l, r): pwr (ClientParams::l, r: the range that is placed)
+};
+
 // floats of padding behind every slot's stream rows: the recurrence kernels' loader waves read whole blocks of 16 ahead of
 // the stream's end (rings of 12 register sets: postchain.h PC_MA_RING, PC_GAIN_RING)
 #define PSDR_PC_PAD (16 * 20)
