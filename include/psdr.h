@@ -301,6 +301,42 @@ int psdr_fetched_carrier(psdr_ctx *ctx, int id, int frame, float *level, float *
  *     every other mode continues behind a tuned stretch as if it had run all along.  To the post chain a tuned USB / LSB
  *     client is an ordinary audio client (DC blocker, AGC, PCM / PCM16), read and fetched like any other. */
 int psdr_client_set_fine_tune(psdr_ctx *ctx, int id, int on);
+/* Selectable-sideband synchronous AM.  A PSDR_SAM client detects both sidebands together against the recovered carrier; with
+ * PSDR_SAM_UPPER or PSDR_SAM_LOWER it detects only that sideband against the SAME carrier, so an interferer that sits in the
+ * other sideband (a heterodyne from the neighbouring channel, splatter) is gone from the audio.  The sideband is a setting
+ * of the client beside its mode, not a mode: psdr_client_set_sam_sideband may be called from any thread and takes force at
+ * the next batch; PSDR_ERR_INVALID for an unknown id or an unknown value.  The default is PSDR_SAM_BOTH - PSDR_SAM as defined
+ * above, the launches and the bits of a library without this call - or what psdr_set_option(ctx, PSDR_OPT_SAM_SIDEBAND, v)
+ * set before psdr_client_add (existing clients keep theirs).  In every mode other than PSDR_SAM the value is stored and has
+ * NO effect; the fine-tune flag still has no effect on a SAM client, whatever its sideband.  There is no psdr_group_* call
+ * (SAM is not served through a group).  With n = audio_fft_size, h = n/2, m = floor(audio_mid), s_f the flip sign:
+ *   Carrier.  c_f, C_f, the carrier tail and the carrier record (level, offset_hz) are exactly PSDR_SAM's, built from the
+ *     WHOLE window [l, r) with the same cutoff: bit-identical to a PSDR_SAM_BOTH client on the same window in the same
+ *     batches.  A change of sideband at a batch boundary does not reset the carrier tail (it is zeroed only under PSDR_SAM's
+ *     rule: the previous batch was not SAM).
+ *   Baseband.  B'_f is the AM / FM placement of the window clipped to the sideband - [max(l, m), r) for PSDR_SAM_UPPER,
+ *     [l, min(r, m + 1)) for PSDR_SAM_LOWER, the clipping rule of tuned USB / LSB - overlap-added from a tail of the client
+ *     type's own: bit-identical to the PSDR_IQ row of a client on the clipped window with the same audio_mid (from the
+ *     second frame after both start: both begin from a zero tail, IQ carries AM's).
+ *   Audio.  audio_f[j] = 2 * ((B'.re * C.re + B'.im * C.im) / |C|) at index j, |C| = sqrtf(C.re^2 + C.im^2); where
+ *     |C| == 0, audio_f[j] = 2 * B'.re.  Every operation is a correctly rounded f32 one in PSDR_SAM's order, the final
+ *     doubling is exact; a modulation tone comes out at the amplitude PSDR_SAM_BOTH gives it.  No batch split changes a bit.
+ *   pwr.  The sum over the whole [l, r).
+ *   NaN flag.  1 if any audio sample of the frame is NaN; the state moves before the guard.
+ *   State.  The tail of B', [2][slots][h] complex, is allocated with the context's first sideband SAM client - the first
+ *     call that makes a client both PSDR_SAM and not PSDR_SAM_BOTH, whichever of the two calls comes second
+ *     (16 * (audio_fft_size/2) bytes per client slot; PSDR_ERR_NOMEM and the sideband - or, from
+ *     psdr_client_set_audio_demodulation, the mode - unchanged if that fails; a context that never sees one allocates
+ *     nothing).  A slot whose previous batch was not SAM with the SAME sideband starts from a ZERO tail of B'.  The AM / FM
+ *     tail and last sample and the USB / LSB tail are copied through: PSDR_SAM_BOTH and every other mode continue behind a
+ *     sideband stretch from the state they had before it.  A paused slot keeps everything frozen.  To the post chain a
+ *     sideband SAM client is an ordinary audio client; psdr_read_carrier, psdr_fetched_carrier and every audio / PCM read
+ *     and fetch behave as for PSDR_SAM.
+ * n = 360 / 720 run the transform's compile-time plan twice per frame (the carrier's slice, the sideband's slice), any
+ * other n (and PSDR_DEMOD_CHAIN=0) transforms the clipped window and sums the carrier's kept bins directly: the two paths
+ * differ as PSDR_SAM's own two do - in the carrier's last bits, never in B'. */
+typedef enum psdr_sam_sideband { PSDR_SAM_BOTH = 0, PSDR_SAM_UPPER = 1, PSDR_SAM_LOWER = 2 } psdr_sam_sideband;
+int psdr_client_set_sam_sideband(psdr_ctx *ctx, int id, int sideband);
 /* A client added after the last psdr_demod_batch has no results in it (the reference's frame loop would not
  * have posted a task for it either, src/websocket.cpp:156-185): psdr_read_audio / psdr_read_pcm / psdr_fetched_audio
  * return PSDR_ERR_NO_DATA for such a slot instead of the previous occupant's samples.
@@ -389,10 +425,13 @@ int psdr_set_post_chain(psdr_ctx *ctx, int enable);
  * PSDR_OPT_WATERFALL_DETECTOR (any time, any thread): the psdr_wf_detector a client gets at psdr_waterfall_add (clients that
  *   exist keep theirs: psdr_waterfall_set_detector).  PSDR_WF_SAMPLE (default): the reference's waterfall.
  * PSDR_OPT_FINE_TUNE (any time, any thread): 0 (default) or 1, the fine-tune flag a client gets at psdr_client_add (clients
- *   that exist keep theirs: psdr_client_set_fine_tune).  PSDR_ERR_INVALID for any other value. */
+ *   that exist keep theirs: psdr_client_set_fine_tune).  PSDR_ERR_INVALID for any other value.
+ * PSDR_OPT_SAM_SIDEBAND (any time, any thread): the psdr_sam_sideband a client gets at psdr_client_add (clients that exist
+ *   keep theirs: psdr_client_set_sam_sideband).  PSDR_SAM_BOTH (default).  PSDR_ERR_INVALID for any other value. */
 enum { PSDR_OPT_POST_CHAIN_STREAMS = 1, PSDR_OPT_POST_CHAIN_AGC = 2, PSDR_OPT_POST_CHAIN_PCM16 = 3 };
 #define PSDR_OPT_WATERFALL_DETECTOR 4
 #define PSDR_OPT_FINE_TUNE 5
+#define PSDR_OPT_SAM_SIDEBAND 6   /* the value a client gets at psdr_client_add; existing clients keep theirs */
 int psdr_set_option(psdr_ctx *ctx, int option, int value);
 /* pcm: [frames of the last demod_batch][audio_fft_size/2]; nframes = rows pcm holds (as psdr_read_audio) */
 int psdr_read_pcm(psdr_ctx *ctx, int id, int nframes, int32_t *pcm, int *nframes_out);

@@ -8,7 +8,7 @@ Importing this package requires the built HIP library (phantomsdr_amd/libpsdr_hi
 there is no CPU implementation behind it.
 """
 from ._lib import PsdrError, load  # noqa: F401
-from .core import (AM, FM, IQ, LSB, MODES, SAM, USB, WF_DETECTORS, WF_MEAN, WF_PEAK, WF_SAMPLE, AudioClient, Context, Group,  # noqa: F401
-                   HipFFT, SpectrumEngine, WaterfallClient, derived_params)
+from .core import (AM, FM, IQ, LSB, MODES, SAM, SAM_BOTH, SAM_LOWER, SAM_SIDEBANDS, SAM_UPPER, USB, WF_DETECTORS, WF_MEAN, WF_PEAK,  # noqa: F401
+                   WF_SAMPLE, AudioClient, Context, Group, HipFFT, SpectrumEngine, WaterfallClient, derived_params)
 
 load()  # fail loudly at import time if the extension is missing

@@ -25,6 +25,9 @@ USB, LSB, AM, FM = 0, 1, 2, 3
 IQ = 4  # PSDR_IQ (include/psdr.h): the overlap-added complex baseband itself as the client's output
 SAM = 5  # PSDR_SAM: synchronous AM, detection against the recovered carrier (audio like AM, plus carrier records)
 MODES = {"USB": USB, "LSB": LSB, "AM": AM, "FM": FM, "IQ": IQ, "SAM": SAM}
+# psdr_sam_sideband (include/psdr.h): which sideband a SAM client detects against the recovered carrier
+SAM_BOTH, SAM_UPPER, SAM_LOWER = 0, 1, 2
+SAM_SIDEBANDS = {"both": SAM_BOTH, "upper": SAM_UPPER, "lower": SAM_LOWER}
 # psdr_wf_detector (include/psdr.h): what a sent waterfall row shows of the frames since the previous one
 WF_SAMPLE, WF_PEAK, WF_MEAN = 0, 1, 2
 WF_DETECTORS = {"sample": WF_SAMPLE, "peak": WF_PEAK, "mean": WF_MEAN}
@@ -160,6 +163,7 @@ class Context:
     OPT_POST_CHAIN_AGC = 2  # 1 (default): chunk maxima + one kernel for the AGC where the rate allows it; 0: the five-kernel form
     OPT_WATERFALL_DETECTOR = 4  # WF_SAMPLE (default) / WF_PEAK / WF_MEAN: the detector of waterfall clients added from now on
     OPT_FINE_TUNE = 5  # 0 (default) / 1: the fine-tune flag of audio clients added from now on (AudioClient.set_fine_tune)
+    OPT_SAM_SIDEBAND = 6  # SAM_BOTH (default) / SAM_UPPER / SAM_LOWER: the SAM sideband of audio clients added from now on
 
     def set_option(self, option, value):
         check(self.lib.psdr_set_option(self.h, int(option), int(value)))
@@ -437,6 +441,12 @@ class AudioClient:
         """tuning below one FFT bin (psdr_client_set_fine_tune): with the flag on, a USB / LSB / IQ client's fraction
         audio_mid - floor(audio_mid) is taken out by a rotator at the audio rate; AM / FM / SAM are not affected."""
         check(self.ctx.lib.psdr_client_set_fine_tune(self.ctx.h, self.id, 1 if on else 0))
+
+    def set_sam_sideband(self, sideband):
+        """selectable-sideband synchronous AM (psdr_client_set_sam_sideband): "both" (default), "upper" or "lower" - in SAM
+        mode only that sideband is detected against the carrier recovered from the whole window; no effect in other modes."""
+        sb = SAM_SIDEBANDS[sideband] if isinstance(sideband, str) else int(sideband)
+        check(self.ctx.lib.psdr_client_set_sam_sideband(self.ctx.h, self.id, sb))
 
     def on_window_message(self, l, m, r):
         """returns False where the reference silently returns (src/signal.cpp:302-311)."""

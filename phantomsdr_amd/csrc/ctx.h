@@ -79,6 +79,10 @@ struct AudioSlot {
     int fine = 0;
     uint32_t ft_phi = 0;    // the rotator's phase at the next tuned batch's first sample (units of 2^-32 turn)
     bool b_tuned = false;   // the last batch took the tuned path (with b_mode: whether the tuned USB / LSB tail continues)
+    // psdr_client_set_sam_sideband: a PSDR_SAM client with another value than PSDR_SAM_BOTH is a SIDEBAND SAM client
+    // (demod.h: k_demod_chain_sbsam); in every other mode the value is kept and has no effect
+    int sam_sb = PSDR_SAM_BOTH;
+    int b_sam_sb = PSDR_SAM_BOTH;  // ... of the last batch (with b_mode: whether the sideband baseband tail continues)
 };
 struct WfSlot {
     bool active = false;
@@ -125,7 +129,9 @@ struct ParamRing {
 };
 
 // the client parameter ring's slot: [ClientParams x S][int x S], then from ft_ring_off(S) on the tuned clients' list,
-// [ClientParams x nt][FtClient x nt] with nt <= S
+// [ClientParams x nt][FtClient x nt], and behind it the sideband SAM clients' list, [ClientParams x nsb][SbClient x nsb],
+// with nt + nsb <= S (no client is on both lists)
+static_assert(sizeof(SbClient) == sizeof(FtClient), "the two lists share the ring's space behind ft_ring_off");
 inline size_t ft_ring_off(size_t S) { return (S * (sizeof(ClientParams) + sizeof(int)) + 15) & ~(size_t)15; }
 
 inline int ilog2(size_t v) {
@@ -301,6 +307,10 @@ struct psdr_ctx {
     // tuned USB / LSB clients (demod.h): their own tail [2][slots][n/2], allocated with the context's first one (under mtx) and kept
     DevBuf<cf> d_ft_tail;
     int opt_fine_tune = 0;  // PSDR_OPT_FINE_TUNE: the flag psdr_client_add hands a new client
+    // sideband SAM clients (demod.h): the tail of their clipped baseband [2][slots][n/2], allocated with the context's first one
+    // (under mtx) and kept
+    DevBuf<cf> d_sb_tail;
+    int opt_sam_sideband = PSDR_SAM_BOTH;  // PSDR_OPT_SAM_SIDEBAND: the value psdr_client_add hands a new client
     DevBuf<unsigned> d_ssb_mark;  // [slots] DemodArgs::ssb_mark (demod.h): USB / LSB batches that need the frame-ordered NaN guard
     ParamRing client_ring;
     int last_demod_frames = 0;

@@ -1550,4 +1550,253 @@ __global__ __launch_bounds__(256) void k_demod_ola_ft(DemodArgs a, int nact, FtA
     }
 }
 
+// ---- selectable-sideband SAM: a PSDR_SAM client with PSDR_SAM_UPPER / PSDR_SAM_LOWER (include/psdr.h) ------------------------
+// The carrier C_f is PSDR_SAM's, from the WHOLE window; the baseband B'_f is built from the window clipped to the sideband
+// (tuned USB / LSB's clipping rule) with a tail of its own in SbArgs::tail;
+//   audio_f[j] = 2 sam_detect(B', C)
+// Sideband SAM clients are listed apart, behind SAM's: a.clients[ci] carries the PLACED range [l, r) (the clipped window)
+// with the AM / FM placement as its mode - the list every IDFT kernel above takes as it is - and SbArgs::sb[ci] (SbClient,
+// types.h) the sideband and the WHOLE window, from which the carrier is built and over which pwr is summed.  The AM / FM
+// tail and last sample and the USB / LSB tail are copied through; the carrier tail is SamArgs::car_tail, shared with
+// PSDR_SAM_BOTH (a change of sideband does not interrupt it).
+// (The bodies are written out beside k_demod_chain_sam / k_demod_ola_sam, not shared with them: those two stay the code
+// they were, register for register.)
+struct SbArgs {
+    SamArgs sa;
+    const SbClient *sb;  // [nact], beside a.clients
+    cf *tail;            // [2][slots][n/2], s_f y'_f[h..n) of the clipped transform
+};
+// n = 360 / 720: the sibling of k_demod_chain_sam - one wave per chain of K frames, ONE warm-up frame, B''s tail in
+// registers and C's in LDS, one loop over (frame, pass).  cp carries the whole window: pass 0 runs on the carrier-masked
+// slice, pass 1 on the slice masked to the sideband (d = t - m >= 0: upper, d <= 0: lower) - the buffer the stages see is the
+// one a PSDR_IQ client on the clipped window gives them, so B' is bit-identical to that client's rows.  Both masks are one
+// range test [lo, hi) on d.  pwr is summed from the unmasked slice exactly as idft_slice_fixed sums it.  Grid and LDS as
+// k_demod_chain_sam.
+template <int N, int R0, int R1, int R2>
+__global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) void k_demod_chain_sbsam(DemodArgs a, int nact, int K, SbArgs sb) {
+    static_assert(R0 * R1 * R2 == N, "plan");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int h = N / 2, NH = (h + 63) / 64;
+    const int lane_ = threadIdx.x & 63, wv = threadIdx.x >> 6, W = blockDim.x >> 6;
+    cf *Wn = stage_twiddles(a, smem, N);
+    const int F = a.nframes;
+    int ci, f0, f1;
+    if (!wave_chain(nact, F, K, ci, f0, f1)) return;
+    ClientParams cp = a.clients[ci];
+    const SbClient sc = sb.sb[ci];
+    cp.l = sc.l, cp.r = sc.r;  // the whole window: what is loaded, summed and placed (behind the masks)
+    cp = wave_uniform(cp);
+    const bool upper = __builtin_amdgcn_readfirstlane(sc.side) == 1;  // PSDR_SAM_UPPER
+    cf *buf = Wn + N + (size_t)wv * N;
+    const size_t srow = (size_t)cp.slot;
+    const SlotState st = slot_state(a, cp, h);
+    const cf *ct_old = sb.sa.car_tail + st.row_old * h;
+    cf *ct_new = sb.sa.car_tail + st.row_new * h;
+    const cf *tl_old = sb.tail + st.row_old * h;
+    cf *tl_new = sb.tail + st.row_new * h;
+    const int fs = f0 == 0 ? 0 : f0 - 1;  // the warm-up frame: transformed, nothing written
+    cf tail[NH];                          // s_{f-1} y'_{f-1}[h + j], j = lane + 64 u
+    // ... and s_{f-1} c_{f-1}[h + j] in h words of LDS of the wave's own behind the transform buffers (k_demod_chain_sam)
+    cf *ctail = Wn + N + (size_t)W * N + (size_t)wv * h;
+#pragma unroll
+    for (int u = 0; u < NH; u++) {
+        const int j = lane_ + 64 * u;
+        tail[u] = make_float2(0.f, 0.f);
+        if (j < h) {
+            ctail[j] = make_float2(0.f, 0.f);
+            if (fs == 0) tail[u] = tl_old[j], ctail[j] = ct_old[j];  // the batch's first frame: the carried tails
+        }
+    }
+    constexpr int NR = (N + 63) / 64;
+    constexpr int HO = NR < 3 ? NR : (N <= 512 ? 3 : 2);
+    unsigned so[HO];
+    idft_slice_offsets<N, HO>(a, cp, lane_, so);
+    const int m = cp.m_floor - cp.l, len = cp.r - cp.l;
+    cf cC[NH];  // C_f[j], from pass 0 of a frame to its pass 1
+#pragma unroll
+    for (int u = 0; u < NH; u++) cC[u] = make_float2(0.f, 0.f);
+    // ONE loop over (frame, pass): a single copy of the transform in the kernel
+    for (int it = 2 * fs; it < 2 * f1; it++) {
+        const int f = it >> 1, pass = it & 1;
+        const bool emit = f >= f0;
+        const float sg = frame_sign(a, cp, f);
+        float *out = a.audio + (srow * a.max_batch + f) * h;
+        const bool last = (f == F - 1);
+        // slice bin t is kept iff lo <= t - m < hi (wave-uniform): the carrier's low-pass, or the sideband
+        const int lo = pass == 0 ? -sb.sa.cutoff : (upper ? 0 : -N);
+        const int hi = pass == 0 ? sb.sa.cutoff : (upper ? N : 1);
+        {
+            const int lane = opaque_lane(lane_);
+            cf sv[NR];  // loads first, LDS after
+            idft_load_slice_at<N, HO>(a, cp, f, so, lane, sv);
+            float pw = 0.f;
+#pragma unroll
+            for (int u = 0; u < NR; u++) {
+                const int t = lane + 64 * u;
+                if (t < len) pw += fmaf(sv[u].x, sv[u].x, sv[u].y * sv[u].y);  // (idft_slice_fixed's sum, over the whole window)
+                const int d = t - m;
+                if (d < lo || d >= hi) sv[u] = make_float2(0.f, 0.f);
+            }
+            pw = wave_sum(pw);
+            idft_slice_fixed<N, R0, R1, R2>(cp, sv, buf, Wn, lane);
+            if (pass == 0) {
+#pragma unroll
+                for (int u = 0; u < NH; u++) {
+                    const int j = lane + 64 * u;
+                    cC[u] = make_float2(0.f, 0.f);
+                    if (j < h) {
+                        const cf v0 = buf[j], v1 = buf[h + j];
+                        const cf ct = ctail[j];
+                        cC[u] = make_float2(__fadd_rn(__fmul_rn(v0.x, sg), ct.x), __fadd_rn(__fmul_rn(v0.y, sg), ct.y));
+                        ctail[j] = make_float2(__fmul_rn(v1.x, sg), __fmul_rn(v1.y, sg));
+                    }
+                }
+            } else {
+                if (emit && lane == 0) a.pwr[srow * a.max_batch + f] = pw;
+                int s_nan = 0;
+                float lvl = 0.f;
+                cf lag = make_float2(0.f, 0.f), ccarry = make_float2(0.f, 0.f);
+#pragma unroll
+                for (int u = 0; u < NH; u++) {
+                    const int j = lane + 64 * u;
+                    const cf c = cC[u];
+                    cf pr = make_float2(__shfl_up(c.x, 1, 64), __shfl_up(c.y, 1, 64));  // C[j-1]
+                    if (lane == 0) pr = ccarry;
+                    ccarry = make_float2(__shfl(c.x, 63, 64), __shfl(c.y, 63, 64));
+                    if (j < h) {
+                        const cf v0 = buf[j], v1 = buf[h + j];
+                        const cf y = make_float2(__fmul_rn(v0.x, sg), __fmul_rn(v0.y, sg));
+                        const cf ynext = make_float2(__fmul_rn(v1.x, sg), __fmul_rn(v1.y, sg));
+                        const cf b = make_float2(__fadd_rn(y.x, tail[u].x), __fadd_rn(y.y, tail[u].y));  // dsp_add_complex :235
+                        float mag;
+                        const float v = __fmul_rn(2.f, sam_detect(b, c, mag));
+                        if (isnan(v)) s_nan = 1;
+                        lvl += mag;
+                        if (j > 0) {
+                            const cf t = sam_lag(c, pr);
+                            lag.x += t.x, lag.y += t.y;
+                        }
+                        if (emit) {
+                            out[j] = v;
+                            if (last) {  // the two tails of its own move (before the NaN guard); every other mode's state is copied through
+                                tl_new[j] = ynext;
+                                ct_new[j] = ctail[j];
+                                st.bt_new[j] = st.bt_old[j];
+                                st.rp_new[j] = st.rp_old[j];
+                                if (j == h - 1) a.bb_last[st.row_new] = a.bb_last[st.row_old];
+                            }
+                        }
+                        tail[u] = ynext;
+                    }
+                }
+                const int any_nan = __any(s_nan);
+                lvl = wave_sum(lvl);
+                lag.x = wave_sum(lag.x), lag.y = wave_sum(lag.y);
+                if (emit && lane == 0) {
+                    a.nan_flags[srow * a.max_batch + f] = any_nan ? 1 : 0;
+                    sb.sa.car_rec[srow * a.max_batch + f] = make_float2(lvl / (float)h, sb.sa.hz_per_rad * atan2f(lag.y, lag.x));
+                }
+            }
+            wave_lds_sync();  // buf is read out: the next transform may overwrite it
+        }
+    }
+}
+
+// any other n (and n = 360 / 720 with PSDR_DEMOD_CHAIN=0): behind the IDFT kernels on the sideband SAM list (the placed
+// ranges), with k_demod_ola_sam's grid.  B' from the client's rows of ypost through ola_step on the client type's own tail;
+// the carrier by sam_carrier_dsum over the WHOLE window's kept bins, exactly as k_demod_ola_sam sums it.  The IDFT kernel
+// summed pwr over the placed range: the whole window's sum is written here, in idft_slice_fixed's order.
+__global__ __launch_bounds__(256) void k_demod_ola_sbsam(DemodArgs a, int nact, SbArgs sb) {
+    constexpr int FG = PSDR_OLA_FG;
+    const int n = a.n, h = n / 2, tid = threadIdx.x & 63, NT = 64;
+    const int F = a.nframes, ngrp = (F + FG - 1) / FG;
+    const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= nact * ngrp) return;
+    const int ci = item / ngrp;
+    const ClientParams cp = a.clients[ci];  // [l, r): the placed range
+    const SbClient sc = sb.sb[ci];
+    ClientParams cw = cp;  // the whole window: the carrier's and pwr's
+    cw.l = sc.l, cw.r = sc.r;
+    const int f0 = (item - ci * ngrp) * FG;
+    const size_t srow = (size_t)cp.slot;
+    const cf *yp = a.ypost + (srow * a.max_batch) * n;  // this client's frames
+    const SlotState st = slot_state(a, cp, h);
+    SlotState sm = st;  // the tail ola_step adds and moves: the client type's own
+    sm.bt_old = sb.tail + st.row_old * h, sm.bt_new = sb.tail + st.row_new * h;
+    const cf *ct_old = sb.sa.car_tail + st.row_old * h;
+    cf *ct_new = sb.sa.car_tail + st.row_new * h;
+    // kept AND placed AND inside the slice (k_demod_ola_sam), of the whole window
+    const int m = cw.m_floor - cw.l, len = cw.r - cw.l;
+    int d0 = -sb.sa.cutoff, d1 = sb.sa.cutoff;
+    if (d0 < -(h - 1)) d0 = -(h - 1);
+    if (d0 < -m) d0 = -m;
+    if (d1 > h) d1 = h;
+    if (d1 > len - m) d1 = len - m;
+    for (int g = 0; g < FG; g++) {
+        const int f = f0 + g;
+        if (f >= F) break;
+        const cf *S = a.spec + (size_t)f * a.spec_stride;
+        float pw = 0.f;
+        for (int t = tid; t < len; t += NT) {
+            const cf v = S[a.lay.pos(cw.l + t)];
+            pw += fmaf(v.x, v.x, v.y * v.y);
+        }
+        pw = wave_sum(pw);
+        if (tid == 0) a.pwr[srow * a.max_batch + f] = pw;
+        const float sg = frame_sign(a, cw, f), sgp = frame_sign(a, cw, f - 1);
+        float *out = a.audio + (srow * a.max_batch + f) * h;
+        int s_nan = 0;
+        const bool last = (f == F - 1);
+        float lvl = 0.f;
+        cf lag = make_float2(0.f, 0.f), ccarry = make_float2(0.f, 0.f);
+        for (int j0 = 0; j0 < h; j0 += NT) {  // (every lane walks every round: the shuffles below need the whole wave)
+            const int j = j0 + tid;
+            const bool ok = j < h;
+            cf c = make_float2(0.f, 0.f);
+            if (ok) {
+                const cf cy = sam_carrier_dsum(a, cw, S, d0, d1, j);
+                cf ct;
+                if (f == 0) {
+                    ct = ct_old[j];
+                } else {
+                    const cf cp1 = sam_carrier_dsum(a, cw, S - a.spec_stride, d0, d1, h + j);
+                    ct = make_float2(__fmul_rn(cp1.x, sgp), __fmul_rn(cp1.y, sgp));
+                }
+                c = make_float2(__fadd_rn(__fmul_rn(cy.x, sg), ct.x), __fadd_rn(__fmul_rn(cy.y, sg), ct.y));
+            }
+            cf pr = make_float2(__shfl_up(c.x, 1, 64), __shfl_up(c.y, 1, 64));  // C[j-1]
+            if (tid == 0) pr = ccarry;
+            ccarry = make_float2(__shfl(c.x, 63, 64), __shfl(c.y, 63, 64));
+            if (ok) {
+                ola_step(a, sm, yp, f, j, [&](cf b) {
+                    float mag;
+                    const float v = __fmul_rn(2.f, sam_detect(b, c, mag));
+                    out[j] = v;
+                    if (isnan(v)) s_nan = 1;
+                    lvl += mag;
+                    if (j > 0) {
+                        const cf t = sam_lag(c, pr);
+                        lag.x += t.x, lag.y += t.y;
+                    }
+                    if (last) {  // the carrier's tail moves with the baseband's
+                        const cf cn = sam_carrier_dsum(a, cw, S, d0, d1, h + j);
+                        ct_new[j] = make_float2(__fmul_rn(cn.x, sg), __fmul_rn(cn.y, sg));
+                    }
+                });
+                if (last) {  // (ola_step moved the client type's own tail as AM's: the AM / FM state is copied through instead)
+                    st.bt_new[j] = st.bt_old[j];
+                    if (j == h - 1) a.bb_last[st.row_new] = a.bb_last[st.row_old];
+                }
+            }
+        }
+        const int any_nan = __any(s_nan);
+        lvl = wave_sum(lvl);
+        lag.x = wave_sum(lag.x), lag.y = wave_sum(lag.y);
+        if (tid == 0) {
+            a.nan_flags[srow * a.max_batch + f] = any_nan ? 1 : 0;
+            sb.sa.car_rec[srow * a.max_batch + f] = make_float2(lvl / (float)h, sb.sa.hz_per_rad * atan2f(lag.y, lag.x));
+        }
+    }
+}
+
 }  // namespace psdr

@@ -19,6 +19,22 @@ static int ft_tail_alloc(psdr_ctx *c) {
     c->d_ft_tail = std::move(tail);
     return PSDR_OK;
 }
+// a sideband SAM client: PSDR_SAM with another sideband than both (in every other mode the value has no effect)
+static bool sb_sam(int mode, int sideband) { return mode == PSDR_SAM && sideband != PSDR_SAM_BOTH; }
+// the context's first sideband SAM client: the tails of its clipped baseband (a context that never sees one allocates
+// nothing); under mtx
+static int sb_tail_alloc(psdr_ctx *c) {
+    if (c->d_sb_tail) return PSDR_OK;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t S = c->aslots.size(), h = (size_t)c->n / 2;
+    DevBuf<cf> tail;
+    if (tail.alloc(2 * S * h, true)) {
+        const std::string msg = psdr_last_error();
+        return fail(PSDR_ERR_NOMEM, "sideband SAM tails (%zu bytes): %s", 2 * S * h * sizeof(cf), msg.c_str());
+    }
+    c->d_sb_tail = std::move(tail);
+    return PSDR_OK;
+}
 static int check_slot(psdr_ctx *c, int id) {
     if (id < 0 || id >= (int)c->aslots.size() || !c->aslots[id].active)
         return fail(PSDR_ERR_INVALID, "no audio client with id %d", id);
@@ -36,6 +52,7 @@ extern "C" int psdr_client_add(psdr_ctx *c, int *id_out) {
             s = AudioSlot();
             s.active = true;
             s.fine = c->opt_fine_tune;
+            s.sam_sb = c->opt_sam_sideband;  // (a new client is a USB client: the value waits for PSDR_SAM)
             s.born = ++c->slot_births;
             // a fresh AudioClient starts from zeroed buffers (src/signal.h:42-51)
             const size_t S = c->aslots.size(), h = (size_t)c->n / 2;
@@ -132,6 +149,7 @@ extern "C" int psdr_client_set_audio_demodulation(psdr_ctx *c, int id, int mode)
         c->car_pool[1] = std::move(pool[1]);
     }
     if (tuned_mode(c->aslots[id].fine, mode) && mode != PSDR_IQ) PSDRCHK(ft_tail_alloc(c));
+    if (sb_sam(mode, c->aslots[id].sam_sb)) PSDRCHK(sb_tail_alloc(c));
     c->aslots[id].mode = mode;
     if (c->aslots[id].agc_reset == 0) c->aslots[id].agc_reset = 1;  // src/signal.cpp:316-328: resets the AGC
     return PSDR_OK;
@@ -144,6 +162,17 @@ extern "C" int psdr_client_set_fine_tune(psdr_ctx *c, int id, int on) {
     AudioSlot &s = c->aslots[id];
     if (on && (s.mode == PSDR_USB || s.mode == PSDR_LSB)) PSDRCHK(ft_tail_alloc(c));
     s.fine = on ? 1 : 0;
+    return PSDR_OK;
+}
+extern "C" int psdr_client_set_sam_sideband(psdr_ctx *c, int id, int sideband) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mtx);
+    int rc = check_slot(c, id);
+    if (rc) return rc;
+    if (sideband < PSDR_SAM_BOTH || sideband > PSDR_SAM_LOWER) return fail(PSDR_ERR_INVALID, "unknown SAM sideband %d", sideband);
+    AudioSlot &s = c->aslots[id];
+    if (sb_sam(s.mode, sideband)) PSDRCHK(sb_tail_alloc(c));
+    s.sam_sb = sideband;
     return PSDR_OK;
 }
 
@@ -177,6 +206,7 @@ static const ChainFamily<cf *> CHAIN_IQ{k_demod_chain_iq<360, 8, 9, 5>, k_demod_
 static const ChainFamily<SamArgs> CHAIN_SAM{k_demod_chain_sam<360, 8, 9, 5>, k_demod_chain_sam<720, 8, 9, 10>};
 static const ChainFamily<FtArgs> CHAIN_FT_SSB{k_demod_chain_ft<360, 8, 9, 5, true>, k_demod_chain_ft<720, 8, 9, 10, true>};
 static const ChainFamily<FtArgs> CHAIN_FT_IQ{k_demod_chain_ft<360, 8, 9, 5, false>, k_demod_chain_ft<720, 8, 9, 10, false>};
+static const ChainFamily<SbArgs> CHAIN_SBSAM{k_demod_chain_sbsam<360, 8, 9, 5>, k_demod_chain_sbsam<720, 8, 9, 10>};
 // frames per chain for `cnt` clients: long chains repeat fewer transforms (1 or 2 per chain), short ones give few
 // clients enough waves
 // (256 clients x 256 frames, same box: K = 4 / 8 / 16 / 32 -> 5.81 / 5.77 / 5.93 / 6.04 us per frame, the
@@ -221,6 +251,9 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     // tuned clients (demod.h: k_demod_chain_ft): listed apart, [0, ntssb) USB / LSB then [ntssb, ntssb + ntiq) IQ
     int ntssb = 0, ntiq = 0;
     std::vector<size_t> ft_zero;         // tuned USB / LSB tails (element offsets into d_ft_tail) that start from zero
+    // sideband SAM clients (demod.h: k_demod_chain_sbsam): listed apart, behind the tuned clients' list
+    int nsb = 0;
+    std::vector<size_t> sb_zero;         // sideband SAM tails (element offsets into d_sb_tail) that start from zero
     const int ring = c->client_ring.acquire();
     if (ring < 0) return fail(PSDR_ERR_HIP, "client parameter ring: event wait failed");
     ClientParams *h_clients = (ClientParams *)c->client_ring.host(ring);
@@ -257,8 +290,14 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
             const bool tuned = tuned_mode(s.fine, s.mode);
             if (tuned && s.mode != PSDR_IQ && (s.last_seq == 0 || !s.b_tuned || s.b_mode != s.mode))
                 ft_zero.push_back(((size_t)s.state_cur * S + i) * ((size_t)c->n / 2));
+            // a sideband SAM client whose previous batch was not SAM with the same sideband: likewise, its own tail from
+            // zero (the carrier tail follows SAM's rule above alone: a change of sideband does not interrupt it)
+            const bool sbc = sb_sam(s.mode, s.sam_sb);
+            if (sbc && (s.last_seq == 0 || s.b_mode != PSDR_SAM || s.b_sam_sb != s.sam_sb))
+                sb_zero.push_back(((size_t)s.state_cur * S + i) * ((size_t)c->n / 2));
+            if (sbc) nsb++;  // listed apart, below
             s.last_seq = c->demod_seq;
-            s.b_l = s.l, s.b_r = s.r, s.b_mid = s.mid, s.b_mode = s.mode, s.b_tuned = tuned;
+            s.b_l = s.l, s.b_r = s.r, s.b_mid = s.mid, s.b_mode = s.mode, s.b_tuned = tuned, s.b_sam_sb = s.sam_sb;
             if (tuned)
                 (s.mode == PSDR_IQ ? ntiq : ntssb)++;  // listed apart, below
             else if (s.mode == PSDR_IQ)
@@ -289,7 +328,7 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
         for (int sam = 0; sam < 2; sam++) {
             for (size_t i = 0; i < c->aslots.size(); i++) {
                 AudioSlot &s = c->aslots[i];
-                if (!s.active || s.paused || s.mode == PSDR_IQ || (s.mode == PSDR_SAM) != (sam == 1) || tuned_mode(s.fine, s.mode)) continue;
+                if (!s.active || s.paused || s.mode == PSDR_IQ || (s.mode == PSDR_SAM) != (sam == 1) || tuned_mode(s.fine, s.mode) || sb_sam(s.mode, s.sam_sb)) continue;
                 fill_params(h_clients[nact++], s, (int)i, c->post_on);
             }
             if (!sam) nold = nact;
@@ -303,6 +342,27 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
                 fill_params(h_clients[nact], s, (int)i, c->post_on);
                 list_tuned(s, h_clients[nact++]);
             }
+        // ... and behind those the sideband SAM clients, audio clients to the post chain too.  Their own list as the kernels
+        // see it: the placed range (the window clipped to the sideband), the AM / FM placement; beside it the sideband and
+        // the whole window.
+        if (nsb > 0) {
+            ClientParams *h_sbc = (ClientParams *)(h_ft + (size_t)(ntssb + ntiq) * (sizeof(ClientParams) + sizeof(FtClient)));
+            SbClient *h_sbp = (SbClient *)(h_sbc + nsb);
+            int k = 0;
+            for (size_t i = 0; i < c->aslots.size(); i++) {
+                AudioSlot &s = c->aslots[i];
+                if (!s.active || s.paused || !sb_sam(s.mode, s.sam_sb)) continue;
+                const ClientParams &p = h_clients[nact];
+                fill_params(h_clients[nact++], s, (int)i, c->post_on);
+                ClientParams &q = h_sbc[k];
+                q = p;
+                q.mode = PSDR_AM;
+                if (s.sam_sb == PSDR_SAM_UPPER) q.l = std::min(std::max(p.l, p.m_floor), p.r);  // [max(l, m), r)
+                if (s.sam_sb == PSDR_SAM_LOWER) q.r = p.m_floor < p.r ? std::max(p.m_floor + 1, p.l) : p.r;  // [l, min(r, m + 1))
+                SbClient &t = h_sbp[k++];
+                t.l = p.l, t.r = p.r, t.side = s.sam_sb, t.pad = 0;
+            }
+        }
         if (c->post_on) {
             for (size_t i = 0; i < S; i++) h_slot_ci[i] = -1;
             for (int i = 0; i < nact; i++) h_slot_ci[h_clients[i].slot] = i;
@@ -376,6 +436,8 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
                           hipMemcpyHostToDevice, c->side));
     if (ntssb + ntiq > 0)
         HIPCHK(hipMemcpyAsync(d_ft, h_ft, (size_t)(ntssb + ntiq) * (sizeof(ClientParams) + sizeof(FtClient)), hipMemcpyHostToDevice, c->side));
+    const size_t sb_off = (size_t)(ntssb + ntiq) * (sizeof(ClientParams) + sizeof(FtClient));  // the sideband SAM list, behind the tuned one
+    if (nsb > 0) HIPCHK(hipMemcpyAsync(d_ft + sb_off, h_ft + sb_off, (size_t)nsb * (sizeof(ClientParams) + sizeof(SbClient)), hipMemcpyHostToDevice, c->side));
     DemodArgs a{};
     a.spec = spec;
     a.spec_stride = spec_stride;
@@ -488,16 +550,19 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
         HIPCHK(launch_ola(c, ola, aa, cnt, extra));
         return PSDR_OK;
     };
-    if (nsam > 0) {
-        // the PSDR_SAM clients: the tail of the active list, launches of their own behind the others' (demod.h)
+    SamArgs sa{};
+    if (nsam + nsb > 0) {
+        // (sam_zero names the slots of both kinds of SAM client: they share the carrier tail)
         for (size_t off : sam_zero) HIPCHK(hipMemsetAsync(c->d_car_tail + off, 0, ((size_t)c->n / 2) * sizeof(cf), c->side));
-        DemodArgs as = a;
-        as.clients = d_clients + nold;
-        SamArgs sa{};
         sa.car_tail = c->d_car_tail;
         sa.car_rec = c->d_car;
         sa.cutoff = (int)((int64_t)500 * c->n / c->cfg.audio_rate);  // src/signal.cpp:217-220
         sa.hz_per_rad = (float)((double)c->cfg.audio_rate / (2.0 * M_PI));
+    }
+    if (nsam > 0) {
+        // the PSDR_SAM clients: the tail of the active list, launches of their own behind the others' (demod.h)
+        DemodArgs as = a;
+        as.clients = d_clients + nold;
         // (a wave's carrier tail lives in n/2 words of LDS behind the transform buffers: two waves per work-group at
         // n = 360, 11.25 KiB, and one at 720, 14.1 KiB - inside the 15 KiB an FFT pass leaves free on a CU)
         PSDRCHK(serve(CHAIN_SAM, k_demod_ola_sam, as, nsam, 2u, (size_t)(c->n / 2) * sizeof(cf), sa));
@@ -526,6 +591,18 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
             fa.ft = (const FtClient *)((const ClientParams *)d_ft + ntssb + ntiq) + ntssb;
             PSDRCHK(serve(CHAIN_FT_IQ, k_demod_ola_ft<false>, at, ntiq, 4u, 0, fa));
         }
+    }
+    if (nsb > 0) {
+        // the sideband SAM clients: their own list, launches of their own behind all the others' (demod.h); LDS as SAM's
+        if (!c->d_sb_tail || !c->d_car_tail) return fail(PSDR_ERR_STATE, "sideband SAM clients without their tails");
+        for (size_t off : sb_zero) HIPCHK(hipMemsetAsync(c->d_sb_tail + off, 0, ((size_t)c->n / 2) * sizeof(cf), c->side));
+        DemodArgs ab = a;
+        ab.clients = (const ClientParams *)(d_ft + sb_off);
+        SbArgs sba{};
+        sba.sa = sa;
+        sba.sb = (const SbClient *)(ab.clients + nsb);
+        sba.tail = c->d_sb_tail;
+        PSDRCHK(serve(CHAIN_SBSAM, k_demod_ola_sbsam, ab, nsb, 2u, (size_t)(c->n / 2) * sizeof(cf), sba));
     }
     hipStream_t last_user = c->side;
     if (c->post_on && nact > 0) {

@@ -162,6 +162,12 @@ extern "C" int psdr_set_option(psdr_ctx *c, int option, int value) {
         c->opt_fine_tune = value;
         return PSDR_OK;
     }
+    case PSDR_OPT_SAM_SIDEBAND: {
+        if (value < PSDR_SAM_BOTH || value > PSDR_SAM_LOWER) return fail(PSDR_ERR_INVALID, "PSDR_OPT_SAM_SIDEBAND: a psdr_sam_sideband, not %d", value);
+        std::lock_guard<std::mutex> lk(c->mtx);
+        c->opt_sam_sideband = value;
+        return PSDR_OK;
+    }
     default:
         return fail(PSDR_ERR_INVALID, "unknown option %d", option);
     }

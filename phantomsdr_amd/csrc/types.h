@@ -26,6 +26,14 @@ struct FtClient {
     int l, r;             // the whole window [l, r): pwr (ClientParams::l, r: the range that is placed)
 };
 
+// a sideband SAM client (demod.h: k_demod_chain_sbsam / k_demod_ola_sbsam), beside its ClientParams in the sideband SAM
+// clients' list
+struct SbClient {
+    int l, r;   // the whole window [l, r): carrier and pwr (ClientParams::l, r: the range that is placed, clipped to the sideband)
+    int side;   // psdr_sam_sideband: PSDR_SAM_UPPER or PSDR_SAM_LOWER
+    int pad;
+};
+
 // floats of padding behind every slot's stream rows: the recurrence kernels' loader waves read whole blocks of 16 ahead of
 // the stream's end (rings of 12 register sets: postchain.h PC_MA_RING, PC_GAIN_RING)
 #define PSDR_PC_PAD (16 * 20)
