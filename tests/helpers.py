@@ -115,3 +115,47 @@ def check_fm(a_gpu, a_ref, baseband, prev, tag="", fwd_scale=0.0):
     bad = dd > tol
     assert not bad.any(), (f"{tag}: FM error {dd[bad].max():.2e} rad above the conditioned bound at {int(bad.sum())} "
                            f"samples (worst ratio {float((dd / tol).max()):.2f})")
+
+
+# ---- the client kinds of the demodulator's lists (include/psdr.h), for the tests that mix them ----------------------------
+# kind -> (mode, fine-tune flag, SAM sideband, family); a family is one list of psdr_demod_batch with launches of its own
+CLIENT_KINDS = {
+    "USB": ("USB", False, "both", "old"), "LSB": ("LSB", False, "both", "old"), "AM": ("AM", False, "both", "old"),
+    "FM": ("FM", False, "both", "old"), "SAM": ("SAM", False, "both", "sam"), "IQ": ("IQ", False, "both", "iq"),
+    "TUSB": ("USB", True, "both", "tuned"), "TLSB": ("LSB", True, "both", "tuned"), "TIQ": ("IQ", True, "both", "tuned"),
+    "SAMU": ("SAM", False, "upper", "sb"), "SAML": ("SAM", False, "lower", "sb"),
+}
+CLIENT_FAMILIES = ("old", "sam", "iq", "tuned", "sb")
+ROW_NAMES = ("rows", "pwr", "nan flags", "carrier level", "carrier offset", "pcm")
+
+
+def set_client_kind(g, kind):
+    """mode, fine-tune flag and SAM sideband of an AudioClient, all three every time: a client may come from any other kind"""
+    mode, fine, side, _ = CLIENT_KINDS[kind]
+    g.set_fine_tune(fine)
+    g.set_sam_sideband(side)
+    g.set_audio_demodulation(mode)
+
+
+def read_client(g, kind, nrows, pcm=False):
+    """the last batch of a client of `kind`: (rows, pwr, nan flags) - complex rows of the IQ kinds, float rows of any other -
+    then (carrier level, carrier offset) of the SAM kinds, then the PCM rows of an audio kind if `pcm`"""
+    mode = CLIENT_KINDS[kind][0]
+    out = g.read_iq(nrows) if mode == "IQ" else g.read_audio(nrows)
+    if mode == "SAM":
+        out = out + g.read_carrier(nrows)
+    if pcm and mode != "IQ":
+        out = out + (g.read_pcm(nrows),)
+    return out
+
+
+def row_names(kind, pcm=False):
+    mode = CLIENT_KINDS[kind][0]
+    return ROW_NAMES[:3] + (ROW_NAMES[3:5] if mode == "SAM" else ()) + (ROW_NAMES[5:] if pcm and mode != "IQ" else ())
+
+
+def assert_same_bits(a, b, tag, names=ROW_NAMES):
+    """two tuples of arrays: the same shapes and the same bytes"""
+    assert len(a) == len(b), f"{tag}: {len(a)} arrays against {len(b)}"
+    for x, y, w in zip(a, b, names):
+        assert x.shape == y.shape and x.dtype == y.dtype and x.tobytes() == y.tobytes(), f"{tag}: {w} differ"

@@ -69,9 +69,10 @@ def clipped(win, side):
 
 
 @functools.lru_cache(maxsize=None)
-def stream(is_real, n):
+def stream(is_real, n, nf=NF):
+    """(raw s16 samples, converted half-frames [nf + 1][N / 2]) of nf frames"""
     N = SHAPES[is_real]
-    ns = (NF + 1) * (N // 2)
+    ns = (nf + 1) * (N // 2)
     rng = np.random.default_rng(170 + is_real)
     t = np.arange(ns, dtype=np.float64)
     amp = 8.0 / np.sqrt(N)
@@ -85,7 +86,7 @@ def stream(is_real, n):
              + 0.25 * amp * np.exp(2j * np.pi * fi * t))
     raw = quantize_raw(x, "s16", bool(is_real))
     conv = O.convert(raw, "s16")
-    halves = (conv if is_real else conv.view(np.complex64)).reshape(NF + 1, N // 2)
+    halves = (conv if is_real else conv.view(np.complex64)).reshape(nf + 1, N // 2)
     return raw, halves
 
 
