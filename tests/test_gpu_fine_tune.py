@@ -87,15 +87,20 @@ def clipped(mode, win):
 
 
 def baseband64(is_real, n, win, fa, fb):
-    """float64: the AM / FM placement of the window's bins, np.fft.ifft * n, flip, overlap-add from a ZERO tail at frame fa:
-    B[fa..fb) complex128 [fb - fa][h]"""
+    """baseband64_of on the oracle's spectra"""
     fo, specs = oracle_spectra(is_real, n)
+    return baseband64_of(specs, lambda s, l, ln: s[fo.slice_ptr_index(l):fo.slice_ptr_index(l) + ln], is_real, n, win, fa, fb)
+
+
+def baseband64_of(specs, slice_of, is_real, n, win, fa, fb):
+    """float64: the AM / FM placement of the window's bins, np.fft.ifft * n, flip, overlap-add from a ZERO tail at frame fa:
+    B[fa..fb) complex128 [fb - fa][h].  specs: one spectrum per frame; slice_of(spectrum, l, ln): its bins [l, l + ln) in
+    client order"""
     l, mid, r = win
     h, m_floor = n // 2, int(np.floor(mid))
-    start = fo.slice_ptr_index(l)
     B, bt = np.zeros((fb - fa, h), np.complex128), np.zeros(h, np.complex128)
     for f in range(fa, fb):
-        S = specs[f][start:start + (r - l)].astype(np.complex128)
+        S = slice_of(specs[f], l, r - l).astype(np.complex128)
         X = np.zeros(n, np.complex128)
         for t in range(r - l):
             d = l + t - m_floor

@@ -88,19 +88,29 @@ def flip_sign(frame, m_floor, is_real):
 
 
 def truth(is_real, n, win, sam_starts=(0,)):
-    """float64, as psdr.h defines the mode: placement, np.fft.ifft * n, mask, flip, overlap-add, detector, carrier record -
-    over the 25 frames of one window.  sam_starts: the frames at which the carrier tail starts from zero.
-    -> dict of B, C [25][h] complex128, audio [25][h], level, offset_hz, pwr, fwd_scale [25]"""
+    """float64, as psdr.h defines the mode, on the oracle's spectra of the 25 frames of one window (truth_of)"""
     fo, specs = oracle_spectra(is_real, n)
+    return truth_of(specs, lambda s, l, ln: s[fo.slice_ptr_index(l):fo.slice_ptr_index(l) + ln], is_real, n, win, sam_starts)
+
+
+def spectrum_rms(s):
+    return float(np.sqrt(np.mean(np.abs(s[:4096].astype(np.complex128)) ** 2)))
+
+
+def truth_of(specs, slice_of, is_real, n, win, sam_starts=(0,), rms_of=spectrum_rms):
+    """float64, as psdr.h defines the mode: placement, np.fft.ifft * n, mask, flip, overlap-add, detector, carrier record -
+    over the frames of one window.  specs: one spectrum per frame; slice_of(spectrum, l, ln): its bins [l, l + ln) in client
+    order; rms_of(spectrum): the rms of its R bins.  sam_starts: the frames at which the carrier tail starts from zero.
+    -> dict of B, C [frames][h] complex128, audio [frames][h], level, offset_hz, pwr, fwd_scale [frames]"""
+    NF = len(specs)
     l, mid, r = win
     h, m_floor = n // 2, int(np.floor(mid))
     m, ln, cut = m_floor - l, r - l, cutoff(n)
-    start = fo.slice_ptr_index(l)
     B, Cc = np.zeros((NF, h), np.complex128), np.zeros((NF, h), np.complex128)
     pw, fs = np.zeros(NF), np.zeros(NF)
     bt, ct = np.zeros(h, np.complex128), np.zeros(h, np.complex128)
     for f in range(NF):
-        S = specs[f][start:start + ln].astype(np.complex128)
+        S = slice_of(specs[f], l, ln).astype(np.complex128)
         X = np.zeros(n, np.complex128)
         for t in range(ln):
             d = t - m
@@ -118,7 +128,7 @@ def truth(is_real, n, win, sam_starts=(0,)):
         B[f], bt = s * y[:h] + bt, s * y[h:]
         Cc[f], ct = s * c[:h] + ct, s * c[h:]
         pw[f] = float((np.abs(S) ** 2).sum())
-        fs[f] = float(np.sqrt(np.mean(np.abs(specs[f][:4096].astype(np.complex128)) ** 2)) * np.sqrt(max(ln, 1)))
+        fs[f] = rms_of(specs[f]) * np.sqrt(max(ln, 1))
     mag = np.abs(Cc)
     with np.errstate(divide="ignore", invalid="ignore"):
         audio = np.where(mag == 0, B.real, (B.real * Cc.real + B.imag * Cc.imag) / mag)
@@ -126,13 +136,18 @@ def truth(is_real, n, win, sam_starts=(0,)):
     return dict(B=B, C=Cc, audio=audio, level=mag.mean(axis=1), offset_hz=RATE / (2 * np.pi) * np.angle(lag), pwr=pw, fwd_scale=fs)
 
 
+def assert_signal_condition(T, tag):
+    """the condition the derived bound stands on: a statement about the signal, checked on the truth"""
+    for f in range(1, len(T["C"])):
+        cmin, cmax, bmax = np.abs(T["C"][f]).min(), np.abs(T["C"][f]).max(), np.abs(T["B"][f]).max()
+        assert cmin >= 0.5 * cmax and bmax / cmin <= 4.0, (tag, f, cmin / cmax, bmax / cmin)
+
+
 @functools.lru_cache(maxsize=None)
 def truths(is_real, n):
     res = [truth(is_real, n, w) for w in windows(n)[:2]]
-    for T in res:  # the condition the derived bound stands on: a statement about the signal, checked on the truth
-        for f in range(1, NF):
-            cmin, cmax, bmax = np.abs(T["C"][f]).min(), np.abs(T["C"][f]).max(), np.abs(T["B"][f]).max()
-            assert cmin >= 0.5 * cmax and bmax / cmin <= 4.0, (is_real, n, f, cmin / cmax, bmax / cmin)
+    for T in res:
+        assert_signal_condition(T, (is_real, n))
     return res
 
 

@@ -112,20 +112,30 @@ def flip_sign(frame, m_floor, is_real):
 
 @functools.lru_cache(maxsize=None)
 def truth(is_real, n, win, side):
-    """float64, as psdr.h defines it: the carrier from the whole window, B' from the window clipped to `side` (BOTH: PSDR_SAM
-    itself, without the doubling), np.fft.ifft * n, flip, overlap-add from zero tails, detector -> dict of B, C [25][h]
-    complex128, audio [25][h], pwr, fwd_scale [25]"""
+    """truth_of on the oracle's spectra of the 25 frames"""
     fo, specs = oracle_spectra(is_real, n)
+    return truth_of(specs, lambda s, l, ln: s[fo.slice_ptr_index(l):fo.slice_ptr_index(l) + ln], is_real, n, win, side)
+
+
+def spectrum_rms(s):
+    return float(np.sqrt(np.mean(np.abs(s[:4096].astype(np.complex128)) ** 2)))
+
+
+def truth_of(specs, slice_of, is_real, n, win, side, rms_of=spectrum_rms):
+    """float64, as psdr.h defines it: the carrier from the whole window, B' from the window clipped to `side` (BOTH: PSDR_SAM
+    itself, without the doubling), np.fft.ifft * n, flip, overlap-add from zero tails, detector.  specs: one spectrum per
+    frame; slice_of(spectrum, l, ln): its bins [l, l + ln) in client order; rms_of(spectrum): the rms of its R bins.
+    -> dict of B, C [frames][h] complex128, audio [frames][h], pwr, fwd_scale [frames]"""
+    NF = len(specs)
     l, mid, r = win
     h, m_floor = n // 2, int(np.floor(mid))
     m, ln, cut = m_floor - l, r - l, cutoff(n)
     cl, _, cr = clipped(win, side)
-    start = fo.slice_ptr_index(l)
     B, Cc = np.zeros((NF, h), np.complex128), np.zeros((NF, h), np.complex128)
     pw, fs = np.zeros(NF), np.zeros(NF)
     bt, ct = np.zeros(h, np.complex128), np.zeros(h, np.complex128)
     for f in range(NF):
-        S = specs[f][start:start + ln].astype(np.complex128)
+        S = slice_of(specs[f], l, ln).astype(np.complex128)
         X, Xb = np.zeros(n, np.complex128), np.zeros(n, np.complex128)
         for t in range(ln):
             d = t - m
@@ -141,7 +151,7 @@ def truth(is_real, n, win, side):
         B[f], bt = s * y[:h] + bt, s * y[h:]
         Cc[f], ct = s * c[:h] + ct, s * c[h:]
         pw[f] = float((np.abs(S) ** 2).sum())
-        fs[f] = float(np.sqrt(np.mean(np.abs(specs[f][:4096].astype(np.complex128)) ** 2)) * np.sqrt(max(ln, 1)))
+        fs[f] = rms_of(specs[f]) * np.sqrt(max(ln, 1))
     mag = np.abs(Cc)
     gain = 1.0 if side == BOTH else 2.0
     with np.errstate(divide="ignore", invalid="ignore"):
