@@ -400,7 +400,14 @@ int psdr_audio_device_ptr(psdr_ctx *ctx, int id, const float **d_audio, const fl
  * mult 65536/4 (src/utils/dsp.cpp:152-165).  Off by default; when on, every demod_batch also
  * produces the int16 PCM (held in int32, like the reference's int32_t buffer) that the reference
  * hands to its audio encoder.  Frames whose NaN flag is set are skipped by the chain (the
- * reference drops them before it, src/signal.cpp:266-271); their PCM rows are zero. */
+ * reference drops them before it, src/signal.cpp:266-271); their PCM rows are zero.
+ * The conversion, for the AGC's output y (never NaN) and t = fma(y, 16384, 32768.5):
+ *   t >= 65536 -> +32767,   t < 0 -> -32768,   otherwise (int)t - 32768.
+ * That is the reference's value wherever the reference's `(int32)t - 32768` is defined (t < 2^31 and t - 32768 >= -2^31).
+ * Beyond int32 - reached for real: digital silence drives the AGC's gain towards 0.2 / 1e-10 = 2e9, and part of it is still
+ * there when a signal returns - the reference's expression is undefined and its x86 build yields +32767 for BOTH signs; this
+ * is the one place where the library deliberately leaves that build: it saturates by sign (a hugely negative sample is
+ * -32768).  int32 rows, the int16 rows of PSDR_OPT_POST_CHAIN_PCM16 and the CPU oracle share the one definition. */
 int psdr_set_post_chain(psdr_ctx *ctx, int enable);
 /* Knobs that are not part of psdr_config (whose layout is frozen per PSDR_ABI_VERSION).
  * PSDR_OPT_POST_CHAIN_STREAMS (before the first psdr_set_post_chain(ctx, 1); PSDR_ERR_STATE after it): which HIP streams the

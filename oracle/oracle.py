@@ -416,14 +416,15 @@ class PostChain:
     def reset_agc(self):
         self._L.orc_agc_reset(self.agc)
 
-    def process(self, audio):
-        """audio: float32 [h] of one frame -> int32 [h] (int16 range)"""
+    def process(self, audio, with_agc_out=False):
+        """audio: float32 [h] of one frame -> int32 [h] (int16 range); with_agc_out: (that, the AGC's float32 output [h] the
+        conversion was fed - what tells a test how far outside int16 / int32 the chain was driven)"""
         a = np.ascontiguousarray(audio, np.float32).copy()
         self._L.orc_dc_remove(self.dc, _p(a), a.size)
         self._L.orc_agc_process(self.agc, _p(a), a.size)
         pcm = np.zeros(a.size, np.int32)
         self._L.orc_float_to_int16(_p(a), _p(pcm), 16384.0, a.size)
-        return pcm
+        return (pcm, a) if with_agc_out else pcm
 
 
 def waterfall_pick_level(levels, min_waterfall_fft, l, r):

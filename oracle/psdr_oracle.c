@@ -821,13 +821,20 @@ void orc_agc_process(orc_agc *a, float *arr, size_t len) {
     }
 }
 
-/* dsp_float_to_int16 src/utils/dsp.cpp:152-165 */
+/* dsp_float_to_int16 src/utils/dsp.cpp:152-165.  With t = fma(x, mult, 32768.5):
+ *   t >= 65536 -> 32767,  t < 0 -> -32768,  otherwise (int)t - 32768
+ * The reference converts t to int32 first and clamps the integer: the same value wherever that conversion is defined
+ * (|t| < 2^31; (int)t truncates towards zero, so t in (-1, 0) is -32768 either way).  Beyond int32 the reference's
+ * expression is undefined (its x86 build returns +32767 for both signs); here t is clamped BEFORE the conversion, which is
+ * plain saturation by sign and leaves no undefined conversion or signed overflow (the library's pc_to_int16, postchain.h,
+ * is this definition; include/psdr.h states it at psdr_set_post_chain).  NaN is out of scope (flagged frames never get
+ * here): it is sent to -32768 so that the conversion stays defined. */
 void orc_float_to_int16(const float *arr, int32_t *out, float mult, size_t len) {
     for (size_t i = 0; i < len; i++) {
-        int32_t v = (int32_t)fmaf(arr[i], mult, 32768.5f) - 32768;
-        if (v > 32767) v = 32767;
-        if (v < -32768) v = -32768;
-        out[i] = v;
+        float t = fmaf(arr[i], mult, 32768.5f);
+        if (!(t >= 0.0f)) t = 0.0f;
+        if (t > 65535.0f) t = 65535.0f;
+        out[i] = (int32_t)t - 32768;
     }
 }
 /* dsp_am_demod src/utils/dsp.cpp:116-126 */

@@ -130,6 +130,18 @@ __global__ __launch_bounds__(256) void k_pc_gather(PostArgs a) {
 // one contiguous KiB into X per wave
 typedef int pc_i4 __attribute__((ext_vector_type(4)));
 typedef int pc_i2 __attribute__((ext_vector_type(2)));
+// dsp_float_to_int16 with mult 65536/4 (src/utils/dsp.cpp:152-165), the ONE definition every output kernel uses (k_pc_out,
+// k_pc_out4, k_pc_agc - int32 rows and the int16 rows of pc_pack16 alike).  With t = fma(y, 16384, 32768.5):
+//   t >= 65536 -> 32767,  t < 0 -> -32768,  otherwise (int)t - 32768
+// The reference converts t first and clamps the integer; for |t| < 2^31 that is this value bit for bit ((int)t truncates
+// towards zero: t in (-1, 0) gives -32768 either way).  Beyond int32 its conversion is undefined (its x86 build: +32767 for
+// both signs); here the clamp comes BEFORE the conversion - one v_med3_f32 - so the result is plain saturation by sign and
+// no out-of-range conversion or signed overflow is left for the compiler to reason from.  (y is never NaN: flagged frames
+// do not enter the chain.)
+__device__ __forceinline__ int pc_to_int16(float y) {
+    const float t = __fmaf_rn(y, 16384.f, 32768.5f);
+    return (int)__builtin_amdgcn_fmed3f(t, 0.f, 65535.f) - 32768;
+}
 // four clamped samples as int16 (PSDR_OPT_POST_CHAIN_PCM16: half the bytes on their way to the host)
 __device__ __forceinline__ pc_i2 pc_pack16(pc_i4 o) {
     return pc_i2{(int)(((unsigned)o[0] & 0xffffu) | ((unsigned)o[1] << 16)), (int)(((unsigned)o[2] & 0xffffu) | ((unsigned)o[3] << 16))};
@@ -862,8 +874,7 @@ __global__ __launch_bounds__(256) void k_pc_out(PostArgs a) {
         if (pos >= 0) {
             const float g = G[pc_el(g0 + j)];
             const float y = g == 0.f ? 0.f : __fmul_rn(V[pc_el(v0 + j)], g);
-            v = (int)__fmaf_rn(y, 16384.f, 32768.5f) - 32768;
-            v = v > 32767 ? 32767 : (v < -32768 ? -32768 : v);
+            v = pc_to_int16(y);
         }
         if (a.pcm16)
             reinterpret_cast<int16_t *>(a.pcm)[((size_t)slot * a.max_batch + f) * a.h + j] = (int16_t)v;
@@ -887,8 +898,7 @@ __global__ __launch_bounds__(256) void k_pc_out4(PostArgs a) {
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 const float y = g[i] == 0.f ? 0.f : __fmul_rn(V[pc_el(v0 + 4 * j4 + i)], g[i]);
-                int v = (int)__fmaf_rn(y, 16384.f, 32768.5f) - 32768;
-                o[i] = v > 32767 ? 32767 : (v < -32768 ? -32768 : v);
+                o[i] = pc_to_int16(y);
             }
         }
         if (a.pcm16)
@@ -1228,8 +1238,7 @@ __global__ __launch_bounds__(64 * (1 + PC_AGC_NP)) void k_pc_agc(PostArgs a) {
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 const float y = g[i] == 0.f ? 0.f : __fmul_rn(dl[i], g[i]);
-                int v = (int)__fmaf_rn(y, 16384.f, 32768.5f) - 32768;  // dsp_float_to_int16, src/utils/dsp.cpp:152-165
-                o[i] = v > 32767 ? 32767 : (v < -32768 ? -32768 : v);
+                o[i] = pc_to_int16(y);
             }
             // (an UNCONDITIONAL store: a row group without a sample goes to a dump line of its own - see the timeline below)
             pcm_t *where = dst[P][q] >= 0 ? pcm + dst[P][q] : dump;

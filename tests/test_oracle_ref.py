@@ -56,6 +56,56 @@ def agc_blocks():
     return [(rng.standard_normal(180) * (0.01 + 0.5 * (it % 7 == 0))).astype(np.float32) for it in range(120)]
 
 
+EDGE_RATE, EDGE_BLOCK = 12000, 180
+
+
+def agc_edge_blocks():
+    """(blocks of 180 samples, the block in front of which the AGC is reset): the script of tests/post_chain_edges.py at
+    12 kHz as the AGC's own input - a tone of each frame's amplitude times 4 (what the USB client's audio is), exact zeros in
+    the silent frames (desired gain 0.2 / 1e-10 = 2e9, reached to about a third in (d)), the burst of amplitude 4 behind them,
+    float32 denormals in (f)"""
+    import post_chain_edges as E
+    s = E.Script(EDGE_RATE, 2 * EDGE_BLOCK)
+    t = np.arange(s.nframes * EDGE_BLOCK)
+    tone = np.cos(2 * np.pi * E.TONE * t / (2 * EDGE_BLOCK) + 0.3)
+    x = (4.0 * np.repeat(s.amp, EDGE_BLOCK) * tone).astype(np.float32)
+    return [x[k * EDGE_BLOCK:(k + 1) * EDGE_BLOCK] for k in range(s.nframes)], s.reset_at
+
+
+
+
+def int16_edge_inputs():
+    """+-0, denormals, every boundary of the conversion (t = fma(x, 16384, 32768.5) = -1, -0.5, 0, 65535, 65535.5, 65536) with
+    its float32 neighbours, decades, and magnitudes up to the last for which the reference's expression `(int32)t - 32768` is
+    defined: t < 2^31 for the conversion and t >= -2^31 + 32768 for the subtraction behind it (x = -131072 is the last)"""
+    f32 = np.float32
+    at = [f32((t - 32768.5) / 16384.0) for t in (-1.0, -0.5, 0.0, 0.5, 1.0, 32768.0, 65534.5, 65535.0, 65535.5, 65536.0, 65536.5)]
+    v = []
+    for x in at:
+        v += [np.nextafter(x, f32(-np.inf)), x, np.nextafter(x, f32(np.inf))]
+    v += [f32(0.0), f32(-0.0)]
+    for m in (1.4e-45, 1e-39, 1.1754942e-38, 1.1754944e-38, 1e-30, 1e-10, 1e-5, 6.1e-5, 1e-3, 0.1, 1.0, 1.99993, 2.0, 3.0, 10.0, 1e2, 1e3, 1e4,
+              1e5, 131069.0, 131069.98):
+        v += [f32(m), f32(-m)]
+    v += [f32(-131072.0), f32(-131071.99), f32(-131071.0), np.nextafter(f32(131070.0), f32(0))]
+    rng = np.random.default_rng(11)
+    v += list((rng.standard_normal(400) * 10.0 ** rng.uniform(-3, 5, 400)).astype(f32).clip(-131071.0, 131069.0))
+    v += [f32(0.0)] * (-len(v) % 64)
+    x = O.aligned(len(v), f32)
+    x[:] = np.array(v, f32)
+    t = (x.astype(np.float64) * 16384.0 + 32768.5).astype(f32)
+    assert (t >= -2.0 ** 31 + 32768).all() and (t < 2.0 ** 31).all()
+    return x
+
+
+def int16_contract(x, mult=16384.0):
+    """include/psdr.h, psdr_set_post_chain: t = fma(x, mult, 32768.5); t >= 65536 -> 32767, t < 0 -> -32768, else (int)t - 32768
+    (x * mult is exact in float64 and so is the sum wherever it decides anything: one rounding, like the fma)"""
+    with np.errstate(over="ignore"):  # (beyond float32: +-Inf, as the fma gives)
+        t = (np.asarray(x, np.float32).astype(np.float64) * mult + 32768.5).astype(np.float32)
+    return np.where(t >= 65536, 32767, np.where(t < 0, -32768, np.trunc(np.clip(t, 0, 65535)) - 32768)).astype(np.int32)
+
+
 def ref_outputs(R):
     """the reference's outputs for the inputs above, by golden key"""
     out = {}
@@ -90,6 +140,22 @@ def ref_outputs(R):
         if it == 60:
             R.ref_agc_reset(ra)
     R.ref_agc_destroy(ra)
+    blocks, reset_at = agc_edge_blocks()
+    ra = R.ref_agc_create(0.2, 50.0, 300.0, 200.0, float(EDGE_RATE))
+    got = []
+    for it, s in enumerate(blocks):
+        if it == reset_at:
+            R.ref_agc_reset(ra)
+        s1 = O.aligned(s.size, np.float32)
+        s1[:] = s
+        R.ref_agc_process(ra, p(s1), s.size)
+        got.append(s1.copy())
+    R.ref_agc_destroy(ra)
+    out["agc_edges"] = np.concatenate(got)
+    x = int16_edge_inputs()
+    i = O.aligned(x.size, np.int32)
+    R.ref_dsp_float_to_int16(p(x), p(i), 16384.0, x.size)
+    out["int16_edges"] = i.copy()
     return out
 
 
@@ -97,7 +163,8 @@ def input_digests():
     z, x = am_fm_int16_inputs()
     a, b = negate_add_inputs()
     return {"am_fm_z": digest(z), "int16_x": digest(x), "negate_add_a": digest(a), "negate_add_b": digest(b),
-            "agc_blocks": digest(np.concatenate(agc_blocks()))}
+            "agc_blocks": digest(np.concatenate(agc_blocks())), "agc_edge_blocks": digest(np.concatenate(agc_edge_blocks()[0])),
+            "int16_edge_x": digest(int16_edge_inputs())}
 
 
 def pin(key, ours, live=None):
@@ -157,3 +224,49 @@ def test_agc_bit_exact_including_reset(live):
         if it == 60:
             L.orc_agc_reset(oa)
     L.orc_agc_destroy(oa)
+
+
+def test_agc_far_from_its_target_bit_exact(live):
+    """silence (the gain climbs towards 2e9), a burst behind it (the attack from 1e8 down), a reset in mid-silence, denormals:
+    orc_agc_process against the reference's own code, every sample of every block"""
+    L = O.lib()
+    blocks, reset_at = agc_edge_blocks()
+    oa = L.orc_agc_create(0.2, 50.0, 300.0, 200.0, float(EDGE_RATE))
+    got = []
+    for it, s in enumerate(blocks):
+        if it == reset_at:
+            L.orc_agc_reset(oa)
+        s2 = s.copy()
+        L.orc_agc_process(oa, p(s2), s.size)
+        got.append(s2)
+    L.orc_agc_destroy(oa)
+    y = np.concatenate(got)
+    pin("agc_edges", y, live)
+    x = np.concatenate(blocks)
+    gain = np.abs(y[x != 0].astype(np.float64) / x[x != 0])
+    assert gain.max() > 1e8 and np.isfinite(y).all()   # the regime, from the input and the pinned output alone
+    assert np.count_nonzero(np.abs(y.astype(np.float64)) * 16384 > 2.0 ** 31) >= 20
+    silent = np.repeat([not b.any() for b in blocks], EDGE_BLOCK)
+    assert not y[reset_at * EDGE_BLOCK:][:EDGE_RATE // 5 - 1].any() and silent[reset_at * EDGE_BLOCK]
+
+
+def test_int16_conversion_at_every_edge_bit_exact(live):
+    """inside int32 the reference's expression is defined, and the oracle's definition - the argument clamped BEFORE the
+    conversion - is that value bit for bit; the contract restated in numpy agrees"""
+    x = int16_edge_inputs()
+    i = np.zeros(x.size, np.int32)
+    O.lib().orc_float_to_int16(p(x), p(i), 16384.0, x.size)
+    pin("int16_edges", i, live)
+    assert np.array_equal(i, int16_contract(x))
+    assert i.max() == 32767 and i.min() == -32768 and not i[np.abs(x) < 1e-5].any()  # (+-0 and denormals: 0)
+
+
+def test_int16_conversion_beyond_int32_saturates_by_sign():
+    """where the reference's expression is undefined (its x86 build: +32767 for both signs) the definition is plain saturation
+    by sign - checked against the contract alone, nothing of this is sent to the reference"""
+    big = np.array([131070.0, 131072.0, 2e5, 1e6, 1e10, 1e20, 3.4e38, np.inf], np.float32)
+    x = np.concatenate([big, -np.concatenate([[131072.5, 131074.5], big[1:]]).astype(np.float32)])
+    i = np.zeros(x.size, np.int32)
+    O.lib().orc_float_to_int16(p(x), p(i), 16384.0, x.size)
+    assert np.array_equal(i, np.where(x > 0, 32767, -32768)), (x, i)
+    assert np.array_equal(i[np.isfinite(x)], int16_contract(x[np.isfinite(x)]))
