@@ -756,5 +756,6 @@ extern "C" int psdr_set_stream(psdr_ctx *c, void *hip_stream) {
         c->stream = c->own_stream;
         c->side = c->own_side;
     }
+    if (c->post_ready) pc_replan(c);  // (whether the post chain is a pipeline is one of its plan's facts)
     return PSDR_OK;
 }

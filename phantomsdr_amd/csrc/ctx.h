@@ -19,6 +19,7 @@
 #include "../../include/psdr.h"
 #include "butterfly.h"
 #include "owned.h"
+#include "postplan.h"
 #include "quantize.h"
 #include "types.h"
 
@@ -280,12 +281,9 @@ struct psdr_ctx {
         DevBuf<int> agc_n0;
     } pc;
     bool post_direct = false;  // the last chain batch's moving averages read d_audio themselves (k_pc_ma2 DIRECT)
-    bool post_agc_ok = false;  // the rate / audio size allow it (L % 16 == 0, h % 4 == 0, h >= 16, D % 4 == 0)
+    psdr::PcPlan post_plan;    // the chain's form (postplan.h), resolved by postchain.hip pc_replan whenever one of its facts changes
     uint64_t chain_seq = 0;
     bool chain_pending = false;
-    int post_reserve = 8;  // CUs the FFT passes leave free while the chain is on (a multiple of 8: one per XCD); 0: none
-    int post_lanes = 32;   // slots per work-group of the chain's two recurrence kernels
-    bool post_own = true;  // their waves allocate a whole SIMD's registers
     // Results of the LAST demodulation batch: d_audio / d_pwr / d_nan point into one of TWO sets that alternate from batch to
     // batch, so that the copies of batch b to the host (psdr_fetch_begin) run beside the demodulation of batch b + 1 instead
     // of holding it up (256 clients: 96 MB per step, 1.7 ms on the link - longer than the demodulation it follows)
@@ -453,7 +451,7 @@ inline unsigned persistent_grid(psdr_ctx *c, unsigned blocks, size_t lds) {
     // (postchain.hip: they allocate a whole SIMD's registers each, or ask for more LDS than a pass leaves, so they land
     // THERE and nowhere else; beside a pass's eight waves and the other consumers a recurrence runs 1.9 - 2.8 ms per 512
     // frames, longer than the step).  0.5 % of the plain step per CU and XCD.
-    unsigned reserve = c->post_on ? (unsigned)c->post_reserve : 0u;
+    unsigned reserve = c->post_on ? (unsigned)c->post_plan.reserve : 0u;
     if (const char *e = psdr_tuning_env("PSDR_GRID_RESERVE")) reserve = (unsigned)atoi(e) & ~7u;  // (tuning build)
     if (lds * 2 > 160 * 1024 && cap >= reserve + 8u) cap -= reserve;
     return blocks <= cap ? blocks : std::max(cap, 8u);
@@ -461,6 +459,8 @@ inline unsigned persistent_grid(psdr_ctx *c, unsigned blocks, size_t lds) {
 
 // context.hip
 int drain(psdr_ctx *c);
+// postchain.hip: resolves post_plan again (after a drain: psdr_set_post_chain, the chain's options, psdr_set_stream)
+void pc_replan(psdr_ctx *c);
 // demod.hip: the next writer of a device-side result buffer on stream `st` waits for the fetch that read it (ev may be null)
 int fetch_guard_wait(psdr_ctx *c, hipStream_t st, hipEvent_t ev);
 void resolve_pending(psdr_ctx *c);

@@ -1,48 +1,47 @@
-// postchain.h — the post-demodulation chain of AudioClient::send_audio, batched for all
-// clients:
+// postchain.h - the kernels of the post-demodulation chain of AudioClient::send_audio, batched for all clients:
 //   dc.removeDC      src/signal.cpp:278, DCBlocker / MovingAverage src/utils.h:76-99,139-169
 //   agc.process      src/signal.cpp:281, src/utils/audioprocessing.cpp:5-68
 //   dsp_float_to_int16 (mult 65536/4)  src/signal.cpp:283-284, src/utils/dsp.cpp:152-165
-// Frames dropped by the NaN guard (src/signal.cpp:266-271) never reach the chain: each
-// client's stream is the concatenation of its surviving frames.
+// Frames dropped by the NaN guard (src/signal.cpp:266-271) never reach the chain: each client's stream is the concatenation
+// of its surviving frames.  How the chain came to this form is DESIGN.md 3.5.1; which of the kernels below a context runs is
+// PcPlan (postplan.h), resolved on the host and launched by postchain.hip.
 //
 // Three f32 recurrences run along time and are bit-exact only in the reference's order:
 //   s1_t = (s1_{t-1} - x_{t-D}) + x_t            first moving average  (m1 = s1 / D)
 //   s2_t = (s2_{t-1} - m1_{t-D}) + m1_t          second moving average (out = x_{t-D+1} - s2 / D)
 //   g_t  = g + (w_t < g ? attack : release) * (w_t - g)           AGC attack / release
-// Nothing else in the chain is sequential, but the recurrences decide the shape of everything: they cannot be split
-// along time, so their parallelism is the CLIENTS - one lane per client, one wave per 64 clients, ~25 cycles per sample
-// (the latency of three dependent f32 operations), 2 ms per 512-frame batch whatever the client count.
+// They cannot be split along time, so their parallelism is the CLIENTS: one lane per client, ~25 cycles per sample (three
+// dependent f32 operations), 2 ms per 512-frame batch whatever the client count.  Nothing else in the chain is sequential.
 //
-// Layout (round 5): every stream is LANE-INTERLEAVED per group of 64 slots - sample t of slot s at float
-//   ((s >> 6) * pitch + (t >> 2) * 4) * 64 + (s & 63) * 4 + (t & 3)
-// i.e. [group][t / 4][lane][4].  Lane l of a wave owns slot 64 g + l: its four next samples are ONE 16-byte access,
-// and the wave's 64 of them one contiguous KiB.  (Rounds 2-4 kept the streams client-major, [slot][t]: a wave's load
-// touched 64 different lines, and with all 64 lanes in use - 256 clients - the two recurrence kernels were bound by the
-// texture addresser, 4.5 ms instead of 2 ms; the parallel kernels ran lanes-along-time through LDS and starved beside
-// the FFT passes, which own all but 32 KiB of every CU's LDS.)  The history a kernel needs sits IN FRONT of the new
-// samples (D rows for the averages, L-1 rows for the AGC look-ahead); the sets rotate per batch (three of them: a
-// batch's chain may still be running when the next two start), the tails are copied into the next set's history rows.
-// EVERY kernel is lane = client now; the ones that are not recurrences split time into independent pieces:
-//   k_pc_index    stream offset of every frame of every client (NaN-flagged frames dropped)
-//   k_pc_gather   audio[slot][frame][j] -> X[slot][D + t]
-//   k_pc_ma2      both running sums in one loop (D = 32)          (sequential)
-//   k_pc_mad      the same for any power-of-two D (48 kHz: 128, 192 kHz: 512): the sums of the last D steps in an LDS ring
-//   k_pc_ma<0|1>  the two running sums, any D                      (sequential, one wave, fallback)
-//   k_pc_history  the last D / L-1 rows become the next set's history
-//   k_pc_submax / k_pc_prefix / k_pc_want
-//                 AGC look-ahead peak: the sliding maximum of |x| over L samples (the reference's monotonic deque) as
-//                 van Herk prefix / suffix maxima of blocks of L rows, a wave per (group, sub-block of a block), then
-//                 w_t = desired / (peak_t + 1e-10)
-//   k_pc_gain     the gain recurrence                              (sequential)
-//   k_pc_out      delayed sample * gain, int16 conversion, straight into pcm[slot][frame][j]
-// Round 6 (PSDR_OPT_POST_CHAIN_AGC = 1, the default; what the chain costs the step is its memory traffic - see the end of
-// this file): k_pc_submax / _prefix / _want / _gain / _out become
-//   k_pc_cm / k_pc_cscan   maxima of |V1| per chunk of 16 floats and their block scans (history chunks only when the moving
-//                 averages leave the maxima of the new samples on their way: k_pc_ma2 CMW)
-//   k_pc_agc      look-ahead peak, w_t, the gain recurrence and the int16 output in ONE four-wave kernel
-//   k_pc_zero     zero rows for dropped frames
-// and k_pc_ma2 reads the demodulator's rows itself where a work-group's streams are whole (DIRECT: no k_pc_gather4 for it).
+// Streams: every stream is LANE-INTERLEAVED per group of 64 slots - sample t of slot s at float
+//   ((s >> 6) * pitch + (t >> 2) * 4) * 64 + (s & 63) * 4 + (t & 3)          i.e. [group][t / 4][lane][4]
+// Lane l of a wave owns slot 64 g + l: its four next samples are ONE 16-byte access, the wave's 64 of them one contiguous
+// KiB.  The history a kernel needs sits IN FRONT of the new samples (D rows for the averages, L - 1 rows for the AGC
+// look-ahead); the sets rotate per batch (three of them: a batch's chain may still be running when the next two start), the
+// tails are copied into the next set's history rows.
+//
+// Kernels (every one lane = client; those that are not recurrences split time into independent pieces):
+//   k_pc_index    stream offset of every frame of every client (NaN-flagged frames dropped), and the list of surviving frames
+//   k_pc_gather   audio[slot][frame][j] -> X[slot][D + t]; k_pc_gather4: the same with lane = slot (PcPlan::rows4)
+//   the moving averages (PcPlan::ma):
+//     k_pc_ma2      MA2: both running sums in one loop for D = 32, a loader and a consumer wave; MA2_CMW: a third wave leaves the
+//                   chunk maxima of the new samples for k_pc_agc.  PcPlan::direct: it reads the demodulator's rows themselves
+//                   where a work-group's streams are whole (k_pc_gather4 then skips them)
+//     k_pc_mad      MAD: the same for any power-of-two D (48 kHz: 128, 192 kHz: 512), the sums of the last D steps in an LDS ring
+//     k_pc_ma<0|1>  MA_POW2 / MA_DIV: the two running sums one after the other, one wave each, any D
+//   k_pc_history  the last D / L - 1 rows become the next set's history
+//   the AGC, five kernels (PcPlan::agc = AGC_FIVE):
+//     k_pc_submax / k_pc_prefix / k_pc_want   look-ahead peak: the sliding maximum of |x| over L samples (the reference's
+//                   monotonic deque) as van Herk prefix / suffix maxima of blocks of L rows, then w_t = desired / (peak_t + 1e-10)
+//     k_pc_gain     the gain recurrence, a loader and a consumer wave
+//     k_pc_out      delayed sample * gain, int16 conversion, into pcm[slot][frame][j]; k_pc_out4: lane = slot (PcPlan::rows4)
+//   the AGC, one kernel behind chunk maxima (AGC_ONE_KERNEL: where PcPlan::agc_ok, the recurrence waves own their SIMDs and
+//   PSDR_OPT_POST_CHAIN_AGC is 1 - what the chain costs the step is its memory traffic, see k_pc_agc):
+//     k_pc_cm / k_pc_cscan   maxima of |V1| per chunk of 16 floats and their block scans
+//     k_pc_agc      look-ahead peak, w_t, the gain recurrence and the int16 output in ONE four-wave kernel
+//     k_pc_zero     zero rows for dropped frames
+// PcPlan::lanes slots per work-group of a recurrence kernel, PcPlan::own: their waves take a SIMD each (the OWN template
+// parameter), PcPlan::att_faster / pcm16: the ATT_FASTER / PCM16 template parameters.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -91,6 +90,47 @@ __device__ __forceinline__ void pc_static_for(F &&f) {
     }
 }
 
+// ---- steps the recurrence kernels (k_pc_ma2, k_pc_mad, k_pc_gain, k_pc_agc) share ------------------------------------
+// A recurrence work-group owns a.lanes (16, 32 or 64) consecutive slots of a group of 64: lane = slot & (a.lanes - 1), the
+// other lanes of its waves leave early.  (A recurrence costs the same for 1 lane or 64, but its memory operations do not:
+// 1 KiB loads and stores per wave are acknowledged later than 256-byte ones beside the passes - 2.8 against 2.0 ms per 512
+// frames.)  The streams of a group are allocated whole: a slot past a.slots is addressable, and not listed.
+struct PcWgSlot {
+    int slot, ci;  // ci: the slot's client in this batch's list, -1 = none
+    bool listed;
+};
+__device__ __forceinline__ PcWgSlot pc_wg_slot(const PostArgs &a, int lane) {
+    const int wpg = 64 / a.lanes;
+    const int slot = ((int)blockIdx.x / wpg) * 64 + ((int)blockIdx.x % wpg) * a.lanes + lane;
+    const int ci = (lane < a.lanes && slot < a.slots) ? a.slot_ci[slot] : -1;
+    return {slot, ci, ci >= 0};
+}
+// the wave's maximum, in every lane: lanes of a group may have streams of different lengths (dropped frames, paused
+// clients) - the trip count is the group's maximum, a lane past its own end keeps its state
+__device__ __forceinline__ int pc_wave_max(int v) {
+#pragma unroll
+    for (int d = 32; d; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
+    return v;
+}
+// a new client in the slot starts from zero history: the D rows in front of a stream
+__device__ __forceinline__ void pc_zero_history(float *rows, int D) {
+    for (int r = 0; r < D; r++) rows[pc_el(r)] = 0.f;
+}
+// The AGC's gain step (src/utils/audioprocessing.cpp:55-66): gain <- gain + (w < gain ? attack : release) * (w - gain), three
+// operations per sample (fma(-a, g - w, g) and fma(a, w - g, g) are the same value: negating both factors is exact).
+// The loop it sits in is ONE wave's dependent chain (~8 cycles from an instruction to the next that needs its result), so
+// what counts is the DEPTH per sample.  Both candidates are computed side by side and the choice is a min / max: with
+// attack > release (the reference's 50 ms against 300 ms) d < 0 makes attack * d the smaller product and d > 0 the
+// larger, and fma rounds monotonically - min(A, R) IS the reference's pick, bit for bit (d = 0: both are the gain).
+// sub -> fma, fma -> min: depth 3 instead of 4.  (ATT_FASTER = attack >= release, a template parameter: as a run-time
+// flag the compiler computed min AND max and selected - six instructions and depth 4 again)
+template <bool ATT_FASTER>
+__device__ __forceinline__ float pc_gain_step(float &gain, float w, float att, float rel) {
+    const float d = __fsub_rn(w, gain);
+    const float ga = __fmaf_rn(att, d, gain), gr = __fmaf_rn(rel, d, gain);
+    gain = ATT_FASTER ? fminf(ga, gr) : fmaxf(ga, gr);
+    return gain;
+}
 // one wave per client: where each surviving frame starts in the client's stream (a ballot per 64
 // frames: the count of surviving frames below a lane is a popcount)
 __global__ __launch_bounds__(64) void k_pc_index(PostArgs a) {
@@ -184,8 +224,7 @@ __global__ __launch_bounds__(64) void k_pc_ma(PostArgs a) {
     const bool fresh = cp.agc_reset == 2;  // a new client in this slot: zero sums and zero history
     const int T = a.len[slot];
     float *inw = (SECOND ? a.M1 : a.X) + pc_base(slot, a.px);
-    if (fresh)
-        for (int r = 0; r < D; r++) inw[pc_el(r)] = 0.f;
+    if (fresh) pc_zero_history(inw, D);
     const float *in = inw;
     const float *X = a.X + pc_base(slot, a.px);
     float *out = SECOND ? a.V1 + pc_base(slot, a.pv) : a.M1 + pc_base(slot, a.px);
@@ -201,7 +240,7 @@ __global__ __launch_bounds__(64) void k_pc_ma(PostArgs a) {
     (SECOND ? a.dc_s2 : a.dc_s1)[slot] = s;
 }
 
-// Both moving averages for D = 32, as TWO waves of one work-group (round 5).  One wave doing both sums issues six
+// Both moving averages for D = 32, as TWO waves of one work-group.  One wave doing both sums issues six
 // instructions per sample - 25 cycles, 1.9 - 2.8 ms per 512 frames at the capped clock beside the FFT passes: longer than
 // the step it is meant to hide behind, and no pipeline helps a stage that is sequential across batches.  Split:
 //   wave 0  loads x (a ring of register sets, the loads nine blocks ahead), runs s1 and leaves each 16-step block of x
@@ -215,7 +254,7 @@ __global__ __launch_bounds__(64) void k_pc_ma(PostArgs a) {
 // the in-memory history (wave 1).  Lanes of a group may have streams of different lengths (dropped frames, paused
 // clients): the trip count is the group's maximum, a lane past its own end keeps its state.
 constexpr int PC_MA_RING = 12;  // wave 0's register sets of x: blocks b-2 .. b (in use), b+1 .. b+9 in flight
-// CMW (round 6, with the one-kernel AGC): a THIRD wave takes the blocks of output from wave 1 through LDS, stores them and
+// CMW (with the one-kernel AGC): a THIRD wave takes the blocks of output from wave 1 through LDS, stores them and
 // leaves the maximum of |V1| over each 16-sample block as CM[L/16 + b] - the chunk maxima k_pc_agc's look-ahead peak is made
 // of, without another pass over V1 (k_pc_cm then covers the L/16 history chunks only).  Wave 1 swaps four global stores per
 // block for four LDS writes: the same number of instructions in its loop.
@@ -225,23 +264,17 @@ __global__ __launch_bounds__(CMW ? 192 : 128) void k_pc_ma2(PostArgs a) {
     __shared__ float fin[64];         // wave 0's s1 after its last block
     __shared__ pc_f4 ohand[CMW ? 2 : 1][4][CMW ? 64 : 1];  // CMW: [buffer][row group][lane] a block of output on its way to wave 2
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    // a work-group owns a.lanes (16, 32 or 64) consecutive slots of a group of 64: lane = slot & (a.lanes - 1), the other
-    // lanes leave below.  (A recurrence costs the same for 1 lane or 64, but its memory operations do not: 1 KiB loads and
-    // stores per wave are acknowledged later than 256-byte ones beside the passes - 2.8 against 2.0 ms per 512 frames.)
-    const int wpg = 64 / a.lanes;
-    const int slot = ((int)blockIdx.x / wpg) * 64 + ((int)blockIdx.x % wpg) * a.lanes + lane;  // (the streams of a group are allocated whole)
-    const int ci = (lane < a.lanes && slot < a.slots) ? a.slot_ci[slot] : -1;
-    const bool listed = ci >= 0;
+    const PcWgSlot ws = pc_wg_slot(a, lane);
+    const int slot = ws.slot, ci = ws.ci;
+    const bool listed = ws.listed;
     const bool fresh = listed && a.clients[ci].agc_reset == 2;  // a new client in this slot: zero sums, zero history rows
     constexpr int KB = 16, D = 32;
     __builtin_amdgcn_s_setprio(PSDR_PC_SETPRIO);
     if constexpr (OWN) PC_OWN_SIMD();  // a few waves next to the FFT passes' issue-bound ones: let them issue first
     const int T = listed ? a.len[slot] : 0;
     const int nfull = T / KB;
-    int nmax = nfull;
-#pragma unroll
-    for (int d = 32; d; d >>= 1) nmax = max(nmax, __shfl_xor(nmax, d, 64));
-    // DIRECT (round 6, a.direct): when every stream of the work-group is the demodulator's rows as they lie - no frame dropped,
+    const int nmax = pc_wave_max(nfull);
+    // DIRECT (a.direct): when every stream of the work-group is the demodulator's rows as they lie - no frame dropped,
     // nobody paused in mid-batch - the new samples are read from a.audio itself and k_pc_gather4 leaves the work-group's X
     // rows alone (it takes the same decision from the same numbers): a pass of 4 bytes per sample written and one read less,
     // of the fifteen the chain cost the step by (profiles/r06_post_chain_ablation.json).  A lane's 16-byte pieces then lie
@@ -259,8 +292,7 @@ __global__ __launch_bounds__(CMW ? 192 : 128) void k_pc_ma2(PostArgs a) {
     if (wid == 0) {
         // ---- wave 0: s1_t = (s1 - x_{t-32}) + x_t
         constexpr int RING = PC_MA_RING, AHEAD = RING - 3;
-        if (fresh)
-            for (int r = 0; r < D; r++) X[pc_el(r)] = 0.f;
+        if (fresh) pc_zero_history(X, D);
         float s1 = (fresh || !listed) ? 0.f : a.dc_s1[slot];
         pc_f4 xr[RING][4];
 #pragma unroll
@@ -357,8 +389,7 @@ __global__ __launch_bounds__(CMW ? 192 : 128) void k_pc_ma2(PostArgs a) {
     // m1 = s1 / 32 is exact (a power of two), so rounding (s2 - m1_old) + m1 and x - s2 / 32 after the exact products is the
     // reference's arithmetic with three fused operations instead of five:
     //   t = s2 - s1_old / 32      s2 = t + s1 / 32      out = x_{t-D+1} - s2 / 32
-    if (fresh)
-        for (int r = 0; r < D; r++) M1[pc_el(r)] = 0.f;
+    if (fresh) pc_zero_history(M1, D);
     float s2 = (fresh || !listed) ? 0.f : a.dc_s2[slot];
     const int vq = (a.vo + a.L - 1) >> 2;  // sample 0's row group (vo makes row L-1 a multiple of 4)
     // x in four register sets (blocks b-2, b-1, b and the block being read: x_{t-31} of the block's last step is the first
@@ -462,10 +493,9 @@ __global__ __launch_bounds__(128) void k_pc_mad(PostArgs a) {
     __shared__ float fin[64];         // wave 0's s1 after its last block
     extern __shared__ pc_f4 sring[];  // [D / 16][4][a.lanes]: wave 1's ring of s1 blocks
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int wpg = 64 / a.lanes;  // (a.lanes slots per work-group: see k_pc_ma2)
-    const int slot = ((int)blockIdx.x / wpg) * 64 + ((int)blockIdx.x % wpg) * a.lanes + lane;
-    const int ci = (lane < a.lanes && slot < a.slots) ? a.slot_ci[slot] : -1;
-    const bool listed = ci >= 0;
+    const PcWgSlot ws = pc_wg_slot(a, lane);
+    const int slot = ws.slot, ci = ws.ci;
+    const bool listed = ws.listed;
     const bool fresh = listed && a.clients[ci].agc_reset == 2;
     constexpr int KB = 16;
     const int D = a.D, NBD = D / KB;
@@ -473,7 +503,7 @@ __global__ __launch_bounds__(128) void k_pc_mad(PostArgs a) {
     if constexpr (OWN) PC_OWN_SIMD();
     const int T = listed ? a.len[slot] : 0;
     const int nfull = T / KB;
-    int nmax = nfull;
+    int nmax = nfull;  // (pc_wave_max written out: through the function this kernel's instructions come out in another order)
 #pragma unroll
     for (int d = 32; d; d >>= 1) nmax = max(nmax, __shfl_xor(nmax, d, 64));
     if (lane >= a.lanes) return;
@@ -485,8 +515,7 @@ __global__ __launch_bounds__(128) void k_pc_mad(PostArgs a) {
     if (wid == 0) {
         // ---- wave 0: s1_t = (s1 - x_{t-D}) + x_t
         constexpr int RING = PC_MAD_RING, AHEAD = RING - 1;
-        if (fresh)
-            for (int r = 0; r < D; r++) X[pc_el(r)] = 0.f;
+        if (fresh) pc_zero_history(X, D);
         float s1 = (fresh || !listed) ? 0.f : a.dc_s1[slot];
         pc_f4 xn[RING][4], xo[RING][4];
         const int dq = D >> 2;
@@ -551,8 +580,7 @@ __global__ __launch_bounds__(128) void k_pc_mad(PostArgs a) {
         return;
     }
     // ---- wave 1: s2_t = (s2 - m1_{t-D}) + m1_t, out_t = x_{t-D+1} - s2_t / D, three blocks behind wave 0
-    if (fresh)
-        for (int r = 0; r < D; r++) M1[pc_el(r)] = 0.f;
+    if (fresh) pc_zero_history(M1, D);
     float s2 = (fresh || !listed) ? 0.f : a.dc_s2[slot];
     const int vq = (a.vo + a.L - 1) >> 2;
     auto ring = [&](int blk, int q) -> pc_f4 & { return sring[((size_t)(blk & (NBD - 1)) * 4 + q) * a.lanes + lane]; };  // (D: a power of two)
@@ -729,7 +757,7 @@ __global__ __launch_bounds__(64) void k_pc_want(PostArgs a) {
 // the gain recurrence (src/utils/audioprocessing.cpp:55-66); g_t -> sample t's row of P (0 while the
 // look-ahead buffer is still filling: the reference outputs 0 there and leaves the gain alone;
 // an active gain is never 0: w_t > 0)
-// Two waves like k_pc_ma2 (round 5): wave 0 loads w (a ring of register sets, the loads far ahead) and leaves each
+// Two waves like k_pc_ma2: wave 0 loads w (a ring of register sets, the loads far ahead) and leaves each
 // 16-step block in LDS, wave 1 takes it a barrier later and runs the recurrence - no global load in its loop, so its
 // s_waitcnt never stands behind the acknowledgement of its own stores (with all 64 lanes in use, 1 KiB per store, the
 // one-wave form took 2.2 - 3.0 ms per 512 frames against 1.5 ms with 16 lanes).
@@ -739,7 +767,7 @@ template <bool ATT_FASTER, bool OWN>
 __global__ __launch_bounds__(128) void k_pc_gain(PostArgs a) {
     __shared__ pc_f4 hand[2][4][64];  // [buffer][row group of the block][lane]: 8 KiB
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int wpg = 64 / a.lanes;  // (a.lanes slots per work-group: see k_pc_ma2)
+    const int wpg = 64 / a.lanes;  // (pc_wg_slot written out: through the function this kernel's instructions come out in another order)
     const int slot = ((int)blockIdx.x / wpg) * 64 + ((int)blockIdx.x % wpg) * a.lanes + lane;
     const int ci = (lane < a.lanes && slot < a.slots) ? a.slot_ci[slot] : -1;
     const bool listed = ci >= 0;
@@ -762,7 +790,7 @@ __global__ __launch_bounds__(128) void k_pc_gain(PostArgs a) {
     const int tfill = min(T, max(0, L - 1 - n0));
     const int t0 = min(T, (tfill + 3) & ~3);
     const int nblk = (T - t0) / KB;
-    int nmax = nblk;
+    int nmax = nblk;  // (pc_wave_max written out, for the same reason)
 #pragma unroll
     for (int d = 32; d; d >>= 1) nmax = max(nmax, __shfl_xor(nmax, d, 64));
     if (lane >= a.lanes) return;
@@ -810,20 +838,7 @@ __global__ __launch_bounds__(128) void k_pc_gain(PostArgs a) {
     }
     // ---- wave 1: the recurrence
     const float att = a.attack, rel = a.release;
-    // gain <- gain + (w < gain ? attack : release) * (w - gain): three operations per sample
-    // (fma(-a, g - w, g) and fma(a, w - g, g) are the same value: negating both factors is exact)
-    // The loop is ONE wave's dependent chain (~8 cycles from an instruction to the next that needs its result), so what
-    // counts is the DEPTH per sample.  Both candidates are computed side by side and the choice is a min / max: with
-    // attack > release (the reference's 50 ms against 300 ms) d < 0 makes attack * d the smaller product and d > 0 the
-    // larger, and fma rounds monotonically - min(A, R) IS the reference's pick, bit for bit (d = 0: both are the gain).
-    // sub -> fma, fma -> min: depth 3 instead of 4.  (ATT_FASTER = attack >= release, a template parameter: as a run-time
-    // flag the compiler computed min AND max and selected - six instructions and depth 4 again)
-    auto step = [&](float w) -> float {
-        const float d = __fsub_rn(w, gain);
-        const float ga = __fmaf_rn(att, d, gain), gr = __fmaf_rn(rel, d, gain);
-        gain = ATT_FASTER ? fminf(ga, gr) : fmaxf(ga, gr);
-        return gain;
-    };
+    auto step = [&](float w) -> float { return pc_gain_step<ATT_FASTER>(gain, w, att, rel); };
     for (int t = 0; t < tfill; t++) G[pc_el(t)] = 0.f;
     for (int t = tfill; t < t0; t++) G[pc_el(t)] = step(W[pc_el(t)]);
     pc_f4 wv[2][4];
@@ -927,7 +942,7 @@ __global__ __launch_bounds__(256) void k_pc_history(PostArgs a) {
     for (int r = threadIdx.x; r < a.L - 1; r += blockDim.x) vn[pc_el(a.vo + r)] = v[pc_el(a.vo + r + T)];
 }
 
-// ==== the AGC in ONE kernel behind chunk maxima (round 6) ==============================================================
+// ==== the AGC in ONE kernel behind chunk maxima =========================================================================
 // What the chain costs the step is its TRAFFIC (profiles/r06_post_chain_ablation.json: 0.6 - 0.8 % of the step per pass of
 // 4 bytes per sample and client over a stream, beside passes that are bound by the memory system): the five kernels above
 // - sub-block maxima, prefix maxima, w_t, gain, int16 - read or write a stream eleven times.  This form reads V1 twice
@@ -1051,9 +1066,7 @@ __global__ __launch_bounds__(64 * (1 + PC_AGC_NP)) void k_pc_agc(PostArgs a) {
     {
         const int s = g64 * 64 + sl0 + (lane & (lanes - 1));
         const int ci = s < a.slots ? a.slot_ci[s] : -1;
-        Tm = ci >= 0 ? a.len[s] : 0;
-#pragma unroll
-        for (int d = 32; d; d >>= 1) Tm = max(Tm, __shfl_xor(Tm, d, 64));
+        Tm = pc_wave_max(ci >= 0 ? a.len[s] : 0);
     }
     const int nchk = (Tm + 15) >> 4;               // chunks with a sample
     // (at least two rounds: the producers' timeline below has two rounds in front of and two behind its steady state; a round
@@ -1079,12 +1092,7 @@ __global__ __launch_bounds__(64 * (1 + PC_AGC_NP)) void k_pc_agc(PostArgs a) {
         // and leaves the gain alone (src/utils/audioprocessing.cpp:40-54)
         const int tfill = min(T, max(0, L - 1 - n0));
         const float att = a.attack, rel = a.release;
-        auto step = [&](float w) -> float {  // (see k_pc_gain: both candidates side by side, the pick is a min / max)
-            const float d = __fsub_rn(w, gain);
-            const float ga = __fmaf_rn(att, d, gain), gr = __fmaf_rn(rel, d, gain);
-            gain = ATT_FASTER ? fminf(ga, gr) : fmaxf(ga, gr);
-            return gain;
-        };
+        auto step = [&](float w) -> float { return pc_gain_step<ATT_FASTER>(gain, w, att, rel); };
         const bool mine = sl < lanes;  // (the other lanes idle along, barriers included)
         // round r of the recurrence runs one barrier behind the producers' round r
         __syncthreads();  // producers: w of round 0 written

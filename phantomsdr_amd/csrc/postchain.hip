@@ -130,6 +130,41 @@ int pc_pick_streams(psdr_ctx *c) {
 }
 }  // namespace
 
+// the tuning overrides of a tuning build (ctx.h psdr_tuning_env: nothing is read by the library that ships), once per resolve
+static PcKnobs pc_knobs() {
+    PcKnobs k;
+    auto num = [](const char *name, int *v) {
+        if (const char *e = psdr_tuning_env(name)) *v = atoi(e);
+    };
+    num("PSDR_PC_LANES", &k.lanes);
+    num("PSDR_PC_RESERVE", &k.reserve);
+    num("PSDR_PC_OWN", &k.own);
+    num("PSDR_PC_FUSED", &k.fused);
+    num("PSDR_PC_CMW", &k.cmw);
+    num("PSDR_PC_DIRECT", &k.direct);
+    num("PSDR_PC_STREAMS", &k.streams);
+    num("PSDR_PC_SPLIT_PEAK", &k.split_peak);
+    num("PSDR_PC_PICK", &k.pick);
+    if (const char *e = psdr_tuning_env("PSDR_PC_SKIP")) k.skip = (int)strtol(e, nullptr, 0);
+    return k;
+}
+static PcPlan pc_plan_of(const psdr_ctx *c, bool piped) {
+    PcFacts f;
+    f.audio_rate = c->cfg.audio_rate;
+    f.n = c->n;
+    f.max_batch = c->max_batch;
+    f.slots = (int)c->aslots.size();
+    f.piped = piped;
+    f.opt_pc_agc = c->opt_pc_agc, f.opt_pc_pcm16 = c->opt_pc_pcm16, f.opt_pc_streams = c->opt_pc_streams;
+    return pc_resolve(f, pc_knobs());
+}
+// (only a context that owns its side stream pipelines the chain: with a caller's stream - group members - everything rides
+// on that one stream)
+void psdr::pc_replan(psdr_ctx *c) {
+    c->post_plan = pc_plan_of(c, c->side != c->stream && c->pc_s[0] != nullptr);
+    pc_fill_args(c->post, c->post_plan);  // (the plan is the record; the kernels' copy of its numbers is written here and nowhere else)
+}
+
 extern "C" int psdr_set_option(psdr_ctx *c, int option, int value) {
     if (!c) return fail(PSDR_ERR_INVALID, "null argument");
     switch (option) {
@@ -144,6 +179,7 @@ extern "C" int psdr_set_option(psdr_ctx *c, int option, int value) {
         const int rc = drain(c);
         if (rc) return rc;
         c->opt_pc_pcm16 = value;
+        if (c->post_ready) pc_replan(c);
         return PSDR_OK;
     }
     case PSDR_OPT_POST_CHAIN_AGC: {
@@ -152,6 +188,7 @@ extern "C" int psdr_set_option(psdr_ctx *c, int option, int value) {
         const int rc = drain(c);
         if (rc) return rc;
         c->opt_pc_agc = value;
+        if (c->post_ready) pc_replan(c);
         return PSDR_OK;
     }
     case PSDR_OPT_WATERFALL_DETECTOR:
@@ -188,55 +225,30 @@ extern "C" int psdr_set_post_chain(psdr_ctx *c, int enable) {
         // (one-time set-up, built in locals and moved into the context only when EVERY allocation and the stream choice went
         // through: a failure half-way leaves the context as it was, and a retry starts from scratch)
         const int rate = c->cfg.audio_rate;
-        if (rate < 750) return fail(PSDR_ERR_INVALID, "audio_rate %d too small for the DC blocker", rate);
+        const PcPlan p = pc_plan_of(c, c->side != c->stream);
+        if (p.verdict == PC_RATE_TOO_SMALL) return fail(PSDR_ERR_INVALID, "audio_rate %d too small for the DC blocker", rate);
+        if (p.verdict == PC_NO_FRAME) return fail(PSDR_ERR_STATE, "audio_fft_size %d: no samples in a frame", c->n);
+        if (p.verdict != PC_OK) return fail(PSDR_ERR_UNSUPPORTED, "audio_rate %d: DC delay %d / look-ahead %d unsupported", rate, p.D, p.L);
         PostArgs a{};
         psdr_ctx::PostChain pc;
-        const size_t S = c->aslots.size(), h = (size_t)c->n / 2, Tm = (size_t)c->max_batch * h;
+        const size_t S = c->aslots.size(), Tm = p.Tm;
         a.max_batch = c->max_batch;
-        a.h = (int)h;
         a.slots = (int)S;
-        a.D = rate / 750 * 2;  // DCBlocker(audio_max_sps / 750 * 2), src/signal.cpp:54
-        // AGC(0.2f, 50.0f, 300.0f, 200.0f, audio_max_sps), src/signal.cpp:55 and
-        // src/utils/audioprocessing.cpp:5-16 (exp() on a float argument is C's double exp)
-        const float sr = (float)rate;
-        a.L = (int)(size_t)(200.0f * sr / 1000.0f);
-        a.desired = 0.2f;
-        a.attack = (float)(1 - std::exp((double)(-1.0f / (50.0f * 0.001f * sr))));
-        a.release = (float)(1 - std::exp((double)(-1.0f / (300.0f * 0.001f * sr))));
-        // (D up to 12288 - audio rates up to 4.6 MHz - as in rounds 2-4; the AGC look-ahead L has no such limit: k_pc_submax /
-        // k_pc_prefix / k_pc_want walk it in 256-row pieces)
-        if (a.D < 1 || a.L < 2 || a.D > 12288)
-            return fail(PSDR_ERR_UNSUPPORTED, "audio_rate %d: DC delay %d / look-ahead %d unsupported", rate, a.D, a.L);
-        // lane-interleaved streams (postchain.h): pitches are multiples of 4 floats per slot, + padding for the
-        // blocked kernels' look-ahead; a block of 64 slots is allocated whole
-        const size_t S64 = (S + 63) / 64 * 64;
-        a.px = ((size_t)a.D + Tm + PSDR_PC_PAD + 3) & ~(size_t)3;
-        a.vo = (4 - ((a.L - 1) & 3)) & 3;
-        a.pv = ((size_t)a.vo + (size_t)a.L - 1 + Tm + PSDR_PC_PAD + 3) & ~(size_t)3;
-        // look-ahead peak: sub-blocks of at most 256 rows of a block of L rows (postchain.h: a wave per sub-block and 64 slots,
-        // 16 rows per round trip to memory - beside the FFT passes a round trip is microseconds)
-        a.nsub = (a.L + 255) / 256;
-        a.sb = (a.L + a.nsub - 1) / a.nsub;
-        const size_t nblk = (((size_t)a.L - 1 + Tm) + a.L - 1) / a.L;
-        // the AGC in one kernel (postchain.h k_pc_agc): whole chunks of 16 floats must line up with sample 0's row and with the
-        // row groups of a frame; stream position / h by one 32-bit multiplication
-        const bool agc_ok = (a.L % 16) == 0 && a.L >= 32 && a.vo == 1 && (h % 4) == 0 && h >= 16 && (a.D % 4) == 0 && (Tm + 4096) * h < ((size_t)1 << 32);
-        a.nch = (int)((size_t)a.L / 16 + (Tm + 15) / 16 + 8);
-        a.h_magic = (unsigned)((((uint64_t)1 << 32) + h - 1) / h);
+        const size_t S64 = (S + 63) / 64 * 64;  // (a block of 64 slots is allocated whole)
         int rc = 0;
         for (int i = 0; i < psdr_ctx::PC_SETS && !rc; i++) {
             rc = pc.fstart[i].alloc(S * c->max_batch, true);
             if (!rc) rc = pc.len[i].alloc(S, true);
-            if (!rc) rc = pc.x[i].alloc(a.px * S64, true);
-            if (!rc) rc = pc.m1[i].alloc(a.px * S64, true);
-            if (!rc) rc = pc.v1[i].alloc(a.pv * S64, true);
-            if (!rc) rc = pc.p[i].alloc(a.pv * S64, true);
-            if (!rc) rc = pc.s[i].alloc(a.pv * S64, true);
-            if (!rc) rc = pc.sm[i].alloc(S64 * nblk * a.nsub, true);
-            if (agc_ok) {
-                if (!rc) rc = pc.cm[i].alloc(S64 * a.nch, true);
-                if (!rc) rc = pc.cp[i].alloc(S64 * a.nch, true);
-                if (!rc) rc = pc.cs[i].alloc(S64 * a.nch, true);
+            if (!rc) rc = pc.x[i].alloc(p.px * S64, true);
+            if (!rc) rc = pc.m1[i].alloc(p.px * S64, true);
+            if (!rc) rc = pc.v1[i].alloc(p.pv * S64, true);
+            if (!rc) rc = pc.p[i].alloc(p.pv * S64, true);
+            if (!rc) rc = pc.s[i].alloc(p.pv * S64, true);
+            if (!rc) rc = pc.sm[i].alloc(S64 * pc_nblk(p.L, Tm) * p.nsub, true);
+            if (p.agc_ok) {
+                if (!rc) rc = pc.cm[i].alloc(S64 * p.nch, true);
+                if (!rc) rc = pc.cp[i].alloc(S64 * p.nch, true);
+                if (!rc) rc = pc.cs[i].alloc(S64 * p.nch, true);
                 if (!rc) rc = pc.falive[i].alloc(S64 * c->max_batch, true);
             }
             for (auto &stage : pc.ev)
@@ -254,17 +266,15 @@ extern "C" int psdr_set_post_chain(psdr_ctx *c, int enable) {
         }
         a.pcm = pc.pcm_pool[0];
         a.pcm_dump = pc.pcm_dump, a.dc_s1 = pc.dc_s1, a.dc_s2 = pc.dc_s2, a.agc_gain = pc.agc_gain, a.agc_n0 = pc.agc_n0;
-        // The chain's streams (only a context that owns its side stream pipelines the chain: with a caller's stream - group
-        // members - everything rides on that one stream and no chain stream is made).  PSDR_OPT_POST_CHAIN_STREAMS:
+        // The chain's streams (a pipelined chain only: with a caller's stream no chain stream is made).
+        // PSDR_OPT_POST_CHAIN_STREAMS (PcPlan::pick_streams):
         //   0 (default)  three streams in creation order, the first and the third used: deterministic; the FIRST context of a
         //                process gets the quiet queues by itself
         //   1 (opt-in)   chosen by measurement (pc_pick_streams: ~60 ms, wall-clock thresholds): what a process that creates
         //                several contexts (bench.py's sub-workloads) needs to see +3 % instead of +15 %; a measurement that
         //                fails falls back to creation order instead of failing the call
         if (!c->pc_s[0] && c->side != c->stream) {
-            int pick = c->opt_pc_streams;
-            if (const char *e = psdr_tuning_env("PSDR_PC_PICK")) pick = atoi(e) != 0;  // (tuning build)
-            if (pick) (void)pc_pick_streams(c);  // (sets pc_s only when the whole measurement went through)
+            if (p.pick_streams) (void)pc_pick_streams(c);  // (sets pc_s only when the whole measurement went through)
             if (!c->pc_s[0]) {
                 int lo = 0, hi = 0;
                 Stream s3[3];
@@ -275,73 +285,42 @@ extern "C" int psdr_set_post_chain(psdr_ctx *c, int enable) {
         }
         c->pc = std::move(pc);
         c->post = a;
-        c->post_agc_ok = agc_ok;
         c->post_ready = true;
     }
-    {
-        // The two recurrence kernels (k_pc_ma2, k_pc_gain: postchain.h): 32 slots per work-group (half a wave in use, 512-byte
-        // memory operations: 256 clients 3.80-3.90 -> 3.55-3.67 ms per step, level at 16 - profiles/r05_post_chain_lanes.jsonl),
-        // whole waves beyond 512 slots.  Their waves own a SIMD each (512 registers allocated) as long as the CUs the passes
-        // leave free hold them all: 2 kernels x 2 waves per work-group = one CU per work-group of either; one, two or three
-        // CUs per XCD stay free (8: +0.5 % on the plain step, 16: +1 %, 24: +2.5 %).
-        const unsigned groups = (unsigned)((c->aslots.size() + 63) / 64);
-        c->post_lanes = groups <= 8 ? 32 : 64;
-        if (const char *e = psdr_tuning_env("PSDR_PC_LANES")) c->post_lanes = atoi(e) == 16 ? 16 : atoi(e) == 32 ? 32 : 64;  // (tuning build)
-        const unsigned rgroups = groups * (unsigned)(64 / c->post_lanes);
-        c->post_reserve = (int)std::min(24u, 8u * (1u + rgroups / 8u));
-        if (const char *e = psdr_tuning_env("PSDR_PC_RESERVE")) c->post_reserve = atoi(e) & ~7;  // (tuning build)
-        c->post_own = (int)rgroups <= c->post_reserve;
-        if (const char *e = psdr_tuning_env("PSDR_PC_OWN")) c->post_own = atoi(e) != 0;  // (tuning build)
-    }
+    pc_replan(c);
     c->post_on = true;
     return PSDR_OK;
 }
 
+// run-time booleans -> template arguments: f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...)
+template <typename F>
+static auto pc_with_bools(F &&f) {
+    return f();
+}
+template <typename F, typename... B>
+static auto pc_with_bools(F &&f, bool b, B... rest) {
+    if (b) return pc_with_bools([&](auto... c) { return f(std::true_type{}, c...); }, rest...);
+    return pc_with_bools([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
+}
+
 // the chain's kernels for the batch whose demodulation has just been enqueued on c->side (d_clients: its parameter
 // block - the nact active clients first, then npaused paused ones with an empty stream - and d_slot_ci: the list index of
-// every slot's client, -1 = not listed)
+// every slot's client, -1 = not listed).  What is launched, where and with how much LDS is c->post_plan's business
+// (postplan.h); only what depends on nframes is worked out here.
 int psdr::post_chain_enqueue(psdr_ctx *c, const ClientParams *d_clients, const int *d_slot_ci, int nact, int npaused, int nframes,
                              hipStream_t *last_user) {
     constexpr int NS = psdr_ctx::PC_SETS;
+    const PcPlan &p = c->post_plan;
     const int set = (int)(c->chain_seq % NS), nxt = (set + 1) % NS;
     const uint64_t seq = c->chain_seq;
-    const bool piped = c->side != c->stream && c->pc_s[0] != nullptr;
-    // Streams: stage 0 rides behind the demodulation on `side` (two short kernels), stage 2 in front of stage 3 on ITS stream
-    // (they are a chain anyway), the moving averages on the other.  Hardware queues are what is scarce: with four chain
-    // streams the fourth shared a queue with the third (the gain recurrence in front of the next batch's peak), and with
-    // three - five busy queues with the main and the side stream - every second launch of the PASSES started 50 - 60 us
-    // late (6 - 9 us with four queues, as without the chain): 4 % of the step.
-    // WHICH queues matters as much (tools/runs/r05_w.sh, r05_y.sh; rocprofv3 Queue_Id): the chain on queues 4 and 6 leaves the
-    // passes' launches alone, on 4 and 5 it delays them as three chain queues do - queue 5 shares its pipe of the command
-    // processor with queue 1, the main stream's.  pc_pick_streams() chose pc_s[0] and pc_s[2] by that measure.
-    hipStream_t sg = c->side, sm = piped ? c->pc_s[0] : c->side, sc = piped ? c->pc_s[2] : c->side, sp = sc;
-    if (const char *e = psdr_tuning_env("PSDR_PC_STREAMS")) {  // (tuning build)
-        if (atoi(e) == 3 && piped) sp = c->pc_s[1];           // the peak kernels on a stream of their own
-        if (atoi(e) == 2 && piped) sp = sc = c->pc_s[1];       // the two chain streams on neighbouring queues
-        if (atoi(e) == 1 && piped) sp = sm;                    // the peak kernels behind the moving averages
-    }
-    // the prefix maxima ride behind the moving averages, w_t in front of the gain recurrence (with 256 clients the gain's
-    // stream is the longer one: 0.8 ms of peak kernels + 1.9 + 0.3 against 2.3)
-    bool split_peak = piped && sp == sc;
-    if (const char *e = psdr_tuning_env("PSDR_PC_SPLIT_PEAK")) split_peak = split_peak && atoi(e) != 0;  // (tuning build)
-    // the recurrence kernels go to the CUs the passes leave free (ctx.h persistent_grid): with this much LDS they do not fit
-    // beside a pass's work-group (128 KiB of 160)
-    size_t home_lds = c->post_reserve > 0 ? 34 * 1024 : 0;
-    const bool rows4 = (c->post.h & 3) == 0 && (c->post.D & 3) == 0;  // every frame starts on a row group: the lane = slot gather / output
-    // The AGC as chunk maxima + ONE four-wave kernel (postchain.h k_pc_agc: V1 read twice, the PCM written once - the five
-    // kernels of the other form pass over a stream eleven times) whenever the rate allows it and its work-groups - a whole
-    // CU each: four waves that own their SIMD - have the CUs the passes leave free
-    bool agc_fused = c->post_agc_ok && c->post_own && c->opt_pc_agc != 0 && c->post_lanes <= 32;
-    if (const char *e = psdr_tuning_env("PSDR_PC_FUSED")) agc_fused = agc_fused && atoi(e) != 0;  // (tuning build)
-    // ... and the chunk maxima of the new samples from a third wave of the moving averages (k_pc_ma2 CMW) instead of a pass over
-    // V1, while the free CUs hold a three-wave work-group of those beside every four-wave one of the AGC (a CU each)
-    bool ma_cmw = false;  // (set below, once the work-group count is known)
+    const bool piped = p.s_ma >= 0;
+    auto stream_of = [&](int i) -> hipStream_t { return i < 0 ? c->side : (hipStream_t)c->pc_s[i]; };
+    const hipStream_t sg = c->side, sm = stream_of(p.s_ma), sc = stream_of(p.s_gain), sp = stream_of(p.s_peak);
     // this batch's PCM goes to the other of two buffers (the copy of the last batch's to the host may still read its own)
     c->pcm_set ^= 1;
     c->post.pcm = c->pc.pcm_pool[c->pcm_set];
     PostArgs pa = c->post;
-    pa.pcm16 = c->opt_pc_pcm16;
-    c->pcm_is16 = pa.pcm16 != 0;
+    c->pcm_is16 = p.pcm16;
     pa.audio = c->d_audio;  // (of THIS demodulation batch: the result sets alternate)
     pa.nan_flags = c->d_nan;
     pa.clients = d_clients;
@@ -358,21 +337,11 @@ int psdr::post_chain_enqueue(psdr_ctx *c, const ClientParams *d_clients, const i
     pa.len = c->pc.len[set];
     pa.CM = c->pc.cm[set], pa.CP = c->pc.cp[set], pa.CS = c->pc.cs[set];
     pa.falive = c->pc.falive[set];
-    pa.ma_fused = pa.D == 32 ? 1 : 0;  // both averages in one loop (postchain.h)
-    // ... which may read the demodulator's rows themselves instead of a gathered copy (k_pc_ma2 DIRECT; part of the round-6
-    // form of the chain, PSDR_OPT_POST_CHAIN_AGC = 1; the demodulation two batches on waits for this batch's stage 1: demod.hip)
-    pa.direct = (pa.ma_fused && rows4 && c->opt_pc_agc != 0) ? 1 : 0;
-    if (const char *e = psdr_tuning_env("PSDR_PC_DIRECT")) pa.direct = pa.direct && atoi(e) != 0;  // (tuning build)
-    c->post_direct = pa.direct != 0;
-    const int nall = nact + npaused;
-    const unsigned groups = (unsigned)((pa.slots + 63) / 64);
-    pa.lanes = c->post_lanes;
-    const unsigned rgroups = groups * (unsigned)(64 / pa.lanes);  // work-groups of each of the two recurrence kernels
-    ma_cmw = agc_fused && pa.D == 32 && 2 * (int)rgroups <= c->post_reserve;
-    if (const char *e = psdr_tuning_env("PSDR_PC_CMW")) ma_cmw = ma_cmw && atoi(e) != 0;  // (tuning build)
-    if (rgroups > 16 || c->post_own) home_lds = 0;  // (waves that own a SIMD fit nowhere else anyway)
+    c->post_direct = p.direct;
+    const int nall = nact + npaused, skip = p.skip;
+    const unsigned groups = p.groups, rgroups = p.rgroups;
     const size_t Tb = (size_t)nframes * pa.h;  // longest possible stream of this batch
-    const unsigned nblk = (unsigned)((pa.L - 1 + Tb + pa.L - 1) / pa.L);
+    const unsigned nblk = (unsigned)pc_nblk(pa.L, Tb);
     // Who touched what last (sets rotate: batch b uses set b mod 3 and writes the history rows of set b + 1):
     //   X[set] rows >= D, fstart / len[set]   gather(b)      <- moving averages, history, output of batch b - 3
     //   V1[set] rows >= L-1                   averages(b)    <- peak / output of batch b - 3
@@ -391,17 +360,13 @@ int psdr::post_chain_enqueue(psdr_ctx *c, const ClientParams *d_clients, const i
         return PSDR_OK;
     };
     int rc = 0;
-    // (tuning build: PSDR_PC_SKIP = bit mask of chain kernels NOT launched - wrong results, a timing bound of what each costs the
-    // step: 1 gather, 2 moving averages, 4 history, 8 sub-block maxima, 16 prefix maxima, 32 w_t, 64 gain, 128 int16 output)
-    int skip = 0;
-    if (const char *e = psdr_tuning_env("PSDR_PC_SKIP")) skip = (int)strtol(e, nullptr, 0);
     {  // ---- stage 0: frame offsets, audio rows -> X
         if (seq >= NS && ((rc = wait(sg, 1, set)) || (rc = wait(sg, 3, set)))) return rc;
         ProfScope ps(c, K_POST, sg);
         hipLaunchKernelGGL(k_pc_index, dim3(nall), dim3(64), 0, sg, pa);
         if (skip & 1)
             ;
-        else if (rows4)
+        else if (p.rows4)
             hipLaunchKernelGGL(k_pc_gather4, dim3(groups, nframes), dim3(256), 0, sg, pa);
         else
             hipLaunchKernelGGL(k_pc_gather, dim3(nall, nframes), dim3(256), 0, sg, pa);
@@ -414,41 +379,40 @@ int psdr::post_chain_enqueue(psdr_ctx *c, const ClientParams *d_clients, const i
         if (seq >= NS - 1 && (rc = wait(sm, 3, nxt))) return rc;
         ProfScope ps(c, K_POST, sm);
         if (skip & 2) {
-        } else if (pa.ma_fused && ma_cmw) {
+        } else if (p.ma == MA2_CMW) {
             hipLaunchKernelGGL((k_pc_ma2<true, true>), dim3(rgroups), dim3(192), 0, sm, pa);
-        } else if (pa.ma_fused) {
-            if (c->post_own)
-                hipLaunchKernelGGL(k_pc_ma2<true>, dim3(rgroups), dim3(128), 0, sm, pa);
-            else
-                hipLaunchKernelGGL(k_pc_ma2<false>, dim3(rgroups), dim3(128), home_lds ? home_lds - 17 * 1024 : 0, sm, pa);
-        } else if ((pa.D & (pa.D - 1)) == 0 && pa.D >= 16 && (size_t)pa.D * pa.lanes * sizeof(float) <= 128 * 1024) {
-            // any other power-of-two delay (48 kHz: 128, 192 kHz: 512): the two-wave form with its ring of sums in LDS
-            const size_t ring_lds = (size_t)pa.D * pa.lanes * sizeof(float);
-            const void *fn = c->post_own ? (const void *)k_pc_mad<true> : (const void *)k_pc_mad<false>;
-            if (c->lds_attr_done.insert(fn).second) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
-            if (c->post_own)
-                hipLaunchKernelGGL(k_pc_mad<true>, dim3(rgroups), dim3(128), ring_lds, sm, pa);
-            else
-                hipLaunchKernelGGL(k_pc_mad<false>, dim3(rgroups), dim3(128), ring_lds, sm, pa);
-        } else if ((pa.D & (pa.D - 1)) == 0) {
-            hipLaunchKernelGGL((k_pc_ma<false, true>), dim3(groups), dim3(64), 0, sm, pa);
-            hipLaunchKernelGGL((k_pc_ma<true, true>), dim3(groups), dim3(64), 0, sm, pa);
+        } else if (p.ma == MA2) {
+            pc_with_bools([&](auto own) { hipLaunchKernelGGL(k_pc_ma2<decltype(own)::value>, dim3(rgroups), dim3(128), p.ma_lds, sm, pa); }, p.own);
+        } else if (p.ma == MAD) {
+            rc = pc_with_bools(
+                [&](auto own) -> int {
+                    const void *fn = (const void *)k_pc_mad<decltype(own)::value>;
+                    if (c->lds_attr_done.insert(fn).second) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
+                    hipLaunchKernelGGL(k_pc_mad<decltype(own)::value>, dim3(rgroups), dim3(128), p.ma_lds, sm, pa);
+                    return PSDR_OK;
+                },
+                p.own);
+            if (rc) return rc;
         } else {
-            hipLaunchKernelGGL((k_pc_ma<false, false>), dim3(groups), dim3(64), 0, sm, pa);
-            hipLaunchKernelGGL((k_pc_ma<true, false>), dim3(groups), dim3(64), 0, sm, pa);
+            pc_with_bools(
+                [&](auto pow2) {
+                    hipLaunchKernelGGL((k_pc_ma<false, decltype(pow2)::value>), dim3(groups), dim3(64), 0, sm, pa);
+                    hipLaunchKernelGGL((k_pc_ma<true, decltype(pow2)::value>), dim3(groups), dim3(64), 0, sm, pa);
+                },
+                p.ma == MA_POW2);
         }
         if (!(skip & 4)) hipLaunchKernelGGL(k_pc_history, dim3(nall), dim3(256), 0, sm, pa);
         HIPCHK(hipGetLastError());
         if ((rc = done(sm, 1))) return rc;
     }
-    if (agc_fused) {
+    if (p.agc == AGC_ONE_KERNEL) {
         // ---- stage 2: chunk maxima of |V1| and their block scans, behind the moving averages on THEIR stream (P / S / SM are not
         // used; CM / CP / CS of this set were last read by stage 3 of batch b - 3: waited for in stage 1)
         const int nchunks = (int)((pa.vo + pa.L - 1 + Tb + 15) / 16);
         const int W = pa.L / 16 - 1;
         {
             ProfScope ps(c, K_POST, sm);
-            const int ncm = ma_cmw ? pa.L / 16 : nchunks;  // (k_pc_ma2 CMW left the new samples' chunk maxima: the history chunks only)
+            const int ncm = p.ma == MA2_CMW ? pa.L / 16 : nchunks;  // (k_pc_ma2 CMW left the new samples' chunk maxima: the history chunks only)
             if (!(skip & 8)) hipLaunchKernelGGL(k_pc_cm, dim3(groups, (ncm + 15) / 16), dim3(64), 0, sm, pa, ncm);
             if (!(skip & 16)) hipLaunchKernelGGL(k_pc_cscan, dim3(groups, (nchunks + W - 1) / W), dim3(64), 0, sm, pa, nchunks, W);
             HIPCHK(hipGetLastError());
@@ -459,23 +423,17 @@ int psdr::post_chain_enqueue(psdr_ctx *c, const ClientParams *d_clients, const i
         if ((rc = fetch_guard_wait(c, sc, c->guard_pcm[c->pcm_set]))) return rc;  // what read this PCM buffer two batches ago has landed
         c->guard_pcm[c->pcm_set] = nullptr;
         if (!(skip & 128)) hipLaunchKernelGGL(k_pc_zero, dim3(groups, nframes), dim3(256), 0, sc, pa);
-        if (skip & 64) {
-        } else if (pa.attack >= pa.release) {
-            if (pa.pcm16)
-                hipLaunchKernelGGL((k_pc_agc<true, true>), dim3(rgroups), dim3(64 * (1 + PC_AGC_NP)), 0, sc, pa);
-            else
-                hipLaunchKernelGGL((k_pc_agc<true, false>), dim3(rgroups), dim3(64 * (1 + PC_AGC_NP)), 0, sc, pa);
-        } else {
-            if (pa.pcm16)
-                hipLaunchKernelGGL((k_pc_agc<false, true>), dim3(rgroups), dim3(64 * (1 + PC_AGC_NP)), 0, sc, pa);
-            else
-                hipLaunchKernelGGL((k_pc_agc<false, false>), dim3(rgroups), dim3(64 * (1 + PC_AGC_NP)), 0, sc, pa);
-        }
+        if (!(skip & 64))
+            pc_with_bools(
+                [&](auto att, auto p16) {
+                    hipLaunchKernelGGL((k_pc_agc<decltype(att)::value, decltype(p16)::value>), dim3(rgroups), dim3(64 * (1 + PC_AGC_NP)), 0, sc, pa);
+                },
+                p.att_faster, p.pcm16);
         HIPCHK(hipGetLastError());
         if ((rc = done(sc, 3))) return rc;
     } else {
         {  // ---- stage 2: look-ahead peak and w_t (parallel along time)
-            hipStream_t sp1 = split_peak ? sm : sp;  // (P[set]'s last readers - gain / output of batch b - 3 - were waited for in stage 1)
+            hipStream_t sp1 = p.split_peak ? sm : sp;  // (P[set]'s last readers - gain / output of batch b - 3 - were waited for in stage 1)
             if (sp1 != sm && (rc = wait(sp1, 1, set))) return rc;
             if (seq >= NS && sp1 != sm && (rc = wait(sp1, 3, set))) return rc;
             {
@@ -483,7 +441,7 @@ int psdr::post_chain_enqueue(psdr_ctx *c, const ClientParams *d_clients, const i
                 if (pa.nsub > 1 && !(skip & 8)) hipLaunchKernelGGL(k_pc_submax, dim3(groups, nblk * pa.nsub), dim3(64), 0, sp1, pa);
                 if (!(skip & 16)) hipLaunchKernelGGL(k_pc_prefix, dim3(groups, nblk * pa.nsub), dim3(64), 0, sp1, pa);
             }
-            if (split_peak) {
+            if (p.split_peak) {
                 if ((rc = done(sp1, 2)) || (rc = wait(sp, 2, set))) return rc;
             }
             {
@@ -491,29 +449,22 @@ int psdr::post_chain_enqueue(psdr_ctx *c, const ClientParams *d_clients, const i
                 if (!(skip & 32)) hipLaunchKernelGGL(k_pc_want, dim3(groups, nblk * pa.nsub), dim3(64), 0, sp, pa);
             }
             HIPCHK(hipGetLastError());
-            if (!split_peak && (rc = done(sp, 2))) return rc;
+            if (!p.split_peak && (rc = done(sp, 2))) return rc;
         }
         {  // ---- stage 3: the gain recurrence (sequential), int16 output
             if (sp != sc && (rc = wait(sc, 2, set))) return rc;
             ProfScope ps(c, K_POST, sc);
-            const size_t glds = home_lds ? home_lds - 8 * 1024 : 0;
-            if (skip & 64) {
-            } else if (pa.attack >= pa.release) {
-                if (c->post_own)
-                    hipLaunchKernelGGL((k_pc_gain<true, true>), dim3(rgroups), dim3(128), 0, sc, pa);
-                else
-                    hipLaunchKernelGGL((k_pc_gain<true, false>), dim3(rgroups), dim3(128), glds, sc, pa);
-            } else {
-                if (c->post_own)
-                    hipLaunchKernelGGL((k_pc_gain<false, true>), dim3(rgroups), dim3(128), 0, sc, pa);
-                else
-                    hipLaunchKernelGGL((k_pc_gain<false, false>), dim3(rgroups), dim3(128), glds, sc, pa);
-            }
+            if (!(skip & 64))
+                pc_with_bools(
+                    [&](auto att, auto own) {
+                        hipLaunchKernelGGL((k_pc_gain<decltype(att)::value, decltype(own)::value>), dim3(rgroups), dim3(128), p.gain_lds, sc, pa);
+                    },
+                    p.att_faster, p.own);
             if ((rc = fetch_guard_wait(c, sc, c->guard_pcm[c->pcm_set]))) return rc;  // what read this PCM buffer two batches ago has landed
             c->guard_pcm[c->pcm_set] = nullptr;
             if (skip & 128)
                 ;
-            else if (rows4)
+            else if (p.rows4)
                 hipLaunchKernelGGL(k_pc_out4, dim3(groups, nframes), dim3(256), 0, sc, pa);
             else
                 hipLaunchKernelGGL(k_pc_out, dim3(nall, nframes), dim3(256), 0, sc, pa);
