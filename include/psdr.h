@@ -337,6 +337,45 @@ int psdr_client_set_fine_tune(psdr_ctx *ctx, int id, int on);
  * differ as PSDR_SAM's own two do - in the carrier's last bits, never in B'. */
 typedef enum psdr_sam_sideband { PSDR_SAM_BOTH = 0, PSDR_SAM_UPPER = 1, PSDR_SAM_LOWER = 2 } psdr_sam_sideband;
 int psdr_client_set_sam_sideband(psdr_ctx *ctx, int id, int sideband);
+/* Notch filters: manual and automatic heterodyne removal.  A steady carrier inside the wanted passband whistles through
+ * every mode and captures the AGC.  A client's passband is held here as FFT bins, so a notch is exact: a NOTCH is a half-open
+ * interval [first, end) of spectrum bins, in the coordinates of the client's l, r and audio_mid (client order for IQ input, k
+ * for real input) - absolute, not relative to the window: it stays on the interferer when the listener retunes.  A client has
+ * up to PSDR_NOTCH_MANUAL manual notches and up to PSDR_NOTCH_AUTO automatic ones.
+ *   The defining rule.  A client with notches is bit-identical to the same client without notches on a spectrum in which
+ *     every bin of every notch is +0.0 + 0.0i: audio, pwr, NaN flags, IQ rows, carrier records, every piece of carried state
+ *     and the PCM behind the post chain; in every mode (tuned and sideband clients included), on both transform paths and
+ *     for every batch split.  So pwr is the power of what is heard, and a NaN or Inf in a notched bin does not flag the frame:
+ *     the kernels do not load a notched bin.  A client with no notch and auto-notch off gives the bits and the launches of
+ *     a library without these calls; manual notches need no allocation of their own (they travel in the client
+ *     parameter ring, which is 48 bytes per client slot and ring slot larger for them in every context).
+ *   psdr_client_set_notch(ctx, id, index, centre_bin, width_bins): manual notch `index` (0 or 1) becomes
+ *     first = floor(centre_bin - width_bins/2 + 0.5), end = floor(centre_bin + width_bins/2 + 0.5), computed in double, at
+ *     least one bin (end = first + 1 if end <= first); width_bins <= 0 clears the entry.  PSDR_ERR_INVALID, and nothing
+ *     changed, for an unknown id, an index outside 0..1, a non-finite argument or a width above audio_fft_size.  Any thread;
+ *     takes force at the next batch, through the batch's snapshot, like psdr_client_set_audio_range.
+ *   psdr_client_set_auto_notch(ctx, id, on): the detector.  Behind every batch one wave per auto-notch client adds the power
+ *     |X|^2 of the client's window bins - un-notched: it keeps seeing a carrier it has removed - to a sum per bin, frame by
+ *     frame; every period = max(1, audio_rate / audio_fft_size) frames (half a second) it evaluates and starts the sums
+ *     again.  With mean = the sums' mean over the window: an automatic entry that is set stays while some bin of it is above
+ *     8 * mean; a free entry takes the strongest bin t that is a local maximum (sum[t] >= sum[t-1], sum[t] > sum[t+1],
+ *     outside the window 0) above 16 * mean, is not within 3 bins of floor(audio_mid) in PSDR_AM, PSDR_FM or PSDR_SAM (the
+ *     wanted carrier) and whose entry [l + t - 1, l + t + 2) overlaps no set one; ties go to the lower bin.  Non-finite sums
+ *     compare false: they set nothing and keep nothing.  A decision made behind batch b is in force from batch b + 1.  The
+ *     sums, the frame counter and both entries start from zero when auto-notch is switched on (also while paused) and whenever [l, r),
+ *     floor(audio_mid) or the mode differ from the client's previous batch; switching it off clears the entries; a paused
+ *     client's stand still.  The state (4 * audio_fft_size + 20 bytes per client slot) is allocated with the context's
+ *     first auto-notch client, all or none: PSDR_ERR_NOMEM and the flag unchanged if that fails.  The default is off, or what
+ *     psdr_set_option(ctx, PSDR_OPT_AUTO_NOTCH, 1) set before psdr_client_add (existing clients keep theirs).
+ *   psdr_read_notches(ctx, id, first, end): the last batch's notches of the client, entries 0..1 the manual ones of its
+ *     snapshot, 2..3 the automatic ones as the batch's detector left them (in force from the next batch); an empty entry
+ *     reads 0, 0.  Synchronises.  PSDR_ERR_NO_DATA under psdr_read_audio's rule (the client was not part of the last batch).
+ * There is no psdr_group_* call: a group's clients have no notches. */
+#define PSDR_NOTCH_MANUAL 2
+#define PSDR_NOTCH_AUTO   2
+int psdr_client_set_notch(psdr_ctx *ctx, int id, int index, double centre_bin, double width_bins);
+int psdr_client_set_auto_notch(psdr_ctx *ctx, int id, int on);
+int psdr_read_notches(psdr_ctx *ctx, int id, int first[4], int end[4]);
 /* A client added after the last psdr_demod_batch has no results in it (the reference's frame loop would not
  * have posted a task for it either, src/websocket.cpp:156-185): psdr_read_audio / psdr_read_pcm / psdr_fetched_audio
  * return PSDR_ERR_NO_DATA for such a slot instead of the previous occupant's samples.
@@ -439,6 +478,7 @@ enum { PSDR_OPT_POST_CHAIN_STREAMS = 1, PSDR_OPT_POST_CHAIN_AGC = 2, PSDR_OPT_PO
 #define PSDR_OPT_WATERFALL_DETECTOR 4
 #define PSDR_OPT_FINE_TUNE 5
 #define PSDR_OPT_SAM_SIDEBAND 6   /* the value a client gets at psdr_client_add; existing clients keep theirs */
+#define PSDR_OPT_AUTO_NOTCH 7     /* 0 (default) or 1: the auto-notch flag a client gets at psdr_client_add; existing clients keep theirs */
 int psdr_set_option(psdr_ctx *ctx, int option, int value);
 /* pcm: [frames of the last demod_batch][audio_fft_size/2]; nframes = rows pcm holds (as psdr_read_audio) */
 int psdr_read_pcm(psdr_ctx *ctx, int id, int nframes, int32_t *pcm, int *nframes_out);
@@ -558,7 +598,8 @@ psdr_ctx *psdr_group_ctx(psdr_group *g, int rank);
 /* PSDR_IQ is not served through a group (its rows are neither migrated nor fetched by gid): psdr_group_client_add and
  * psdr_group_client_set_audio_demodulation answer PSDR_ERR_UNSUPPORTED for it.  The same holds for PSDR_SAM: the carrier
  * tail is not migrated and the carrier records are not fetched by gid.  There is no psdr_group_* call for the fine-tune
- * flag: a group's clients are untuned, and a band migration carries the flag's value 0. */
+ * flag: a group's clients are untuned, and a band migration carries the flag's value 0.  There is none for notches either
+ * (psdr_client_set_notch, psdr_client_set_auto_notch): a group's clients have none, and a band migration carries none. */
 int psdr_group_client_add(psdr_group *g, int l, double audio_mid, int r, int mode, int *gid_out);
 int psdr_group_client_remove(psdr_group *g, int gid);
 int psdr_group_client_set_audio_range(psdr_group *g, int gid, int l, double audio_mid, int r);

@@ -164,6 +164,7 @@ class Context:
     OPT_WATERFALL_DETECTOR = 4  # WF_SAMPLE (default) / WF_PEAK / WF_MEAN: the detector of waterfall clients added from now on
     OPT_FINE_TUNE = 5  # 0 (default) / 1: the fine-tune flag of audio clients added from now on (AudioClient.set_fine_tune)
     OPT_SAM_SIDEBAND = 6  # SAM_BOTH (default) / SAM_UPPER / SAM_LOWER: the SAM sideband of audio clients added from now on
+    OPT_AUTO_NOTCH = 7  # 0 (default) / 1: the auto-notch flag of audio clients added from now on (AudioClient.set_auto_notch)
 
     def set_option(self, option, value):
         check(self.lib.psdr_set_option(self.h, int(option), int(value)))
@@ -447,6 +448,22 @@ class AudioClient:
         mode only that sideband is detected against the carrier recovered from the whole window; no effect in other modes."""
         sb = SAM_SIDEBANDS[sideband] if isinstance(sideband, str) else int(sideband)
         check(self.ctx.lib.psdr_client_set_sam_sideband(self.ctx.h, self.id, sb))
+
+    def set_notch(self, index, centre_bin, width_bins):
+        """manual notch `index` (0 or 1) on the spectrum bins around centre_bin (psdr_client_set_notch): the client's kernels
+        take those bins as zero; width_bins <= 0 clears the entry.  Takes force at the next batch."""
+        check(self.ctx.lib.psdr_client_set_notch(self.ctx.h, self.id, int(index), float(centre_bin), float(width_bins)))
+
+    def set_auto_notch(self, on):
+        """automatic notches (psdr_client_set_auto_notch): every half second the detector behind the batches notches up to two
+        steady carriers that stand 16 times above the window's mean power."""
+        check(self.ctx.lib.psdr_client_set_auto_notch(self.ctx.h, self.id, 1 if on else 0))
+
+    def notches(self):
+        """[(first, end)] x 4 of the last batch (psdr_read_notches): entries 0..1 manual, 2..3 automatic; (0, 0) = empty"""
+        first, end = (C.c_int * 4)(), (C.c_int * 4)()
+        check(self.ctx.lib.psdr_read_notches(self.ctx.h, self.id, first, end))
+        return [(first[k], end[k]) for k in range(4)]
 
     def on_window_message(self, l, m, r):
         """returns False where the reference silently returns (src/signal.cpp:302-311)."""

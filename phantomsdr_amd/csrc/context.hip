@@ -306,7 +306,7 @@ int build(psdr_ctx *c) {
         PSDRCHK(c->d_ssb_mark.alloc(S, true));
         if (c->lds_mode == 2) PSDRCHK(c->d_gscratch.alloc(S * F * 2 * n));
         // the batch's client list + the slot -> list index table; behind them the tuned clients' list (ctx.h: ft_ring_off)
-        if (c->client_ring.init(ft_ring_off(S) + S * (sizeof(ClientParams) + sizeof(FtClient))))
+        if (c->client_ring.init(client_ring_bytes(S)))
             return fail(PSDR_ERR_HIP, "client parameter ring allocation failed");
     }
     // ---- waterfall clients

@@ -84,6 +84,13 @@ struct AudioSlot {
     // (demod.h: k_demod_chain_sbsam); in every other mode the value is kept and has no effect
     int sam_sb = PSDR_SAM_BOTH;
     int b_sam_sb = PSDR_SAM_BOTH;  // ... of the last batch (with b_mode: whether the sideband baseband tail continues)
+    // psdr_client_set_notch: the two manual notches, [first, end) in the coordinates of l / r (0, 0: empty); b_notch: the
+    // last batch's snapshot (psdr_read_notches)
+    int notch[4] = {0, 0, 0, 0}, b_notch[4] = {0, 0, 0, 0};  // first0, end0, first1, end1
+    // psdr_client_set_auto_notch; b_auto: of the last batch (with b_l / b_r / b_mid / b_mode: whether the detector's state continues)
+    int auto_notch = 0;
+    bool b_auto = false;
+    bool auto_fresh = false;  // switched on since the slot's last batch (a paused client may be switched off and on again)
 };
 struct WfSlot {
     bool active = false;
@@ -131,9 +138,12 @@ struct ParamRing {
 
 // the client parameter ring's slot: [ClientParams x S][int x S], then from ft_ring_off(S) on the tuned clients' list,
 // [ClientParams x nt][FtClient x nt], and behind it the sideband SAM clients' list, [ClientParams x nsb][SbClient x nsb],
-// with nt + nsb <= S (no client is on both lists)
+// with nt + nsb <= S (no client is on both lists); from notch_ring_off(S) on the manual notches of the batch's snapshot,
+// [int4 x S] by slot (DemodArgs::notch_man), and k_notch_detect's list of the batch's auto-notch clients, [ClientParams x S]
 static_assert(sizeof(SbClient) == sizeof(FtClient), "the two lists share the ring's space behind ft_ring_off");
 inline size_t ft_ring_off(size_t S) { return (S * (sizeof(ClientParams) + sizeof(int)) + 15) & ~(size_t)15; }
+inline size_t notch_ring_off(size_t S) { return (ft_ring_off(S) + S * (sizeof(ClientParams) + sizeof(FtClient)) + 15) & ~(size_t)15; }
+inline size_t client_ring_bytes(size_t S) { return notch_ring_off(S) + S * (sizeof(int4) + sizeof(ClientParams)); }
 
 inline int ilog2(size_t v) {
     int l = 0;
@@ -309,6 +319,14 @@ struct psdr_ctx {
     // (under mtx) and kept
     DevBuf<cf> d_sb_tail;
     int opt_sam_sideband = PSDR_SAM_BOTH;  // PSDR_OPT_SAM_SIDEBAND: the value psdr_client_add hands a new client
+    // auto-notch (demod.h: k_notch_detect): per slot the power sums acc [slots][n], the frame counter and the table of the two
+    // automatic entries (DemodArgs::notch_auto) - all three allocated with the context's first auto-notch client (under mtx),
+    // or none, and kept.  Manual notches travel in the client ring and need no allocation.
+    DevBuf<float> d_notch_acc;
+    DevBuf<int> d_notch_cnt;
+    DevBuf<int4> d_notch_tab;
+    int opt_auto_notch = 0;  // PSDR_OPT_AUTO_NOTCH: the value psdr_client_add hands a new client
+    const void *dbg_notch_man = nullptr, *dbg_notch_auto = nullptr;  // DemodArgs::notch_man / notch_auto of the last batch (psdr_debug_notch_ptrs)
     DevBuf<unsigned> d_ssb_mark;  // [slots] DemodArgs::ssb_mark (demod.h): USB / LSB batches that need the frame-ordered NaN guard
     ParamRing client_ring;
     int last_demod_frames = 0;

@@ -69,6 +69,12 @@ struct DemodArgs {
     unsigned *ssb_mark;   // [slots]: == mark_epoch: the slot's batch needs the sequential walk
     unsigned mark_epoch;  // of this batch (never 0)
     int replay;           // 1: the sequential walk itself (marked slots only)
+    // Notches (include/psdr.h: psdr_client_set_notch / _set_auto_notch): half-open intervals [first, end) of spectrum bins, in
+    // the coordinates of ClientParams::l / r, that a client's kernels take as +0.0 + 0.0i instead of loading them
+    const int4 *notch_man;   // [slots] (first0, end0, first1, end1): the batch's snapshot of the manual notches, uploaded with the
+                             // client list; null: no client of the batch has one
+    const int4 *notch_auto;  // [slots] (first2, end2, first3, end3): the device-resident table k_notch_detect writes behind the
+                             // batch's last demodulation kernel; null: no client of the context has ever switched auto-notch on
 };
 __device__ __forceinline__ bool not_finite(float v) { return !(fabsf(v) <= 3.402823466e38f); }  // NaN or +-Inf
 
@@ -119,6 +125,38 @@ __device__ __forceinline__ ClientParams wave_uniform(ClientParams cp) {
     cp.slot = __builtin_amdgcn_readfirstlane(cp.slot);
     cp.state_cur = __builtin_amdgcn_readfirstlane(cp.state_cur);
     return cp;
+}
+// A client's notches: up to four half-open intervals of spectrum bins, wave-uniform, in scalar registers (an empty entry is
+// 0, 0).  `any`: one of them is set - a client without notches passes every test with one scalar compare.
+struct Notches {
+    int f0, e0, f1, e1, f2, e2, f3, e3;
+    int any;
+};
+__device__ __forceinline__ Notches notch_load(const DemodArgs &a, int slot) {
+    int4 m = make_int4(0, 0, 0, 0), t = make_int4(0, 0, 0, 0);
+    if (a.notch_man) m = a.notch_man[slot];
+    if (a.notch_auto) t = a.notch_auto[slot];
+    Notches nz;
+    nz.f0 = __builtin_amdgcn_readfirstlane(m.x), nz.e0 = __builtin_amdgcn_readfirstlane(m.y);
+    nz.f1 = __builtin_amdgcn_readfirstlane(m.z), nz.e1 = __builtin_amdgcn_readfirstlane(m.w);
+    nz.f2 = __builtin_amdgcn_readfirstlane(t.x), nz.e2 = __builtin_amdgcn_readfirstlane(t.y);
+    nz.f3 = __builtin_amdgcn_readfirstlane(t.z), nz.e3 = __builtin_amdgcn_readfirstlane(t.w);
+    nz.any = (nz.e0 > nz.f0) | (nz.e1 > nz.f1) | (nz.e2 > nz.f2) | (nz.e3 > nz.f3);
+    return nz;
+}
+// "is slice bin t of this client notched": THE definition - every place a kernel reads a client's spectrum bins asks it
+// and takes +0.0 + 0.0i for a notched bin instead of loading it.  (The defining rule of include/psdr.h follows: whatever is
+// computed from the bins is computed from a spectrum whose notched bins are zero.)
+__device__ __forceinline__ bool notched(const Notches &nz, const ClientParams &cp, int t) {
+    const int b = cp.l + t;
+    return nz.any && ((b >= nz.f0 && b < nz.e0) || (b >= nz.f1 && b < nz.e1) || (b >= nz.f2 && b < nz.e2) || (b >= nz.f3 && b < nz.e3));
+}
+// ... loaded again for every frame of a chain, behind an opaque copy of the slot (two scalar loads that hit the constant
+// cache): held across the frame loop the nine scalars pushed k_demod_chain_sam<720> and k_demod_chain_sbsam<720> into 12
+// bytes of scratch (scalar registers spilled into vector lanes) - DESIGN.md 3.11
+__device__ __forceinline__ Notches notch_load_frame(const DemodArgs &a, int slot) {
+    asm volatile("" : "+s"(slot));
+    return notch_load(a, slot);
 }
 // a client's double-buffered state (src/signal.h:86-101): this batch reads half state_cur and writes the other one
 struct SlotState {
@@ -230,13 +268,14 @@ __device__ __forceinline__ void idft_item(const DemodArgs &a, const ClientParams
     const int len = cp.r - cp.l;
     const int m = cp.m_floor - cp.l;  // audio_m
     const cf *S = a.spec + (size_t)f * a.spec_stride;  // slice bin t at lay.pos(cp.l + t)
+    const Notches nz = notch_load(a, cp.slot);
 
     for (int i = tid; i < n; i += NT) bufA[i] = make_float2(0.f, 0.f);
     sy.sync();
 
     float pw = 0.f;
     for (int t = tid; t < len; t += NT) {
-        const cf v = S[a.lay.pos(cp.l + t)];
+        const cf v = notched(nz, cp, t) ? make_float2(0.f, 0.f) : S[a.lay.pos(cp.l + t)];
         pw += fmaf(v.x, v.x, v.y * v.y);
         if (cp.mode == 0) {  // USB :125-137
             if (t >= m && t < m + n) bufA[t - m] = v;
@@ -490,13 +529,13 @@ __device__ __forceinline__ void idft_stage_fixed(cf *buf, const cf *Wn, int lane
 // stages.  Leaves the n outputs in buf (before reversal / sign flip) and returns the slice power (all lanes).
 // the slice of one (client, frame) item, bin t = lane + 64 u in sv[u] (at most n bins, src/signal.cpp:309-311)
 template <int N>
-__device__ __forceinline__ void idft_load_slice(const DemodArgs &a, const ClientParams &cp, int f, int lane, cf (&sv)[(N + 63) / 64]) {
+__device__ __forceinline__ void idft_load_slice(const DemodArgs &a, const ClientParams &cp, const Notches &nz, int f, int lane, cf (&sv)[(N + 63) / 64]) {
     const int len = cp.r - cp.l;
     const cf *S = a.spec + (size_t)f * a.spec_stride;  // slice bin t at lay.pos(cp.l + t)
 #pragma unroll
     for (int u = 0; u < (N + 63) / 64; u++) {
         const int t = lane + 64 * u;
-        sv[u] = t < len ? S[a.lay.pos(cp.l + t)] : make_float2(0.f, 0.f);
+        sv[u] = t < len && !notched(nz, cp, t) ? S[a.lay.pos(cp.l + t)] : make_float2(0.f, 0.f);
     }
 }
 // the same in two steps for a wave that walks SEVERAL frames of one client: where bin t of the slice sits inside a frame
@@ -513,17 +552,20 @@ __device__ __forceinline__ void idft_slice_offsets(const DemodArgs &a, const Cli
         so[u] = t < len ? (unsigned)a.lay.pos(cp.l + t) : 0u;  // (element index inside a frame / band region: < 2^32)
     }
 }
-template <int N, int HO>
-__device__ __forceinline__ void idft_load_slice_at(const DemodArgs &a, const ClientParams &cp, int f, const unsigned (&so)[HO], int lane, cf (&sv)[(N + 63) / 64]) {
+// (NZ = false: the notch test left out - k_demod_chain_iq, which has neither a vector nor a scalar register to spare; its
+// twin k_demod_chain_iq_nz serves the lists that contain a notched client)
+template <int N, int HO, bool NZ = true>
+__device__ __forceinline__ void idft_load_slice_at(const DemodArgs &a, const ClientParams &cp, const Notches &nz, int f, const unsigned (&so)[HO], int lane, cf (&sv)[(N + 63) / 64]) {
     const int len = cp.r - cp.l;
     const cf *S = a.spec + (size_t)f * a.spec_stride;
 #pragma unroll
     for (int u = 0; u < (N + 63) / 64; u++) {
         const int t = lane + 64 * u;
+        const bool in = t < len && !(NZ && notched(nz, cp, t));
         if (u < HO)
-            sv[u] = t < len ? S[so[u]] : make_float2(0.f, 0.f);
+            sv[u] = in ? S[so[u]] : make_float2(0.f, 0.f);
         else
-            sv[u] = t < len ? S[a.lay.pos(cp.l + t)] : make_float2(0.f, 0.f);
+            sv[u] = in ? S[a.lay.pos(cp.l + t)] : make_float2(0.f, 0.f);
     }
 }
 template <int N, int R0, int R1, int R2>
@@ -531,7 +573,7 @@ __device__ __forceinline__ float idft_slice_fixed(const ClientParams &cp, const 
 template <int N, int R0, int R1, int R2>
 __device__ __forceinline__ float idft_item_fixed(const DemodArgs &a, const ClientParams &cp, int f, cf *buf, const cf *Wn, int lane) {
     cf sv[(N + 63) / 64];  // loads first, LDS after
-    idft_load_slice<N>(a, cp, f, lane, sv);
+    idft_load_slice<N>(a, cp, notch_load(a, cp.slot), f, lane, sv);
     return idft_slice_fixed<N, R0, R1, R2>(cp, sv, buf, Wn, lane);
 }
 template <int N, int R0, int R1, int R2>
@@ -835,6 +877,7 @@ __global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) 
     constexpr int HO = NR < 3 ? NR : (N <= 512 ? 3 : 6);
     unsigned so[HO];  // where the slice's first 64 HO bins sit inside a frame: the same for every frame of the chain
     idft_slice_offsets<N, HO>(a, cp, lane_, so);
+    const Notches nz = notch_load(a, cp.slot);
     while (f < f1) {
         const bool emit = f >= f0;
         const int lane = opaque_lane(lane_);
@@ -845,16 +888,16 @@ __global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) 
 #pragma unroll
                 for (int u = 0; u < NR; u++) sv[u] = svn[u];
             } else {
-                idft_load_slice_at<N, HO>(a, cp, f, so, lane, sv);  // the chain's first frame; a warm-up frame looked for further back
+                idft_load_slice_at<N, HO>(a, cp, nz, f, so, lane, sv);  // the chain's first frame; a warm-up frame looked for further back
             }
             if (f + 1 < f1) {
-                idft_load_slice_at<N, HO>(a, cp, f + 1, so, lane, svn);
+                idft_load_slice_at<N, HO>(a, cp, nz, f + 1, so, lane, svn);
                 fpre = f + 1;
             }
             pw = idft_slice_fixed<N, R0, R1, R2>(cp, sv, buf, Wn, lane);
         } else {
             cf sv[NR];  // loads first, LDS after
-            idft_load_slice_at<N, HO>(a, cp, f, so, lane, sv);
+            idft_load_slice_at<N, HO>(a, cp, nz, f, so, lane, sv);
             pw = idft_slice_fixed<N, R0, R1, R2>(cp, sv, buf, Wn, lane);
         }
         if (emit && lane == 0) a.pwr[srow * a.max_batch + f] = pw;
@@ -991,8 +1034,12 @@ __global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) 
 // ONE warm-up frame (no sample of IQ_f0 looks further back than y_{f0-1}), no detector, no NaN-guard replay, no
 // ssb_mark.  Same operations in the same order as k_demod_idft_fixed + k_demod_ola_iq (__fmul_rn / __fadd_rn: see
 // k_demod_chain_fixed): bit-identical outputs.  Grid and LDS as k_demod_chain_fixed.
-template <int N, int R0, int R1, int R2>
-__global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) void k_demod_chain_iq(DemodArgs a, int nact, int K, cf *iq) {
+// NZ: the notch test (notched, above) is part of the slice load.  Beside a pass k_demod_chain_iq<360> holds 62 VGPRs and 102
+// scalar registers; with the test in, every form tried took 65 - 67 (scalars spilled into vector lanes).  So the kernel
+// without the test stays what it was, and k_demod_chain_iq_nz - the same body, NZ = true - serves the IQ lists that contain
+// a notched client.
+template <int N, int R0, int R1, int R2, bool NZ>
+__device__ __forceinline__ void demod_chain_iq_body(const DemodArgs &a, int nact, int K, cf *iq) {
     static_assert(R0 * R1 * R2 == N, "plan");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int h = N / 2, NH = (h + 63) / 64;
@@ -1020,8 +1067,10 @@ __global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) 
     for (int f = fs; f < f1; f++) {
         const bool emit = f >= f0;
         const int lane = opaque_lane(lane_);
+        Notches nz{};
+        if constexpr (NZ) nz = notch_load_frame(a, cp.slot);
         cf sv[NR];  // loads first, LDS after
-        idft_load_slice_at<N, HO>(a, cp, f, so, lane, sv);
+        idft_load_slice_at<N, HO, NZ>(a, cp, nz, f, so, lane, sv);
         const float pw = idft_slice_fixed<N, R0, R1, R2>(cp, sv, buf, Wn, lane);
         if (emit && lane == 0) a.pwr[srow * a.max_batch + f] = pw;
         const float sg = frame_sign(a, cp, f);
@@ -1052,6 +1101,14 @@ __global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) 
         if (emit && lane == 0) a.nan_flags[srow * a.max_batch + f] = any_nan ? 1 : 0;
         wave_lds_sync();  // buf is read out: the next frame's transform may overwrite it
     }
+}
+template <int N, int R0, int R1, int R2>
+__global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) void k_demod_chain_iq(DemodArgs a, int nact, int K, cf *iq) {
+    demod_chain_iq_body<N, R0, R1, R2, false>(a, nact, K, iq);
+}
+template <int N, int R0, int R1, int R2>
+__global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) void k_demod_chain_iq_nz(DemodArgs a, int nact, int K, cf *iq) {
+    demod_chain_iq_body<N, R0, R1, R2, true>(a, nact, K, iq);
 }
 
 // any other n (and n = 360 / 720 with PSDR_DEMOD_CHAIN=0): the overlap-add of an IQ client's rows of ypost, beside
@@ -1165,8 +1222,9 @@ __global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) 
         const bool last = (f == F - 1);
         {
             const int lane = opaque_lane(lane_);
+            const Notches nz = notch_load_frame(a, cp.slot);
             cf sv[NR];  // loads first, LDS after
-            idft_load_slice_at<N, HO>(a, cp, f, so, lane, sv);
+            idft_load_slice_at<N, HO>(a, cp, nz, f, so, lane, sv);
             if (pass == 0) {
 #pragma unroll
                 for (int u = 0; u < NR; u++) {
@@ -1239,11 +1297,11 @@ __global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) 
 
 // c_f[jout] of a SAM client by the direct sum over its kept bins d = t - m in [d0, d1), read from the spectrum:
 //   sum_d X[m_floor + d] W_n^{(d mod n) jout}
-__device__ __forceinline__ cf sam_carrier_dsum(const DemodArgs &a, const ClientParams &cp, const cf *S, int d0, int d1, int jout) {
+__device__ __forceinline__ cf sam_carrier_dsum(const DemodArgs &a, const ClientParams &cp, const Notches &nz, const cf *S, int d0, int d1, int jout) {
     const unsigned n = (unsigned)a.n;
     float ar = 0.f, ai = 0.f;
     for (int d = d0; d < d1; d++) {
-        const cf x = S[a.lay.pos(cp.m_floor + d)];
+        const cf x = notched(nz, cp, cp.m_floor + d - cp.l) ? make_float2(0.f, 0.f) : S[a.lay.pos(cp.m_floor + d)];
         const cf w = a.Wn[((unsigned)(d < 0 ? (int)n + d : d) * (unsigned)jout) % n];  // (< n^2: audio sizes stay far below 2^16)
         ar = fmaf(x.x, w.x, fmaf(-x.y, w.y, ar));
         ai = fmaf(x.x, w.y, fmaf(x.y, w.x, ai));
@@ -1270,6 +1328,7 @@ __global__ __launch_bounds__(256) void k_demod_ola_sam(DemodArgs a, int nact, Sa
     const SlotState st = slot_state(a, cp, h);
     const cf *ct_old = sa.car_tail + st.row_old * h;
     cf *ct_new = sa.car_tail + st.row_new * h;
+    const Notches nz = notch_load(a, cp.slot);
     // kept AND placed AND inside the slice: d = t - m with 0 <= t < r - l, -(h - 1) <= d < h, -cutoff <= d < cutoff
     const int m = cp.m_floor - cp.l, len = cp.r - cp.l;
     int d0 = -sa.cutoff, d1 = sa.cutoff;
@@ -1292,12 +1351,12 @@ __global__ __launch_bounds__(256) void k_demod_ola_sam(DemodArgs a, int nact, Sa
             const bool ok = j < h;
             cf c = make_float2(0.f, 0.f);
             if (ok) {
-                const cf cy = sam_carrier_dsum(a, cp, S, d0, d1, j);
+                const cf cy = sam_carrier_dsum(a, cp, nz, S, d0, d1, j);
                 cf ct;
                 if (f == 0) {
                     ct = ct_old[j];
                 } else {
-                    const cf cp1 = sam_carrier_dsum(a, cp, S - a.spec_stride, d0, d1, h + j);
+                    const cf cp1 = sam_carrier_dsum(a, cp, nz, S - a.spec_stride, d0, d1, h + j);
                     ct = make_float2(__fmul_rn(cp1.x, sgp), __fmul_rn(cp1.y, sgp));
                 }
                 c = make_float2(__fadd_rn(__fmul_rn(cy.x, sg), ct.x), __fadd_rn(__fmul_rn(cy.y, sg), ct.y));
@@ -1317,7 +1376,7 @@ __global__ __launch_bounds__(256) void k_demod_ola_sam(DemodArgs a, int nact, Sa
                         lag.x += t.x, lag.y += t.y;
                     }
                     if (last) {  // the carrier's tail moves with the baseband's
-                        const cf cn = sam_carrier_dsum(a, cp, S, d0, d1, h + j);
+                        const cf cn = sam_carrier_dsum(a, cp, nz, S, d0, d1, h + j);
                         ct_new[j] = make_float2(__fmul_rn(cn.x, sg), __fmul_rn(cn.y, sg));
                     }
                 });
@@ -1428,11 +1487,12 @@ __global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) 
     constexpr int HO = NR < 3 ? NR : (N <= 512 ? 3 : 6);
     unsigned so[HO];
     idft_slice_offsets<N, HO>(a, cw, lane_, so);
+    const Notches nz = notch_load(a, cp.slot);
     for (int f = fs; f < f1; f++) {
         const bool emit = f >= f0;
         const int lane = opaque_lane(lane_);
         cf sv[NR];  // loads first, LDS after
-        idft_load_slice_at<N, HO>(a, cw, f, so, lane, sv);
+        idft_load_slice_at<N, HO>(a, cw, nz, f, so, lane, sv);
         float pw = 0.f;
 #pragma unroll
         for (int u = 0; u < NR; u++) {
@@ -1507,6 +1567,9 @@ __global__ __launch_bounds__(256) void k_demod_ola_ft(DemodArgs a, int nact, FtA
     const int ci = item / ngrp;
     const ClientParams cp = a.clients[ci];
     const FtClient fc = fa.ft[ci];
+    ClientParams cw = cp;  // the whole window: pwr's
+    cw.l = fc.l, cw.r = fc.r;
+    const Notches nz = notch_load(a, cp.slot);
     const int f0 = (item - ci * ngrp) * FG;
     const size_t srow = (size_t)cp.slot;
     const cf *yp = a.ypost + (srow * a.max_batch) * n;  // this client's frames
@@ -1520,7 +1583,7 @@ __global__ __launch_bounds__(256) void k_demod_ola_ft(DemodArgs a, int nact, FtA
         const cf *S = a.spec + (size_t)f * a.spec_stride;
         float pw = 0.f;
         for (int t = tid; t < fc.r - fc.l; t += NT) {
-            const cf v = S[a.lay.pos(fc.l + t)];
+            const cf v = notched(nz, cw, t) ? make_float2(0.f, 0.f) : S[a.lay.pos(fc.l + t)];
             pw += fmaf(v.x, v.x, v.y * v.y);
         }
         pw = wave_sum(pw);
@@ -1627,8 +1690,9 @@ __global__ __launch_bounds__(256, N <= 512 ? PSDR_IDFT_WPE : PSDR_IDFT_WPE - 1) 
         const int hi = pass == 0 ? sb.sa.cutoff : (upper ? N : 1);
         {
             const int lane = opaque_lane(lane_);
+            const Notches nz = notch_load_frame(a, cp.slot);
             cf sv[NR];  // loads first, LDS after
-            idft_load_slice_at<N, HO>(a, cp, f, so, lane, sv);
+            idft_load_slice_at<N, HO>(a, cp, nz, f, so, lane, sv);
             float pw = 0.f;
 #pragma unroll
             for (int u = 0; u < NR; u++) {
@@ -1725,6 +1789,7 @@ __global__ __launch_bounds__(256) void k_demod_ola_sbsam(DemodArgs a, int nact, 
     sm.bt_old = sb.tail + st.row_old * h, sm.bt_new = sb.tail + st.row_new * h;
     const cf *ct_old = sb.sa.car_tail + st.row_old * h;
     cf *ct_new = sb.sa.car_tail + st.row_new * h;
+    const Notches nz = notch_load(a, cp.slot);
     // kept AND placed AND inside the slice (k_demod_ola_sam), of the whole window
     const int m = cw.m_floor - cw.l, len = cw.r - cw.l;
     int d0 = -sb.sa.cutoff, d1 = sb.sa.cutoff;
@@ -1738,7 +1803,7 @@ __global__ __launch_bounds__(256) void k_demod_ola_sbsam(DemodArgs a, int nact, 
         const cf *S = a.spec + (size_t)f * a.spec_stride;
         float pw = 0.f;
         for (int t = tid; t < len; t += NT) {
-            const cf v = S[a.lay.pos(cw.l + t)];
+            const cf v = notched(nz, cw, t) ? make_float2(0.f, 0.f) : S[a.lay.pos(cw.l + t)];
             pw += fmaf(v.x, v.x, v.y * v.y);
         }
         pw = wave_sum(pw);
@@ -1754,12 +1819,12 @@ __global__ __launch_bounds__(256) void k_demod_ola_sbsam(DemodArgs a, int nact, 
             const bool ok = j < h;
             cf c = make_float2(0.f, 0.f);
             if (ok) {
-                const cf cy = sam_carrier_dsum(a, cw, S, d0, d1, j);
+                const cf cy = sam_carrier_dsum(a, cw, nz, S, d0, d1, j);
                 cf ct;
                 if (f == 0) {
                     ct = ct_old[j];
                 } else {
-                    const cf cp1 = sam_carrier_dsum(a, cw, S - a.spec_stride, d0, d1, h + j);
+                    const cf cp1 = sam_carrier_dsum(a, cw, nz, S - a.spec_stride, d0, d1, h + j);
                     ct = make_float2(__fmul_rn(cp1.x, sgp), __fmul_rn(cp1.y, sgp));
                 }
                 c = make_float2(__fadd_rn(__fmul_rn(cy.x, sg), ct.x), __fadd_rn(__fmul_rn(cy.y, sg), ct.y));
@@ -1779,7 +1844,7 @@ __global__ __launch_bounds__(256) void k_demod_ola_sbsam(DemodArgs a, int nact, 
                         lag.x += t.x, lag.y += t.y;
                     }
                     if (last) {  // the carrier's tail moves with the baseband's
-                        const cf cn = sam_carrier_dsum(a, cw, S, d0, d1, h + j);
+                        const cf cn = sam_carrier_dsum(a, cw, nz, S, d0, d1, h + j);
                         ct_new[j] = make_float2(__fmul_rn(cn.x, sg), __fmul_rn(cn.y, sg));
                     }
                 });
@@ -1796,6 +1861,95 @@ __global__ __launch_bounds__(256) void k_demod_ola_sbsam(DemodArgs a, int nact, 
             a.nan_flags[srow * a.max_batch + f] = any_nan ? 1 : 0;
             sb.sa.car_rec[srow * a.max_batch + f] = make_float2(lvl / (float)h, sb.sa.hz_per_rad * atan2f(lag.y, lag.x));
         }
+    }
+}
+
+// ---- auto-notch: the detector behind a batch's last demodulation kernel (include/psdr.h: psdr_client_set_auto_notch) ------
+// One wave (one work-group of 64 threads) per auto-notch client of the batch.  It sums the power of the client's UN-notched
+// window bins over `period` frames - half a second - in acc[slot][t], then evaluates: the mean over the window, which of the
+// slot's two automatic entries stay (some bin above 8 x mean), which local maxima above 16 x mean become new entries
+// [l + t - 1, l + t + 2).  It writes the table the demodulation kernels of THIS batch have just read (DemodArgs::notch_auto,
+// same stream): a decision made during batch b is in force from batch b + 1.  Lane i owns the bins t = i + 64 k in every loop;
+// a bin's sum grows in frame order, the window's sum per lane in ascending t and across lanes through wave_sum's xor tree:
+// the bits do not depend on the batch split.  Non-finite sums compare false everywhere: they set nothing and keep nothing.
+struct NotchArgs {
+    const ClientParams *det;  // [nact] the batch's auto-notch clients: l, r, m_floor, the client's OWN mode, slot
+    float *acc;               // [slots][n]
+    int *cnt;                 // [slots] frames summed since the last evaluation
+    int4 *tab;                // [slots] DemodArgs::notch_auto
+    int period;               // max(1, audio_rate / audio_fft_size) frames
+};
+__global__ __launch_bounds__(64) void k_notch_detect(DemodArgs a, int nact, NotchArgs na) {
+    const int lane = threadIdx.x, ci = blockIdx.x;
+    if (ci >= nact) return;
+    const ClientParams cp = wave_uniform(na.det[ci]);
+    const int len = cp.r - cp.l, m = cp.m_floor - cp.l;
+    if (len <= 0) return;
+    float *acc = na.acc + (size_t)cp.slot * a.n;  // (len <= n: psdr_client_set_audio_range)
+    int cnt = na.cnt[cp.slot];
+    const int4 e0 = na.tab[cp.slot];
+    int ef[2] = {e0.x, e0.z}, ee[2] = {e0.y, e0.w};
+    const bool carrier = cp.mode == 2 || cp.mode == 3 || cp.mode == 5;  // AM, FM, SAM: the wanted carrier sits at m
+    int f = 0;
+    while (f < a.nframes) {
+        const int fe = min(a.nframes, f + na.period - cnt);
+        for (int t = lane; t < len; t += 64) {
+            const cf *S = a.spec + a.lay.pos(cp.l + t);
+            float s = acc[t];
+            for (int g = f; g < fe; g++) {
+                const cf v = S[(size_t)g * a.spec_stride];
+                s += fmaf(v.x, v.x, v.y * v.y);
+            }
+            acc[t] = s;
+        }
+        cnt += fe - f;
+        f = fe;
+        if (cnt < na.period) break;
+        // evaluate (every lane reads its neighbours' sums: one wave, but through memory)
+        __threadfence_block();
+        __syncthreads();
+        float part = 0.f;
+        for (int t = lane; t < len; t += 64) part += acc[t];
+        const float mean = wave_sum(part) / (float)len;
+        const float keep_thr = 8.f * mean, new_thr = 16.f * mean;
+        for (int k = 0; k < 2; k++) {
+            if (ee[k] <= ef[k]) continue;
+            bool keep = false;
+            for (int b = ef[k]; b < ee[k]; b++) {
+                const int t = b - cp.l;
+                if (t >= 0 && t < len && acc[t] > keep_thr) keep = true;
+            }
+            if (!keep) ef[k] = ee[k] = 0;
+        }
+        for (int k = 0; k < 2; k++) {
+            if (ee[k] > ef[k]) continue;
+            int best = -1;
+            float bv = 0.f;
+            for (int t = lane; t < len; t += 64) {
+                const float x = acc[t], lf = t > 0 ? acc[t - 1] : 0.f, rt = t + 1 < len ? acc[t + 1] : 0.f;
+                const int d = t - m;
+                const bool prot = carrier && d >= -3 && d <= 3;
+                bool ok = !prot && x >= lf && x > rt && x > new_thr;
+                const int nf = cp.l + t - 1, ne = cp.l + t + 2;
+                for (int q = 0; q < 2; q++)
+                    if (ee[q] > ef[q] && nf < ee[q] && ef[q] < ne) ok = false;  // overlaps a set entry
+                if (ok && (best < 0 || x > bv)) best = t, bv = x;  // (ascending t: a tie stays with the lower one)
+            }
+#pragma unroll
+            for (int dd = 32; dd > 0; dd >>= 1) {
+                const float ov = __shfl_xor(bv, dd, 64);
+                const int ot = __shfl_xor(best, dd, 64);
+                if (ot >= 0 && (best < 0 || ov > bv || (ov == bv && ot < best))) best = ot, bv = ov;
+            }
+            if (best >= 0) ef[k] = cp.l + best - 1, ee[k] = cp.l + best + 2;
+        }
+        __syncthreads();  // every lane has read what it needs of acc
+        for (int t = lane; t < len; t += 64) acc[t] = 0.f;
+        cnt = 0;
+    }
+    if (lane == 0) {
+        na.cnt[cp.slot] = cnt;
+        na.tab[cp.slot] = make_int4(ef[0], ee[0], ef[1], ee[1]);
     }
 }
 

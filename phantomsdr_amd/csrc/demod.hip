@@ -35,6 +35,31 @@ static int sb_tail_alloc(psdr_ctx *c) {
     c->d_sb_tail = std::move(tail);
     return PSDR_OK;
 }
+// the context's first auto-notch client: the detector's sums, counters and table, all three or none (a context that never
+// sees one allocates nothing); under mtx
+static int notch_alloc(psdr_ctx *c) {
+    if (c->d_notch_tab) return PSDR_OK;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t S = c->aslots.size(), n = (size_t)c->n;
+    DevBuf<float> acc;
+    DevBuf<int> cnt;
+    DevBuf<int4> tab;
+    if (acc.alloc(S * n, true) || cnt.alloc(S, true) || tab.alloc(S, true)) {
+        const std::string msg = psdr_last_error();
+        return fail(PSDR_ERR_NOMEM, "auto-notch state (%zu bytes): %s", S * (n * sizeof(float) + sizeof(int) + sizeof(int4)), msg.c_str());
+    }
+    c->d_notch_acc = std::move(acc);
+    c->d_notch_cnt = std::move(cnt);
+    c->d_notch_tab = std::move(tab);
+    return PSDR_OK;
+}
+// the detector's state of one slot back to zero: sums, counter, both automatic entries (stream-ordered on `side`)
+static int notch_zero(psdr_ctx *c, size_t slot) {
+    HIPCHK(hipMemsetAsync(c->d_notch_acc + slot * (size_t)c->n, 0, (size_t)c->n * sizeof(float), c->side));
+    HIPCHK(hipMemsetAsync(c->d_notch_cnt + slot, 0, sizeof(int), c->side));
+    HIPCHK(hipMemsetAsync(c->d_notch_tab + slot, 0, sizeof(int4), c->side));
+    return PSDR_OK;
+}
 static int check_slot(psdr_ctx *c, int id) {
     if (id < 0 || id >= (int)c->aslots.size() || !c->aslots[id].active)
         return fail(PSDR_ERR_INVALID, "no audio client with id %d", id);
@@ -49,10 +74,13 @@ extern "C" int psdr_client_add(psdr_ctx *c, int *id_out) {
         if (!c->aslots[i].active) {
             AudioSlot &s = c->aslots[i];
             if (c->opt_fine_tune) PSDRCHK(ft_tail_alloc(c));  // (a new client is a USB client: a tuned one under PSDR_OPT_FINE_TUNE)
+            if (c->opt_auto_notch) PSDRCHK(notch_alloc(c));
+            if (c->d_notch_tab) PSDRCHK(notch_zero(c, i));  // (the previous occupant's automatic entries do not outlive it)
             s = AudioSlot();
             s.active = true;
             s.fine = c->opt_fine_tune;
             s.sam_sb = c->opt_sam_sideband;  // (a new client is a USB client: the value waits for PSDR_SAM)
+            s.auto_notch = c->opt_auto_notch;
             s.born = ++c->slot_births;
             // a fresh AudioClient starts from zeroed buffers (src/signal.h:42-51)
             const size_t S = c->aslots.size(), h = (size_t)c->n / 2;
@@ -175,6 +203,61 @@ extern "C" int psdr_client_set_sam_sideband(psdr_ctx *c, int id, int sideband) {
     s.sam_sb = sideband;
     return PSDR_OK;
 }
+// A manual notch: [first, end) = [floor(centre - width/2 + 0.5), floor(centre + width/2 + 0.5)), at least one bin; host code
+// alone (psdr_debug_notch_interval: tests/test_notch_host.py drives it without a device).  The ends are kept inside +-2^30: no spectrum reaches there.
+static void notch_interval(double centre, double width, int *first, int *end) {
+    const double lim = 1073741824.0;
+    const double a = std::min(std::max(std::floor(centre - width / 2 + 0.5), -lim), lim);
+    const double b = std::min(std::max(std::floor(centre + width / 2 + 0.5), -lim), lim);
+    *first = (int)a;
+    *end = b <= a ? (int)a + 1 : (int)b;
+}
+// (debug entries, beside psdr_debug_trace: exported for the tests, not part of include/psdr.h)
+extern "C" int psdr_debug_notch_interval(double centre_bin, double width_bins, int *first, int *end) {
+    if (!first || !end) return fail(PSDR_ERR_INVALID, "null argument");
+    if (!std::isfinite(centre_bin) || !std::isfinite(width_bins)) return fail(PSDR_ERR_INVALID, "non-finite notch");
+    if (width_bins <= 0) {
+        *first = *end = 0;
+        return PSDR_OK;
+    }
+    notch_interval(centre_bin, width_bins, first, end);
+    return PSDR_OK;
+}
+extern "C" int psdr_client_set_notch(psdr_ctx *c, int id, int index, double centre_bin, double width_bins) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mtx);
+    int rc = check_slot(c, id);
+    if (rc) return rc;
+    if (index < 0 || index >= PSDR_NOTCH_MANUAL) return fail(PSDR_ERR_INVALID, "notch index %d outside 0..%d", index, PSDR_NOTCH_MANUAL - 1);
+    if (!std::isfinite(centre_bin) || !std::isfinite(width_bins)) return fail(PSDR_ERR_INVALID, "non-finite notch");
+    if (width_bins > (double)c->n) return fail(PSDR_ERR_INVALID, "notch wider than audio_fft_size %d", c->n);
+    AudioSlot &s = c->aslots[id];
+    if (width_bins <= 0)
+        s.notch[2 * index] = s.notch[2 * index + 1] = 0;
+    else
+        notch_interval(centre_bin, width_bins, &s.notch[2 * index], &s.notch[2 * index + 1]);
+    return PSDR_OK;
+}
+extern "C" int psdr_client_set_auto_notch(psdr_ctx *c, int id, int on) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mtx);
+    int rc = check_slot(c, id);
+    if (rc) return rc;
+    if (on) PSDRCHK(notch_alloc(c));
+    AudioSlot &s = c->aslots[id];
+    if (on && !s.auto_notch) s.auto_fresh = true;
+    s.auto_notch = on ? 1 : 0;
+    return PSDR_OK;
+}
+// out[0..2]: the detector's table, sums and counters (null until the context's first auto-notch client); out[3..4]:
+// DemodArgs::notch_man / notch_auto of the last demodulation batch
+extern "C" int psdr_debug_notch_ptrs(psdr_ctx *c, const void *out[5]) {
+    if (!c || !out) return fail(PSDR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mtx);
+    out[0] = c->d_notch_tab.get(), out[1] = c->d_notch_acc.get(), out[2] = c->d_notch_cnt.get();
+    out[3] = c->dbg_notch_man, out[4] = c->dbg_notch_auto;
+    return PSDR_OK;
+}
 
 // One client of a batch's list: the window and the mode it is demodulated with; its double-buffered state flips.  To the
 // post chain a PSDR_IQ client is a paused one (no audio of its own this batch): a pending AGC reset stays with the slot.
@@ -203,6 +286,7 @@ struct ChainFamily {
 };
 static const ChainFamily<> CHAIN_FIXED{k_demod_chain_fixed<360, 8, 9, 5>, k_demod_chain_fixed<720, 8, 9, 10>};
 static const ChainFamily<cf *> CHAIN_IQ{k_demod_chain_iq<360, 8, 9, 5>, k_demod_chain_iq<720, 8, 9, 10>};
+static const ChainFamily<cf *> CHAIN_IQ_NZ{k_demod_chain_iq_nz<360, 8, 9, 5>, k_demod_chain_iq_nz<720, 8, 9, 10>};  // IQ lists with a notched client
 static const ChainFamily<SamArgs> CHAIN_SAM{k_demod_chain_sam<360, 8, 9, 5>, k_demod_chain_sam<720, 8, 9, 10>};
 static const ChainFamily<FtArgs> CHAIN_FT_SSB{k_demod_chain_ft<360, 8, 9, 5, true>, k_demod_chain_ft<720, 8, 9, 10, true>};
 static const ChainFamily<FtArgs> CHAIN_FT_IQ{k_demod_chain_ft<360, 8, 9, 5, false>, k_demod_chain_ft<720, 8, 9, 10, false>};
@@ -262,6 +346,13 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     const size_t S = c->aslots.size();
     int *h_slot_ci = (int *)(h_clients + S), *d_slot_ci = (int *)(d_clients + S);
     unsigned char *h_ft = (unsigned char *)h_clients + ft_ring_off(S), *d_ft = (unsigned char *)d_clients + ft_ring_off(S);
+    // notches: the manual ones of the snapshot by slot, and the detector's list of the batch's auto-notch clients
+    int4 *h_notch = (int4 *)((unsigned char *)h_clients + notch_ring_off(S)), *d_notch = (int4 *)((unsigned char *)d_clients + notch_ring_off(S));
+    ClientParams *h_det = (ClientParams *)(h_notch + S), *d_det = (ClientParams *)(d_notch + S);
+    bool any_manual = false, iq_notched = false;
+    int ndet = 0;
+    std::vector<size_t> notch_zeros;  // slots whose detector state starts this batch from zero
+    int4 *notch_tab = nullptr;
     cf *iq_rows[2] = {nullptr, nullptr}, *car_rows[2] = {nullptr, nullptr};
     {
         std::lock_guard<std::mutex> lk(c->mtx);
@@ -277,6 +368,7 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
             }
         }
         iq_rows[0] = c->iq_pool[0], iq_rows[1] = c->iq_pool[1];  // (allocated under this lock, once)
+        notch_tab = c->d_notch_tab;
         car_rows[0] = c->car_pool[0], car_rows[1] = c->car_pool[1];
         c->demod_seq++;
         for (size_t i = 0; i < c->aslots.size(); i++) {
@@ -296,6 +388,28 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
             if (sbc && (s.last_seq == 0 || s.b_mode != PSDR_SAM || s.b_sam_sb != s.sam_sb))
                 sb_zero.push_back(((size_t)s.state_cur * S + i) * ((size_t)c->n / 2));
             if (sbc) nsb++;  // listed apart, below
+            // notches: the manual ones as they are now; the detector's state from zero when auto-notch was switched (on: a fresh
+            // start; off: its entries go), or the window, floor(audio_mid) or the mode are not the previous batch's
+            const bool nm = s.notch[1] > s.notch[0] || s.notch[3] > s.notch[2];
+            if (nm) {
+                if (!any_manual)
+                    for (size_t k = 0; k < S; k++) h_notch[k] = make_int4(0, 0, 0, 0);
+                any_manual = true;
+                h_notch[i] = make_int4(s.notch[0], s.notch[1], s.notch[2], s.notch[3]);
+            }
+            if ((nm || s.auto_notch) && s.mode == PSDR_IQ && !tuned) iq_notched = true;
+            if (notch_tab) {
+                const bool moved = s.last_seq == 0 || s.l != s.b_l || s.r != s.b_r || std::floor(s.mid) != std::floor(s.b_mid) || s.mode != s.b_mode;
+                if ((s.auto_notch != 0) != s.b_auto || (s.auto_notch && (moved || s.auto_fresh))) notch_zeros.push_back(i);
+                s.auto_fresh = false;
+                if (s.auto_notch) {
+                    ClientParams &q = h_det[ndet++];
+                    q = ClientParams{};
+                    q.l = s.l, q.r = s.r, q.m_floor = (int)std::floor(s.mid), q.mode = s.mode, q.slot = (int)i;
+                }
+            }
+            for (int k = 0; k < 4; k++) s.b_notch[k] = s.notch[k];
+            s.b_auto = s.auto_notch != 0;
             s.last_seq = c->demod_seq;
             s.b_l = s.l, s.b_r = s.r, s.b_mid = s.mid, s.b_mode = s.mode, s.b_tuned = tuned, s.b_sam_sb = s.sam_sb;
             if (tuned)
@@ -438,7 +552,13 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
         HIPCHK(hipMemcpyAsync(d_ft, h_ft, (size_t)(ntssb + ntiq) * (sizeof(ClientParams) + sizeof(FtClient)), hipMemcpyHostToDevice, c->side));
     const size_t sb_off = (size_t)(ntssb + ntiq) * (sizeof(ClientParams) + sizeof(FtClient));  // the sideband SAM list, behind the tuned one
     if (nsb > 0) HIPCHK(hipMemcpyAsync(d_ft + sb_off, h_ft + sb_off, (size_t)nsb * (sizeof(ClientParams) + sizeof(SbClient)), hipMemcpyHostToDevice, c->side));
+    if (any_manual) HIPCHK(hipMemcpyAsync(d_notch, h_notch, S * sizeof(int4), hipMemcpyHostToDevice, c->side));
+    if (ndet > 0) HIPCHK(hipMemcpyAsync(d_det, h_det, (size_t)ndet * sizeof(ClientParams), hipMemcpyHostToDevice, c->side));
+    for (size_t slot : notch_zeros) PSDRCHK(notch_zero(c, slot));
     DemodArgs a{};
+    a.notch_man = any_manual ? d_notch : nullptr;
+    a.notch_auto = notch_tab;
+    c->dbg_notch_man = a.notch_man, c->dbg_notch_auto = a.notch_auto;
     a.spec = spec;
     a.spec_stride = spec_stride;
     a.is_real = c->is_real ? 1 : 0;
@@ -571,7 +691,7 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
         // the PSDR_IQ clients: launches of their own behind the others', on the same stream (demod.h)
         DemodArgs ai = a;
         ai.clients = d_clients + iq_off;
-        PSDRCHK(serve(CHAIN_IQ, k_demod_ola_iq, ai, niq, 4u, 0, c->d_iq));
+        PSDRCHK(serve(iq_notched ? CHAIN_IQ_NZ : CHAIN_IQ, k_demod_ola_iq, ai, niq, 4u, 0, c->d_iq));
     }
     if (ntssb > 0 && !c->d_ft_tail) return fail(PSDR_ERR_STATE, "tuned USB / LSB clients without their tails");
     if (ntssb + ntiq > 0) {
@@ -603,6 +723,17 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
         sba.sb = (const SbClient *)(ab.clients + nsb);
         sba.tail = c->d_sb_tail;
         PSDRCHK(serve(CHAIN_SBSAM, k_demod_ola_sbsam, ab, nsb, 2u, (size_t)(c->n / 2) * sizeof(cf), sba));
+    }
+    if (ndet > 0) {
+        // the detector, behind the batch's last demodulation kernel: it writes the table those have just read (demod.h)
+        NotchArgs na{};
+        na.det = d_det;
+        na.acc = c->d_notch_acc;
+        na.cnt = c->d_notch_cnt;
+        na.tab = notch_tab;
+        na.period = std::max(1, c->cfg.audio_rate / c->n);
+        hipLaunchKernelGGL(k_notch_detect, dim3((unsigned)ndet), dim3(64), 0, c->side, a, ndet, na);
+        HIPCHK(hipGetLastError());
     }
     hipStream_t last_user = c->side;
     if (c->post_on && nact > 0) {
@@ -1053,6 +1184,30 @@ extern "C" int psdr_read_audio(psdr_ctx *c, int id, int nframes, float *audio, f
         HIPCHK(hipMemcpyAsync(nan_flags, c->d_nan + (size_t)id * mb, F * sizeof(int),
                               hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    return PSDR_OK;
+}
+extern "C" int psdr_read_notches(psdr_ctx *c, int id, int first[4], int end[4]) {
+    if (!c || !first || !end) return fail(PSDR_ERR_INVALID, "null argument");
+    int man[4];
+    bool have_tab = false;
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);
+        int rc = check_slot(c, id);
+        if (rc) return rc;
+        if (c->last_demod_frames == 0 || c->demod_seq == 0) return fail(PSDR_ERR_STATE, "no demodulated batch to read");
+        if (c->aslots[id].last_seq != c->demod_seq) return fail(PSDR_ERR_NO_DATA, "client %d was not part of the last demodulation batch", id);
+        for (int k = 0; k < 4; k++) man[k] = c->aslots[id].b_notch[k];
+        have_tab = (bool)c->d_notch_tab;
+    }
+    int4 t = make_int4(0, 0, 0, 0);
+    if (have_tab) {  // the table as the batch's detector left it: in force from the next batch on
+        HIPCHK(hipSetDevice(c->device));
+        int rc = drain(c);
+        if (rc) return rc;
+        HIPCHK(hipMemcpy(&t, c->d_notch_tab + id, sizeof(int4), hipMemcpyDeviceToHost));
+    }
+    first[0] = man[0], end[0] = man[1], first[1] = man[2], end[1] = man[3];
+    first[2] = t.x, end[2] = t.y, first[3] = t.z, end[3] = t.w;
     return PSDR_OK;
 }
 extern "C" int psdr_audio_device_ptr(psdr_ctx *c, int id, const float **d_audio, const float **d_pwr) {

@@ -299,6 +299,7 @@ extern "C" int psdr_group_client_add(psdr_group *g, int l, double audio_mid, int
     int rc = psdr_client_add(g->ctx[rank], &id);
     if (rc) return rc;
     rc = psdr_client_set_fine_tune(g->ctx[rank], id, 0);  // a group's clients are untuned, whatever PSDR_OPT_FINE_TUNE of the rank's context says
+    if (!rc) rc = psdr_client_set_auto_notch(g->ctx[rank], id, 0);  // ... and without notches, whatever PSDR_OPT_AUTO_NOTCH says
     if (!rc) rc = psdr_client_set_audio_demodulation(g->ctx[rank], id, mode);
     if (!rc) rc = psdr_client_set_audio_range(g->ctx[rank], id, l, audio_mid, r);
     if (rc) {
@@ -367,6 +368,7 @@ extern "C" int psdr_group_client_set_audio_range(psdr_group *g, int gid, int l, 
     rc = psdr_client_add(dst, &nid);
     if (rc) return rc;
     rc = psdr_client_set_fine_tune(dst, nid, 0);  // the fine-tune flag travels as 0
+    if (!rc) rc = psdr_client_set_auto_notch(dst, nid, 0);  // notches do not travel
     if (!rc) rc = psdr_client_set_audio_demodulation(dst, nid, mode);
     if (!rc) rc = psdr_client_set_audio_range(dst, nid, l, audio_mid, r);
     if (!rc && paused) rc = psdr_client_set_paused(dst, nid, 1);

@@ -205,6 +205,12 @@ extern "C" int psdr_set_option(psdr_ctx *c, int option, int value) {
         c->opt_sam_sideband = value;
         return PSDR_OK;
     }
+    case PSDR_OPT_AUTO_NOTCH: {
+        if (value != 0 && value != 1) return fail(PSDR_ERR_INVALID, "PSDR_OPT_AUTO_NOTCH: 0 or 1, not %d", value);
+        std::lock_guard<std::mutex> lk(c->mtx);
+        c->opt_auto_notch = value;
+        return PSDR_OK;
+    }
     default:
         return fail(PSDR_ERR_INVALID, "unknown option %d", option);
     }
