@@ -18,6 +18,7 @@
 
 #include "../../include/psdr.h"
 #include "butterfly.h"
+#include "demodplan.h"
 #include "owned.h"
 #include "postplan.h"
 #include "quantize.h"
@@ -61,36 +62,6 @@ extern const char *kKernelNames[K_COUNT];
 struct PendingEvent {
     Event a, b;
     int kid;
-};
-struct AudioSlot {
-    bool active = false;
-    int l = 0, r = 0;
-    double mid = 0;
-    int mode = PSDR_USB;
-    int state_cur = 0;
-    int agc_reset = 2;  // post chain: 1 = AGC::reset pending (set_audio_demodulation), 2 = fresh client
-    bool paused = false;  // psdr_client_set_paused: sits out the demodulation batches, all state frozen
-    uint64_t last_seq = 0;  // the demodulation batch (ctx->demod_seq) that last included this slot; 0: none yet
-    int b_l = 0, b_r = 0;   // the window that batch was demodulated with (psdr_fetch_begin copies it into its FetchSet)
-    double b_mid = 0;
-    int b_mode = PSDR_USB;  // ... and the mode: a batch demodulated as PSDR_IQ left complex rows (iq_pool) and no audio / PCM; one
-                            // demodulated as PSDR_SAM left carrier records and a carrier tail the next SAM batch continues
-    uint64_t born = 0;      // psdr_client_add's serial number: a fetched set answers only for the occupant it was filled with
-    // psdr_client_set_fine_tune: with the flag on, a USB / LSB / IQ client is a TUNED client (demod.h: k_demod_chain_ft)
-    int fine = 0;
-    uint32_t ft_phi = 0;    // the rotator's phase at the next tuned batch's first sample (units of 2^-32 turn)
-    bool b_tuned = false;   // the last batch took the tuned path (with b_mode: whether the tuned USB / LSB tail continues)
-    // psdr_client_set_sam_sideband: a PSDR_SAM client with another value than PSDR_SAM_BOTH is a SIDEBAND SAM client
-    // (demod.h: k_demod_chain_sbsam); in every other mode the value is kept and has no effect
-    int sam_sb = PSDR_SAM_BOTH;
-    int b_sam_sb = PSDR_SAM_BOTH;  // ... of the last batch (with b_mode: whether the sideband baseband tail continues)
-    // psdr_client_set_notch: the two manual notches, [first, end) in the coordinates of l / r (0, 0: empty); b_notch: the
-    // last batch's snapshot (psdr_read_notches)
-    int notch[4] = {0, 0, 0, 0}, b_notch[4] = {0, 0, 0, 0};  // first0, end0, first1, end1
-    // psdr_client_set_auto_notch; b_auto: of the last batch (with b_l / b_r / b_mid / b_mode: whether the detector's state continues)
-    int auto_notch = 0;
-    bool b_auto = false;
-    bool auto_fresh = false;  // switched on since the slot's last batch (a paused client may be switched off and on again)
 };
 struct WfSlot {
     bool active = false;
@@ -136,14 +107,8 @@ struct ParamRing {
     }
 };
 
-// the client parameter ring's slot: [ClientParams x S][int x S], then from ft_ring_off(S) on the tuned clients' list,
-// [ClientParams x nt][FtClient x nt], and behind it the sideband SAM clients' list, [ClientParams x nsb][SbClient x nsb],
-// with nt + nsb <= S (no client is on both lists); from notch_ring_off(S) on the manual notches of the batch's snapshot,
-// [int4 x S] by slot (DemodArgs::notch_man), and k_notch_detect's list of the batch's auto-notch clients, [ClientParams x S]
-static_assert(sizeof(SbClient) == sizeof(FtClient), "the two lists share the ring's space behind ft_ring_off");
-inline size_t ft_ring_off(size_t S) { return (S * (sizeof(ClientParams) + sizeof(int)) + 15) & ~(size_t)15; }
-inline size_t notch_ring_off(size_t S) { return (ft_ring_off(S) + S * (sizeof(ClientParams) + sizeof(FtClient)) + 15) & ~(size_t)15; }
-inline size_t client_ring_bytes(size_t S) { return notch_ring_off(S) + S * (sizeof(int4) + sizeof(ClientParams)); }
+// the client parameter ring's slot: demodplan.h (host-only: it spells sizeof(int4) as a number)
+static_assert(sizeof(int4) == NOTCH_ENTRY, "a slot's manual notches are one int4 (DemodArgs::notch_man)");
 
 inline int ilog2(size_t v) {
     int l = 0;

@@ -4,8 +4,6 @@
 #include "ctx.h"
 #include "demod.h"
 
-// a tuned client: the fine-tune flag in a mode the rotator means something in (AM, FM, SAM: the flag has no effect)
-static bool tuned_mode(int fine, int mode) { return fine && (mode == PSDR_USB || mode == PSDR_LSB || mode == PSDR_IQ); }
 // the context's first tuned USB / LSB client: its family's tails (a context that never sees one allocates nothing); under mtx
 static int ft_tail_alloc(psdr_ctx *c) {
     if (c->d_ft_tail) return PSDR_OK;
@@ -19,8 +17,6 @@ static int ft_tail_alloc(psdr_ctx *c) {
     c->d_ft_tail = std::move(tail);
     return PSDR_OK;
 }
-// a sideband SAM client: PSDR_SAM with another sideband than both (in every other mode the value has no effect)
-static bool sb_sam(int mode, int sideband) { return mode == PSDR_SAM && sideband != PSDR_SAM_BOTH; }
 // the context's first sideband SAM client: the tails of its clipped baseband (a context that never sees one allocates
 // nothing); under mtx
 static int sb_tail_alloc(psdr_ctx *c) {
@@ -188,7 +184,7 @@ extern "C" int psdr_client_set_fine_tune(psdr_ctx *c, int id, int on) {
     int rc = check_slot(c, id);
     if (rc) return rc;
     AudioSlot &s = c->aslots[id];
-    if (on && (s.mode == PSDR_USB || s.mode == PSDR_LSB)) PSDRCHK(ft_tail_alloc(c));
+    if (tuned_mode(on, s.mode) && s.mode != PSDR_IQ) PSDRCHK(ft_tail_alloc(c));
     s.fine = on ? 1 : 0;
     return PSDR_OK;
 }
@@ -259,25 +255,6 @@ extern "C" int psdr_debug_notch_ptrs(psdr_ctx *c, const void *out[5]) {
     return PSDR_OK;
 }
 
-// One client of a batch's list: the window and the mode it is demodulated with; its double-buffered state flips.  To the
-// post chain a PSDR_IQ client is a paused one (no audio of its own this batch): a pending AGC reset stays with the slot.
-static void fill_params(ClientParams &p, AudioSlot &s, int slot, bool post_on) {
-    const bool audio = s.mode != PSDR_IQ;
-    p = ClientParams{};
-    p.l = s.l;
-    p.r = s.r;
-    p.m_floor = (int)std::floor(s.mid);
-    p.mode = s.mode;
-    p.slot = slot;
-    p.state_cur = s.state_cur;
-    s.state_cur ^= 1;
-    p.paused = audio ? 0 : 1;
-    if (audio && post_on) {
-        p.agc_reset = s.agc_reset;
-        s.agc_reset = 0;
-    }
-}
-
 // The one-kernel path (demod.h): a family of chain kernels is its two compile-time plans, 360 = 8*9*5 and 720 = 8*9*10
 template <class... X>
 struct ChainFamily {
@@ -323,242 +300,13 @@ static hipError_t launch_ola(psdr_ctx *c, void (*k)(DemodArgs, int, X...), Demod
     return hipLaunchKernel((const void *)k, dim3((items + 3) / 4), dim3(256), args, 0, c->side);
 }
 
+// What every list's launches of a batch share: the spectrum and its layout, the transform's plan, the result rows and the carried
+// state (each list sets `clients`, demod_impl the notch tables).
 // band != nullptr: `spec` is a window of bins [band[0], band[0] + band[1]) per frame - linear, or (band_tiled) one
 // band region of a banded spectrum (SpecLayout mode 4)
-static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nframes, uint64_t first_frame_num,
-                      const uint32_t *band = nullptr, bool band_tiled = false) {
-    if (c->n <= 0) return fail(PSDR_ERR_STATE, "context created with audio_fft_size 0");
-    HIPCHK(hipSetDevice(c->device));
-    int nact = 0, npaused = 0, niq = 0, iq_off = 0;
-    int nold = 0, nsam = 0;              // the active list: [0, nold) USB / LSB / AM / FM, [nold, nact) PSDR_SAM
-    std::vector<size_t> sam_zero;        // carrier tails (element offsets into d_car_tail) that start this batch from zero
-    // tuned clients (demod.h: k_demod_chain_ft): listed apart, [0, ntssb) USB / LSB then [ntssb, ntssb + ntiq) IQ
-    int ntssb = 0, ntiq = 0;
-    std::vector<size_t> ft_zero;         // tuned USB / LSB tails (element offsets into d_ft_tail) that start from zero
-    // sideband SAM clients (demod.h: k_demod_chain_sbsam): listed apart, behind the tuned clients' list
-    int nsb = 0;
-    std::vector<size_t> sb_zero;         // sideband SAM tails (element offsets into d_sb_tail) that start from zero
-    const int ring = c->client_ring.acquire();
-    if (ring < 0) return fail(PSDR_ERR_HIP, "client parameter ring: event wait failed");
-    ClientParams *h_clients = (ClientParams *)c->client_ring.host(ring);
-    ClientParams *d_clients = (ClientParams *)c->client_ring.dev(ring);
-    // behind the list, for the post chain: the list index of every slot's client (its kernels walk the SLOTS, lane = slot & 63)
-    const size_t S = c->aslots.size();
-    int *h_slot_ci = (int *)(h_clients + S), *d_slot_ci = (int *)(d_clients + S);
-    unsigned char *h_ft = (unsigned char *)h_clients + ft_ring_off(S), *d_ft = (unsigned char *)d_clients + ft_ring_off(S);
-    // notches: the manual ones of the snapshot by slot, and the detector's list of the batch's auto-notch clients
-    int4 *h_notch = (int4 *)((unsigned char *)h_clients + notch_ring_off(S)), *d_notch = (int4 *)((unsigned char *)d_clients + notch_ring_off(S));
-    ClientParams *h_det = (ClientParams *)(h_notch + S), *d_det = (ClientParams *)(d_notch + S);
-    bool any_manual = false, iq_notched = false;
-    int ndet = 0;
-    std::vector<size_t> notch_zeros;  // slots whose detector state starts this batch from zero
-    int4 *notch_tab = nullptr;
-    cf *iq_rows[2] = {nullptr, nullptr}, *car_rows[2] = {nullptr, nullptr};
-    {
-        std::lock_guard<std::mutex> lk(c->mtx);
-        if (band) {  // checked under the same lock that fixes the windows this batch is demodulated with
-            for (size_t i = 0; i < c->aslots.size(); i++) {
-                const AudioSlot &s = c->aslots[i];
-                // an empty window (a client between psdr_client_add and its first set_audio_range) reads no bin
-                if (s.active && !s.paused && s.r > s.l && ((uint32_t)s.l < band[0] || (uint64_t)s.r > (uint64_t)band[0] + band[1])) {
-                    c->client_ring.idx = (c->client_ring.idx + ParamRing::K - 1) % ParamRing::K;  // hand the slot back
-                    return fail(PSDR_ERR_INVALID, "client %zu: window [%d, %d) outside the band [%u, %u)", i, s.l, s.r,
-                                band[0], band[0] + band[1]);
-                }
-            }
-        }
-        iq_rows[0] = c->iq_pool[0], iq_rows[1] = c->iq_pool[1];  // (allocated under this lock, once)
-        notch_tab = c->d_notch_tab;
-        car_rows[0] = c->car_pool[0], car_rows[1] = c->car_pool[1];
-        c->demod_seq++;
-        for (size_t i = 0; i < c->aslots.size(); i++) {
-            AudioSlot &s = c->aslots[i];
-            if (!s.active || s.paused) continue;
-            // PSDR_SAM: a slot whose previous batch was not SAM (a fresh slot, another mode in between) holds no carrier
-            // tail of its own - the other modes' kernels do not carry it along: it starts from zero
-            if (s.mode == PSDR_SAM && (s.last_seq == 0 || s.b_mode != PSDR_SAM))
-                sam_zero.push_back(((size_t)s.state_cur * S + i) * ((size_t)c->n / 2));
-            // a tuned USB / LSB client whose previous batch was not tuned in the same mode: likewise, its own tail from zero
-            const bool tuned = tuned_mode(s.fine, s.mode);
-            if (tuned && s.mode != PSDR_IQ && (s.last_seq == 0 || !s.b_tuned || s.b_mode != s.mode))
-                ft_zero.push_back(((size_t)s.state_cur * S + i) * ((size_t)c->n / 2));
-            // a sideband SAM client whose previous batch was not SAM with the same sideband: likewise, its own tail from
-            // zero (the carrier tail follows SAM's rule above alone: a change of sideband does not interrupt it)
-            const bool sbc = sb_sam(s.mode, s.sam_sb);
-            if (sbc && (s.last_seq == 0 || s.b_mode != PSDR_SAM || s.b_sam_sb != s.sam_sb))
-                sb_zero.push_back(((size_t)s.state_cur * S + i) * ((size_t)c->n / 2));
-            if (sbc) nsb++;  // listed apart, below
-            // notches: the manual ones as they are now; the detector's state from zero when auto-notch was switched (on: a fresh
-            // start; off: its entries go), or the window, floor(audio_mid) or the mode are not the previous batch's
-            const bool nm = s.notch[1] > s.notch[0] || s.notch[3] > s.notch[2];
-            if (nm) {
-                if (!any_manual)
-                    for (size_t k = 0; k < S; k++) h_notch[k] = make_int4(0, 0, 0, 0);
-                any_manual = true;
-                h_notch[i] = make_int4(s.notch[0], s.notch[1], s.notch[2], s.notch[3]);
-            }
-            if ((nm || s.auto_notch) && s.mode == PSDR_IQ && !tuned) iq_notched = true;
-            if (notch_tab) {
-                const bool moved = s.last_seq == 0 || s.l != s.b_l || s.r != s.b_r || std::floor(s.mid) != std::floor(s.b_mid) || s.mode != s.b_mode;
-                if ((s.auto_notch != 0) != s.b_auto || (s.auto_notch && (moved || s.auto_fresh))) notch_zeros.push_back(i);
-                s.auto_fresh = false;
-                if (s.auto_notch) {
-                    ClientParams &q = h_det[ndet++];
-                    q = ClientParams{};
-                    q.l = s.l, q.r = s.r, q.m_floor = (int)std::floor(s.mid), q.mode = s.mode, q.slot = (int)i;
-                }
-            }
-            for (int k = 0; k < 4; k++) s.b_notch[k] = s.notch[k];
-            s.b_auto = s.auto_notch != 0;
-            s.last_seq = c->demod_seq;
-            s.b_l = s.l, s.b_r = s.r, s.b_mid = s.mid, s.b_mode = s.mode, s.b_tuned = tuned, s.b_sam_sb = s.sam_sb;
-            if (tuned)
-                (s.mode == PSDR_IQ ? ntiq : ntssb)++;  // listed apart, below
-            else if (s.mode == PSDR_IQ)
-                niq++;  // listed apart, below
-        }
-        // The tuned clients' list as the kernels see it: the placed range, the AM / FM placement; beside it phase, step and
-        // the whole window.  The phase moves on by the batch's samples here, from the snapshot.
-        ClientParams *h_ftc = (ClientParams *)h_ft;
-        FtClient *h_ftp = (FtClient *)(h_ftc + ntssb + ntiq);
-        int kt_ssb = 0, kt_iq = ntssb;
-        auto list_tuned = [&](AudioSlot &s, const ClientParams &p) {
-            const int k = s.mode == PSDR_IQ ? kt_iq++ : kt_ssb++;
-            ClientParams &q = h_ftc[k];
-            q = p;
-            q.mode = PSDR_AM;
-            if (s.mode == PSDR_USB) q.l = std::min(std::max(p.l, p.m_floor), p.r);  // [max(l, m), r)
-            if (s.mode == PSDR_LSB) q.r = p.m_floor < p.r ? std::max(p.m_floor + 1, p.l) : p.r;  // [l, min(r, m + 1))
-            const double delta = s.mid - std::floor(s.mid);
-            FtClient &t = h_ftp[k];
-            t.step = (uint32_t)std::floor(delta * 4294967296.0 / c->n + 0.5);
-            t.phi0 = s.ft_phi;
-            t.l = p.l, t.r = p.r;
-            s.ft_phi += (uint32_t)nframes * (uint32_t)(c->n / 2) * t.step;
-        };
-        // The active list: USB / LSB / AM / FM, then the PSDR_SAM clients - audio clients like the others (the post chain
-        // takes all nact, in any order: it walks the slots through h_slot_ci), listed behind them for launches of their own.
-        // Without one the list is what it always was.
-        for (int sam = 0; sam < 2; sam++) {
-            for (size_t i = 0; i < c->aslots.size(); i++) {
-                AudioSlot &s = c->aslots[i];
-                if (!s.active || s.paused || s.mode == PSDR_IQ || (s.mode == PSDR_SAM) != (sam == 1) || tuned_mode(s.fine, s.mode) || sb_sam(s.mode, s.sam_sb)) continue;
-                fill_params(h_clients[nact++], s, (int)i, c->post_on);
-            }
-            if (!sam) nold = nact;
-        }
-        nsam = nact - nold;
-        // ... and behind SAM's tail the tuned USB / LSB clients: audio clients to the post chain, launches of their own
-        if (ntssb > 0)
-            for (size_t i = 0; i < c->aslots.size(); i++) {
-                AudioSlot &s = c->aslots[i];
-                if (!s.active || s.paused || s.mode == PSDR_IQ || !tuned_mode(s.fine, s.mode)) continue;
-                fill_params(h_clients[nact], s, (int)i, c->post_on);
-                list_tuned(s, h_clients[nact++]);
-            }
-        // ... and behind those the sideband SAM clients, audio clients to the post chain too.  Their own list as the kernels
-        // see it: the placed range (the window clipped to the sideband), the AM / FM placement; beside it the sideband and
-        // the whole window.
-        if (nsb > 0) {
-            ClientParams *h_sbc = (ClientParams *)(h_ft + (size_t)(ntssb + ntiq) * (sizeof(ClientParams) + sizeof(FtClient)));
-            SbClient *h_sbp = (SbClient *)(h_sbc + nsb);
-            int k = 0;
-            for (size_t i = 0; i < c->aslots.size(); i++) {
-                AudioSlot &s = c->aslots[i];
-                if (!s.active || s.paused || !sb_sam(s.mode, s.sam_sb)) continue;
-                const ClientParams &p = h_clients[nact];
-                fill_params(h_clients[nact++], s, (int)i, c->post_on);
-                ClientParams &q = h_sbc[k];
-                q = p;
-                q.mode = PSDR_AM;
-                if (s.sam_sb == PSDR_SAM_UPPER) q.l = std::min(std::max(p.l, p.m_floor), p.r);  // [max(l, m), r)
-                if (s.sam_sb == PSDR_SAM_LOWER) q.r = p.m_floor < p.r ? std::max(p.m_floor + 1, p.l) : p.r;  // [l, min(r, m + 1))
-                SbClient &t = h_sbp[k++];
-                t.l = p.l, t.r = p.r, t.side = s.sam_sb, t.pad = 0;
-            }
-        }
-        if (c->post_on) {
-            for (size_t i = 0; i < S; i++) h_slot_ci[i] = -1;
-            for (int i = 0; i < nact; i++) h_slot_ci[h_clients[i].slot] = i;
-        }
-        // Paused clients (psdr_client_set_paused) are not demodulated: signal_loop never calls send_audio for a client
-        // whose socket is backed up (src/websocket.cpp:170-176), so its overlap-add tails, FM sample, DC blocker and
-        // AGC stand still (src/signal.cpp:273-284).  The post chain lists them BEHIND the active ones with an empty
-        // stream: its double-buffered histories alternate per batch for every listed client, state unchanged.  A
-        // pending AGC reset stays pending until the client's next batch (it only takes effect there anyway).
-        if (c->post_on && nact > 0)
-            for (size_t i = 0; i < c->aslots.size(); i++) {
-                const AudioSlot &s = c->aslots[i];
-                if (!s.active || !s.paused || s.agc_reset == 2) continue;  // (a client that never ran has no history)
-                ClientParams &p = h_clients[nact + npaused++];
-                p = ClientParams{};
-                p.slot = (int)i;
-                p.state_cur = s.state_cur;
-                p.paused = 1;
-                h_slot_ci[i] = nact + npaused - 1;
-            }
-        // PSDR_IQ clients, behind both: the list of k_demod_chain_iq / k_demod_ola_iq.  To the post chain an IQ client IS a
-        // paused one - no audio of its own this batch, histories standing still, a pending AGC reset kept for its next
-        // audio batch - so those with a history come first and the chain's count of paused clients takes them in
-        // (tuned IQ clients: the kernels take them from the tuned list; this list names those with a history, as paused ones)
-        if (ntiq > 0)
-            for (size_t i = 0; i < c->aslots.size(); i++) {
-                AudioSlot &s = c->aslots[i];
-                if (!s.active || s.paused || s.mode != PSDR_IQ || !tuned_mode(s.fine, s.mode)) continue;
-                ClientParams p;
-                fill_params(p, s, (int)i, c->post_on);
-                list_tuned(s, p);
-                if (s.agc_reset != 2 && c->post_on && nact > 0) {
-                    h_clients[nact + npaused] = p;
-                    h_slot_ci[i] = nact + npaused++;
-                }
-            }
-        if (niq > 0) {
-            iq_off = nact + npaused;
-            int k = iq_off;
-            for (int fresh = 0; fresh < 2; fresh++)
-                for (size_t i = 0; i < c->aslots.size(); i++) {
-                    AudioSlot &s = c->aslots[i];
-                    if (!s.active || s.paused || s.mode != PSDR_IQ || (s.agc_reset == 2) != (fresh == 1) || tuned_mode(s.fine, s.mode)) continue;
-                    fill_params(h_clients[k], s, (int)i, c->post_on);
-                    if (!fresh && c->post_on && nact > 0) {
-                        h_slot_ci[i] = k;
-                        npaused++;
-                    }
-                    k++;
-                }
-        }
-    }
-    c->last_demod_frames = nframes;
-    if (nact + niq + ntiq == 0) return PSDR_OK;
-    {  // this batch's results go to the OTHER set (the copies of the last batch to the host may still be reading theirs); what
-       // read this set two batches ago must have landed
-        c->out_set ^= 1;
-        c->d_audio = c->audio_pool[c->out_set], c->d_pwr = c->pwr_pool[c->out_set], c->d_nan = c->nan_pool[c->out_set];
-        c->d_iq = iq_rows[c->out_set];  // (null until the context's first IQ client)
-        c->d_car = car_rows[c->out_set];  // (... first SAM client)
-        int rc = fetch_guard_wait(c, c->side, c->guard_audio[c->out_set]);
-        if (rc) return rc;
-        c->guard_audio[c->out_set] = nullptr;
-        // ... and the post chain's moving averages of that batch, which read its audio rows themselves (postchain.h k_pc_ma2
-        // DIRECT) on a stream of their own, up to two steps behind the passes (psdr_set_post_chain drains: the chain has
-        // been on for every batch since chain_seq started to count)
-        if (c->post_on && c->post_direct && c->chain_seq >= 2 && c->pc_s[0] && c->side != c->stream)
-            HIPCHK(hipStreamWaitEvent(c->side, c->pc.ev[1][(c->chain_seq - 2) % psdr_ctx::PC_SETS], 0));
-    }
-    HIPCHK(hipMemcpyAsync(d_clients, h_clients, c->post_on ? S * (sizeof(ClientParams) + sizeof(int)) : (size_t)(nact + niq) * sizeof(ClientParams),
-                          hipMemcpyHostToDevice, c->side));
-    if (ntssb + ntiq > 0)
-        HIPCHK(hipMemcpyAsync(d_ft, h_ft, (size_t)(ntssb + ntiq) * (sizeof(ClientParams) + sizeof(FtClient)), hipMemcpyHostToDevice, c->side));
-    const size_t sb_off = (size_t)(ntssb + ntiq) * (sizeof(ClientParams) + sizeof(FtClient));  // the sideband SAM list, behind the tuned one
-    if (nsb > 0) HIPCHK(hipMemcpyAsync(d_ft + sb_off, h_ft + sb_off, (size_t)nsb * (sizeof(ClientParams) + sizeof(SbClient)), hipMemcpyHostToDevice, c->side));
-    if (any_manual) HIPCHK(hipMemcpyAsync(d_notch, h_notch, S * sizeof(int4), hipMemcpyHostToDevice, c->side));
-    if (ndet > 0) HIPCHK(hipMemcpyAsync(d_det, h_det, (size_t)ndet * sizeof(ClientParams), hipMemcpyHostToDevice, c->side));
-    for (size_t slot : notch_zeros) PSDRCHK(notch_zero(c, slot));
+static DemodArgs demod_args(psdr_ctx *c, const cf *spec, size_t spec_stride, int nframes, uint64_t first_frame_num, const uint32_t *band,
+                            bool band_tiled) {
     DemodArgs a{};
-    a.notch_man = any_manual ? d_notch : nullptr;
-    a.notch_auto = notch_tab;
-    c->dbg_notch_man = a.notch_man, c->dbg_notch_auto = a.notch_auto;
     a.spec = spec;
     a.spec_stride = spec_stride;
     a.is_real = c->is_real ? 1 : 0;
@@ -580,7 +328,6 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     a.nframes = nframes;
     a.max_batch = c->max_batch;
     a.first_frame_num = first_frame_num;
-    a.clients = d_clients;
     a.Wn = c->d_Wn;
     a.nstages = c->nstages;
     for (int i = 0; i < c->nstages; i++) a.radix[i] = c->radix[i];
@@ -598,6 +345,80 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     a.ssb_mark = c->d_ssb_mark;
     a.mark_epoch = (unsigned)(c->demod_seq % 0xFFFFFFFFull) + 1u;  // never 0
     a.replay = 0;
+    return a;
+}
+// what a plan's byte offset names inside the ring slot's device copy
+template <class T>
+static const T *ring_at(const unsigned char *d_ring, size_t off) {
+    return (const T *)(d_ring + off);
+}
+
+// One batch: demod_plan (demodplan.h) says who is demodulated, in which list of the ring slot and from which state; this
+// copies, zeroes and launches what it names.
+static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nframes, uint64_t first_frame_num,
+                      const uint32_t *band = nullptr, bool band_tiled = false) {
+    if (c->n <= 0) return fail(PSDR_ERR_STATE, "context created with audio_fft_size 0");
+    HIPCHK(hipSetDevice(c->device));
+    const int ring = c->client_ring.acquire();
+    if (ring < 0) return fail(PSDR_ERR_HIP, "client parameter ring: event wait failed");
+    unsigned char *h_ring = (unsigned char *)c->client_ring.host(ring), *d_ring = (unsigned char *)c->client_ring.dev(ring);
+    DemodFacts f;
+    f.n = c->n, f.nframes = nframes;
+    if (band) f.has_band = true, f.band_first = band[0], f.band_count = band[1];
+    DemodPlan p;
+    int4 *notch_tab = nullptr;
+    cf *iq_rows[2] = {nullptr, nullptr}, *car_rows[2] = {nullptr, nullptr};
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);  // (the band is checked under the same lock that fixes the windows of the batch)
+        iq_rows[0] = c->iq_pool[0], iq_rows[1] = c->iq_pool[1];  // (allocated under this lock, once)
+        notch_tab = c->d_notch_tab;
+        car_rows[0] = c->car_pool[0], car_rows[1] = c->car_pool[1];
+        f.post_on = c->post_on, f.have_notch_tab = notch_tab != nullptr;
+        p = demod_plan(c->aslots.data(), c->aslots.size(), c->demod_seq, f, h_ring);
+        if (p.verdict == DP_BAND_OUTSIDE) {
+            c->client_ring.idx = (c->client_ring.idx + ParamRing::K - 1) % ParamRing::K;  // hand the slot back
+            return fail(PSDR_ERR_INVALID, "client %d: window [%d, %d) outside the band [%u, %u)", p.bad_slot, p.bad_l, p.bad_r, band[0],
+                        band[0] + band[1]);
+        }
+    }
+    c->last_demod_frames = nframes;
+    if (p.idle()) return PSDR_OK;
+    {  // this batch's results go to the OTHER set (the copies of the last batch to the host may still be reading theirs); what
+       // read this set two batches ago must have landed
+        c->out_set ^= 1;
+        c->d_audio = c->audio_pool[c->out_set], c->d_pwr = c->pwr_pool[c->out_set], c->d_nan = c->nan_pool[c->out_set];
+        c->d_iq = iq_rows[c->out_set];  // (null until the context's first IQ client)
+        c->d_car = car_rows[c->out_set];  // (... first SAM client)
+        int rc = fetch_guard_wait(c, c->side, c->guard_audio[c->out_set]);
+        if (rc) return rc;
+        c->guard_audio[c->out_set] = nullptr;
+        // ... and the post chain's moving averages of that batch, which read its audio rows themselves (postchain.h k_pc_ma2
+        // DIRECT) on a stream of their own, up to two steps behind the passes (psdr_set_post_chain drains: the chain has
+        // been on for every batch since chain_seq started to count)
+        if (c->post_on && c->post_direct && c->chain_seq >= 2 && c->pc_s[0] && c->side != c->stream)
+            HIPCHK(hipStreamWaitEvent(c->side, c->pc.ev[1][(c->chain_seq - 2) % psdr_ctx::PC_SETS], 0));
+    }
+    for (int i = 0; i < p.ncopies; i++)
+        HIPCHK(hipMemcpyAsync(d_ring + p.copies[i].off, h_ring + p.copies[i].off, p.copies[i].bytes, hipMemcpyHostToDevice, c->side));
+    // what starts from zero (car_zero names the slots of both kinds of SAM client: they share the carrier tail)
+    if (p.ntssb > 0 && !c->d_ft_tail) return fail(PSDR_ERR_STATE, "tuned USB / LSB clients without their tails");
+    if (p.nsb > 0 && (!c->d_sb_tail || !c->d_car_tail)) return fail(PSDR_ERR_STATE, "sideband SAM clients without their tails");
+    const size_t tail_bytes = ((size_t)c->n / 2) * sizeof(cf);
+    for (size_t slot : p.det_zero) PSDRCHK(notch_zero(c, slot));
+    for (size_t off : p.car_zero) HIPCHK(hipMemsetAsync(c->d_car_tail + off, 0, tail_bytes, c->side));
+    for (size_t off : p.ft_zero) HIPCHK(hipMemsetAsync(c->d_ft_tail + off, 0, tail_bytes, c->side));
+    for (size_t off : p.sb_zero) HIPCHK(hipMemsetAsync(c->d_sb_tail + off, 0, tail_bytes, c->side));
+    DemodArgs a = demod_args(c, spec, spec_stride, nframes, first_frame_num, band, band_tiled);
+    a.clients = ring_at<ClientParams>(d_ring, p.plain.clients);
+    a.notch_man = p.any_manual ? ring_at<int4>(d_ring, p.notch) : nullptr;
+    a.notch_auto = notch_tab;
+    c->dbg_notch_man = a.notch_man, c->dbg_notch_auto = a.notch_auto;
+    // a list with launches of its own: the batch's arguments with its clients
+    auto of_list = [&](const RingList &l) {
+        DemodArgs al = a;
+        al.clients = ring_at<ClientParams>(d_ring, l.clients);
+        return al;
+    };
     // the frame-ordered second walk of marked USB / LSB slots (demod.h: DemodArgs::ssb_mark) can only find work where
     // non-finite values can arise: float input formats, or a spectrum that comes from the caller
     const bool can_be_nonfinite = c->cfg.input_format >= PSDR_FMT_F32 || spec != c->d_spec;
@@ -631,6 +452,7 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
         }
         return PSDR_OK;
     };
+    const int nold = p.nold;
     if (nold > 0) {
         ProfScope ps(c, K_IDFT, c->side);
         if (fixed_plan && c->demod_chain) {
@@ -671,75 +493,52 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
         return PSDR_OK;
     };
     SamArgs sa{};
-    if (nsam + nsb > 0) {
-        // (sam_zero names the slots of both kinds of SAM client: they share the carrier tail)
-        for (size_t off : sam_zero) HIPCHK(hipMemsetAsync(c->d_car_tail + off, 0, ((size_t)c->n / 2) * sizeof(cf), c->side));
+    if (p.nsam + p.nsb > 0) {
         sa.car_tail = c->d_car_tail;
         sa.car_rec = c->d_car;
         sa.cutoff = (int)((int64_t)500 * c->n / c->cfg.audio_rate);  // src/signal.cpp:217-220
         sa.hz_per_rad = (float)((double)c->cfg.audio_rate / (2.0 * M_PI));
     }
-    if (nsam > 0) {
-        // the PSDR_SAM clients: the tail of the active list, launches of their own behind the others' (demod.h)
-        DemodArgs as = a;
-        as.clients = d_clients + nold;
-        // (a wave's carrier tail lives in n/2 words of LDS behind the transform buffers: two waves per work-group at
-        // n = 360, 11.25 KiB, and one at 720, 14.1 KiB - inside the 15 KiB an FFT pass leaves free on a CU)
-        PSDRCHK(serve(CHAIN_SAM, k_demod_ola_sam, as, nsam, 2u, (size_t)(c->n / 2) * sizeof(cf), sa));
+    // the PSDR_SAM clients: the tail of the active list, launches of their own behind the others' (demod.h)
+    // (a wave's carrier tail lives in n/2 words of LDS behind the transform buffers: two waves per work-group at
+    // n = 360, 11.25 KiB, and one at 720, 14.1 KiB - inside the 15 KiB an FFT pass leaves free on a CU)
+    if (p.nsam > 0) PSDRCHK(serve(CHAIN_SAM, k_demod_ola_sam, of_list(p.sam), p.nsam, 2u, tail_bytes, sa));
+    // the PSDR_IQ clients: launches of their own behind the others', on the same stream (demod.h)
+    if (p.niq > 0) PSDRCHK(serve(p.iq_notched ? CHAIN_IQ_NZ : CHAIN_IQ, k_demod_ola_iq, of_list(p.iq), p.niq, 4u, 0, c->d_iq));
+    // the tuned clients: their own list, launches of their own behind the others' (demod.h)
+    FtArgs fa{};
+    fa.tail = c->d_ft_tail;
+    fa.iq = c->d_iq;
+    if (p.ntssb > 0) {
+        fa.ft = ring_at<FtClient>(d_ring, p.tssb.side);
+        PSDRCHK(serve(CHAIN_FT_SSB, k_demod_ola_ft<true>, of_list(p.tssb), p.ntssb, 4u, 0, fa));
     }
-    if (niq > 0) {
-        // the PSDR_IQ clients: launches of their own behind the others', on the same stream (demod.h)
-        DemodArgs ai = a;
-        ai.clients = d_clients + iq_off;
-        PSDRCHK(serve(iq_notched ? CHAIN_IQ_NZ : CHAIN_IQ, k_demod_ola_iq, ai, niq, 4u, 0, c->d_iq));
+    if (p.ntiq > 0) {
+        fa.ft = ring_at<FtClient>(d_ring, p.tiq.side);
+        PSDRCHK(serve(CHAIN_FT_IQ, k_demod_ola_ft<false>, of_list(p.tiq), p.ntiq, 4u, 0, fa));
     }
-    if (ntssb > 0 && !c->d_ft_tail) return fail(PSDR_ERR_STATE, "tuned USB / LSB clients without their tails");
-    if (ntssb + ntiq > 0) {
-        // the tuned clients: their own list, launches of their own behind the others' (demod.h)
-        for (size_t off : ft_zero) HIPCHK(hipMemsetAsync(c->d_ft_tail + off, 0, ((size_t)c->n / 2) * sizeof(cf), c->side));
-        DemodArgs at = a;
-        FtArgs fa{};
-        fa.tail = c->d_ft_tail;
-        fa.iq = c->d_iq;
-        if (ntssb > 0) {
-            at.clients = (const ClientParams *)d_ft;
-            fa.ft = (const FtClient *)(at.clients + ntssb + ntiq);
-            PSDRCHK(serve(CHAIN_FT_SSB, k_demod_ola_ft<true>, at, ntssb, 4u, 0, fa));
-        }
-        if (ntiq > 0) {
-            at.clients = (const ClientParams *)d_ft + ntssb;
-            fa.ft = (const FtClient *)((const ClientParams *)d_ft + ntssb + ntiq) + ntssb;
-            PSDRCHK(serve(CHAIN_FT_IQ, k_demod_ola_ft<false>, at, ntiq, 4u, 0, fa));
-        }
-    }
-    if (nsb > 0) {
+    if (p.nsb > 0) {
         // the sideband SAM clients: their own list, launches of their own behind all the others' (demod.h); LDS as SAM's
-        if (!c->d_sb_tail || !c->d_car_tail) return fail(PSDR_ERR_STATE, "sideband SAM clients without their tails");
-        for (size_t off : sb_zero) HIPCHK(hipMemsetAsync(c->d_sb_tail + off, 0, ((size_t)c->n / 2) * sizeof(cf), c->side));
-        DemodArgs ab = a;
-        ab.clients = (const ClientParams *)(d_ft + sb_off);
         SbArgs sba{};
         sba.sa = sa;
-        sba.sb = (const SbClient *)(ab.clients + nsb);
+        sba.sb = ring_at<SbClient>(d_ring, p.sb.side);
         sba.tail = c->d_sb_tail;
-        PSDRCHK(serve(CHAIN_SBSAM, k_demod_ola_sbsam, ab, nsb, 2u, (size_t)(c->n / 2) * sizeof(cf), sba));
+        PSDRCHK(serve(CHAIN_SBSAM, k_demod_ola_sbsam, of_list(p.sb), p.nsb, 2u, tail_bytes, sba));
     }
-    if (ndet > 0) {
+    if (p.ndet > 0) {
         // the detector, behind the batch's last demodulation kernel: it writes the table those have just read (demod.h)
         NotchArgs na{};
-        na.det = d_det;
+        na.det = ring_at<ClientParams>(d_ring, p.det.clients);
         na.acc = c->d_notch_acc;
         na.cnt = c->d_notch_cnt;
         na.tab = notch_tab;
         na.period = std::max(1, c->cfg.audio_rate / c->n);
-        hipLaunchKernelGGL(k_notch_detect, dim3((unsigned)ndet), dim3(64), 0, c->side, a, ndet, na);
+        hipLaunchKernelGGL(k_notch_detect, dim3((unsigned)p.ndet), dim3(64), 0, c->side, a, p.ndet, na);
         HIPCHK(hipGetLastError());
     }
     hipStream_t last_user = c->side;
-    if (c->post_on && nact > 0) {
-        int rc = post_chain_enqueue(c, d_clients, d_slot_ci, nact, npaused, nframes, &last_user);
-        if (rc) return rc;
-    }
+    if (f.post_on && p.nact > 0)
+        PSDRCHK(post_chain_enqueue(c, a.clients, ring_at<int>(d_ring, p.slot_ci), p.nact, p.npaused, nframes, &last_user));
     HIPCHK(c->client_ring.release(ring, last_user));
     if (c->side != c->stream) {
         HIPCHK(hipEventRecord(c->ev_side_done, c->side));
