@@ -163,7 +163,8 @@ int psdr_client_on_window_message(psdr_ctx *ctx, int id, int l, double audio_mid
  * batch frame, i.e. 16 * (audio_fft_size/2) * max_clients * max_batch bytes in all (a context that never sees an IQ client
  * allocates none); PSDR_ERR_NOMEM, and the mode unchanged, if that fails.  The first PSDR_SAM allocates the carrier tails
  * (16 * (audio_fft_size/2) bytes per client slot) and two sets of carrier records (8 bytes per client slot and batch
- * frame each), all or none, with the same answer on failure; PSDR_ERR_STATE if the context's audio_rate is not positive. */
+ * frame each), all or none, with the same answer on failure; PSDR_ERR_STATE if the context's audio_rate is not positive;
+ * PSDR_ERR_UNSUPPORTED, and the mode unchanged, if audio_fft_size >= 65536 (PSDR_SAM below: the carrier's direct sum). */
 int psdr_client_set_audio_demodulation(psdr_ctx *ctx, int id, int mode);
 /* signal_loop's slow-client rule (src/websocket.cpp:170-176): the reference does not call send_audio at all for a
  * client with more than 50 kB queued on its socket, so NOTHING of that client moves for the frame - overlap-add tails and
@@ -259,7 +260,9 @@ int psdr_iq_device_ptr(psdr_ctx *ctx, int id, const float **d_iq, const float **
  *     S = sum over j < h - 1 of C[j+1] * conj(C[j]): positive when the carrier sits above the centre of bin
  *     floor(audio_mid), 0 when S = 0.
  * n = 360 / 720 run the transform's compile-time plan twice per frame, any other n (and PSDR_DEMOD_CHAIN=0) sums the kept
- * bins directly: the two paths may differ in the carrier's last bits, never in B.
+ * bins directly: the two paths may differ in the carrier's last bits, never in B.  The direct sum looks its twiddles up at
+ * (bin * sample) mod n with a 32-bit product: PSDR_SAM is served for audio_fft_size < 65536 only, and
+ * psdr_client_set_audio_demodulation answers PSDR_ERR_UNSUPPORTED for it above that (every other mode is served at any size).
  * psdr_read_carrier: level / offset_hz [nframes] (either may be NULL), otherwise the contract of psdr_read_audio;
  * PSDR_ERR_NO_DATA for a slot whose batch was not SAM.  psdr_fetched_carrier answers from the fetched set: a fetch that
  * carries audio, PCM or IQ also copies the carrier records, ONE extra copy of the span from the lowest to the highest SAM

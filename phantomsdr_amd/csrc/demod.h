@@ -1302,7 +1302,7 @@ __device__ __forceinline__ cf sam_carrier_dsum(const DemodArgs &a, const ClientP
     float ar = 0.f, ai = 0.f;
     for (int d = d0; d < d1; d++) {
         const cf x = notched(nz, cp, cp.m_floor + d - cp.l) ? make_float2(0.f, 0.f) : S[a.lay.pos(cp.m_floor + d)];
-        const cf w = a.Wn[((unsigned)(d < 0 ? (int)n + d : d) * (unsigned)jout) % n];  // (< n^2: audio sizes stay far below 2^16)
+        const cf w = a.Wn[((unsigned)(d < 0 ? (int)n + d : d) * (unsigned)jout) % n];  // (< n^2 < 2^32: demodplan.h sam_size_served, no client becomes PSDR_SAM at n >= 2^16)
         ar = fmaf(x.x, w.x, fmaf(-x.y, w.y, ar));
         ai = fmaf(x.x, w.y, fmaf(x.y, w.x, ai));
     }

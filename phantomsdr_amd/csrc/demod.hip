@@ -145,6 +145,8 @@ extern "C" int psdr_client_set_audio_demodulation(psdr_ctx *c, int id, int mode)
     int rc = check_slot(c, id);
     if (rc) return rc;
     if (mode < PSDR_USB || mode > PSDR_SAM) return fail(PSDR_ERR_INVALID, "unknown mode %d", mode);
+    if (mode == PSDR_SAM && !sam_size_served(c->n))
+        return fail(PSDR_ERR_UNSUPPORTED, "PSDR_SAM needs audio_fft_size < %d (this context: %d): the carrier's direct sum indexes its twiddles with a 32-bit product", PSDR_SAM_MAX_AUDIO_FFT, c->n);
     if (mode == PSDR_IQ && !c->iq_pool[1]) {
         // the first IQ client of the context: its rows' two pools (a context that never sees one allocates nothing); both
         // exist before either is kept, and the mode changes only then

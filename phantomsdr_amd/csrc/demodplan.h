@@ -60,6 +60,12 @@ inline size_t client_ring_bytes(size_t S) { return notch_ring_off(S) + S * (NOTC
 inline bool tuned_mode(int fine, int mode) { return fine && (mode == PSDR_USB || mode == PSDR_LSB || mode == PSDR_IQ); }
 // a sideband SAM client: PSDR_SAM with another sideband than both (in every other mode the value has no effect)
 inline bool sb_sam(int mode, int sideband) { return mode == PSDR_SAM && sideband != PSDR_SAM_BOTH; }
+// PSDR_SAM (either kind) outside the compile-time plans sums the carrier's kept bins directly (demod.h: sam_carrier_dsum) and
+// looks the twiddle up at (d * j) mod n with d, j < n in 32-bit unsigned arithmetic: exact while (n - 1)^2 < 2^32.
+// psdr_client_set_audio_demodulation refuses the mode above that; every other mode has no such product.
+constexpr int PSDR_SAM_MAX_AUDIO_FFT = 65536;
+static_assert((uint64_t)(PSDR_SAM_MAX_AUDIO_FFT - 1) * (uint64_t)(PSDR_SAM_MAX_AUDIO_FFT - 1) <= 0xFFFFFFFFull, "sam_carrier_dsum's index product");
+inline bool sam_size_served(int n) { return n < PSDR_SAM_MAX_AUDIO_FFT; }
 
 // What a slot is to a batch - the one place that combines active, paused, mode, fine and sam_sb.  CK_PLAIN: USB / LSB / AM /
 // FM, the list of k_demod_chain_fixed; every kind behind it has a list and launches of its own.

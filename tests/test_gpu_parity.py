@@ -234,7 +234,7 @@ def test_demod_single_frame_batches():
     run_demod_case(N, 0, n, clients, nbatches=6, F=1, seed=31)
 
 
-@pytest.mark.parametrize("n", [8, 60, 124, 256, 720, 1000, 2048, 2 * 839 * 2, 10068])
+@pytest.mark.parametrize("n", [8, 60, 124, 256, 720, 1000, 2048, 2 * 839 * 2, 10068, 32, 48, 160, 224, 44, 6400])
 def test_demod_audio_fft_sizes(n):
     """any multiple of 4, including large prime factors (31, 839) and power-of-two sizes."""
     N = 1 << 16
