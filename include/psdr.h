@@ -379,6 +379,48 @@ int psdr_client_set_sam_sideband(psdr_ctx *ctx, int id, int sideband);
 int psdr_client_set_notch(psdr_ctx *ctx, int id, int index, double centre_bin, double width_bins);
 int psdr_client_set_auto_notch(psdr_ctx *ctx, int id, int on);
 int psdr_read_notches(psdr_ctx *ctx, int id, int first[4], int end[4]);
+/* Squelch: a level gate per client, with hysteresis, attack and hang.  A client parked on a quiet channel costs the served
+ * path what a client on a busy one costs, and the AGC pumps its noise up to full scale; a squelch-closed frame is to the post
+ * chain what a NaN-flagged one is - no chain work, no PCM, nothing to encode or send.  The decision uses the frame's pwr, the
+ * number the reference puts into every audio packet: the threshold is in the units of the S-meter.
+ * With P_f the frame's pwr exactly as psdr_read_audio / psdr_read_iq deliver it (notches applied, any mode):
+ *   Thresholds.  T_open = (float)pow(10.0, open_db / 10.0), computed in double and rounded once to f32; T_close the same
+ *     from close_db.
+ *   State per client, carried from frame to frame and batch to batch: open (0 / 1) and a run counter cnt (both int32).  For
+ *     each frame of a batch, in order:
+ *       closed:  above = (P_f >= T_open),   cnt = above ? cnt + 1 : 0;  if (cnt >= attack_frames) open = 1, cnt = 0
+ *       open:    below = !(P_f >= T_close), cnt = below ? cnt + 1 : 0;  if (cnt > hang_frames)    open = 0, cnt = 0
+ *     The frame's flag is `open` AFTER the update: the frame that completes the attack is heard, the frame that exhausts the
+ *     hang is not.  NaN compares false both ways - it never opens, and it counts as below; +Inf is above.
+ *   Start.  The state starts from (closed, 0) when squelch is switched ON for the client - while paused too, and for a fresh
+ *     slot.  A change of thresholds or counts while on keeps the state and takes effect at the next batch, through the
+ *     batch's snapshot.  A retune or a mode change does NOT reset it: the threshold is absolute, unlike the notch detector's
+ *     (which is relative to the window's mean).  A paused client's state stands still.
+ *   The demodulator is untouched.  Audio rows, IQ rows, pwr, NaN flags, carrier records and every piece of demodulation
+ *     state are bit for bit those of the same client without squelch, in every client kind (USB, LSB, AM, FM, SAM, IQ,
+ *     tuned, sideband SAM).
+ *   The post chain treats a closed frame exactly as a NaN-flagged one: it is not part of the client's stream, the DC blocker
+ *     and the AGC stand still across it, its PCM row (int32 or PCM16) is zero, and a batch that is closed throughout is an
+ *     empty stream, as an all-NaN batch is.  Other clients are not affected by a bit.
+ *   Nothing changes without squelch: a context with no squelch client launches and allocates exactly what a library
+ *     without these calls does, and a batch with none hands the chain the NaN flags' own pointer.
+ * psdr_client_set_squelch: any thread; in force from the client's next batch.  PSDR_ERR_INVALID, with nothing changed, for an
+ *   unknown id, non-finite dB values or values outside [-300, 300], close_db > open_db, attack_frames outside 1..2^20 or
+ *   hang_frames outside 0..2^20.  on = 0 ignores the other arguments.  The device state (flag rows, state, the batch's table:
+ *   12 * max_batch + 200 bytes per client slot) is allocated with the context's first squelch client, all or none:
+ *   PSDR_ERR_NOMEM and the setting unchanged if that fails.  There is deliberately NO PSDR_OPT_SQUELCH (it would be 8): an
+ *   option hands psdr_client_add ONE value, and this setting has five.
+ * psdr_read_squelch: open[nframes] (1 = heard), otherwise the contract of psdr_read_audio, for a client of any mode.  A
+ *   client whose last batch ran with squelch off reads 1 for every frame - answered from the host snapshot, no device access.
+ *   PSDR_ERR_NO_DATA under psdr_read_audio's rule.
+ * psdr_fetched_squelch answers from the fetched set: a fetch (with any of the audio bits) of a batch that had squelch clients
+ *   carries their flags as ONE extra copy, the span from the lowest to the highest squelch slot - the rule of the carrier
+ *   records; keep squelch clients in neighbouring slots.  Squelch-off clients read 1.  Errors as psdr_fetched_audio, for a
+ *   client of any mode.
+ * There is no psdr_group_* call: a group's clients have no squelch. */
+int psdr_client_set_squelch(psdr_ctx *ctx, int id, int on, double open_db, double close_db, int attack_frames, int hang_frames);
+int psdr_read_squelch(psdr_ctx *ctx, int id, int nframes, int32_t *open, int *nframes_out);
+int psdr_fetched_squelch(psdr_ctx *ctx, int id, int frame, int32_t *open);
 /* A client added after the last psdr_demod_batch has no results in it (the reference's frame loop would not
  * have posted a task for it either, src/websocket.cpp:156-185): psdr_read_audio / psdr_read_pcm / psdr_fetched_audio
  * return PSDR_ERR_NO_DATA for such a slot instead of the previous occupant's samples.
@@ -602,7 +644,9 @@ psdr_ctx *psdr_group_ctx(psdr_group *g, int rank);
  * psdr_group_client_set_audio_demodulation answer PSDR_ERR_UNSUPPORTED for it.  The same holds for PSDR_SAM: the carrier
  * tail is not migrated and the carrier records are not fetched by gid.  There is no psdr_group_* call for the fine-tune
  * flag: a group's clients are untuned, and a band migration carries the flag's value 0.  There is none for notches either
- * (psdr_client_set_notch, psdr_client_set_auto_notch): a group's clients have none, and a band migration carries none. */
+ * (psdr_client_set_notch, psdr_client_set_auto_notch): a group's clients have none, and a band migration carries none.  Nor
+ * is there one for the squelch (psdr_client_set_squelch): a group's clients are always open, and a band migration carries
+ * neither the setting nor the gate's state. */
 int psdr_group_client_add(psdr_group *g, int l, double audio_mid, int r, int mode, int *gid_out);
 int psdr_group_client_remove(psdr_group *g, int gid);
 int psdr_group_client_set_audio_range(psdr_group *g, int gid, int l, double audio_mid, int r);

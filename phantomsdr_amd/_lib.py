@@ -71,6 +71,9 @@ SYMBOLS = [
     ("psdr_client_set_notch", _i, [_vp, _i, _i, C.c_double, C.c_double]),
     ("psdr_client_set_auto_notch", _i, [_vp, _i, _i]),
     ("psdr_read_notches", _i, [_vp, _i, C.POINTER(_i), C.POINTER(_i)]),
+    ("psdr_client_set_squelch", _i, [_vp, _i, _i, C.c_double, C.c_double, _i, _i]),
+    ("psdr_read_squelch", _i, [_vp, _i, _i, _vp, C.POINTER(_i)]),
+    ("psdr_fetched_squelch", _i, [_vp, _i, _i, C.POINTER(C.c_int32)]),
     ("psdr_demod_batch", _i, [_vp, _u64]),
     ("psdr_demod_batch_from", _i, [_vp, _vp, _sz, _i, _u64]),
     ("psdr_pack_band", _i, [_vp, _i, C.c_uint32, C.c_uint32, _vp, _sz]),

@@ -229,6 +229,12 @@ class Context:
         check(self.lib.psdr_fetched_carrier(self.h, int(cid), int(frame), C.byref(lv), C.byref(off)))
         return lv.value, off.value
 
+    def fetched_squelch(self, cid, frame):
+        """1 / 0: one frame of the fetched batch is heard / squelched (psdr.h: psdr_fetched_squelch); 1 for a client without squelch"""
+        o = C.c_int32(0)
+        check(self.lib.psdr_fetched_squelch(self.h, int(cid), int(frame), C.byref(o)))
+        return o.value
+
     def fetched_iq_span(self):
         """(first slot, slots, bytes) the fetched batch's IQ copy covered (psdr.h: psdr_fetched_iq_span)"""
         lo, ns, nb = C.c_int(0), C.c_int(0), C.c_size_t(0)
@@ -464,6 +470,23 @@ class AudioClient:
         first, end = (C.c_int * 4)(), (C.c_int * 4)()
         check(self.ctx.lib.psdr_read_notches(self.ctx.h, self.id, first, end))
         return [(first[k], end[k]) for k in range(4)]
+
+    def set_squelch(self, on, open_db=0.0, close_db=None, attack_frames=1, hang_frames=0):
+        """level gate with hysteresis (psdr_client_set_squelch): the client opens after attack_frames consecutive frames whose
+        pwr is at least 10^(open_db/10) and closes after more than hang_frames consecutive frames below 10^(close_db/10)
+        (close_db None: open_db, no hysteresis).  A closed frame stays out of the post chain's stream like a NaN-flagged one;
+        the demodulated rows are not touched.  Switching it on starts from closed; in force from the next batch."""
+        close_db = open_db if close_db is None else close_db
+        check(self.ctx.lib.psdr_client_set_squelch(self.ctx.h, self.id, 1 if on else 0, float(open_db), float(close_db),
+                                                   int(attack_frames), int(hang_frames)))
+
+    def read_squelch(self, nframes=None):
+        """open[F] (int32, 1 = heard) of the last demod batch (psdr.h: psdr_read_squelch); all 1 for a client without squelch"""
+        F = nframes or self.ctx.last_demod_frames or self.ctx.last_nframes
+        o = np.empty(F, np.int32)
+        got = C.c_int(0)
+        check(self.ctx.lib.psdr_read_squelch(self.ctx.h, self.id, F, _ptr(o), C.byref(got)))
+        return o[:got.value]
 
     def on_window_message(self, l, m, r):
         """returns False where the reference silently returns (src/signal.cpp:302-311)."""

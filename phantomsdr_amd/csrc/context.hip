@@ -25,7 +25,8 @@ extern "C" const char *psdr_version(void) {
 namespace psdr {
 const char *kKernelNames[K_COUNT] = {"fft_pass1",  "fft_pass2", "untangle_real", "pyramid_tail",
                                      "demod_idft", "demod_ola", "waterfall_gather", "post_chain",
-                                     "real_seam",  "band_pack",  "waterfall_hold", "waterfall_carry"};
+                                     "real_seam",  "band_pack",  "waterfall_hold", "waterfall_carry",
+                                     "squelch"};
 
 void resolve_pending(psdr_ctx *c) {
     if (c->pending.empty()) return;

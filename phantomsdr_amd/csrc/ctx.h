@@ -22,6 +22,7 @@
 #include "owned.h"
 #include "postplan.h"
 #include "quantize.h"
+#include "squelchplan.h"
 #include "types.h"
 
 // sets psdr_last_error() of the calling thread and returns `code`
@@ -56,7 +57,7 @@ inline const char *psdr_tuning_env(const char *name) {
 
 namespace psdr {
 
-enum KernelId { K_PASS1, K_PASS2, K_UNTANGLE, K_TAIL, K_IDFT, K_OLA, K_WFALL, K_POST, K_SEAM, K_BAND, K_WFHOLD, K_WFCARRY, K_COUNT };
+enum KernelId { K_PASS1, K_PASS2, K_UNTANGLE, K_TAIL, K_IDFT, K_OLA, K_WFALL, K_POST, K_SEAM, K_BAND, K_WFHOLD, K_WFCARRY, K_SQUELCH, K_COUNT };
 extern const char *kKernelNames[K_COUNT];
 
 struct PendingEvent {
@@ -292,6 +293,16 @@ struct psdr_ctx {
     DevBuf<int4> d_notch_tab;
     int opt_auto_notch = 0;  // PSDR_OPT_AUTO_NOTCH: the value psdr_client_add hands a new client
     const void *dbg_notch_man = nullptr, *dbg_notch_auto = nullptr;  // DemodArgs::notch_man / notch_auto of the last batch (psdr_debug_notch_ptrs)
+    // squelch (squelch.h: k_squelch): the frames' open flags [slots][max_batch] in two sets that alternate with out_set like
+    // nan_pool (d_sq: the last batch's), the post chain's drop flags [slots][max_batch] (written and read on `side` within one
+    // batch: one set), the gates' state [slots] and the batch's table (squelchplan.h) - one image of [slots] entries per slot of
+    // client_ring, with the ring's discipline: the manual notches' way is closed, the client ring's layout is pinned.  All of
+    // it is allocated with the context's first squelch client (under mtx), or none, and kept.
+    DevBuf<int> sq_pool[2], d_sq_drop;
+    int *d_sq = nullptr;
+    DevBuf<SquelchState> d_sq_state;
+    HostBuf<SquelchEntry> h_sq_tab;
+    DevBuf<SquelchEntry> d_sq_tab;
     DevBuf<unsigned> d_ssb_mark;  // [slots] DemodArgs::ssb_mark (demod.h): USB / LSB batches that need the frame-ordered NaN guard
     ParamRing client_ring;
     int last_demod_frames = 0;
@@ -314,6 +325,10 @@ struct psdr_ctx {
         HostBuf<cf> car;
         size_t car_cap = 0;
         int car_lo = 0, car_n = 0;
+        // the squelch flags [slot - sq_lo][max_batch] of the sq_n slots from the lowest to the highest that ran with squelch
+        HostBuf<int32_t> sq;
+        size_t sq_cap = 0;
+        int sq_lo = 0, sq_n = 0;
         Event done;                      // every copy of the fetch on the first copy stream has landed
         Event ev_pcm;                    // ... and the PCM (its own copy stream: it waits for the post chain, up to two steps late)
         bool has_pcm = false;
@@ -329,6 +344,7 @@ struct psdr_ctx {
             int l = 0, r = 0;
             double mid = 0;
             int mode = PSDR_USB;
+            bool sq = false;  // the batch ran with squelch for the slot (psdr_fetched_squelch: 1 for every frame otherwise)
         };
         std::vector<Win> win;      // per audio slot: the window the batch was demodulated with
         std::vector<WfSlot> wfm;   // per waterfall slot: what psdr_waterfall_batch gathered (out_off, nsent, b_*)
@@ -464,8 +480,9 @@ int launch_pass2(psdr_ctx *c, int L, int T, bool fused, const Pass2Args &a, unsi
 int launch_pass2_band(psdr_ctx *c, const Pass2Args &a, unsigned blocks);
 int launch_pass2_real(psdr_ctx *c, const Pass2Args &a);
 // postchain.hip: the chain's kernels for the batch demod_impl has just enqueued; *last_user = the last stream that reads
-// the client parameter block
+// the client parameter block; d_drop: the flags [slots][max_batch] of the frames that stay out of the clients' streams - the
+// batch's NaN flags themselves, or (a batch with squelch clients) k_squelch's merged drop flags
 int post_chain_enqueue(psdr_ctx *c, const ClientParams *d_clients, const int *d_slot_ci, int nact, int npaused, int nframes,
-                       hipStream_t *last_user);
+                       const int *d_drop, hipStream_t *last_user);
 
 }  // namespace psdr

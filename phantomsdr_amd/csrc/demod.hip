@@ -3,6 +3,7 @@
 // every frame of a batch, and the read-back of its results.
 #include "ctx.h"
 #include "demod.h"
+#include "squelch.h"
 
 // the context's first tuned USB / LSB client: its family's tails (a context that never sees one allocates nothing); under mtx
 static int ft_tail_alloc(psdr_ctx *c) {
@@ -54,6 +55,29 @@ static int notch_zero(psdr_ctx *c, size_t slot) {
     HIPCHK(hipMemsetAsync(c->d_notch_acc + slot * (size_t)c->n, 0, (size_t)c->n * sizeof(float), c->side));
     HIPCHK(hipMemsetAsync(c->d_notch_cnt + slot, 0, sizeof(int), c->side));
     HIPCHK(hipMemsetAsync(c->d_notch_tab + slot, 0, sizeof(int4), c->side));
+    return PSDR_OK;
+}
+// the context's first squelch client: flag rows, drop flags, state and the batch's table, all or none (a context that never sees
+// one allocates nothing); under mtx
+static int squelch_alloc(psdr_ctx *c) {
+    if (c->d_sq_tab) return PSDR_OK;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t S = c->aslots.size(), rows = S * (size_t)c->max_batch;
+    DevBuf<int> pool[2], drop;
+    DevBuf<SquelchState> state;
+    HostBuf<SquelchEntry> h_tab;
+    DevBuf<SquelchEntry> d_tab;
+    if (pool[0].alloc(rows, true) || pool[1].alloc(rows, true) || drop.alloc(rows, true) || state.alloc(S, true) || h_tab.alloc(S * ParamRing::K) ||
+        d_tab.alloc(S * ParamRing::K, true)) {
+        const std::string msg = psdr_last_error();
+        return fail(PSDR_ERR_NOMEM, "squelch flags, state and table (%zu bytes): %s",
+                    3 * rows * sizeof(int) + S * sizeof(SquelchState) + S * ParamRing::K * sizeof(SquelchEntry), msg.c_str());
+    }
+    c->sq_pool[0] = std::move(pool[0]), c->sq_pool[1] = std::move(pool[1]);
+    c->d_sq_drop = std::move(drop);
+    c->d_sq_state = std::move(state);
+    c->h_sq_tab = std::move(h_tab);
+    c->d_sq_tab = std::move(d_tab);
     return PSDR_OK;
 }
 static int check_slot(psdr_ctx *c, int id) {
@@ -247,6 +271,21 @@ extern "C" int psdr_client_set_auto_notch(psdr_ctx *c, int id, int on) {
     s.auto_notch = on ? 1 : 0;
     return PSDR_OK;
 }
+extern "C" int psdr_client_set_squelch(psdr_ctx *c, int id, int on, double open_db, double close_db, int attack_frames, int hang_frames) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mtx);
+    switch (squelch_check(c->aslots.data(), c->aslots.size(), id, on, open_db, close_db, attack_frames, hang_frames)) {
+    case SQ_OK: break;
+    case SQ_BAD_ID: return fail(PSDR_ERR_INVALID, "no audio client with id %d", id);
+    case SQ_BAD_DB: return fail(PSDR_ERR_INVALID, "squelch thresholds %g dB / %g dB: finite values inside [-300, 300]", open_db, close_db);
+    case SQ_CLOSE_ABOVE_OPEN: return fail(PSDR_ERR_INVALID, "squelch: close_db %g above open_db %g", close_db, open_db);
+    case SQ_BAD_ATTACK: return fail(PSDR_ERR_INVALID, "squelch: attack_frames %d outside 1..%d", attack_frames, SQUELCH_FRAMES_MAX);
+    case SQ_BAD_HANG: return fail(PSDR_ERR_INVALID, "squelch: hang_frames %d outside 0..%d", hang_frames, SQUELCH_FRAMES_MAX);
+    }
+    if (on) PSDRCHK(squelch_alloc(c));
+    squelch_apply(c->aslots[id], on, open_db, close_db, attack_frames, hang_frames);
+    return PSDR_OK;
+}
 // out[0..2]: the detector's table, sums and counters (null until the context's first auto-notch client); out[3..4]:
 // DemodArgs::notch_man / notch_auto of the last demodulation batch
 extern "C" int psdr_debug_notch_ptrs(psdr_ctx *c, const void *out[5]) {
@@ -368,6 +407,9 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     f.n = c->n, f.nframes = nframes;
     if (band) f.has_band = true, f.band_first = band[0], f.band_count = band[1];
     DemodPlan p;
+    SquelchPlan sq;
+    int *sq_rows[2] = {nullptr, nullptr};
+    SquelchEntry *h_sq = nullptr, *d_sq_list = nullptr;  // this ring slot's image of the squelch table
     int4 *notch_tab = nullptr;
     cf *iq_rows[2] = {nullptr, nullptr}, *car_rows[2] = {nullptr, nullptr};
     {
@@ -382,15 +424,24 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
             return fail(PSDR_ERR_INVALID, "client %d: window [%d, %d) outside the band [%u, %u)", p.bad_slot, p.bad_l, p.bad_r, band[0],
                         band[0] + band[1]);
         }
+        if (c->d_sq_tab) {  // (null until the context's first squelch client)
+            sq_rows[0] = c->sq_pool[0], sq_rows[1] = c->sq_pool[1];
+            h_sq = c->h_sq_tab + (size_t)ring * c->aslots.size(), d_sq_list = c->d_sq_tab + (size_t)ring * c->aslots.size();
+            sq = squelch_plan(c->aslots.data(), c->aslots.size(), c->demod_seq, f.post_on && p.nact > 0, h_sq);
+        }
     }
     c->last_demod_frames = nframes;
     if (p.idle()) return PSDR_OK;
+    // the gates that start from (closed, 0): squelch_plan has taken sq_fresh off these slots, so the zeroing is enqueued before
+    // anything below can fail the batch (`side` orders it behind the last batch's k_squelch and in front of this one's)
+    for (size_t slot : sq.zero) HIPCHK(hipMemsetAsync(c->d_sq_state + slot, 0, sizeof(SquelchState), c->side));
     {  // this batch's results go to the OTHER set (the copies of the last batch to the host may still be reading theirs); what
        // read this set two batches ago must have landed
         c->out_set ^= 1;
         c->d_audio = c->audio_pool[c->out_set], c->d_pwr = c->pwr_pool[c->out_set], c->d_nan = c->nan_pool[c->out_set];
         c->d_iq = iq_rows[c->out_set];  // (null until the context's first IQ client)
         c->d_car = car_rows[c->out_set];  // (... first SAM client)
+        c->d_sq = sq_rows[c->out_set];    // (... first squelch client)
         int rc = fetch_guard_wait(c, c->side, c->guard_audio[c->out_set]);
         if (rc) return rc;
         c->guard_audio[c->out_set] = nullptr;
@@ -410,6 +461,7 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     for (size_t off : p.car_zero) HIPCHK(hipMemsetAsync(c->d_car_tail + off, 0, tail_bytes, c->side));
     for (size_t off : p.ft_zero) HIPCHK(hipMemsetAsync(c->d_ft_tail + off, 0, tail_bytes, c->side));
     for (size_t off : p.sb_zero) HIPCHK(hipMemsetAsync(c->d_sb_tail + off, 0, tail_bytes, c->side));
+    if (sq.any()) HIPCHK(hipMemcpyAsync(d_sq_list, h_sq, (size_t)(sq.nsq + sq.ncopy) * sizeof(SquelchEntry), hipMemcpyHostToDevice, c->side));
     DemodArgs a = demod_args(c, spec, spec_stride, nframes, first_frame_num, band, band_tiled);
     a.clients = ring_at<ClientParams>(d_ring, p.plain.clients);
     a.notch_man = p.any_manual ? ring_at<int4>(d_ring, p.notch) : nullptr;
@@ -538,9 +590,24 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
         hipLaunchKernelGGL(k_notch_detect, dim3((unsigned)p.ndet), dim3(64), 0, c->side, a, p.ndet, na);
         HIPCHK(hipGetLastError());
     }
+    const bool chain = f.post_on && p.nact > 0;
+    const int *chain_drop = c->d_nan;  // what stays out of the chain's streams: the NaN guard's frames ...
+    if (sq.any()) {
+        // the squelch, behind the batch's last demodulation kernel and in front of the chain: it reads pwr and the NaN flags
+        SquelchArgs qa{};
+        qa.list = d_sq_list, qa.nlist = sq.nsq + sq.ncopy;
+        qa.pwr = c->d_pwr, qa.nan_flags = c->d_nan;
+        qa.open = c->d_sq, qa.drop = chain ? c->d_sq_drop.get() : nullptr;
+        qa.state = c->d_sq_state;
+        qa.nframes = nframes, qa.max_batch = c->max_batch;
+        ProfScope ps(c, K_SQUELCH, c->side);
+        hipLaunchKernelGGL(k_squelch, dim3((unsigned)qa.nlist), dim3(64), 0, c->side, qa);
+        HIPCHK(hipGetLastError());
+        if (chain) chain_drop = c->d_sq_drop;  // ... and the closed ones
+    }
     hipStream_t last_user = c->side;
-    if (f.post_on && p.nact > 0)
-        PSDRCHK(post_chain_enqueue(c, a.clients, ring_at<int>(d_ring, p.slot_ci), p.nact, p.npaused, nframes, &last_user));
+    if (chain)
+        PSDRCHK(post_chain_enqueue(c, a.clients, ring_at<int>(d_ring, p.slot_ci), p.nact, p.npaused, nframes, chain_drop, &last_user));
     HIPCHK(c->client_ring.release(ring, last_user));
     if (c->side != c->stream) {
         HIPCHK(hipEventRecord(c->ev_side_done, c->side));
@@ -618,6 +685,7 @@ extern "C" int psdr_fetch_begin(psdr_ctx *c, unsigned what) {
     size_t wf_bytes = 0;
     int iq_lo = (int)S, iq_hi = -1;  // PSDR_FETCH_IQ: the span from the lowest to the highest slot that was IQ in the batch
     int car_lo = (int)S, car_hi = -1;  // the carrier records: ... that was SAM (with any of the audio bits)
+    int sq_lo = (int)S, sq_hi = -1;    // the squelch flags: ... that ran with squelch (with any of the audio bits)
     {
         std::lock_guard<std::mutex> lk(c->mtx);
         fs.win.resize(S);
@@ -626,6 +694,11 @@ extern "C" int psdr_fetch_begin(psdr_ctx *c, unsigned what) {
             fs.win[i].last_seq = sl.active ? sl.last_seq : 0;
             fs.win[i].born = sl.born;
             fs.win[i].l = sl.b_l, fs.win[i].r = sl.b_r, fs.win[i].mid = sl.b_mid, fs.win[i].mode = sl.b_mode;
+            fs.win[i].sq = want_audio && sl.active && sl.last_seq == c->demod_seq && sl.b_sq_on;
+            if (fs.win[i].sq) {
+                sq_lo = std::min(sq_lo, (int)i);
+                sq_hi = (int)i;
+            }
             if ((what & PSDR_FETCH_IQ) && sl.active && sl.last_seq == c->demod_seq && sl.b_mode == PSDR_IQ) {
                 iq_lo = std::min(iq_lo, (int)i);
                 iq_hi = (int)i;
@@ -652,6 +725,12 @@ extern "C" int psdr_fetch_begin(psdr_ctx *c, unsigned what) {
     if ((size_t)fs.car_n > fs.car_cap) {
         PSDRCHK(fs.car.alloc((size_t)fs.car_n * mb));
         fs.car_cap = (size_t)fs.car_n;
+    }
+    fs.sq_lo = sq_hi < 0 ? 0 : sq_lo;
+    fs.sq_n = sq_hi < 0 ? 0 : sq_hi - sq_lo + 1;
+    if ((size_t)fs.sq_n > fs.sq_cap) {
+        PSDRCHK(fs.sq.alloc((size_t)fs.sq_n * mb));
+        fs.sq_cap = (size_t)fs.sq_n;
     }
     if (wf_bytes > fs.wf_cap) {
         PSDRCHK(fs.wf.alloc(wf_bytes));  // (the old rows are given up only once the new buffer exists)
@@ -696,6 +775,15 @@ extern "C" int psdr_fetch_begin(psdr_ctx *c, unsigned what) {
                 HIPCHK(hipMemcpyAsync(fs.car, src, nsl * mb * rb, hipMemcpyDeviceToHost, fst));
             else
                 HIPCHK(hipMemcpy2DAsync(fs.car, mb * rb, src, mb * rb, F * rb, nsl, hipMemcpyDeviceToHost, fst));
+        }
+        if (fs.sq_n > 0) {
+            // the squelch flags of the span's slots, one copy (their pools alternate with the audio's: ev_audio guards them)
+            const size_t rb = sizeof(int32_t), nsl = (size_t)fs.sq_n;
+            const int *src = c->d_sq + (size_t)fs.sq_lo * mb;
+            if (F == mb)
+                HIPCHK(hipMemcpyAsync(fs.sq, src, nsl * mb * rb, hipMemcpyDeviceToHost, fst));
+            else
+                HIPCHK(hipMemcpy2DAsync(fs.sq, mb * rb, src, mb * rb, F * rb, nsl, hipMemcpyDeviceToHost, fst));
         }
         HIPCHK(hipEventRecord(fs.ev_audio, fst));
         c->guard_audio[c->out_set] = fs.ev_audio;
@@ -863,6 +951,24 @@ extern "C" int psdr_fetched_carrier(psdr_ctx *c, int id, int frame, float *level
     if (offset_hz) *offset_hz = rec.y;
     return PSDR_OK;
 }
+extern "C" int psdr_fetched_squelch(psdr_ctx *c, int id, int frame, int32_t *open) {
+    if (!c || !open) return fail(PSDR_ERR_INVALID, "null argument");
+    const psdr_ctx::FetchSet *fs = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);
+        int rc = check_slot(c, id);
+        if (rc) return rc;
+        if ((rc = fetched_set(c, &fs))) return rc;
+        if (fs->seq == 0) return fail(PSDR_ERR_STATE, "the fetched batch carries no audio (PSDR_FETCH_AUDIO / _PCM / _IQ)");
+        if ((size_t)id >= fs->win.size() || fs->win[id].last_seq != fs->seq || fs->win[id].born != c->aslots[id].born)
+            return fail(PSDR_ERR_NO_DATA, "client %d was not part of the fetched batch", id);
+    }
+    if (frame < 0 || frame >= fs->frames) return fail(PSDR_ERR_INVALID, "frame %d not in the fetched batch of %d", frame, fs->frames);
+    // (a slot that ran with squelch lies inside the span by construction; any other reads open)
+    const bool have = fs->win[id].sq && id >= fs->sq_lo && id < fs->sq_lo + fs->sq_n;
+    *open = have ? fs->sq[(size_t)(id - fs->sq_lo) * (size_t)c->max_batch + (size_t)frame] : 1;
+    return PSDR_OK;
+}
 extern "C" int psdr_fetched_iq_span(psdr_ctx *c, int *first_slot, int *nslots, size_t *bytes) {
     if (!c) return fail(PSDR_ERR_INVALID, "null argument");
     const psdr_ctx::FetchSet *fs = nullptr;
@@ -985,6 +1091,31 @@ extern "C" int psdr_read_audio(psdr_ctx *c, int id, int nframes, float *audio, f
         HIPCHK(hipMemcpyAsync(nan_flags, c->d_nan + (size_t)id * mb, F * sizeof(int),
                               hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    return PSDR_OK;
+}
+extern "C" int psdr_read_squelch(psdr_ctx *c, int id, int nframes, int32_t *open, int *nframes_out) {
+    if (!c || !open) return fail(PSDR_ERR_INVALID, "null argument");
+    bool on = false;
+    const size_t F = (size_t)c->last_demod_frames, mb = (size_t)c->max_batch;
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);
+        int rc = check_slot(c, id);
+        if (rc) return rc;
+        if (F == 0) return fail(PSDR_ERR_STATE, "no demodulated batch to read");
+        if (nframes < (int)F) return fail(PSDR_ERR_INVALID, "buffer holds %d frames, the last batch has %zu", nframes, F);
+        if (c->demod_seq == 0 || c->aslots[id].last_seq != c->demod_seq)
+            return fail(PSDR_ERR_NO_DATA, "client %d was not part of the last demodulation batch", id);
+        on = c->aslots[id].b_sq_on;
+    }
+    if (nframes_out) *nframes_out = (int)F;
+    if (!on) {  // the batch ran without squelch for this client: every frame is heard (the host snapshot answers)
+        std::fill(open, open + F, 1);
+        return PSDR_OK;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    int rc = drain(c);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(open, c->d_sq + (size_t)id * mb, F * sizeof(int32_t), hipMemcpyDeviceToHost));
     return PSDR_OK;
 }
 extern "C" int psdr_read_notches(psdr_ctx *c, int id, int first[4], int end[4]) {

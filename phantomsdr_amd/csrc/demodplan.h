@@ -43,6 +43,12 @@ struct AudioSlot {
     int auto_notch = 0;
     bool b_auto = false;
     bool auto_fresh = false;  // switched on since the slot's last batch (a paused client may be switched off and on again)
+    // psdr_client_set_squelch (squelchplan.h): the level gate's thresholds (f32, in the units of pwr) and frame counts; b_sq_on: the
+    // last batch ran with it (psdr_read_squelch); sq_fresh: switched on since the slot's last batch - the state starts from zero
+    int sq_on = 0;
+    float sq_t_open = 1.f, sq_t_close = 1.f;
+    int sq_attack = 1, sq_hang = 0;
+    bool b_sq_on = false, sq_fresh = false;
 };
 
 // The client parameter ring's slot.  [ClientParams x S][int x S]: the batch's list and, for the post chain, the list index of

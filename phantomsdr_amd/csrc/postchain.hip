@@ -314,7 +314,7 @@ static auto pc_with_bools(F &&f, bool b, B... rest) {
 // every slot's client, -1 = not listed).  What is launched, where and with how much LDS is c->post_plan's business
 // (postplan.h); only what depends on nframes is worked out here.
 int psdr::post_chain_enqueue(psdr_ctx *c, const ClientParams *d_clients, const int *d_slot_ci, int nact, int npaused, int nframes,
-                             hipStream_t *last_user) {
+                             const int *d_drop, hipStream_t *last_user) {
     constexpr int NS = psdr_ctx::PC_SETS;
     const PcPlan &p = c->post_plan;
     const int set = (int)(c->chain_seq % NS), nxt = (set + 1) % NS;
@@ -328,7 +328,7 @@ int psdr::post_chain_enqueue(psdr_ctx *c, const ClientParams *d_clients, const i
     PostArgs pa = c->post;
     c->pcm_is16 = p.pcm16;
     pa.audio = c->d_audio;  // (of THIS demodulation batch: the result sets alternate)
-    pa.nan_flags = c->d_nan;
+    pa.nan_flags = d_drop;  // (c->d_nan itself unless the batch has squelch clients: demod.hip)
     pa.clients = d_clients;
     pa.slot_ci = d_slot_ci;
     pa.nact = nact + npaused;
