@@ -31,10 +31,34 @@ CASES = {
     "12k n360 600 slots": (dict(rate=12000, n=360, slots=600),
                            dict(D=32, L=2400, vo=1, agc_ok=1, ma="MA2", agc=FIVE, direct=1, groups=10, lanes=64, rgroups=10, reserve=16, own=1, ma_lds=0, gain_lds=0)),
     "12k n360 600 slots agc0": (dict(rate=12000, n=360, slots=600, agc=0), dict(ma="MA2", agc=FIVE, direct=0, lanes=64, rgroups=10, reserve=16, own=1)),
-    # (the form that shares CUs with the passes: no GPU test reaches it)
+    # (the form that shares CUs with the passes: test_gpu_post_chain_forms.py::test_post_chain_form_is_bit_exact[12000-n360-2000])
     "12k n360 2000 slots": (dict(rate=12000, n=360, slots=2000),
                             dict(D=32, L=2400, vo=1, agc_ok=1, ma="MA2", agc=FIVE, direct=1, groups=32, lanes=64, rgroups=32, reserve=24, own=0, ma_lds=0, gain_lds=0)),
     "12k n360 2000 slots agc0": (dict(rate=12000, n=360, slots=2000, agc=0), dict(ma="MA2", agc=FIVE, direct=0, lanes=64, rgroups=32, reserve=24, own=0, ma_lds=0)),
+    # ---- the rates and frame sizes of test_gpu_post_chain_forms.py: the two one-wave moving averages (MA_POW2: D a power of two
+    # below 16; MA_DIV: any D) in front of either AGC, a look-ahead of one sub-block, frames of one row group
+    "1k n248": (dict(rate=1000, n=248, slots=4), dict(SMALL, D=2, L=200, vo=1, agc_ok=0, ma="MA_POW2", agc=FIVE, rows4=0, nsub=1, sb=200, direct=0, ma_lds=0)),
+    "1.5k n248": (dict(rate=1500, n=248, slots=4), dict(SMALL, D=4, L=300, vo=1, agc_ok=0, ma="MA_POW2", agc=FIVE, rows4=1, nsub=2, sb=150, direct=0)),
+    "3.2k n248": (dict(rate=3200, n=248, slots=4), dict(SMALL, D=8, L=640, vo=1, agc_ok=1, ma="MA_POW2", agc=ONE, rows4=1, nsub=3, direct=0, ma_lds=0)),
+    "3.2k n248 agc0": (dict(rate=3200, n=248, slots=4, agc=0), dict(SMALL, ma="MA_POW2", agc=FIVE, rows4=1, direct=0)),
+    "8k n248": (dict(rate=8000, n=248, slots=4), dict(SMALL, D=20, L=1600, vo=1, agc_ok=1, ma="MA_DIV", agc=ONE, rows4=1, direct=0, ma_lds=0)),
+    "8k n360": (dict(rate=8000, n=360, slots=4), dict(SMALL, D=20, L=1600, h=180, agc_ok=1, ma="MA_DIV", agc=ONE, rows4=1, direct=0)),
+    "8k n248 agc0": (dict(rate=8000, n=248, slots=4, agc=0), dict(SMALL, ma="MA_DIV", agc=FIVE, rows4=1, direct=0)),
+    "16k n248": (dict(rate=16000, n=248, slots=4), dict(SMALL, D=42, L=3200, vo=1, agc_ok=0, ma="MA_DIV", agc=FIVE, rows4=0, direct=0)),
+    "22.05k n248": (dict(rate=22050, n=248, slots=4), dict(SMALL, D=58, L=4410, agc_ok=0, ma="MA_DIV", agc=FIVE, rows4=0, direct=0)),
+    "12k n8": (dict(rate=12000, n=8, slots=4), dict(SMALL, D=32, L=2400, h=4, agc_ok=0, ma="MA2", agc=FIVE, rows4=1, direct=1, ma_lds=0, gain_lds=0)),
+    "12k n32": (dict(rate=12000, n=32, slots=4), dict(SMALL, D=32, L=2400, h=16, agc_ok=1, ma="MA2_CMW", agc=ONE, rows4=1, direct=1)),
+    "12k n32 agc0": (dict(rate=12000, n=32, slots=4, agc=0), dict(SMALL, h=16, agc_ok=1, ma="MA2", agc=FIVE, direct=0)),
+    # ---- ... and its slot counts: whole waves keep k_pc_mad's ring of D * 64 sums in LDS (192 kHz: 128 KiB, the largest request
+    # the library makes), more than 24 work-groups no longer own their SIMDs
+    "48k n248 600 slots": (dict(rate=48000, n=248, slots=600),
+                           dict(D=128, L=9600, agc_ok=1, ma="MAD", agc=FIVE, direct=0, groups=10, lanes=64, rgroups=10, reserve=16, own=1, ma_lds=32 * KiB, gain_lds=0)),
+    "192k n248 600 slots": (dict(rate=192000, n=248, slots=600, max_batch=128),
+                            dict(D=512, L=38400, agc_ok=1, ma="MAD", agc=FIVE, groups=10, lanes=64, rgroups=10, reserve=16, own=1, ma_lds=128 * KiB, gain_lds=0)),
+    "48k n248 1600 slots": (dict(rate=48000, n=248, slots=1600),
+                            dict(D=128, L=9600, ma="MAD", agc=FIVE, groups=25, lanes=64, rgroups=25, reserve=24, own=0, ma_lds=32 * KiB, gain_lds=0)),
+    "3.2k n248 600 slots": (dict(rate=3200, n=248, slots=600), dict(ma="MA_POW2", agc=FIVE, lanes=64, rgroups=10, reserve=16, own=1, ma_lds=0)),
+    "8k n248 600 slots": (dict(rate=8000, n=248, slots=600), dict(ma="MA_DIV", agc=FIVE, lanes=64, rgroups=10, reserve=16, own=1, ma_lds=0)),
     # ---- the derived numbers of the first row, spelled out (max_batch 512: Tm = 63488)
     "12k n248 numbers": (dict(rate=12000, n=248, slots=4),
                          dict(h=124, px=63840, pv=66208, nsub=10, sb=240, nch=150 + 3968 + 8, h_magic=34636834, nblk=28, att_faster=1, pcm16=0, skip=0)),
