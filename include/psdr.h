@@ -143,6 +143,46 @@ int psdr_ring_write_async(psdr_ctx *ctx, uint64_t half_index, const void *host_h
 int psdr_ring_wait(psdr_ctx *ctx, uint64_t half_index);
 int psdr_process_ring(psdr_ctx *ctx, uint64_t first_half, int nframes);
 
+/* ---- wideband impulse blanker on the ring, ahead of the forward FFT (no counterpart in the reference: its browser-side
+ * blanker, jsdsp/lib/NB.c, works on the 12 kHz audio, where an impulse is already as long as the client's filter) ----------
+ * An impulse from a power line, an electric fence or a switching supply is a few samples long at the input rate; behind an
+ * N-point frame it is a raised floor in every bin, for every audio client and every waterfall row.  The raw ring is the
+ * only place where it is still short.  Opt-in per context: a context that never calls psdr_ring_set_blanker allocates,
+ * launches and computes exactly what it did without it.  The rule, per half-frame H of N/2 samples:
+ *   power      P_i, one f32 per sample.  Integer formats: the converter's unscaled integers a, b (behind the MSB flip of u8 /
+ *              u16), a*a + b*b (real input: a*a) exactly in unsigned 32-bit arithmetic (at most 2^31), converted once to f32,
+ *              round to nearest even.  f32: fl(fl(re*re) + fl(im*im)), nothing fused.  f64: narrowed to f32 first, as the first
+ *              FFT pass does.  Every maximum is m = (P > m) ? P : m from +0.0: a NaN P is never a maximum and never above a
+ *              threshold.
+ *   reference  the half is cut into blocks of 256 consecutive samples (at least 8).  M_b = the maximum of P over block b,
+ *              R_H = the minimum of M_b over the half's blocks: a few impulses raise a few M_b and leave the minimum alone.
+ *              For complex Gaussian noise of mean power mu, R sits around 4 - 6 mu: threshold_db is relative to R, NOT to
+ *              the mean power.
+ *   threshold  kf = (float)pow(10, threshold_db / 10); T_H = kf * R_(H-1), one f32 product: the level comes from the RAW
+ *              samples of the half before.  If half H - 1 was not blanked by this context directly before H (the first half
+ *              after switching on, a jump ahead in first_half), R_(H-1) := R_H.  T_H = 0 (digital silence) or not finite (an
+ *              Inf half): nothing in half H is blanked.
+ *   blanking   exceed_j = (P_j > T_H) on the raw samples; sample i of half H is zeroed if and only if some j of the SAME half
+ *              with |i - j| <= guard exceeds (the guard is clipped to the half).  Both components are zeroed, to the code the
+ *              converter maps to 0.0: 0 for signed formats, +0.0 for floats, 0x80 for u8, 0x8000 for u16.
+ * Each half is blanked exactly once, in place, inside the psdr_process_ring call that first reads it: on the context's stream,
+ * behind the waits for the half's copy and in front of the first FFT pass.  The half in slot 0 exists twice (slot 0 and its
+ * mirror behind the last slot): both copies get the same bytes.  The library keeps the index of the next half to blank: halves
+ * below it are skipped (a call that re-reads old halves), a call whose first half lies above it restarts the reference.  Any
+ * split of the same stream into psdr_process_ring calls gives the same ring bytes, counts and levels.
+ * psdr_ring_set_blanker: frame-loop thread only, like the ring calls; takes force at the next psdr_process_ring; switching on
+ * starts the reference afresh.  threshold_db finite in [0, 90], guard in 0..255 (on = 0 ignores both) - anything else is
+ * PSDR_ERR_INVALID and changes nothing; PSDR_ERR_STATE without a ring.  The first on = 1 allocates the device state (block
+ * maxima, levels and counts of max_batch + 1 halves, the blocks' masks), all or none: PSDR_ERR_NOMEM leaves the setting as
+ * it was.  psdr_process_batch (the caller's const buffer), the Level-1 path and psdr_group_* are not touched.
+ * psdr_ring_read_blanker: for a half blanked by the LAST psdr_process_ring call, the number of samples zeroed (what a
+ * "blanker active" indicator shows) and R_H; synchronises; PSDR_ERR_NO_DATA for any other half; either pointer may be NULL.
+ * psdr_ring_read: drains, then copies slot half_index % nhalves to host_half (psdr_half_frame_bytes) - the slot's bytes as
+ * the first pass reads them; for a server that records. */
+int psdr_ring_set_blanker(psdr_ctx *ctx, int on, double threshold_db, int guard);
+int psdr_ring_read_blanker(psdr_ctx *ctx, uint64_t half_index, uint32_t *blanked, float *ref_level);
+int psdr_ring_read(psdr_ctx *ctx, uint64_t half_index, void *host_half);
+
 /* ---- Level 2: batched frames ------------------------------------------------------ */
 /* Frame loop body, src/fft.cpp:47-105, for nframes consecutive frames at once.
  * d_halves: device pointer to nframes+1 consecutive raw half-frames (cfg.input_format);

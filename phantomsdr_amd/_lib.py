@@ -59,6 +59,9 @@ SYMBOLS = [
     ("psdr_ring_write_async", _i, [_vp, _u64, _vp]),
     ("psdr_ring_wait", _i, [_vp, _u64]),
     ("psdr_process_ring", _i, [_vp, _u64, _i]),
+    ("psdr_ring_set_blanker", _i, [_vp, _i, C.c_double, _i]),
+    ("psdr_ring_read_blanker", _i, [_vp, _u64, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
+    ("psdr_ring_read", _i, [_vp, _u64, _vp]),
     ("psdr_process_batch", _i, [_vp, _vp, _i]),
     ("psdr_client_add", _i, [_vp, C.POINTER(_i)]),
     ("psdr_client_remove", _i, [_vp, _i]),

@@ -268,6 +268,26 @@ class Context:
         check(self.lib.psdr_process_ring(self.h, int(first_half), int(nframes)))
         self.last_nframes = nframes
 
+    def ring_set_blanker(self, on, threshold_db=0.0, guard=0):
+        """the impulse blanker on the ring, ahead of the FFT (psdr.h: psdr_ring_set_blanker); threshold_db is relative to the
+        reference level R (the smallest block maximum of the half before), not to the mean power"""
+        check(self.lib.psdr_ring_set_blanker(self.h, int(bool(on)), float(threshold_db), int(guard)))
+
+    def ring_read_blanker(self, half_index):
+        """(samples zeroed, R) of a half the last process_ring blanked, or None for any other half"""
+        n, r = C.c_uint32(0), C.c_float(0.0)
+        rc = self.lib.psdr_ring_read_blanker(self.h, int(half_index), C.byref(n), C.byref(r))
+        if rc == -7:  # PSDR_ERR_NO_DATA
+            return None
+        check(rc)
+        return n.value, np.float32(r.value)
+
+    def ring_read(self, half_index, dtype=np.uint8):
+        """the bytes of slot half_index % nhalves as the first pass reads them (drains first)"""
+        out = np.empty(self.half_frame_bytes(), np.uint8)
+        check(self.lib.psdr_ring_read(self.h, int(half_index), _ptr(out)))
+        return out.view(dtype)
+
     def pinned_array(self, nbytes, dtype=np.uint8):
         """numpy view of pinned host memory from psdr_host_alloc (freed with the context)"""
         p = C.c_void_p()

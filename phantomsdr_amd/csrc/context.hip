@@ -26,7 +26,7 @@ namespace psdr {
 const char *kKernelNames[K_COUNT] = {"fft_pass1",  "fft_pass2", "untangle_real", "pyramid_tail",
                                      "demod_idft", "demod_ola", "waterfall_gather", "post_chain",
                                      "real_seam",  "band_pack",  "waterfall_hold", "waterfall_carry",
-                                     "squelch"};
+                                     "squelch",    "blanker_scan", "blanker_apply"};
 
 void resolve_pending(psdr_ctx *c) {
     if (c->pending.empty()) return;
@@ -610,6 +610,11 @@ extern "C" int psdr_process_ring(psdr_ctx *c, uint64_t first_half, int nframes) 
     r.seq++;
     hipEvent_t ev = r.ev_read[r.seq % psdr_ctx::IngestRing::NEV];
     HIPCHK(hipEventSynchronize(ev));  // the call that used it NEV calls ago (no-op if never recorded)
+    // the impulse blanker (blanker.hip): behind the waits for the copies, in front of pass 1, so that `ev` covers it too
+    if (c->nb.on)
+        PSDRCHK(blanker_enqueue(c, first_half, nframes));
+    else
+        c->nb.last_n = 0;
     int rc = process_frames(c, r.d + (size_t)s0 * r.hb, nframes, c->cfg.input_format, ev);
     if (rc) return rc;
     for (int i = 0; i <= nframes; i++) r.reader_seq[(s0 + i) % r.nhalves] = r.seq;

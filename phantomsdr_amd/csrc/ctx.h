@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/psdr.h"
+#include "blankerplan.h"
 #include "butterfly.h"
 #include "demodplan.h"
 #include "owned.h"
@@ -57,7 +58,7 @@ inline const char *psdr_tuning_env(const char *name) {
 
 namespace psdr {
 
-enum KernelId { K_PASS1, K_PASS2, K_UNTANGLE, K_TAIL, K_IDFT, K_OLA, K_WFALL, K_POST, K_SEAM, K_BAND, K_WFHOLD, K_WFCARRY, K_SQUELCH, K_COUNT };
+enum KernelId { K_PASS1, K_PASS2, K_UNTANGLE, K_TAIL, K_IDFT, K_OLA, K_WFALL, K_POST, K_SEAM, K_BAND, K_WFHOLD, K_WFCARRY, K_SQUELCH, K_NB_SCAN, K_NB_APPLY, K_COUNT };
 extern const char *kKernelNames[K_COUNT];
 
 struct PendingEvent {
@@ -389,6 +390,21 @@ struct psdr_ctx {
         Event ev_read[NEV];                   // pass 1 of process call seq % NEV has consumed its halves
         uint64_t seq = 0;
     } ring;
+    // impulse blanker on the ring (blanker.h, in front of pass 1): the block maxima [max_batch + 1][N/2/256], the ring of
+    // reference levels [max_batch + 2] (blankerplan.h: NbState::rpos), the blocks' masks [..][8], the work list and the counts
+    // [max_batch + 1] with the list's length behind them - all of it allocated by the first psdr_ring_set_blanker(on = 1), or
+    // none, and kept.  Frame-loop thread only, like the ring.
+    struct Blanker {
+        bool on = false;
+        float kf = 1.f;
+        int guard = 0;
+        NbState st;
+        int rcap = 0;
+        DevBuf<float> d_bmax, d_R;
+        DevBuf<unsigned> d_mask, d_list, d_count;
+        uint64_t last_first = 0;  // the halves the LAST psdr_process_ring blanked (psdr_ring_read_blanker), and where their R sits
+        int last_n = 0, last_r0 = 0;
+    } nb;
 
     // instrumentation
     bool profiling = false;   // psdr_set_profiling mode 1: hipEvent brackets around every launch
@@ -472,6 +488,8 @@ void seg_plan_counts(const psdr_ctx *c, int nframes, unsigned *nsegs, unsigned *
 int seg_plan(psdr_ctx *c, int nframes, const psdr_ctx::SegPlan **out);  // (built and uploaded on first use of a batch size)
 int process_frames(psdr_ctx *c, const void *d_halves, int nframes, int fmt, hipEvent_t ev_raw_consumed = nullptr);
 int set_wf_default_detector(psdr_ctx *c, int detector);  // PSDR_OPT_WATERFALL_DETECTOR
+// blanker.hip: the blanker's kernels for the halves this psdr_process_ring call reads first, on c->stream
+int blanker_enqueue(psdr_ctx *c, uint64_t first_half, int nframes);
 // pass1.hip / pass2.hip (Pass1Args / Pass2Args: fft_pass.h)
 struct Pass1Args;
 struct Pass2Args;
