@@ -188,24 +188,17 @@ int build(psdr_ctx *c) {
     if (c->real_fused) {
         // one frame of k-order staging for psdr_read_spectrum / psdr_get_output_buffer
         PSDRCHK(c->d_Z.alloc(c->M + 2));
-        if (const char *e = getenv("PSDR_SEG_LEN")) c->seg_len_env = atoi(e);
-        size_t cap = 0, capc = 0;
-        for (int nf = 1; nf <= c->max_batch; nf++) {
-            unsigned ns, nm;
-            bool ho;
-            seg_plan_counts(c, nf, &ns, &nm, &ho);
-            cap = std::max(cap, (size_t)nm);
-            capc = std::max(capc, (size_t)ns);
-        }
-        c->seam_cap = cap;
-        c->seg_cap = capc;
+        c->seg_facts.G = c->M1 / c->T2;
+        c->seg_facts.num_cus = c->num_cus;
+        if (const char *e = getenv("PSDR_SEG_LEN")) c->seg_facts.seg_len_env = atoi(e);
+        const size_t cap = c->seg_cap = seg_cap(c->seg_facts, c->max_batch);  // (in hand-off mode any segment may fall back to a seam)
         for (int st = 0; st < 2; st++) {  // part of the double-buffered result sets: k_real_seam is a consumer
             PSDRCHK(c->seam_pool[st][0].alloc(cap * (size_t)c->M2 * (size_t)(c->T2 / 2)));  // [segment][M2][couples per tile]
-            PSDRCHK(c->seam_pool[st][1].alloc(capc * (size_t)c->M2));
+            PSDRCHK(c->seam_pool[st][1].alloc(cap * (size_t)c->M2));
         }
         // flags (inside a launch only), then the fallback marks - ONE ARRAY PER RESULT SET: k_real_seam is a consumer, it may
         // run after the next batch's second pass has started writing its own marks
-        PSDRCHK(c->d_segflag.alloc(3 * capc, true));
+        PSDRCHK(c->d_segflag.alloc(3 * cap, true));
         {  // the plans of the two batch sizes every caller uses, now rather than in the first batch (a synchronous upload)
             const psdr_ctx::SegPlan *sp;
             int rc = seg_plan(c, c->max_batch, &sp);
@@ -223,6 +216,12 @@ int build(psdr_ctx *c) {
     }
     select_set(c, 0);
     c->q_untiled.assign(F, 0);
+    {  // the pyramid levels above the tile
+        TailFacts t;
+        t.R = c->R, t.levels = c->levels, t.LT = c->LT, t.log2M2 = c->log2M2, t.M2 = c->M2, t.real_fused = c->real_fused;
+        t.mapped = c->recmap.mapped, t.l2gpt = c->recmap.l2gpt, t.pair = c->recmap.pair;
+        c->tails = tails_plan(t);
+    }
     // ---- level-1 staging
     PSDRCHK(c->d_stage.alloc(c->is_real ? c->N : 2 * c->N));
     {
@@ -621,6 +620,14 @@ extern "C" int psdr_process_ring(psdr_ctx *c, uint64_t first_half, int nframes) 
     return PSDR_OK;
 }
 
+int psdr::side_done(psdr_ctx *c) {
+    if (c->side == c->stream) return PSDR_OK;
+    HIPCHK(hipEventRecord(c->ev_side_done, c->side));
+    c->side_pending = true;
+    HIPCHK(hipEventRecord(c->ev_set_done[c->cur_set], c->side));
+    c->set_pending[c->cur_set] = true;
+    return PSDR_OK;
+}
 int psdr::drain(psdr_ctx *c) {
     if (c->ring.copy) HIPCHK(hipStreamSynchronize(c->ring.copy));
     HIPCHK(hipStreamSynchronize(c->stream));

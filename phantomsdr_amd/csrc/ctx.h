@@ -20,6 +20,7 @@
 #include "blankerplan.h"
 #include "butterfly.h"
 #include "demodplan.h"
+#include "forwardplan.h"
 #include "owned.h"
 #include "postplan.h"
 #include "quantize.h"
@@ -65,17 +66,6 @@ struct PendingEvent {
     Event a, b;
     int kid;
 };
-struct WfSlot {
-    bool active = false;
-    int level = 0, l = 0, r = 0;
-    int det = PSDR_WF_SAMPLE;  // psdr_waterfall_set_detector
-    // the last psdr_waterfall_batch: what was gathered, and with which window (set_range may run
-    // on another thread between the batch and psdr_read_waterfall)
-    size_t out_off = 0;
-    int nsent = 0;
-    int b_level = 0, b_l = 0, b_r = 0;
-    int b_det = PSDR_WF_SAMPLE;
-};
 
 // Small host->device parameter blocks (client lists) are double-buffered K deep so a new
 // batch can be enqueued without waiting for the previous one to drain.
@@ -111,6 +101,8 @@ struct ParamRing {
 
 // the client parameter ring's slot: demodplan.h (host-only: it spells sizeof(int4) as a number)
 static_assert(sizeof(int4) == NOTCH_ENTRY, "a slot's manual notches are one int4 (DemodArgs::notch_man)");
+// the segment table's entry: forwardplan.h (host-only: it spells uint4 as four unsigneds)
+static_assert(sizeof(uint4) == sizeof(SegEntry), "a segment table entry is one uint4 (Pass2Args::segtab, SeamArgs::segtab)");
 
 inline int ilog2(size_t v) {
     int l = 0;
@@ -135,15 +127,15 @@ struct psdr_ctx {
     bool real_fused = false;
     SpecLayout lay{};                // device layout of the spectrum (natural unless real_fused)
     int nbands = 0, band_H = 0;      // psdr_set_band_layout: band regions (SpecLayout mode 3), halo columns per band
-    int seg_len_env = 0;             // PSDR_SEG_LEN: tiles per chain segment (uniform segments, every one with a seam)
+    SegFacts seg_facts;              // what the chain segments are planned from (forwardplan.h); seg_len_env: PSDR_SEG_LEN, read at create
     float *d_seamP = nullptr, *d_seamC = nullptr;  // views: seam_pool[cur_set][0 / 1]
     DevBuf<float> seam_pool[2][2];
-    size_t seam_cap = 0, seg_cap = 0;  // segments without a carry-in the seamP buffers hold; segments (seamC, flags)
-    // chain segments of the fused real second pass for a batch of `nframes` frames (forward.hip: seg_plan)
+    size_t seg_cap = 0;  // segments the seam buffers (seamP, seamC) and the flags hold: seg_cap(seg_facts, max_batch)
+    // chain segments of the fused real second pass for a batch of `nframes` frames (forwardplan.h; forward.hip: seg_plan)
     struct SegPlan {
         int nframes = 0;
-        unsigned nsegs = 0, nseam = 0;  // the nseam segments without a carry-in come first
-        bool handoff = false;           // the others get their carried row through memory inside the launch
+        unsigned nsegs = 0;
+        bool handoff = false;  // all but a frame's top segment get their carried row through memory inside the launch
         DevBuf<uint4> d_tab;
     };
     std::vector<SegPlan> seg_plans;  // one per batch size seen
@@ -155,6 +147,7 @@ struct psdr_ctx {
     size_t spec_stride = 0;  // complex elements per frame
     size_t q_len = 0, q_stride = 0;
     int LT = 0;  // pyramid levels finished inside the fused kernel
+    TailPlan tails;  // ... and who finishes the others (forwardplan.h), resolved at create
     size_t p_stride = 0;
     int max_batch = 1;
     int min_waterfall_fft = 0;  // input.waterfall_size (src/spectrumserver.cpp:56)
@@ -372,10 +365,8 @@ struct psdr_ctx {
     int opt_wf_det = PSDR_WF_SAMPLE;   // PSDR_OPT_WATERFALL_DETECTOR: what psdr_waterfall_add hands a new client
     DevBuf<int8_t> d_wf_peak;
     DevBuf<uint32_t> d_wf_sum;
-    size_t wf_lenA = 0, wf_qB0 = 0, wf_lenB = 0;
-    bool wf_run = false;               // the last psdr_waterfall_batch kept the carry (some client had a detector)
-    uint64_t wf_next = 0;              // ... and the first_frame_num that continues it
-    int wf_carry_n = 0;                // frames the carry stands for
+    WfCarryLayout wf_lay;              // which bytes of a frame's record buffers the carry mirrors (forwardplan.h)
+    WfCarry wf_carry;                  // the run the carry belongs to
 
     // streaming ingest ring (psdr_ring_*)
     struct IngestRing {
@@ -474,6 +465,8 @@ inline unsigned persistent_grid(psdr_ctx *c, unsigned blocks, size_t lds) {
 
 // context.hip
 int drain(psdr_ctx *c);
+// what was just enqueued on `side` reads the current result set: the next drain and the set's next writer wait for it
+int side_done(psdr_ctx *c);
 // postchain.hip: resolves post_plan again (after a drain: psdr_set_post_chain, the chain's options, psdr_set_stream)
 void pc_replan(psdr_ctx *c);
 // demod.hip: the next writer of a device-side result buffer on stream `st` waits for the fetch that read it (ev may be null)
@@ -483,8 +476,6 @@ void resolve_kclock(psdr_ctx *c);
 int reset_kclock(psdr_ctx *c);
 // forward.hip
 void select_set(psdr_ctx *c, int set);
-int real_seg_len(const psdr_ctx *c, int nframes);
-void seg_plan_counts(const psdr_ctx *c, int nframes, unsigned *nsegs, unsigned *nseam, bool *handoff);
 int seg_plan(psdr_ctx *c, int nframes, const psdr_ctx::SegPlan **out);  // (built and uploaded on first use of a batch size)
 int process_frames(psdr_ctx *c, const void *d_halves, int nframes, int fmt, hipEvent_t ev_raw_consumed = nullptr);
 int set_wf_default_detector(psdr_ctx *c, int detector);  // PSDR_OPT_WATERFALL_DETECTOR

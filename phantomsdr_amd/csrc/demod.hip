@@ -609,13 +609,7 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     if (chain)
         PSDRCHK(post_chain_enqueue(c, a.clients, ring_at<int>(d_ring, p.slot_ci), p.nact, p.npaused, nframes, chain_drop, &last_user));
     HIPCHK(c->client_ring.release(ring, last_user));
-    if (c->side != c->stream) {
-        HIPCHK(hipEventRecord(c->ev_side_done, c->side));
-        c->side_pending = true;
-        HIPCHK(hipEventRecord(c->ev_set_done[c->cur_set], c->side));
-        c->set_pending[c->cur_set] = true;
-    }
-    return PSDR_OK;
+    return side_done(c);
 }
 
 // A slot whose client attached AFTER the last demodulation batch holds the previous occupant's results (or

@@ -26,83 +26,9 @@ static int next_tickets(psdr_ctx *c, int which, hipStream_t st, unsigned **out) 
     pos++;
     return PSDR_OK;
 }
-// Tiles of one frame a work-group walks in a chain: long chains carry the mirror-side octets in LDS
-// (nothing extra in HBM), short chains give the persistent grid enough independent segments.  Aim
-// for about two segments per work-group: the pass is bound by memory, not by balance (256 frames of
-// 2^21 points, same box: 1012-1023 us with 16 segments per work-group, 990-1030 with 8, 4 or 2), and
-// every segment costs one seam (k_real_seam: 177 / 89 / 52 / 31 us at 4 / 8 / 16 / 32 tiles per segment,
-// run beside the next batch's pass 1, which it slows).
-int real_seg_len(const psdr_ctx *c, int nframes) {
-    const int G = c->M1 / c->T2;  // tiles of a frame
-    if (c->seg_len_env > 0) {
-        int sl = 1;
-        while (sl * 2 <= c->seg_len_env && sl * 2 <= G) sl *= 2;
-        return sl;
-    }
-    const int W = std::max(c->num_cus, 1);
-    const long long tiles = (long long)G * nframes;  // of the batch
-    auto pow2_floor = [&](long long v) {
-        int sl = 1;
-        while (sl * 2 <= v && sl * 2 <= G) sl *= 2;
-        return sl;
-    };
-    const long long want = tiles / (2LL * W);
-    // What the measurements say (cfg3's stream, tools/ab_small_batches.sh, profiles/r04b_uniform_segments_small_batches.jsonl):
-    // up to 16 tiles per work-group ONE static segment each, rounded up to a power of two (32 frames: 256 segments of 8
-    // tiles 151 GS/s, 512 of 4 - the old choice - 140; 48 frames: 192 of 16 tiles 155, 768 of 4 141); two static segments per
-    // work-group when that comes out even (128, 256 frames of 2^21 points: nothing to balance, nothing drawn); else five
-    // to ten segments per work-group, so that the ticket counter has something to balance with - a work-group draws two
-    // tickets ahead, and with three or four segments each half the chip ends up with one more than the other half (192
-    // frames: 16-tile segments 158 GS/s, 8-tile segments 168; 384 frames: 162 / 182).
-    const long long per_wg = (tiles + W - 1) / W;
-    if (per_wg <= 16) {
-        int sl = 1;
-        while (sl < per_wg && sl * 2 <= G) sl *= 2;
-        return sl;
-    }
-    if (2LL * W * want == tiles && (want & (want - 1)) == 0 && want <= G) return (int)want;
-    return pow2_floor(tiles / (5LL * W));
-}
-// Chain segments of a batch (k_fft_pass2_real, fft_pass.h).  Two forms:
-//  * uniform segments of real_seg_len() tiles, frame-major, every segment's first tile WITHOUT a carry-in (it leaves its
-//    partial octets in seamP, k_real_seam completes them): small batches, PSDR_SEG_LEN, static tile hand-out;
-//  * hand-off (batches of more than one frame per work-group - seg_plan_counts): a frame is cut into segments of G/4, G/4, G/4, G/8, ... 2,
-//    1, 1 tiles from the top, handed out LEVEL-major - all frames' top segments first, then all second segments, ... - by
-//    the ticket counter alone.  Only the top segment of a frame has no carry-in (the ring closes through tile 0's row
-//    M1/2: one seam per frame, as with whole-frame segments); every other segment reads the carried row its predecessor -
-//    handed out nframes tickets earlier, i.e. finished about a round of segments ago - left in seamC behind its flag.
-//    What it buys: the work-groups of a launch differ by +-3.5 % in speed (the even XCDs are ~3 % slower: tools/trace_real.py),
-//    and with two whole-frame segments each nothing balanced that - the launch ended with its slowest work-group, 3.4 %
-//    after the median one.  With tickets and segments that shrink to single tiles the spread at the end is one tile, at
-//    a cost of 8 KiB of traffic per hand-off (a seam: 92 KiB and a record written twice).
-// tiles per segment from the top of a frame: G/4, G/4, G/4, G/8, ... 2, 1, 1
-static std::vector<int> seg_plan_lens(const psdr_ctx *c) {
-    const int G = c->M1 / c->T2;  // tiles of a frame
-    std::vector<int> lens = {G / 4, G / 4, G / 4};
-    for (int l = G / 8; l >= 1; l >>= 1) lens.push_back(l);
-    lens.push_back(1);
-    return lens;
-}
-void seg_plan_counts(const psdr_ctx *c, int nframes, unsigned *nsegs, unsigned *nseam, bool *handoff) {
-    const int G = c->M1 / c->T2;  // tiles of a frame
-    // (PSDR_SEG_LEN=n is the way back to uniform segments)
-    // Which batches take the hand-off plan: those of more than one frame per work-group (cfg3's stream at 258 / 288 / 320 /
-    // 384 / 448 / 512 frames: +11 / +29 / +25 / +12 / +6 / +1.5 % over the uniform segments of round 3; against the uniform
-    // segments real_seg_len() picks now it is level at 320 and 384 frames and 1 - 5 % ahead at 512).  Up to one frame per
-    // work-group a segment's predecessor is less than a segment ahead, most hand-offs end as seams, and well-chosen uniform
-    // segments are 3 - 9 % faster (profiles/r04b_handoff_vs_uniform_by_batch.jsonl, r04b_uniform_segments_small_batches.jsonl).
-    const int W = std::max(c->num_cus, 1);
-    const bool want = nframes >= W + 1;
-    const bool ho = c->seg_len_env <= 0 && G >= 16 && want;
-    if (ho) {
-        const int levels = (int)seg_plan_lens(c).size();
-        *nsegs = (unsigned)(levels * nframes);
-        *nseam = *nsegs;  // (any segment may fall back to a seam: seamP has room for all of them)
-    } else {
-        *nsegs = *nseam = (unsigned)(nframes * (G / real_seg_len(c, nframes)));
-    }
-    *handoff = ho;
-}
+static_assert(SEG_CARRY_MEM == PSDR_SEG_CARRY_MEM, "forwardplan.h writes the flag fft_pass.h reads");
+// the chain segments of a batch of nframes frames (forwardplan.h): planned, checked against what the seam buffers hold and
+// uploaded on first use of a batch size
 int seg_plan(psdr_ctx *c, int nframes, const psdr_ctx::SegPlan **out) {
     for (const auto &sp : c->seg_plans)
         if (sp.nframes == nframes) {
@@ -111,34 +37,13 @@ int seg_plan(psdr_ctx *c, int nframes, const psdr_ctx::SegPlan **out) {
         }
     psdr_ctx::SegPlan sp;
     sp.nframes = nframes;
-    seg_plan_counts(c, nframes, &sp.nsegs, &sp.nseam, &sp.handoff);
-    const int G = c->M1 / c->T2;  // tiles of a frame
-    std::vector<uint4> tab(sp.nsegs);
-    if (sp.handoff) {
-        const std::vector<int> lens = seg_plan_lens(c);
-        const int levels = (int)lens.size();
-        // Level-major, frames in order: a segment's predecessor - the same frame one level up - is handed out nframes >=
-        // 2 * grid indices earlier, i.e. about two segments of every work-group earlier.
-        int g = G - 1;
-        for (int lv = 0; lv < levels; lv++) {
-            for (int f = 0; f < nframes; f++) {
-                const unsigned above = (unsigned)((lv ? lv - 1 : levels - 1) * nframes + f);  // (the top segment's: the bottom one)
-                tab[(size_t)lv * nframes + f] = make_uint4((unsigned)f, (unsigned)g | ((unsigned)lens[lv] << 16), above,
-                                                           lv ? (unsigned)PSDR_SEG_CARRY_MEM : 0u);
-            }
-            g -= lens[lv];
-        }
-    } else {
-        const int SL = real_seg_len(c, nframes), S = G / SL;
-        for (int f = 0; f < nframes; f++)
-            for (int si = 0; si < S; si++)
-                tab[(size_t)f * S + si] = make_uint4((unsigned)f, (unsigned)((si + 1) * SL - 1) | ((unsigned)SL << 16),
-                                                     (unsigned)(f * S + (si + 1) % S), 0u);
-    }
-    if (sp.nseam > c->seam_cap || sp.nsegs > c->seg_cap)
-        return fail(PSDR_ERR_STATE, "seam buffers too small (%u + %u segments, %zu + %zu allocated)", sp.nseam, sp.nsegs, c->seam_cap, c->seg_cap);
+    sp.nsegs = seg_count(c->seg_facts, nframes);
+    sp.handoff = seg_handoff(c->seg_facts, nframes);
+    if (sp.nsegs > c->seg_cap) return fail(PSDR_ERR_STATE, "seam buffers too small (%u segments, %zu allocated)", sp.nsegs, c->seg_cap);
+    std::vector<SegEntry> tab(sp.nsegs);
+    seg_table(c->seg_facts, nframes, tab.data());
     PSDRCHK(sp.d_tab.alloc(tab.size()));
-    HIPCHK(hipMemcpy(sp.d_tab, tab.data(), tab.size() * sizeof(uint4), hipMemcpyHostToDevice));  // (once per batch size)
+    HIPCHK(hipMemcpy(sp.d_tab, tab.data(), tab.size() * sizeof(SegEntry), hipMemcpyHostToDevice));  // (once per batch size)
     c->seg_plans.push_back(std::move(sp));
     *out = &c->seg_plans.back();
     return PSDR_OK;
@@ -174,79 +79,63 @@ static int enqueue_tails(psdr_ctx *c) {
         sa.Pscr = c->d_pscr[0];
         sa.p_stride = c->p_stride;
         ProfScope ps(c, K_SEAM, c->side);
-        hipLaunchKernelGGL(k_real_seam, dim3(plan->handoff ? plan->nsegs : plan->nseam), dim3(256), 0, c->side, sa);
+        hipLaunchKernelGGL(k_real_seam, dim3(plan->nsegs), dim3(256), 0, c->side, sa);
         HIPCHK(hipGetLastError());
     }
-    // remaining pyramid levels from the partial level in scratch
-    int lvl = c->LT;
-    size_t len = c->R >> lvl;
-    int cur = 0;
-    // tile-major sums of a fused pass 2 (rows of 1024 outputs): one thread per output row takes the
-    // levels inside a row (k_col_tail), the generic kernel the few above
-    const int ng = (int)(len >> c->log2M2);  // groups per output row
-    const bool col_tail = c->recmap.mapped && (c->M2 == 1024 || (c->M2 == 2048 && c->real_fused)) && c->recmap.l2gpt == 0 &&
-                          (ng == 64 || ng == 128 || ng == 256);
-    if (col_tail && lvl + 1 < c->levels) {
-        ColTailArgs t{};
-        t.Pin = c->d_pscr[0];
-        t.in_stride = c->p_stride;
-        t.mode = c->recmap.mapped;
-        t.L = c->M2;
-        t.l2L = c->log2M2;
-        t.lvl_in = lvl;
-        t.nlevels = c->levels;
-        t.size_log2 = c->size_log2;
-        t.Q = c->d_q;
-        t.q_stride = c->q_stride;
-        t.R = c->R;
-        t.Pout = c->d_pscr[1];
-        t.out_stride = c->p_stride;
+    // remaining pyramid levels from the partial level in scratch: the steps psdr_create planned (forwardplan.h: tails_plan)
+    for (int i = 0; i < c->tails.n; i++) {
+        const TailStep &st = c->tails.step[i];
         ProfScope ps(c, K_TAIL, c->side);
-        const dim3 grid((unsigned)(c->M2 / 64), (unsigned)nframes);
-        if (ng == 64)
-            hipLaunchKernelGGL(k_col_tail<64>, grid, dim3(64), 0, c->side, t);
-        else if (ng == 128)
-            hipLaunchKernelGGL(k_col_tail<128>, grid, dim3(64), 0, c->side, t);
-        else if (c->recmap.pair)  // quartet records side by side (2048-point rows): one 8-byte load per (tile, column)
-            hipLaunchKernelGGL((k_col_tail<256, true>), grid, dim3(64), 0, c->side, t);
-        else
-            hipLaunchKernelGGL(k_col_tail<256>, grid, dim3(64), 0, c->side, t);
+        if (st.kind == TAIL_GENERIC) {
+            TailArgs t{};
+            t.Pin = c->d_pscr[st.src];
+            t.in_stride = c->p_stride;
+            t.len_in = st.len_in;
+            t.lvl_in = st.lvl_in;
+            t.nlevels = c->levels;
+            t.size_log2 = c->size_log2;
+            t.Q = c->d_q;
+            t.q_stride = c->q_stride;
+            t.R = c->R;
+            t.Pout = c->d_pscr[st.dst];
+            t.out_stride = c->p_stride;
+            t.map = c->recmap;
+            if (!st.mapped) t.map.mapped = 0;  // only pass 2's own output is tile-major
+            const unsigned nb = (unsigned)((st.len_in / 2 + 255) / 256);
+            hipLaunchKernelGGL(k_pyramid_tail, dim3(nb, nframes), dim3(256), 0, c->side, t);
+        } else {
+            ColTailArgs t{};
+            t.Pin = c->d_pscr[st.src];
+            t.in_stride = c->p_stride;
+            t.mode = c->recmap.mapped;
+            t.L = c->M2;
+            t.l2L = c->log2M2;
+            t.lvl_in = st.lvl_in;
+            t.nlevels = c->levels;
+            t.size_log2 = c->size_log2;
+            t.Q = c->d_q;
+            t.q_stride = c->q_stride;
+            t.R = c->R;
+            t.Pout = c->d_pscr[st.dst];
+            t.out_stride = c->p_stride;
+            const dim3 grid((unsigned)(c->M2 / 64), (unsigned)nframes);
+            switch (st.kind) {
+            case TAIL_COL_64:
+                hipLaunchKernelGGL(k_col_tail<64>, grid, dim3(64), 0, c->side, t);
+                break;
+            case TAIL_COL_128:
+                hipLaunchKernelGGL(k_col_tail<128>, grid, dim3(64), 0, c->side, t);
+                break;
+            case TAIL_COL_256_PAIRED:
+                hipLaunchKernelGGL((k_col_tail<256, true>), grid, dim3(64), 0, c->side, t);
+                break;
+            default:
+                hipLaunchKernelGGL(k_col_tail<256>, grid, dim3(64), 0, c->side, t);
+            }
+        }
         HIPCHK(hipGetLastError());
-        lvl += ilog2((size_t)ng);
-        len = (size_t)c->M2;
-        cur = 1;
     }
-    const int lvl_mapped = col_tail ? -1 : c->LT;  // the level whose sums are still in RecMap order
-    while (lvl + 1 < c->levels && len >= 2) {
-        TailArgs t{};
-        t.Pin = c->d_pscr[cur];
-        t.in_stride = c->p_stride;
-        t.len_in = len;
-        t.lvl_in = lvl;
-        t.nlevels = c->levels;
-        t.size_log2 = c->size_log2;
-        t.Q = c->d_q;
-        t.q_stride = c->q_stride;
-        t.R = c->R;
-        t.Pout = c->d_pscr[cur ^ 1];
-        t.out_stride = c->p_stride;
-        t.map = c->recmap;
-        if (lvl != lvl_mapped) t.map.mapped = 0;  // only pass 2's own output is tile-major
-        ProfScope ps(c, K_TAIL, c->side);
-        const unsigned nb = (unsigned)((len / 2 + 255) / 256);
-        hipLaunchKernelGGL(k_pyramid_tail, dim3(nb, nframes), dim3(256), 0, c->side, t);
-        HIPCHK(hipGetLastError());
-        lvl += 7;
-        len >>= 7;
-        cur ^= 1;
-    }
-    if (c->side != c->stream) {
-        HIPCHK(hipEventRecord(c->ev_side_done, c->side));
-        c->side_pending = true;
-        HIPCHK(hipEventRecord(c->ev_set_done[c->cur_set], c->side));
-        c->set_pending[c->cur_set] = true;
-    }
-    return PSDR_OK;
+    return side_done(c);
 }
 
 // forward FFT + power + int8 pyramid for nframes frames (src/fft.cpp:61-98 per frame)
@@ -255,9 +144,8 @@ int process_frames(psdr_ctx *c, const void *d_halves, int nframes, int fmt, hipE
     // (banded spectrum: also on a caller's stream - the regions of batch b are read by the peers, asynchronously,
     // while batch b+1 is transformed)
     if (c->side != c->stream || c->nbands || c->alt_sets) select_set(c, c->cur_set ^ 1);
-    const int cols = 1;
     const int sb = fmt <= PSDR_FMT_S8 ? 2 : (fmt <= PSDR_FMT_S16 ? 4 : 8);  // image bytes per sample
-    const unsigned tiles1 = (unsigned)(c->M2 / (c->T1 * cols)), tiles2 = (unsigned)(c->M1 / c->T2);
+    const unsigned tiles1 = (unsigned)(c->M2 / c->T1), tiles2 = (unsigned)(c->M1 / c->T2);
     c->input_on_main = false;
     cf *Y = c->d_Y;
     Pass1Args a1{};
@@ -265,11 +153,11 @@ int process_frames(psdr_ctx *c, const void *d_halves, int nframes, int fmt, hipE
     a1.Y = Y;
     a1.Wl = c->d_Wl1;
     a1.TB = c->d_TB;
-    a1.yblk = (size_t)c->M1 * (c->T1 * cols);  // plain: one linear block per pass-1 tile
+    a1.yblk = (size_t)c->M1 * c->T1;  // plain: one linear block per pass-1 tile
     a1.l2t2 = ilog2((size_t)c->T2);
     // fused real: pass-2-tile-major (fft_pass.h, "Y layout")
     a1.ytile = (size_t)c->M2 * c->T2;
-    a1.ytl = (size_t)c->T2 * (c->T1 * cols);
+    a1.ytl = (size_t)c->T2 * c->T1;
     a1.yframe = c->M;
     a1.wdelta = c->wdelta;
     a1.M2 = c->M2;
@@ -300,12 +188,12 @@ int process_frames(psdr_ctx *c, const void *d_halves, int nframes, int fmt, hipE
     a2.Wl = c->d_Wl2;
     a2.M1 = c->M1;
     a2.log2M1 = c->log2M1;
-    a2.TW = c->T1 * cols;
+    a2.TW = c->T1;
     a2.yblk = a1.yblk;
     a2.ytile = a1.ytile;
-    a2.yjs = (size_t)c->T2 * (c->T1 * cols);
+    a2.yjs = (size_t)c->T2 * c->T1;
     a2.yframe = a1.yframe;
-    a2.log2TW = ilog2((size_t)(c->T1 * cols));
+    a2.log2TW = ilog2((size_t)c->T1);
     a2.inv_n = 1.0f / (float)c->N;
     a2.size_log2 = c->size_log2;
     a2.nlevels = c->levels;
@@ -419,7 +307,10 @@ int process_frames(psdr_ctx *c, const void *d_halves, int nframes, int fmt, hipE
 
 }  // namespace psdr
 
-static int ensure_level_major(psdr_ctx *c, int frame) {
+// the level-major pyramid of `frame`, complete and at rest: behind everything enqueued, with the levels that live in tiled
+// records copied out (once per frame and batch)
+static int level_major_ready(psdr_ctx *c, int frame) {
+    PSDRCHK(drain(c));
     if (c->tiled_lt < 0 || c->q_untiled[frame]) return PSDR_OK;
     const size_t nrec = c->R / (size_t)c->tile_ch;
     hipLaunchKernelGGL(k_untile_q, dim3((unsigned)((nrec + 255) / 256)), dim3(256), 0, c->side,
@@ -427,7 +318,7 @@ static int ensure_level_major(psdr_ctx *c, int frame) {
                        c->tile_ch, c->tiled_lt, c->levels, c->recmap);
     HIPCHK(hipGetLastError());
     c->q_untiled[frame] = 1;
-    return PSDR_OK;
+    return drain(c);
 }
 
 // spectrum of `frame` to host in the reference's k order
@@ -474,14 +365,7 @@ extern "C" int psdr_get_quantized_buffer(psdr_ctx *c, int8_t **out) {
     if (!c || !out) return fail(PSDR_ERR_INVALID, "null argument");
     HIPCHK(hipSetDevice(c->device));
     if (c->last_nframes > 0 && !c->q_valid) {
-        {
-            int rc = drain(c);
-            if (rc) return rc;
-            rc = ensure_level_major(c, 0);
-            if (rc) return rc;
-            rc = drain(c);
-            if (rc) return rc;
-        }
+        PSDRCHK(level_major_ready(c, 0));
         HIPCHK(hipMemcpyAsync(c->h_q, c->d_q, c->q_len, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         c->q_valid = true;
@@ -672,57 +556,23 @@ extern "C" int psdr_waterfall_batch(psdr_ctx *c, uint64_t first_frame_num) {
     WfClient *d_wf = (WfClient *)c->wf_ring.dev(ring);
     int *h_sent = (int *)((unsigned char *)c->wf_ring.host(ring) + c->wf_sent_off);
     int *d_sent = (int *)((unsigned char *)c->wf_ring.dev(ring) + c->wf_sent_off);
-    int nsent = 0;
-    for (int f = 0; f < c->last_nframes; f++)
-        if ((first_frame_num + (uint64_t)f) % (uint64_t)c->cfg.skip_num == 0) h_sent[nsent++] = f;
-    size_t total = 0;
-    int maxid = -1;
-    bool hold = false, any_sample = false;  // an active client with a detector / on PSDR_WF_SAMPLE
-    size_t q_up = 0;                        // byte offset of level tiled_lt + 1 in the level-major buffer
-    for (int t = 0; t <= c->tiled_lt && t < c->levels; t++) q_up += c->R >> t;
-    for (size_t i = 0; i < c->wslots.size(); i++) {
-        WfSlot &s = c->wslots[i];
-        WfClient &w = h_wf[i];
-        w.active = s.active ? 1 : 0;
-        w.level = s.level;
-        w.l = s.l;
-        w.r = s.r;
-        w.qoff = 0;
-        for (int t = 0; t < s.level; t++) w.qoff += c->R >> t;
-        w.out_off = total;
-        w.det = s.det;
-        // (k_waterfall_hold) tiled records hold ch >> level values of the level side by side, at a multiple of that many
-        // bytes; a level-major level starts at qoff and a dword must not reach past its end
-        w.vec = s.level <= c->tiled_lt ? ((c->tile_ch >> s.level) >= 4) : ((c->R >> s.level) % 4 == 0 && w.qoff % 4 == 0);
-        s.out_off = total;
-        s.nsent = s.active ? nsent : 0;
-        s.b_level = s.level;
-        s.b_l = s.l;
-        s.b_r = s.r;
-        s.b_det = s.det;
-        if (s.active) {
-            total += (size_t)nsent * (size_t)(s.r - s.l);
-            total = (total + 15) & ~(size_t)15;
-            maxid = (int)i;
-            (s.det != PSDR_WF_SAMPLE ? hold : any_sample) = true;
-        }
-    }
-    // detectors: does this call continue the run the carry belongs to?  (header: psdr_waterfall_batch)
     const int nf = c->last_nframes;
-    if (!(hold && c->wf_run && first_frame_num == c->wf_next)) c->wf_carry_n = 0;
-    c->wf_run = false;  // (true again once everything below is enqueued)
-    const bool gather = maxid >= 0 && nsent > 0 && total > 0;
-    if (!gather && !hold) return PSDR_OK;
+    WfFacts facts;
+    facts.R = c->R, facts.levels = c->levels, facts.tiled_lt = c->tiled_lt, facts.tile_ch = c->tile_ch, facts.skip_num = c->cfg.skip_num;
+    // who is sent which frames and where, and what becomes of the detectors' carry (forwardplan.h)
+    const WfPlan p = wf_plan(c->wslots.data(), c->wslots.size(), facts, c->wf_carry, first_frame_num, nf, h_wf, h_sent);
+    c->wf_carry.carry_n = p.carry_n;  // (0 unless this call continues the carry's run: before anything below can fail)
+    c->wf_carry.run = false;          // (true again once everything below is enqueued)
+    if (!p.gather && !p.hold) return PSDR_OK;
+    const int nsent = p.nsent, maxid = p.maxid;
     WfHoldArgs ha{};
-    if (hold) {
+    if (p.hold) {
         if (!c->d_wf_peak) {  // first use: the carry mirrors one frame's records and upper levels
-            c->wf_lenA = c->tiled_lt >= 0 ? c->qt_stride : 0;
-            c->wf_qB0 = q_up & ~(size_t)15;
-            const size_t qB1 = (c->q_len + 15) & ~(size_t)15;  // <= q_stride, a multiple of 128
-            c->wf_lenB = qB1 > c->wf_qB0 ? qB1 - c->wf_qB0 : 0;
-            if ((c->wf_lenA & 15) || (c->qt_stride & 15) || qB1 > c->q_stride)
+            const WfCarryLayout lay = wf_carry_layout(c->tiled_lt, c->levels, c->R, c->q_len, c->q_stride, c->qt_stride);
+            if (!lay.ok)
                 return fail(PSDR_ERR_UNSUPPORTED, "waterfall detectors: record buffers of %zu / %zu bytes per frame", c->qt_stride, c->q_stride);
-            const size_t len = c->wf_lenA + c->wf_lenB;
+            c->wf_lay = lay;
+            const size_t len = lay.lenA + lay.lenB;
             DevBuf<int8_t> pk;
             DevBuf<uint32_t> sm;
             if (pk.alloc(len) || sm.alloc(len)) {
@@ -736,19 +586,19 @@ extern "C" int psdr_waterfall_batch(psdr_ctx *c, uint64_t first_frame_num) {
         ha.Qt = c->d_qt;
         ha.q_stride = c->q_stride;
         ha.qt_stride = c->qt_stride;
-        ha.lenA = c->wf_lenA;
-        ha.qB0 = c->wf_qB0;
-        ha.lenB = c->wf_lenB;
+        ha.lenA = c->wf_lay.lenA;
+        ha.qB0 = c->wf_lay.qB0;
+        ha.lenB = c->wf_lay.lenB;
         ha.peak = c->d_wf_peak;
         ha.sum = c->d_wf_sum;
-        ha.carry_n = c->wf_carry_n;
+        ha.carry_n = p.carry_n;
         ha.skip = c->cfg.skip_num;
         ha.nframes = nf;
     }
-    if (gather) {
-        if (total > c->wfout_cap) {
-            PSDRCHK(c->d_wfout.alloc(total));  // (the old rows are given up only once the new buffer exists)
-            c->wfout_cap = total;
+    if (p.gather) {
+        if (p.total > c->wfout_cap) {
+            PSDRCHK(c->d_wfout.alloc(p.total));  // (the old rows are given up only once the new buffer exists)
+            c->wfout_cap = p.total;
         }
         {  // d_wfout exists once: a result fetch in flight (psdr_fetch_begin) reads it first
             int rc = fetch_guard_wait(c, c->side, c->guard_wf);
@@ -759,14 +609,14 @@ extern "C" int psdr_waterfall_batch(psdr_ctx *c, uint64_t first_frame_num) {
                               c->side));
         HIPCHK(hipMemcpyAsync(d_sent, h_sent, (size_t)nsent * sizeof(int), hipMemcpyHostToDevice,
                               c->side));
-        if (any_sample || !hold) {
+        if (p.any_sample || !p.hold) {
             ProfScope ps(c, K_WFALL, c->side);
             hipLaunchKernelGGL(k_waterfall_gather, dim3(maxid + 1, nsent), dim3(256), 0, c->side, c->d_q,
                                c->q_stride, c->d_qt, c->qt_stride, c->tiled_lt, c->tile_ch, c->recmap, d_wf, d_sent, nsent,
                                c->d_wfout);
             HIPCHK(hipGetLastError());
         }
-        if (hold) {  // behind the gather: it rewrites the rows of the clients with a detector
+        if (p.hold) {  // behind the gather: it rewrites the rows of the clients with a detector
             ProfScope ps(c, K_WFHOLD, c->side);
             hipLaunchKernelGGL(k_waterfall_hold, dim3(maxid + 1, nsent), dim3(256), 0, c->side, ha, c->tiled_lt, c->tile_ch,
                                c->recmap, d_wf, d_sent, nsent, c->d_wfout);
@@ -774,28 +624,16 @@ extern "C" int psdr_waterfall_batch(psdr_ctx *c, uint64_t first_frame_num) {
         }
         HIPCHK(c->wf_ring.release(ring, c->side));
     }
-    if (hold) {
-        // the carry for the next call: the frames behind the batch's last sent frame replace it; a batch without a sent
-        // frame is reduced onto it (onto nothing, at the start of a run)
-        const int f0 = nsent > 0 ? h_sent[nsent - 1] + 1 : 0;
-        const int accumulate = nsent == 0 && c->wf_carry_n > 0;
-        if (f0 < nf) {
+    if (p.hold) {
+        if (p.f0 < nf) {  // the carry for the next call
             ProfScope ps(c, K_WFCARRY, c->side);
             const size_t lanes = (ha.lenA + ha.lenB) / 16;
-            hipLaunchKernelGGL(k_waterfall_carry, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, c->side, ha, f0, accumulate);
+            hipLaunchKernelGGL(k_waterfall_carry, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, c->side, ha, p.f0, p.accumulate);
             HIPCHK(hipGetLastError());
         }
-        c->wf_carry_n = (accumulate ? c->wf_carry_n : 0) + (nf - f0);
-        c->wf_next = first_frame_num + (uint64_t)nf;
-        c->wf_run = true;
+        c->wf_carry = p.after;
     }
-    if (c->side != c->stream) {
-        HIPCHK(hipEventRecord(c->ev_side_done, c->side));
-        c->side_pending = true;
-        HIPCHK(hipEventRecord(c->ev_set_done[c->cur_set], c->side));
-        c->set_pending[c->cur_set] = true;
-    }
-    return PSDR_OK;
+    return side_done(c);
 }
 extern "C" int psdr_read_waterfall(psdr_ctx *c, int id, int8_t *out, size_t out_cap, int *nsent_out, int *level_out,
                                    int *l_out, int *r_out) {
@@ -834,14 +672,7 @@ extern "C" int psdr_spectrum_device_ptr(psdr_ctx *c, int frame, const float **d_
 extern "C" int psdr_quantized_device_ptr(psdr_ctx *c, int frame, const int8_t **d_q, size_t *nbytes) {
     if (!c) return fail(PSDR_ERR_INVALID, "null argument");
     if (frame < 0 || frame >= c->max_batch) return fail(PSDR_ERR_INVALID, "frame %d out of range", frame);
-    {
-        int rc = drain(c);
-        if (rc) return rc;
-        rc = ensure_level_major(c, frame);
-        if (rc) return rc;
-        rc = drain(c);
-        if (rc) return rc;
-    }
+    PSDRCHK(level_major_ready(c, frame));
     if (d_q) *d_q = c->d_q + (size_t)frame * c->q_stride;
     if (nbytes) *nbytes = c->q_len;
     return PSDR_OK;
@@ -856,14 +687,7 @@ extern "C" int psdr_read_quantized(psdr_ctx *c, int frame, int8_t *out) {
     if (!c || !out) return fail(PSDR_ERR_INVALID, "null argument");
     if (frame < 0 || frame >= c->last_nframes) return fail(PSDR_ERR_INVALID, "frame %d not in the last batch", frame);
     HIPCHK(hipSetDevice(c->device));
-    {
-        int rc = drain(c);
-        if (rc) return rc;
-        rc = ensure_level_major(c, frame);
-        if (rc) return rc;
-        rc = drain(c);
-        if (rc) return rc;
-    }
+    PSDRCHK(level_major_ready(c, frame));
     HIPCHK(hipMemcpyAsync(out, c->d_q + (size_t)frame * c->q_stride, c->q_len, hipMemcpyDeviceToHost,
                           c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));

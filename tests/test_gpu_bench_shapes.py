@@ -4,7 +4,7 @@ test_gpu_fullsize.py runs every BASELINE shape for 3-5 frames: a fused real-inpu
 walks chains of 1 or 2 tiles, and no frame of a 256-frame launch ever meets the oracle.  Here:
 
   * the fused real-input second pass (k_fft_pass2_real) with chain segments of 4, 16, 32 and 64 tiles
-    at 2^21 points and of 64 tiles at 2^22 points (PSDR_SEG_LEN pins what real_seg_len() would pick
+    at 2^21 points and of 64 tiles at 2^22 points (PSDR_SEG_LEN pins what seg_len() would pick
     for F = 256: 32 tiles at 2^21, 64 at 2^22) - a chain of >= 3 tiles has a MIDDLE tile, with carry-in
     AND carry-out and the LDS double-buffer toggle - spectrum, int8 pyramid, every client's audio and
     the gathered waterfall rows against the oracle                    (src/fft_impl.cpp:144-174)
@@ -62,10 +62,10 @@ def test_fused_real_pass_long_chains_vs_oracle(wl_name, seg_len, splits, seg_len
 
 
 def test_bench_seg_len_is_what_the_chain_tests_cover():
-    """what the segment plan (forward.hip: real_seg_len / seg_plan, restated in test_real_fused_model.py) picks for the
+    """what the segment plan (forwardplan.h: seg_len / seg_table, through tests/forward_plan_table.py) picks for the
     batch sizes the bench has used: uniform 32- and 64-tile segments at 256 frames, the hand-off plan at 512"""
     import bench
-    from test_real_fused_model import seg_plan
+    from forward_plan_table import seg_plan
     for G, sl in ((64, 32), (128, 64)):
         tab, handoff, _ = seg_plan(G, 256)
         assert not handoff and {t[2] for t in tab} == {sl}
@@ -313,13 +313,13 @@ def test_handoff_two_contexts_interleaved_and_640_frames(monkeypatch):
 
 @pytest.mark.parametrize("log2n,F", [(21, 320), (21, 257), (22, 288)])
 def test_handoff_plan_between_one_and_two_frames_per_work_group(log2n, F, monkeypatch):
-    """Batches of more than one frame per work-group take the hand-off plan (forward.hip: seg_plan_counts).  Below two
+    """Batches of more than one frame per work-group take the hand-off plan (forwardplan.h: seg_handoff).  Below two
     frames per work-group a segment's predecessor is less than two segments ahead: many first tiles fall back to a seam -
     every frame's pyramid and spectrum must still be bit-identical to whole-frame segments."""
     import ctypes as C
     import hashlib
     from phantomsdr_amd import Context, _lib
-    from test_real_fused_model import seg_plan
+    from forward_plan_table import seg_plan
     N = 1 << log2n
     G = (N // 2 // 1024) // 16
     assert seg_plan(G, F)[1]

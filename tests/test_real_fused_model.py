@@ -17,6 +17,8 @@ numpy.fft.rfft.  This is host-side logic (no GPU): it pins
 import numpy as np
 import pytest
 
+from forward_plan_table import seg_plan  # the chain segments the library plans (phantomsdr_amd/csrc/forwardplan.h)
+
 
 def spec_layout_pos(k, M1, M2, CP=8):
     """SpecLayout::pos (quantize.h): lines of 2 CP bins [low octet of column c | mirror octet of column L-1-c],
@@ -61,54 +63,6 @@ def untangle_pair(a, b, w, h):
     s, d = a + b, a - b
     wo = w * (-1j * d)
     return (s + wo) * h, np.conj((s - wo) * h)
-
-
-def seg_plan(G, nframes, num_cus=256, seg_len_env=0, static_tiles=False):
-    """forward.hip: seg_plan_counts / seg_plan.  Returns (table, handoff, nseam): table[sg] = (frame, first tile, tiles,
-    segment above, carry-in through memory)."""
-    def pow2_floor(v):
-        sl = 1
-        while sl * 2 <= v and sl * 2 <= G:
-            sl *= 2
-        return sl
-
-    def uniform_len():   # forward.hip: real_seg_len
-        if seg_len_env > 0:
-            return pow2_floor(seg_len_env)
-        W = max(num_cus, 1)
-        tiles = G * nframes
-        want = tiles // (2 * W)
-        per_wg = -(-tiles // W)
-        if per_wg <= 16:                     # one static segment per work-group
-            sl = 1
-            while sl < per_wg and sl * 2 <= G:
-                sl *= 2
-            return sl
-        if 2 * W * want == tiles and want & (want - 1) == 0 and want <= G:
-            return want                      # two static segments per work-group
-        return pow2_floor(tiles // (5 * W))  # five to ten per work-group: the tickets have something to balance with
-    want = nframes > num_cus                 # the hand-off plan: more than one frame per work-group
-    handoff = seg_len_env <= 0 and not static_tiles and G >= 16 and want
-    tab = []
-    if handoff:
-        lens = [G // 4] * 3
-        l = G // 8
-        while l >= 1:
-            lens.append(l)
-            l //= 2
-        lens.append(1)
-        g = G - 1
-        for lv, ln in enumerate(lens):
-            for f in range(nframes):
-                tab.append((f, g, ln, ((lv - 1) if lv else len(lens) - 1) * nframes + f, lv > 0))
-            g -= ln
-        return tab, True, nframes
-    sl = uniform_len()
-    S = G // sl
-    for f in range(nframes):
-        for si in range(S):
-            tab.append((f, (si + 1) * sl - 1, sl, f * S + (si + 1) % S, False))
-    return tab, False, len(tab)
 
 
 def fused_pass2(slots, M1, M2, seg_len, CP=8):
@@ -208,7 +162,7 @@ def test_fused_real_pass2_model_matches_rfft(M1, M2, seg_len, CP):
 @pytest.mark.parametrize("G,nframes", [(64, 512), (128, 512), (64, 640), (16, 600), (64, 513), (64, 511), (64, 256), (64, 1), (128, 7), (64, 320), (64, 160), (128, 160),
                                       (64, 128), (64, 192), (64, 96), (64, 384), (64, 257)])
 def test_segment_plan_partitions_frames_and_orders_the_hand_offs(G, nframes):
-    """the table k_fft_pass2_real walks (forward.hip, seg_plan): every tile of every frame in exactly one segment; the
+    """the table k_fft_pass2_real walks (forwardplan.h, seg_table): every tile of every frame in exactly one segment; the
     segments without a carry-in first (k_real_seam's grid); in hand-off mode a segment's predecessor is the segment of
     the SAME frame that ends one tile above it, handed out exactly nframes tickets earlier, and only a frame's top
     segment needs a seam (the ring closes through tile 0's row M1/2)"""
