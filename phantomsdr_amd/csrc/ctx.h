@@ -1,7 +1,8 @@
 // ctx.h - internal: the context behind the C-ABI (include/psdr.h) and what the translation units of libpsdr_hip.so
 // share.  context.hip (lifetime, Level 1, ingest ring, instrumentation), pass1.hip / pass2.hip (the FFT pass
 // launchers), forward.hip (the frame loop: passes + pyramid tails, spectrum / pyramid read-back, band layout,
-// waterfall), demod.hip (audio clients + demodulation), postchain.hip (DC blocker / AGC / int16), wire.hip (packets).
+// waterfall), demod.hip (audio clients + demodulation), fetch.hip (the served end: results to host memory), postchain.hip
+// (DC blocker / AGC / int16), wire.hip (packets).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -20,6 +21,7 @@
 #include "blankerplan.h"
 #include "butterfly.h"
 #include "demodplan.h"
+#include "fetchplan.h"
 #include "forwardplan.h"
 #include "owned.h"
 #include "postplan.h"
@@ -305,43 +307,38 @@ struct psdr_ctx {
     // src/waterfall.cpp:44-51 hand HOST buffers to the encoders).  A ring of pinned host sets, [slot][frame][...] each; a fetch is
     // enqueued on `fetch_stream` behind the kernels that produce the batch's results and runs beside the next batch's passes;
     // the device buffers it reads exist once, so the next batch's WRITERS (demodulation, waterfall gather, the chain's
-    // output kernel) wait for `done` of the newest fetch in stream order (fetch_guard).
+    // output kernel) wait for `done` of the newest fetch in stream order (fetch_guard).  fetch.hip; what a fetch copies and the
+    // ring's arithmetic: fetchplan.h.
     struct FetchSet {
         HostBuf<float> audio, pwr;
         HostBuf<int32_t> nan, pcm;
         HostBuf<int8_t> wf;
         size_t wf_cap = 0;
-        // PSDR_FETCH_IQ: rows [slot - iq_lo][max_batch][n/2] of the iq_n slots from the lowest to the highest that were IQ
-        HostBuf<cf> iq;
-        size_t iq_cap = 0, iq_bytes = 0;  // slots the buffer holds; bytes the fetch's IQ copy moved
-        int iq_lo = 0, iq_n = 0;
-        // the carrier records [slot - car_lo][max_batch] of the car_n slots from the lowest to the highest that were SAM
-        HostBuf<cf> car;
-        size_t car_cap = 0;
-        int car_lo = 0, car_n = 0;
-        // the squelch flags [slot - sq_lo][max_batch] of the sq_n slots from the lowest to the highest that ran with squelch
-        HostBuf<int32_t> sq;
-        size_t sq_cap = 0;
-        int sq_lo = 0, sq_n = 0;
+        // rows that only some slots have: [slot - at.lo][max_batch][...] of the at.n slots from the lowest to the highest that
+        // have them (fetchplan.h span_of), in a buffer that holds `cap` slots and only grows
+        template <typename T>
+        struct Span {
+            HostBuf<T> buf;
+            size_t cap = 0;
+            FetchSpan at;
+        };
+        Span<cf> iq;          // PSDR_FETCH_IQ: the IQ rows [..][n/2] of the slots that were IQ
+        size_t iq_bytes = 0;  // ... and the bytes the fetch's IQ copy moved
+        Span<cf> car;         // the carrier records of the slots that were SAM
+        Span<int32_t> sq;     // the squelch flags of the slots that ran with squelch
         Event done;                      // every copy of the fetch on the first copy stream has landed
         Event ev_pcm;                    // ... and the PCM (its own copy stream: it waits for the post chain, up to two steps late)
         bool has_pcm = false;
         bool pcm16 = false;              // its PCM rows are int16 (PSDR_OPT_POST_CHAIN_PCM16 at that batch)
         Event ev_wf;                     // ... the waterfall rows (first in the copy stream: d_wfout exists once)
-        Event ev_audio;                  // ... pwr, NaN flags, float audio, IQ rows (what the demodulation of batch b + 2 overwrites)
+        Event ev_audio;                  // ... pwr, NaN flags, float audio and the spans' rows (what the demodulation of batch b + 2 overwrites)
         bool inflight = false;
         unsigned what = 0;     // PSDR_FETCH_* bits the copies covered
         int frames = 0;        // frames of the demodulation batch (0: none was fetched)
         uint64_t seq = 0;      // its demod_seq
-        struct Win {
-            uint64_t last_seq = 0, born = 0;
-            int l = 0, r = 0;
-            double mid = 0;
-            int mode = PSDR_USB;
-            bool sq = false;  // the batch ran with squelch for the slot (psdr_fetched_squelch: 1 for every frame otherwise)
-        };
-        std::vector<Win> win;      // per audio slot: the window the batch was demodulated with
-        std::vector<WfSlot> wfm;   // per waterfall slot: what psdr_waterfall_batch gathered (out_off, nsent, b_*)
+        std::vector<FetchWin> win;     // per audio slot: the window the batch was demodulated with
+        std::vector<FetchSlot> slots;  // ... and what psdr_fetch_begin planned the copies from (kept for its capacity)
+        std::vector<WfSlot> wfm;       // per waterfall slot: what psdr_waterfall_batch gathered (out_off, nsent, b_*)
     } fset[PSDR_FETCH_SETS];
     uint64_t slot_births = 0;      // psdr_client_add calls so far (AudioSlot::born)
     int fetch_fill = 0;            // the set the next psdr_fetch_begin fills (a ring: the oldest in flight is fetch_fill - fetch_inflight)
@@ -469,7 +466,9 @@ int drain(psdr_ctx *c);
 int side_done(psdr_ctx *c);
 // postchain.hip: resolves post_plan again (after a drain: psdr_set_post_chain, the chain's options, psdr_set_stream)
 void pc_replan(psdr_ctx *c);
-// demod.hip: the next writer of a device-side result buffer on stream `st` waits for the fetch that read it (ev may be null)
+// demod.hip: PSDR_ERR_INVALID unless `id` is an audio slot with a client (under mtx)
+int check_slot(psdr_ctx *c, int id);
+// fetch.hip: the next writer of a device-side result buffer on stream `st` waits for the fetch that read it (ev may be null)
 int fetch_guard_wait(psdr_ctx *c, hipStream_t st, hipEvent_t ev);
 void resolve_pending(psdr_ctx *c);
 void resolve_kclock(psdr_ctx *c);

@@ -1,6 +1,6 @@
 // demod.hip - the audio clients (AudioClient, src/signal.h:53-123) and their batched demodulation: signal_loop +
 // AudioClient::send_audio up to the NaN guard (src/websocket.cpp:156-185, src/signal.cpp:102-275) for every client and
-// every frame of a batch, and the read-back of its results.
+// every frame of a batch.  (The read-back of its results: fetch.hip.)
 #include "ctx.h"
 #include "demod.h"
 #include "squelch.h"
@@ -80,7 +80,7 @@ static int squelch_alloc(psdr_ctx *c) {
     c->d_sq_tab = std::move(d_tab);
     return PSDR_OK;
 }
-static int check_slot(psdr_ctx *c, int id) {
+int psdr::check_slot(psdr_ctx *c, int id) {
     if (id < 0 || id >= (int)c->aslots.size() || !c->aslots[id].active)
         return fail(PSDR_ERR_INVALID, "no audio client with id %d", id);
     return PSDR_OK;
@@ -612,413 +612,6 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     return side_done(c);
 }
 
-// A slot whose client attached AFTER the last demodulation batch holds the previous occupant's results (or
-// nothing): the reference's per-client task would not exist for that frame either (src/websocket.cpp:156-185 walks
-// signal_slices at the time of the frame).  PSDR_ERR_NO_DATA, nothing is copied.
-// ... and a batch demodulated as PSDR_IQ holds complex rows and no audio / PCM, any other batch no IQ rows (want_iq:
-// the caller asks for IQ rows)
-static int slot_in_last_batch(psdr_ctx *c, int id, bool want_iq = false) {
-    std::lock_guard<std::mutex> lk(c->mtx);
-    if (c->demod_seq == 0 || c->aslots[id].last_seq != c->demod_seq)
-        return fail(PSDR_ERR_NO_DATA, "client %d was not part of the last demodulation batch", id);
-    if ((c->aslots[id].b_mode == PSDR_IQ) != want_iq)
-        return fail(PSDR_ERR_NO_DATA, want_iq ? "client %d was not demodulated as PSDR_IQ in the last batch" : "client %d was demodulated as PSDR_IQ in the last batch: psdr_read_iq", id);
-    return PSDR_OK;
-}
-// the same for a fetched set
-static int slot_in_fetched_set(psdr_ctx *c, const psdr_ctx::FetchSet *fs, int id, bool want_iq) {
-    // (a slot handed to a new client since the batch was demodulated holds the previous occupant's rows: not this client's)
-    if ((size_t)id >= fs->win.size() || fs->win[id].last_seq != fs->seq || fs->win[id].born != c->aslots[id].born)
-        return fail(PSDR_ERR_NO_DATA, "client %d was not part of the fetched batch", id);
-    if ((fs->win[id].mode == PSDR_IQ) != want_iq)
-        return fail(PSDR_ERR_NO_DATA, want_iq ? "client %d was not demodulated as PSDR_IQ in the fetched batch" : "client %d was demodulated as PSDR_IQ in the fetched batch: psdr_fetched_iq", id);
-    return PSDR_OK;
-}
-
-// ---- batched read-back: the served end of the path --------------------------------------------------------------
-// (src/websocket.cpp:156-185 makes one pass over signal_slices per frame and every send_audio ends in host memory:
-// src/signal.cpp:283-291 -> src/audio.cpp:26-44; send_waterfall: src/waterfall.cpp:44-51.  Per-client psdr_read_audio
-// would pay a synchronisation and three copies per client and frame.)
-// psdr_fetch_begin ENQUEUES the copies of the last demodulation batch (and of the last waterfall batch) into one of a ring
-// of PSDR_FETCH_SETS pinned host sets on a copy stream, behind the kernels that produce them, and returns; psdr_fetch_end waits for the
-// oldest fetch in flight and makes its set the one psdr_fetched_* read.  Between the two the caller enqueues the NEXT batch:
-// the copies run beside its FFT passes.  The device-side result buffers exist once: the next batch's demodulation,
-// waterfall gather and PCM output wait (in stream order, no host wait) for the newest fetch's copies.
-int psdr::fetch_guard_wait(psdr_ctx *c, hipStream_t st, hipEvent_t ev) {
-    (void)c;
-    if (ev) HIPCHK(hipStreamWaitEvent(st, ev, 0));
-    return PSDR_OK;
-}
-extern "C" int psdr_fetch_begin(psdr_ctx *c, unsigned what) {
-    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
-    if (what == 0 || (what & ~(PSDR_FETCH_AUDIO | PSDR_FETCH_PCM | PSDR_FETCH_WATERFALL | PSDR_FETCH_IQ))) return fail(PSDR_ERR_INVALID, "PSDR_FETCH_* bits 0x%x", what);
-    const bool want_audio = (what & (PSDR_FETCH_AUDIO | PSDR_FETCH_PCM | PSDR_FETCH_IQ)) != 0;
-    if (want_audio && c->n <= 0) return fail(PSDR_ERR_STATE, "context created with audio_fft_size 0");
-    const size_t F = (size_t)c->last_demod_frames, h = (size_t)c->n / 2, mb = (size_t)c->max_batch, S = c->aslots.size();
-    if (want_audio && (F == 0 || c->demod_seq == 0)) return fail(PSDR_ERR_STATE, "no demodulated batch to fetch");
-    if ((what & PSDR_FETCH_PCM) && !c->post_on) return fail(PSDR_ERR_STATE, "PSDR_FETCH_PCM: post chain not enabled (psdr_set_post_chain)");
-    HIPCHK(hipSetDevice(c->device));
-    if (!c->fetch_stream) PSDRCHK(c->fetch_stream.create());
-    if ((what & PSDR_FETCH_PCM) && !c->fetch_stream_pcm) PSDRCHK(c->fetch_stream_pcm.create());
-    if (!c->ev_fetch_src) PSDRCHK(c->ev_fetch_src.create());
-    psdr_ctx::FetchSet &fs = c->fset[c->fetch_fill];
-    if (fs.inflight) {  // every set in flight: the oldest one has to land first (its results are given up: psdr_fetch_end was not called)
-        HIPCHK(hipEventSynchronize(fs.done));
-        if (fs.has_pcm) HIPCHK(hipEventSynchronize(fs.ev_pcm));
-        fs.inflight = false;
-        c->fetch_inflight--;
-    }
-    if (c->fetch_cur == c->fetch_fill) c->fetch_cur = -1;  // its pointers die now
-    // (each block on its own: a failed allocation leaves nothing half-initialised behind for the next call)
-    for (Event *e : {&fs.done, &fs.ev_wf, &fs.ev_audio, &fs.ev_pcm})
-        if (!*e) PSDRCHK(e->create());
-    if (want_audio && !fs.pwr) PSDRCHK(fs.pwr.alloc(S * mb));
-    if (want_audio && !fs.nan) PSDRCHK(fs.nan.alloc(S * mb));
-    if ((what & PSDR_FETCH_AUDIO) && !fs.audio) PSDRCHK(fs.audio.alloc(S * mb * h));
-    if ((what & PSDR_FETCH_PCM) && !fs.pcm) PSDRCHK(fs.pcm.alloc(S * mb * h));
-    size_t wf_bytes = 0;
-    int iq_lo = (int)S, iq_hi = -1;  // PSDR_FETCH_IQ: the span from the lowest to the highest slot that was IQ in the batch
-    int car_lo = (int)S, car_hi = -1;  // the carrier records: ... that was SAM (with any of the audio bits)
-    int sq_lo = (int)S, sq_hi = -1;    // the squelch flags: ... that ran with squelch (with any of the audio bits)
-    {
-        std::lock_guard<std::mutex> lk(c->mtx);
-        fs.win.resize(S);
-        for (size_t i = 0; i < S; i++) {
-            const AudioSlot &sl = c->aslots[i];
-            fs.win[i].last_seq = sl.active ? sl.last_seq : 0;
-            fs.win[i].born = sl.born;
-            fs.win[i].l = sl.b_l, fs.win[i].r = sl.b_r, fs.win[i].mid = sl.b_mid, fs.win[i].mode = sl.b_mode;
-            fs.win[i].sq = want_audio && sl.active && sl.last_seq == c->demod_seq && sl.b_sq_on;
-            if (fs.win[i].sq) {
-                sq_lo = std::min(sq_lo, (int)i);
-                sq_hi = (int)i;
-            }
-            if ((what & PSDR_FETCH_IQ) && sl.active && sl.last_seq == c->demod_seq && sl.b_mode == PSDR_IQ) {
-                iq_lo = std::min(iq_lo, (int)i);
-                iq_hi = (int)i;
-            }
-            if (want_audio && sl.active && sl.last_seq == c->demod_seq && sl.b_mode == PSDR_SAM) {
-                car_lo = std::min(car_lo, (int)i);
-                car_hi = (int)i;
-            }
-        }
-        fs.wfm.assign(c->wslots.begin(), c->wslots.end());
-        if (what & PSDR_FETCH_WATERFALL)
-            for (const WfSlot &w : fs.wfm)
-                if (w.active && w.nsent > 0) wf_bytes = std::max(wf_bytes, (w.out_off + (size_t)w.nsent * (size_t)(w.b_r - w.b_l) + 15) & ~(size_t)15);
-    }
-    fs.iq_lo = iq_hi < 0 ? 0 : iq_lo;
-    fs.iq_n = iq_hi < 0 ? 0 : iq_hi - iq_lo + 1;
-    fs.iq_bytes = 0;
-    if ((size_t)fs.iq_n > fs.iq_cap) {
-        PSDRCHK(fs.iq.alloc((size_t)fs.iq_n * mb * h));
-        fs.iq_cap = (size_t)fs.iq_n;
-    }
-    fs.car_lo = car_hi < 0 ? 0 : car_lo;
-    fs.car_n = car_hi < 0 ? 0 : car_hi - car_lo + 1;
-    if ((size_t)fs.car_n > fs.car_cap) {
-        PSDRCHK(fs.car.alloc((size_t)fs.car_n * mb));
-        fs.car_cap = (size_t)fs.car_n;
-    }
-    fs.sq_lo = sq_hi < 0 ? 0 : sq_lo;
-    fs.sq_n = sq_hi < 0 ? 0 : sq_hi - sq_lo + 1;
-    if ((size_t)fs.sq_n > fs.sq_cap) {
-        PSDRCHK(fs.sq.alloc((size_t)fs.sq_n * mb));
-        fs.sq_cap = (size_t)fs.sq_n;
-    }
-    if (wf_bytes > fs.wf_cap) {
-        PSDRCHK(fs.wf.alloc(wf_bytes));  // (the old rows are given up only once the new buffer exists)
-        fs.wf_cap = wf_bytes;
-    }
-    hipStream_t fst = c->fetch_stream;
-    // rows [slot][0..F) of a device array [slot][max_batch][row_bytes]: ONE plain copy when the batch fills max_batch (the
-    // DMA engines' case; a pitched copy may be done by a copy kernel on the CUs the passes are using), else one strided copy
-    auto rows_d2h = [&](void *dst, const void *src, size_t row_bytes) -> hipError_t {
-        if (F == mb) return hipMemcpyAsync(dst, src, S * mb * row_bytes, hipMemcpyDeviceToHost, fst);
-        return hipMemcpy2DAsync(dst, mb * row_bytes, src, mb * row_bytes, F * row_bytes, S, hipMemcpyDeviceToHost, fst);
-    };
-    // behind the demodulation and the waterfall gather of the last batch (both on `side`) ...
-    HIPCHK(hipEventRecord(c->ev_fetch_src, c->side));
-    HIPCHK(hipStreamWaitEvent(fst, c->ev_fetch_src, 0));
-    // the waterfall rows first (small; their device buffer exists once: the next gather waits for ev_wf alone)
-    if (wf_bytes) {
-        HIPCHK(hipMemcpyAsync(fs.wf, c->d_wfout, wf_bytes, hipMemcpyDeviceToHost, fst));
-        HIPCHK(hipEventRecord(fs.ev_wf, fst));
-        c->guard_wf = fs.ev_wf;
-    }
-    // rows [slot][0..F) of the device arrays [slot][max_batch][...]: one strided copy each
-    if (want_audio) {
-        HIPCHK(rows_d2h(fs.pwr, c->d_pwr, sizeof(float)));
-        HIPCHK(rows_d2h(fs.nan, c->d_nan, sizeof(int32_t)));
-        if (what & PSDR_FETCH_AUDIO) HIPCHK(rows_d2h(fs.audio, c->d_audio, h * sizeof(float)));
-        if (fs.iq_n > 0) {
-            // the IQ rows of the span's slots only (the pools alternate with the audio's: ev_audio guards this set's too)
-            const size_t rb = h * sizeof(cf), nsl = (size_t)fs.iq_n;
-            const cf *src = c->d_iq + (size_t)fs.iq_lo * mb * h;
-            if (F == mb)
-                HIPCHK(hipMemcpyAsync(fs.iq, src, nsl * mb * rb, hipMemcpyDeviceToHost, fst));
-            else
-                HIPCHK(hipMemcpy2DAsync(fs.iq, mb * rb, src, mb * rb, F * rb, nsl, hipMemcpyDeviceToHost, fst));
-            fs.iq_bytes = nsl * F * rb;
-        }
-        if (fs.car_n > 0) {
-            // the carrier records of the span's slots, one copy (their pools alternate with the audio's: ev_audio guards them)
-            const size_t rb = sizeof(cf), nsl = (size_t)fs.car_n;
-            const cf *src = c->d_car + (size_t)fs.car_lo * mb;
-            if (F == mb)
-                HIPCHK(hipMemcpyAsync(fs.car, src, nsl * mb * rb, hipMemcpyDeviceToHost, fst));
-            else
-                HIPCHK(hipMemcpy2DAsync(fs.car, mb * rb, src, mb * rb, F * rb, nsl, hipMemcpyDeviceToHost, fst));
-        }
-        if (fs.sq_n > 0) {
-            // the squelch flags of the span's slots, one copy (their pools alternate with the audio's: ev_audio guards them)
-            const size_t rb = sizeof(int32_t), nsl = (size_t)fs.sq_n;
-            const int *src = c->d_sq + (size_t)fs.sq_lo * mb;
-            if (F == mb)
-                HIPCHK(hipMemcpyAsync(fs.sq, src, nsl * mb * rb, hipMemcpyDeviceToHost, fst));
-            else
-                HIPCHK(hipMemcpy2DAsync(fs.sq, mb * rb, src, mb * rb, F * rb, nsl, hipMemcpyDeviceToHost, fst));
-        }
-        HIPCHK(hipEventRecord(fs.ev_audio, fst));
-        c->guard_audio[c->out_set] = fs.ev_audio;
-    }
-    HIPCHK(hipEventRecord(fs.done, fst));
-    fs.has_pcm = false;
-    if (what & PSDR_FETCH_PCM) {
-        // ... the PCM behind the chain's output kernel of that batch (up to two steps after the passes) on a copy stream of
-        // ITS OWN: on the one stream the next batch's waterfall rows and audio would queue behind a copy that waits for
-        // the chain - and the gather / demodulation that wait for THOSE copies with them (256 clients: +33 % on the step)
-        hipStream_t fsp = c->fetch_stream_pcm;
-        HIPCHK(hipStreamWaitEvent(fsp, c->ev_fetch_src, 0));
-        if (c->chain_seq > 0 && c->pc_s[0] && c->side != c->stream)
-            HIPCHK(hipStreamWaitEvent(fsp, c->pc.ev[3][(c->chain_seq - 1) % psdr_ctx::PC_SETS], 0));
-        // (PSDR_OPT_POST_CHAIN_PCM16: the rows are int16 - the same buffers, half the bytes)
-        const size_t sb = c->pcm_is16 ? sizeof(int16_t) : sizeof(int32_t);
-        fs.pcm16 = c->pcm_is16;
-        if (F == mb)
-            HIPCHK(hipMemcpyAsync(fs.pcm, c->post.pcm, S * mb * h * sb, hipMemcpyDeviceToHost, fsp));
-        else
-            HIPCHK(hipMemcpy2DAsync(fs.pcm, mb * h * sb, c->post.pcm, mb * h * sb, F * h * sb, S, hipMemcpyDeviceToHost, fsp));
-        HIPCHK(hipEventRecord(fs.ev_pcm, fsp));
-        c->guard_pcm[c->pcm_set] = fs.ev_pcm;
-        fs.has_pcm = true;
-    }
-    fs.inflight = true;
-    fs.what = what;
-    fs.frames = want_audio ? (int)F : 0;
-    fs.seq = want_audio ? c->demod_seq : 0;
-    c->fetch_fill = (c->fetch_fill + 1) % PSDR_FETCH_SETS;
-    c->fetch_inflight++;
-    return PSDR_OK;
-}
-extern "C" int psdr_fetch_end(psdr_ctx *c) {
-    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
-    // the oldest fetch in flight: the set that would be filled next if it is in flight, else the other one
-    if (c->fetch_inflight <= 0) return fail(PSDR_ERR_STATE, "psdr_fetch_end without a psdr_fetch_begin in flight");
-    const int k = (c->fetch_fill - c->fetch_inflight + 2 * PSDR_FETCH_SETS) % PSDR_FETCH_SETS;
-    psdr_ctx::FetchSet &fs = c->fset[k];
-    if (!fs.inflight) return fail(PSDR_ERR_STATE, "psdr_fetch_end: the fetch ring is out of step");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipEventSynchronize(fs.done));
-    if (fs.has_pcm) HIPCHK(hipEventSynchronize(fs.ev_pcm));
-    fs.inflight = false;
-    c->fetch_inflight--;
-    // (everything of this fetch has landed: nothing left for a writer to wait for)
-    if (c->guard_wf == fs.ev_wf) c->guard_wf = nullptr;
-    for (int i = 0; i < 2; i++) {
-        if (c->guard_audio[i] == fs.ev_audio) c->guard_audio[i] = nullptr;
-        if (c->guard_pcm[i] == fs.ev_pcm) c->guard_pcm[i] = nullptr;
-    }
-    c->fetch_cur = k;
-    return PSDR_OK;
-}
-extern "C" int psdr_fetch_batch(psdr_ctx *c) {
-    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
-    if (c->n <= 0) return fail(PSDR_ERR_STATE, "context created with audio_fft_size 0");
-    if (c->last_demod_frames == 0 || c->demod_seq == 0) return fail(PSDR_ERR_STATE, "no demodulated batch to fetch");
-    // the synchronous form: everything there is, and the device drained (errors of the batch surface here)
-    while (c->fetch_inflight > 0) {
-        int rc = psdr_fetch_end(c);
-        if (rc) return rc;
-    }
-    {
-        int rc = drain(c);
-        if (rc) return rc;
-    }
-    int rc = psdr_fetch_begin(c, PSDR_FETCH_AUDIO | (c->post_on ? PSDR_FETCH_PCM : 0u) | PSDR_FETCH_WATERFALL | (c->d_iq ? PSDR_FETCH_IQ : 0u));
-    if (rc) return rc;
-    return psdr_fetch_end(c);
-}
-static int fetched_set(psdr_ctx *c, const psdr_ctx::FetchSet **out) {
-    if (c->fetch_cur < 0) return fail(PSDR_ERR_STATE, "psdr_fetch_batch() / psdr_fetch_end() first");
-    *out = &c->fset[c->fetch_cur];
-    return PSDR_OK;
-}
-extern "C" int psdr_fetched_window(psdr_ctx *c, int id, int *l, double *audio_mid, int *r) {
-    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
-    std::lock_guard<std::mutex> lk(c->mtx);
-    int rc = check_slot(c, id);
-    if (rc) return rc;
-    const psdr_ctx::FetchSet *fs = nullptr;
-    if ((rc = fetched_set(c, &fs))) return rc;
-    if (fs->seq == 0) return fail(PSDR_ERR_STATE, "the fetched batch carries no audio (PSDR_FETCH_AUDIO / _PCM)");
-    if ((size_t)id >= fs->win.size() || fs->win[id].last_seq != fs->seq || fs->win[id].born != c->aslots[id].born)
-        return fail(PSDR_ERR_NO_DATA, "client %d was not part of the fetched batch", id);
-    if (l) *l = fs->win[id].l;
-    if (audio_mid) *audio_mid = fs->win[id].mid;
-    if (r) *r = fs->win[id].r;
-    return PSDR_OK;
-}
-extern "C" int psdr_fetched_audio(psdr_ctx *c, int id, int frame, const float **audio, float *pwr, int32_t *nan_flag,
-                                  const int32_t **pcm) {
-    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
-    const psdr_ctx::FetchSet *fs = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(c->mtx);
-        int rc = check_slot(c, id);
-        if (rc) return rc;
-        if ((rc = fetched_set(c, &fs))) return rc;
-        if (fs->seq == 0) return fail(PSDR_ERR_STATE, "the fetched batch carries no audio (PSDR_FETCH_AUDIO / _PCM)");
-        if ((rc = slot_in_fetched_set(c, fs, id, false))) return rc;
-    }
-    if (frame < 0 || frame >= fs->frames) return fail(PSDR_ERR_INVALID, "frame %d not in the fetched batch of %d", frame, fs->frames);
-    const size_t h = (size_t)c->n / 2, mb = (size_t)c->max_batch, row = (size_t)id * mb + (size_t)frame;
-    if (audio) *audio = (fs->what & PSDR_FETCH_AUDIO) ? fs->audio + row * h : nullptr;
-    if (pwr) *pwr = fs->pwr[row];
-    if (nan_flag) *nan_flag = fs->nan[row];
-    if (pcm) *pcm = ((fs->what & PSDR_FETCH_PCM) && !fs->pcm16) ? fs->pcm + row * h : nullptr;  // (int16 rows: psdr_fetched_pcm16)
-    return PSDR_OK;
-}
-extern "C" int psdr_fetched_pcm16(psdr_ctx *c, int id, int frame, const int16_t **pcm) {
-    if (!c || !pcm) return fail(PSDR_ERR_INVALID, "null argument");
-    const psdr_ctx::FetchSet *fs = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(c->mtx);
-        int rc = check_slot(c, id);
-        if (rc) return rc;
-        if ((rc = fetched_set(c, &fs))) return rc;
-        if (fs->seq == 0 || !(fs->what & PSDR_FETCH_PCM)) return fail(PSDR_ERR_STATE, "the fetched batch carries no PCM (PSDR_FETCH_PCM)");
-        if (!fs->pcm16) return fail(PSDR_ERR_STATE, "the fetched PCM rows are int32 (PSDR_OPT_POST_CHAIN_PCM16 was 0 for that batch): psdr_fetched_audio");
-        if ((rc = slot_in_fetched_set(c, fs, id, false))) return rc;
-    }
-    if (frame < 0 || frame >= fs->frames) return fail(PSDR_ERR_INVALID, "frame %d not in the fetched batch of %d", frame, fs->frames);
-    const size_t h = (size_t)c->n / 2, mb = (size_t)c->max_batch, row = (size_t)id * mb + (size_t)frame;
-    *pcm = reinterpret_cast<const int16_t *>(fs->pcm.get()) + row * h;
-    return PSDR_OK;
-}
-extern "C" int psdr_fetched_iq(psdr_ctx *c, int id, int frame, const float **iq, float *pwr, int32_t *nan_flag) {
-    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
-    const psdr_ctx::FetchSet *fs = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(c->mtx);
-        int rc = check_slot(c, id);
-        if (rc) return rc;
-        if ((rc = fetched_set(c, &fs))) return rc;
-        if (fs->seq == 0) return fail(PSDR_ERR_STATE, "the fetched batch carries no audio (PSDR_FETCH_AUDIO / _PCM / _IQ)");
-        if ((rc = slot_in_fetched_set(c, fs, id, true))) return rc;
-    }
-    if (frame < 0 || frame >= fs->frames) return fail(PSDR_ERR_INVALID, "frame %d not in the fetched batch of %d", frame, fs->frames);
-    const size_t h = (size_t)c->n / 2, mb = (size_t)c->max_batch, row = (size_t)id * mb + (size_t)frame;
-    // (an IQ slot of a set fetched with PSDR_FETCH_IQ lies inside the span by construction)
-    const bool have = (fs->what & PSDR_FETCH_IQ) && id >= fs->iq_lo && id < fs->iq_lo + fs->iq_n;
-    if (iq) *iq = have ? reinterpret_cast<const float *>(fs->iq.get() + ((size_t)(id - fs->iq_lo) * mb + (size_t)frame) * h) : nullptr;
-    if (pwr) *pwr = fs->pwr[row];
-    if (nan_flag) *nan_flag = fs->nan[row];
-    return PSDR_OK;
-}
-extern "C" int psdr_fetched_carrier(psdr_ctx *c, int id, int frame, float *level, float *offset_hz) {
-    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
-    const psdr_ctx::FetchSet *fs = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(c->mtx);
-        int rc = check_slot(c, id);
-        if (rc) return rc;
-        if ((rc = fetched_set(c, &fs))) return rc;
-        if (fs->seq == 0) return fail(PSDR_ERR_STATE, "the fetched batch carries no audio (PSDR_FETCH_AUDIO / _PCM / _IQ)");
-        if ((rc = slot_in_fetched_set(c, fs, id, false))) return rc;
-        if (fs->win[id].mode != PSDR_SAM || id < fs->car_lo || id >= fs->car_lo + fs->car_n)
-            return fail(PSDR_ERR_NO_DATA, "client %d was not demodulated as PSDR_SAM in the fetched batch", id);
-    }
-    if (frame < 0 || frame >= fs->frames) return fail(PSDR_ERR_INVALID, "frame %d not in the fetched batch of %d", frame, fs->frames);
-    const cf rec = fs->car[(size_t)(id - fs->car_lo) * (size_t)c->max_batch + (size_t)frame];
-    if (level) *level = rec.x;
-    if (offset_hz) *offset_hz = rec.y;
-    return PSDR_OK;
-}
-extern "C" int psdr_fetched_squelch(psdr_ctx *c, int id, int frame, int32_t *open) {
-    if (!c || !open) return fail(PSDR_ERR_INVALID, "null argument");
-    const psdr_ctx::FetchSet *fs = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(c->mtx);
-        int rc = check_slot(c, id);
-        if (rc) return rc;
-        if ((rc = fetched_set(c, &fs))) return rc;
-        if (fs->seq == 0) return fail(PSDR_ERR_STATE, "the fetched batch carries no audio (PSDR_FETCH_AUDIO / _PCM / _IQ)");
-        if ((size_t)id >= fs->win.size() || fs->win[id].last_seq != fs->seq || fs->win[id].born != c->aslots[id].born)
-            return fail(PSDR_ERR_NO_DATA, "client %d was not part of the fetched batch", id);
-    }
-    if (frame < 0 || frame >= fs->frames) return fail(PSDR_ERR_INVALID, "frame %d not in the fetched batch of %d", frame, fs->frames);
-    // (a slot that ran with squelch lies inside the span by construction; any other reads open)
-    const bool have = fs->win[id].sq && id >= fs->sq_lo && id < fs->sq_lo + fs->sq_n;
-    *open = have ? fs->sq[(size_t)(id - fs->sq_lo) * (size_t)c->max_batch + (size_t)frame] : 1;
-    return PSDR_OK;
-}
-extern "C" int psdr_fetched_iq_span(psdr_ctx *c, int *first_slot, int *nslots, size_t *bytes) {
-    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
-    const psdr_ctx::FetchSet *fs = nullptr;
-    int rc = fetched_set(c, &fs);
-    if (rc) return rc;
-    if (!(fs->what & PSDR_FETCH_IQ)) return fail(PSDR_ERR_STATE, "the fetched batch carries no IQ rows (PSDR_FETCH_IQ)");
-    if (first_slot) *first_slot = fs->iq_lo;
-    if (nslots) *nslots = fs->iq_n;
-    if (bytes) *bytes = fs->iq_bytes;
-    return PSDR_OK;
-}
-extern "C" int psdr_fetched_waterfall(psdr_ctx *c, int id, const int8_t **rows, int *nsent_out, int *level_out, int *l_out, int *r_out) {
-    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
-    const psdr_ctx::FetchSet *fs = nullptr;
-    int rc = fetched_set(c, &fs);
-    if (rc) return rc;
-    if (!(fs->what & PSDR_FETCH_WATERFALL)) return fail(PSDR_ERR_STATE, "the fetched batch carries no waterfall rows (PSDR_FETCH_WATERFALL)");
-    if (id < 0 || (size_t)id >= fs->wfm.size() || !fs->wfm[id].active) return fail(PSDR_ERR_NO_DATA, "waterfall client %d was not part of the fetched batch", id);
-    const WfSlot &w = fs->wfm[id];
-    if (rows) *rows = w.nsent > 0 ? fs->wf + w.out_off : nullptr;
-    if (nsent_out) *nsent_out = w.nsent;
-    if (level_out) *level_out = w.b_level;
-    if (l_out) *l_out = w.b_l;
-    if (r_out) *r_out = w.b_r;
-    return PSDR_OK;
-}
-
-extern "C" int psdr_read_pcm(psdr_ctx *c, int id, int nframes, int32_t *pcm, int *nframes_out) {
-    if (!c || !pcm) return fail(PSDR_ERR_INVALID, "null argument");
-    {
-        std::lock_guard<std::mutex> lk(c->mtx);
-        int rc = check_slot(c, id);
-        if (rc) return rc;
-    }
-    if (!c->post_on) return fail(PSDR_ERR_STATE, "post chain not enabled (psdr_set_post_chain)");
-    HIPCHK(hipSetDevice(c->device));
-    const size_t F = (size_t)c->last_demod_frames, h = (size_t)c->n / 2, mb = (size_t)c->max_batch;
-    if (F == 0) return fail(PSDR_ERR_STATE, "no demodulated batch to read");
-    if (nframes < (int)F) return fail(PSDR_ERR_INVALID, "buffer holds %d frames, the last batch has %zu", nframes, F);
-    {
-        int rc = slot_in_last_batch(c, id);
-        if (rc) return rc;
-        rc = drain(c);
-        if (rc) return rc;
-    }
-    if (c->pcm_is16) {  // PSDR_OPT_POST_CHAIN_PCM16: the rows are int16 on the device; this call still delivers the reference's int32 buffer
-        std::vector<int16_t> tmp(F * h);
-        HIPCHK(hipMemcpy(tmp.data(), reinterpret_cast<const int16_t *>(c->post.pcm) + (size_t)id * mb * h, F * h * sizeof(int16_t), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < F * h; i++) pcm[i] = tmp[i];
-    } else {
-        HIPCHK(hipMemcpy(pcm, c->post.pcm + (size_t)id * mb * h, F * h * sizeof(int32_t), hipMemcpyDeviceToHost));
-    }
-    if (nframes_out) *nframes_out = (int)F;
-    return PSDR_OK;
-}
-
 extern "C" int psdr_demod_batch(psdr_ctx *c, uint64_t first_frame_num) {
     if (!c) return fail(PSDR_ERR_INVALID, "null argument");
     if (c->last_nframes < 1) return fail(PSDR_ERR_STATE, "demod_batch before process_batch/execute");
@@ -1054,161 +647,4 @@ extern "C" int psdr_demod_batch_from_band_region(psdr_ctx *c, const float *d_reg
     if (frame_stride_bins < nbins) return fail(PSDR_ERR_INVALID, "frame stride smaller than the band");
     const uint32_t band[2] = {first_bin, nbins};
     return demod_impl(c, (const cf *)d_region, frame_stride_bins, nframes, first_frame_num, band, true);
-}
-
-extern "C" int psdr_read_audio(psdr_ctx *c, int id, int nframes, float *audio, float *pwr, int32_t *nan_flags,
-                               int *nframes_out) {
-    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
-    {
-        std::lock_guard<std::mutex> lk(c->mtx);
-        int rc = check_slot(c, id);
-        if (rc) return rc;
-    }
-    HIPCHK(hipSetDevice(c->device));
-    const size_t F = (size_t)c->last_demod_frames, h = (size_t)c->n / 2, mb = (size_t)c->max_batch;
-    if (F == 0) return fail(PSDR_ERR_STATE, "no demodulated batch to read");
-    if (nframes < (int)F) return fail(PSDR_ERR_INVALID, "buffers hold %d frames, the last batch has %zu", nframes, F);
-    if (nframes_out) *nframes_out = (int)F;
-    {
-        int rc = slot_in_last_batch(c, id);
-        if (rc) return rc;
-        rc = drain(c);
-        if (rc) return rc;
-    }
-    if (audio)
-        HIPCHK(hipMemcpyAsync(audio, c->d_audio + (size_t)id * mb * h, F * h * sizeof(float),
-                              hipMemcpyDeviceToHost, c->stream));
-    if (pwr)
-        HIPCHK(hipMemcpyAsync(pwr, c->d_pwr + (size_t)id * mb, F * sizeof(float), hipMemcpyDeviceToHost,
-                              c->stream));
-    if (nan_flags)
-        HIPCHK(hipMemcpyAsync(nan_flags, c->d_nan + (size_t)id * mb, F * sizeof(int),
-                              hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return PSDR_OK;
-}
-extern "C" int psdr_read_squelch(psdr_ctx *c, int id, int nframes, int32_t *open, int *nframes_out) {
-    if (!c || !open) return fail(PSDR_ERR_INVALID, "null argument");
-    bool on = false;
-    const size_t F = (size_t)c->last_demod_frames, mb = (size_t)c->max_batch;
-    {
-        std::lock_guard<std::mutex> lk(c->mtx);
-        int rc = check_slot(c, id);
-        if (rc) return rc;
-        if (F == 0) return fail(PSDR_ERR_STATE, "no demodulated batch to read");
-        if (nframes < (int)F) return fail(PSDR_ERR_INVALID, "buffer holds %d frames, the last batch has %zu", nframes, F);
-        if (c->demod_seq == 0 || c->aslots[id].last_seq != c->demod_seq)
-            return fail(PSDR_ERR_NO_DATA, "client %d was not part of the last demodulation batch", id);
-        on = c->aslots[id].b_sq_on;
-    }
-    if (nframes_out) *nframes_out = (int)F;
-    if (!on) {  // the batch ran without squelch for this client: every frame is heard (the host snapshot answers)
-        std::fill(open, open + F, 1);
-        return PSDR_OK;
-    }
-    HIPCHK(hipSetDevice(c->device));
-    int rc = drain(c);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(open, c->d_sq + (size_t)id * mb, F * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return PSDR_OK;
-}
-extern "C" int psdr_read_notches(psdr_ctx *c, int id, int first[4], int end[4]) {
-    if (!c || !first || !end) return fail(PSDR_ERR_INVALID, "null argument");
-    int man[4];
-    bool have_tab = false;
-    {
-        std::lock_guard<std::mutex> lk(c->mtx);
-        int rc = check_slot(c, id);
-        if (rc) return rc;
-        if (c->last_demod_frames == 0 || c->demod_seq == 0) return fail(PSDR_ERR_STATE, "no demodulated batch to read");
-        if (c->aslots[id].last_seq != c->demod_seq) return fail(PSDR_ERR_NO_DATA, "client %d was not part of the last demodulation batch", id);
-        for (int k = 0; k < 4; k++) man[k] = c->aslots[id].b_notch[k];
-        have_tab = (bool)c->d_notch_tab;
-    }
-    int4 t = make_int4(0, 0, 0, 0);
-    if (have_tab) {  // the table as the batch's detector left it: in force from the next batch on
-        HIPCHK(hipSetDevice(c->device));
-        int rc = drain(c);
-        if (rc) return rc;
-        HIPCHK(hipMemcpy(&t, c->d_notch_tab + id, sizeof(int4), hipMemcpyDeviceToHost));
-    }
-    first[0] = man[0], end[0] = man[1], first[1] = man[2], end[1] = man[3];
-    first[2] = t.x, end[2] = t.y, first[3] = t.z, end[3] = t.w;
-    return PSDR_OK;
-}
-extern "C" int psdr_audio_device_ptr(psdr_ctx *c, int id, const float **d_audio, const float **d_pwr) {
-    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
-    if (id < 0 || id >= (int)c->aslots.size()) return fail(PSDR_ERR_INVALID, "bad id %d", id);
-    const size_t h = (size_t)c->n / 2, mb = (size_t)c->max_batch;
-    if (d_audio) *d_audio = c->d_audio + (size_t)id * mb * h;
-    if (d_pwr) *d_pwr = c->d_pwr + (size_t)id * mb;
-    return PSDR_OK;
-}
-extern "C" int psdr_read_iq(psdr_ctx *c, int id, int nframes, float *iq, float *pwr, int32_t *nan_flags, int *nframes_out) {
-    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
-    {
-        std::lock_guard<std::mutex> lk(c->mtx);
-        int rc = check_slot(c, id);
-        if (rc) return rc;
-    }
-    HIPCHK(hipSetDevice(c->device));
-    const size_t F = (size_t)c->last_demod_frames, h = (size_t)c->n / 2, mb = (size_t)c->max_batch;
-    if (F == 0) return fail(PSDR_ERR_STATE, "no demodulated batch to read");
-    if (nframes < (int)F) return fail(PSDR_ERR_INVALID, "buffers hold %d frames, the last batch has %zu", nframes, F);
-    if (nframes_out) *nframes_out = (int)F;
-    {
-        int rc = slot_in_last_batch(c, id, true);
-        if (rc) return rc;
-        rc = drain(c);
-        if (rc) return rc;
-    }
-    if (iq)
-        HIPCHK(hipMemcpyAsync(iq, c->d_iq + (size_t)id * mb * h, F * h * sizeof(cf), hipMemcpyDeviceToHost, c->stream));
-    if (pwr)
-        HIPCHK(hipMemcpyAsync(pwr, c->d_pwr + (size_t)id * mb, F * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (nan_flags)
-        HIPCHK(hipMemcpyAsync(nan_flags, c->d_nan + (size_t)id * mb, F * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return PSDR_OK;
-}
-extern "C" int psdr_iq_device_ptr(psdr_ctx *c, int id, const float **d_iq, const float **d_pwr) {
-    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
-    if (id < 0 || id >= (int)c->aslots.size()) return fail(PSDR_ERR_INVALID, "bad id %d", id);
-    if (!c->d_iq) return fail(PSDR_ERR_NO_DATA, "no batch with a PSDR_IQ client has been demodulated");
-    const size_t h = (size_t)c->n / 2, mb = (size_t)c->max_batch;
-    if (d_iq) *d_iq = reinterpret_cast<const float *>(c->d_iq + (size_t)id * mb * h);
-    if (d_pwr) *d_pwr = c->d_pwr + (size_t)id * mb;
-    return PSDR_OK;
-}
-extern "C" int psdr_read_carrier(psdr_ctx *c, int id, int nframes, float *level, float *offset_hz, int *nframes_out) {
-    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
-    {
-        std::lock_guard<std::mutex> lk(c->mtx);
-        int rc = check_slot(c, id);
-        if (rc) return rc;
-    }
-    HIPCHK(hipSetDevice(c->device));
-    const size_t F = (size_t)c->last_demod_frames, mb = (size_t)c->max_batch;
-    if (F == 0) return fail(PSDR_ERR_STATE, "no demodulated batch to read");
-    if (nframes < (int)F) return fail(PSDR_ERR_INVALID, "buffers hold %d frames, the last batch has %zu", nframes, F);
-    if (nframes_out) *nframes_out = (int)F;
-    {
-        int rc = slot_in_last_batch(c, id);
-        if (rc) return rc;
-        {
-            std::lock_guard<std::mutex> lk(c->mtx);
-            if (c->aslots[id].b_mode != PSDR_SAM || !c->d_car)
-                return fail(PSDR_ERR_NO_DATA, "client %d was not demodulated as PSDR_SAM in the last batch", id);
-        }
-        rc = drain(c);
-        if (rc) return rc;
-    }
-    std::vector<cf> rec(F);
-    HIPCHK(hipMemcpyAsync(rec.data(), c->d_car + (size_t)id * mb, F * sizeof(cf), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    for (size_t f = 0; f < F; f++) {
-        if (level) level[f] = rec[f].x;
-        if (offset_hz) offset_hz[f] = rec[f].y;
-    }
-    return PSDR_OK;
 }
