@@ -461,6 +461,49 @@ int psdr_read_notches(psdr_ctx *ctx, int id, int first[4], int end[4]);
 int psdr_client_set_squelch(psdr_ctx *ctx, int id, int on, double open_db, double close_db, int attack_frames, int hang_frames);
 int psdr_read_squelch(psdr_ctx *ctx, int id, int nframes, int32_t *open, int *nframes_out);
 int psdr_fetched_squelch(psdr_ctx *ctx, int id, int frame, int32_t *open);
+/* Audio filter: a cascade of 1 or 2 biquad sections per client on the audio BEHIND the detector - the one place the window
+ * [l, r) cannot reach: FM de-emphasis, a cut against a sub-audible tone, hum on an AM carrier, a CW peak filter.
+ *   Form.  Each section is in transposed direct form II with two f32 states, from sample to sample:
+ *       y = fma(b0, x, s1);  s1 = fma(b1, x, fma(-a1, y, s2));  s2 = fma(b2, x, -a2 * y)
+ *     with the coefficients rounded once from double to f32, every operation a fused multiply-add or a lone multiply, subnormals
+ *     kept.  The second section takes the first one's y.  The device evaluates a client's stream in blocks of 64 chunks of 16
+ *     samples (a zero-state pass per chunk, a scan of the chunks' end states over the powers of the section's state matrix, a
+ *     pass from the true entry state): a re-association of the recurrence above whose rounding differs from the sample-by-
+ *     sample form by a few units in the last place; phantomsdr_amd/csrc/audiofilterplan.h is its one definition, for the
+ *     device and for a host program alike, bit for bit.
+ *   Who.  Every client of a batch whose kind writes audio rows: USB / LSB / AM / FM, SAM, sideband SAM, tuned USB / LSB.  A
+ *     PSDR_IQ client (tuned or not) keeps its setting, is not filtered and its state stands still; a paused client's too.
+ *   What.  A client's batch is the contiguous stream of nframes * audio_fft_size / 2 floats of its rows, filtered in place:
+ *     psdr_read_audio, the fetches, psdr_audio_device_ptr and the post chain see filtered rows; pwr, NaN flags, carrier
+ *     records and every piece of demodulation state are untouched.  A frame whose NaN flag is set enters the filter as zeros -
+ *     the state advances, time passes - and its row is left exactly as the demodulator wrote it.  Frames the squelch closes
+ *     are filtered like any others.
+ *   State.  It starts from zero when psdr_client_set_audio_filter is called with nsections >= 1 - switching on, or new
+ *     coefficients - and at no other time: a retune or a mode change does not reset it.
+ * psdr_client_set_audio_filter: any thread; in force from the client's next batch; nsections = 0 switches it off and ignores
+ *   `sections`.  PSDR_ERR_INVALID, with nothing changed, for an unknown id, nsections outside 0..2, a null pointer with
+ *   nsections > 0, a non-finite coefficient, a section that is not stable (stable: |a2| < 1 and |a1| < 1 + a2) or one whose
+ *   pole radius exceeds 0.9995 - in this order, each looked for in every section before the next.  Stability and the radius are
+ *   those of the coefficients AS GIVEN, in double; the rounding to f32 moves 1 + a1 + a2 by 1.5e-7 at the most, less than the
+ *   2.5e-7 two real poles at the limit leave, so an accepted section stays stable, with a pole up to 3e-4 past the limit.  The device state (16 bytes
+ *   per client slot and the batches' table, 2176 bytes per slot) is allocated with the context's first filter client, all or
+ *   none: PSDR_ERR_NOMEM and the setting unchanged if that fails.
+ * psdr_audio_filter_design: needs no context.  The bilinear transform, in double, with K = tan(pi f0 / audio_rate):
+ *   PSDR_AF_DEEMPHASIS  b0 = b1 = K / (1 + K), b2 = 0, a1 = (K - 1) / (K + 1), a2 = 0 (q ignored)
+ *   with N = 1 / (1 + K / q + K^2), a1 = 2 (K^2 - 1) N, a2 = (1 - K / q + K^2) N:
+ *   PSDR_AF_LOWPASS     b0 = b2 = K^2 N, b1 = 2 b0          PSDR_AF_HIGHPASS  b0 = b2 = N, b1 = -2 N
+ *   PSDR_AF_PEAK        b0 = (K / q) N, b1 = 0, b2 = -b0
+ *   PSDR_ERR_INVALID for an unknown kind, a null `out`, a rate or f0 that is not finite, f0 outside (0, audio_rate / 2), q <= 0
+ *   or not finite (but for PSDR_AF_DEEMPHASIS), and for any result psdr_client_set_audio_filter would refuse.
+ * There is no psdr_group_* call: a group's clients have no audio filter. */
+#define PSDR_AUDIO_FILTER_SECTIONS 2
+typedef struct { double b0, b1, b2, a1, a2; } psdr_biquad;   /* y = b0 x + b1 x[-1] + b2 x[-2] - a1 y[-1] - a2 y[-2] */
+int psdr_client_set_audio_filter(psdr_ctx *ctx, int id, int nsections, const psdr_biquad *sections); /* 0: off */
+#define PSDR_AF_DEEMPHASIS 0   /* first order low-pass, corner f0 (tau = 1 / (2 pi f0)); q ignored */
+#define PSDR_AF_HIGHPASS   1
+#define PSDR_AF_LOWPASS    2
+#define PSDR_AF_PEAK       3   /* band-pass with 0 dB at f0, bandwidth f0 / q */
+int psdr_audio_filter_design(int kind, double audio_rate, double f0, double q, psdr_biquad *out);    /* no context */
 /* A client added after the last psdr_demod_batch has no results in it (the reference's frame loop would not
  * have posted a task for it either, src/websocket.cpp:156-185): psdr_read_audio / psdr_read_pcm / psdr_fetched_audio
  * return PSDR_ERR_NO_DATA for such a slot instead of the previous occupant's samples.

@@ -25,6 +25,11 @@ class psdr_config(C.Structure):
     ]
 
 
+class psdr_biquad(C.Structure):
+    """one section of psdr_client_set_audio_filter: y = b0 x + b1 x[-1] + b2 x[-2] - a1 y[-1] - a2 y[-2]"""
+    _fields_ = [(n, C.c_double) for n in ("b0", "b1", "b2", "a1", "a2")]
+
+
 # every symbol include/psdr.h declares: (name, restype, argtypes)
 _vp, _i, _sz, _u64 = C.c_void_p, C.c_int, C.c_size_t, C.c_uint64
 _pp = C.POINTER(C.c_void_p)
@@ -77,6 +82,8 @@ SYMBOLS = [
     ("psdr_client_set_squelch", _i, [_vp, _i, _i, C.c_double, C.c_double, _i, _i]),
     ("psdr_read_squelch", _i, [_vp, _i, _i, _vp, C.POINTER(_i)]),
     ("psdr_fetched_squelch", _i, [_vp, _i, _i, C.POINTER(C.c_int32)]),
+    ("psdr_client_set_audio_filter", _i, [_vp, _i, _i, _vp]),
+    ("psdr_audio_filter_design", _i, [_i, C.c_double, C.c_double, C.c_double, _vp]),
     ("psdr_demod_batch", _i, [_vp, _u64]),
     ("psdr_demod_batch_from", _i, [_vp, _vp, _sz, _i, _u64]),
     ("psdr_pack_band", _i, [_vp, _i, C.c_uint32, C.c_uint32, _vp, _sz]),

@@ -32,7 +32,22 @@ SAM_SIDEBANDS = {"both": SAM_BOTH, "upper": SAM_UPPER, "lower": SAM_LOWER}
 WF_SAMPLE, WF_PEAK, WF_MEAN = 0, 1, 2
 WF_DETECTORS = {"sample": WF_SAMPLE, "peak": WF_PEAK, "mean": WF_MEAN}
 
+# PSDR_AF_* (include/psdr.h): the presets of psdr_audio_filter_design
+AF_DEEMPHASIS, AF_HIGHPASS, AF_LOWPASS, AF_PEAK = 0, 1, 2, 3
+AF_KINDS = {"deemphasis": AF_DEEMPHASIS, "highpass": AF_HIGHPASS, "lowpass": AF_LOWPASS, "peak": AF_PEAK}
+AUDIO_FILTER_SECTIONS = 2
+
 FFTW_MEASURE, FFTW_DESTROY_INPUT, FFTW_ESTIMATE = 0, 1, 1 << 6  # accepted and ignored
+
+
+def design_audio_filter(kind, rate, f0, q=math.sqrt(0.5)):
+    """one section (b0, b1, b2, a1, a2) for AudioClient.set_audio_filter (psdr_audio_filter_design; needs no context): kind
+    "deemphasis" (first-order low-pass with its corner at f0, q ignored), "highpass", "lowpass" or "peak" (0 dB at f0, bandwidth
+    f0 / q), or an AF_* constant"""
+    b = _lib.psdr_biquad()
+    k = AF_KINDS[kind] if isinstance(kind, str) else int(kind)
+    check(_lib.load().psdr_audio_filter_design(k, float(rate), float(f0), float(q), C.byref(b)))
+    return (b.b0, b.b1, b.b2, b.a1, b.a2)
 
 
 def derived_params(sps, fft_size, is_real, audio_sps=12000, waterfall_size=1024):
@@ -507,6 +522,16 @@ class AudioClient:
         got = C.c_int(0)
         check(self.ctx.lib.psdr_read_squelch(self.ctx.h, self.id, F, _ptr(o), C.byref(got)))
         return o[:got.value]
+
+    def set_audio_filter(self, sections):
+        """biquad sections behind the detector (psdr_client_set_audio_filter): a list of one or two (b0, b1, b2, a1, a2), for
+        instance from design_audio_filter(); the empty list switches the filter off.  The client's audio rows are filtered in
+        place from its next batch on; the state starts from zero with every call that sets sections."""
+        sections = [tuple(float(v) for v in s) for s in sections]
+        if any(len(s) != 5 for s in sections):
+            raise ValueError("a section is (b0, b1, b2, a1, a2)")
+        arr = (_lib.psdr_biquad * max(len(sections), 1))(*[_lib.psdr_biquad(*s) for s in sections])
+        check(self.ctx.lib.psdr_client_set_audio_filter(self.ctx.h, self.id, len(sections), C.cast(arr, C.c_void_p) if sections else None))
 
     def on_window_message(self, l, m, r):
         """returns False where the reference silently returns (src/signal.cpp:302-311)."""

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/psdr.h"
+#include "audiofilterplan.h"
 #include "blankerplan.h"
 #include "butterfly.h"
 #include "demodplan.h"
@@ -61,7 +62,7 @@ inline const char *psdr_tuning_env(const char *name) {
 
 namespace psdr {
 
-enum KernelId { K_PASS1, K_PASS2, K_UNTANGLE, K_TAIL, K_IDFT, K_OLA, K_WFALL, K_POST, K_SEAM, K_BAND, K_WFHOLD, K_WFCARRY, K_SQUELCH, K_NB_SCAN, K_NB_APPLY, K_COUNT };
+enum KernelId { K_PASS1, K_PASS2, K_UNTANGLE, K_TAIL, K_IDFT, K_OLA, K_WFALL, K_POST, K_SEAM, K_BAND, K_WFHOLD, K_WFCARRY, K_SQUELCH, K_NB_SCAN, K_NB_APPLY, K_AUDIO_FILTER, K_COUNT };
 extern const char *kKernelNames[K_COUNT];
 
 struct PendingEvent {
@@ -299,6 +300,12 @@ struct psdr_ctx {
     DevBuf<SquelchState> d_sq_state;
     HostBuf<SquelchEntry> h_sq_tab;
     DevBuf<SquelchEntry> d_sq_tab;
+    // audio filter (audiofilter.h: k_audio_filter): the sections' carried state [slots][2 sections][2] and the batch's table
+    // (audiofilterplan.h), one image of [slots] entries per slot of client_ring like the squelch's - allocated with the context's
+    // first filter client (under mtx), both or none, and kept
+    DevBuf<float> d_af_state;
+    HostBuf<AfEntry> h_af_tab;
+    DevBuf<AfEntry> d_af_tab;
     DevBuf<unsigned> d_ssb_mark;  // [slots] DemodArgs::ssb_mark (demod.h): USB / LSB batches that need the frame-ordered NaN guard
     ParamRing client_ring;
     int last_demod_frames = 0;

@@ -4,6 +4,7 @@
 #include "ctx.h"
 #include "demod.h"
 #include "squelch.h"
+#include "audiofilter.h"
 
 // the context's first tuned USB / LSB client: its family's tails (a context that never sees one allocates nothing); under mtx
 static int ft_tail_alloc(psdr_ctx *c) {
@@ -78,6 +79,25 @@ static int squelch_alloc(psdr_ctx *c) {
     c->d_sq_state = std::move(state);
     c->h_sq_tab = std::move(h_tab);
     c->d_sq_tab = std::move(d_tab);
+    return PSDR_OK;
+}
+// the context's first audio filter client: the sections' state and the batch's table, all or none (a context that never sees one
+// allocates nothing); under mtx
+static int audio_filter_alloc(psdr_ctx *c) {
+    if (c->d_af_tab) return PSDR_OK;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t S = c->aslots.size();
+    DevBuf<float> state;
+    HostBuf<AfEntry> h_tab;
+    DevBuf<AfEntry> d_tab;
+    if (state.alloc(S * 2 * PSDR_AUDIO_FILTER_SECTIONS, true) || h_tab.alloc(S * ParamRing::K) || d_tab.alloc(S * ParamRing::K, true)) {
+        const std::string msg = psdr_last_error();
+        return fail(PSDR_ERR_NOMEM, "audio filter state and table (%zu bytes): %s",
+                    S * (2 * PSDR_AUDIO_FILTER_SECTIONS * sizeof(float) + ParamRing::K * sizeof(AfEntry)), msg.c_str());
+    }
+    c->d_af_state = std::move(state);
+    c->h_af_tab = std::move(h_tab);
+    c->d_af_tab = std::move(d_tab);
     return PSDR_OK;
 }
 int psdr::check_slot(psdr_ctx *c, int id) {
@@ -286,6 +306,50 @@ extern "C" int psdr_client_set_squelch(psdr_ctx *c, int id, int on, double open_
     squelch_apply(c->aslots[id], on, open_db, close_db, attack_frames, hang_frames);
     return PSDR_OK;
 }
+extern "C" int psdr_client_set_audio_filter(psdr_ctx *c, int id, int nsections, const psdr_biquad *sections) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mtx);
+    switch (audio_filter_check(c->aslots.data(), c->aslots.size(), id, nsections, sections)) {
+    case AF_OK: break;
+    case AF_BAD_ID: return fail(PSDR_ERR_INVALID, "no audio client with id %d", id);
+    case AF_BAD_COUNT: return fail(PSDR_ERR_INVALID, "audio filter: %d sections outside 0..%d", nsections, PSDR_AUDIO_FILTER_SECTIONS);
+    case AF_NULL: return fail(PSDR_ERR_INVALID, "audio filter: %d sections and a null pointer", nsections);
+    case AF_NONFINITE: return fail(PSDR_ERR_INVALID, "audio filter: a coefficient that is not a finite f32 number");
+    case AF_UNSTABLE: return fail(PSDR_ERR_INVALID, "audio filter: a section that is not stable (|a2| < 1 and |a1| < 1 + a2)");
+    case AF_POLE: return fail(PSDR_ERR_INVALID, "audio filter: a pole radius above %g", AF_POLE_MAX);
+    }
+    if (nsections > 0) PSDRCHK(audio_filter_alloc(c));
+    audio_filter_apply(c->aslots[id], nsections, sections);
+    return PSDR_OK;
+}
+// (a debug entry, beside psdr_debug_notch_ptrs: exported for the tests, not part of include/psdr.h)  out[0..1]: the audio filter's
+// table and state (null until the context's first filter client)
+extern "C" int psdr_debug_audio_filter_ptrs(psdr_ctx *c, const void *out[2]) {
+    if (!c || !out) return fail(PSDR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mtx);
+    out[0] = c->d_af_tab.get(), out[1] = c->d_af_state.get();
+    return PSDR_OK;
+}
+// (... and whether the last chain batch's moving averages read the audio rows themselves, k_pc_ma2 DIRECT: the form in which the
+// chain reads what k_audio_filter has just written without a gathered copy between them)
+extern "C" int psdr_debug_post_direct(psdr_ctx *c, int *direct) {
+    if (!c || !direct) return fail(PSDR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mtx);
+    *direct = c->post_direct ? 1 : 0;
+    return PSDR_OK;
+}
+extern "C" int psdr_audio_filter_design(int kind, double audio_rate, double f0, double q, psdr_biquad *out) {
+    switch (audio_filter_design(kind, audio_rate, f0, q, out)) {
+    case AD_OK: break;
+    case AD_NULL: return fail(PSDR_ERR_INVALID, "null argument");
+    case AD_BAD_KIND: return fail(PSDR_ERR_INVALID, "audio filter design: unknown kind %d", kind);
+    case AD_BAD_RATE: return fail(PSDR_ERR_INVALID, "audio filter design: audio_rate %g", audio_rate);
+    case AD_BAD_F0: return fail(PSDR_ERR_INVALID, "audio filter design: f0 %g outside (0, %g)", f0, audio_rate / 2);
+    case AD_BAD_Q: return fail(PSDR_ERR_INVALID, "audio filter design: q %g", q);
+    case AD_REFUSED: return fail(PSDR_ERR_INVALID, "audio filter design: kind %d at f0 %g, q %g, rate %g gives a section psdr_client_set_audio_filter refuses", kind, f0, q, audio_rate);
+    }
+    return PSDR_OK;
+}
 // out[0..2]: the detector's table, sums and counters (null until the context's first auto-notch client); out[3..4]:
 // DemodArgs::notch_man / notch_auto of the last demodulation batch
 extern "C" int psdr_debug_notch_ptrs(psdr_ctx *c, const void *out[5]) {
@@ -410,6 +474,8 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     SquelchPlan sq;
     int *sq_rows[2] = {nullptr, nullptr};
     SquelchEntry *h_sq = nullptr, *d_sq_list = nullptr;  // this ring slot's image of the squelch table
+    AfPlan af;
+    AfEntry *h_af = nullptr, *d_af_list = nullptr;  // this ring slot's image of the audio filter's table
     int4 *notch_tab = nullptr;
     cf *iq_rows[2] = {nullptr, nullptr}, *car_rows[2] = {nullptr, nullptr};
     {
@@ -429,12 +495,19 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
             h_sq = c->h_sq_tab + (size_t)ring * c->aslots.size(), d_sq_list = c->d_sq_tab + (size_t)ring * c->aslots.size();
             sq = squelch_plan(c->aslots.data(), c->aslots.size(), c->demod_seq, f.post_on && p.nact > 0, h_sq);
         }
+        if (c->d_af_tab) {  // (null until the context's first audio filter client)
+            h_af = c->h_af_tab + (size_t)ring * c->aslots.size(), d_af_list = c->d_af_tab + (size_t)ring * c->aslots.size();
+            af = audio_filter_plan(c->aslots.data(), c->aslots.size(), c->demod_seq, h_af);
+        }
     }
     c->last_demod_frames = nframes;
     if (p.idle()) return PSDR_OK;
     // the gates that start from (closed, 0): squelch_plan has taken sq_fresh off these slots, so the zeroing is enqueued before
     // anything below can fail the batch (`side` orders it behind the last batch's k_squelch and in front of this one's)
     for (size_t slot : sq.zero) HIPCHK(hipMemsetAsync(c->d_sq_state + slot, 0, sizeof(SquelchState), c->side));
+    // ... and the audio filters that start from zero, by the same rule (audio_filter_plan has taken af_fresh off these slots)
+    for (size_t slot : af.zero)
+        HIPCHK(hipMemsetAsync(c->d_af_state + slot * 2 * PSDR_AUDIO_FILTER_SECTIONS, 0, 2 * PSDR_AUDIO_FILTER_SECTIONS * sizeof(float), c->side));
     {  // this batch's results go to the OTHER set (the copies of the last batch to the host may still be reading theirs); what
        // read this set two batches ago must have landed
         c->out_set ^= 1;
@@ -462,6 +535,7 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     for (size_t off : p.ft_zero) HIPCHK(hipMemsetAsync(c->d_ft_tail + off, 0, tail_bytes, c->side));
     for (size_t off : p.sb_zero) HIPCHK(hipMemsetAsync(c->d_sb_tail + off, 0, tail_bytes, c->side));
     if (sq.any()) HIPCHK(hipMemcpyAsync(d_sq_list, h_sq, (size_t)(sq.nsq + sq.ncopy) * sizeof(SquelchEntry), hipMemcpyHostToDevice, c->side));
+    if (af.any()) HIPCHK(hipMemcpyAsync(d_af_list, h_af, (size_t)af.n * sizeof(AfEntry), hipMemcpyHostToDevice, c->side));
     DemodArgs a = demod_args(c, spec, spec_stride, nframes, first_frame_num, band, band_tiled);
     a.clients = ring_at<ClientParams>(d_ring, p.plain.clients);
     a.notch_man = p.any_manual ? ring_at<int4>(d_ring, p.notch) : nullptr;
@@ -604,6 +678,17 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
         hipLaunchKernelGGL(k_squelch, dim3((unsigned)qa.nlist), dim3(64), 0, c->side, qa);
         HIPCHK(hipGetLastError());
         if (chain) chain_drop = c->d_sq_drop;  // ... and the closed ones
+    }
+    if (af.any()) {
+        // the audio filter, behind the batch's last demodulation kernel and in front of the chain: it filters the listed clients'
+        // rows in place (k_squelch reads pwr and flags, not rows: their order does not matter)
+        AudioFilterArgs fa2{};
+        fa2.list = d_af_list, fa2.nlist = af.n;
+        fa2.audio = c->d_audio, fa2.nan_flags = c->d_nan;
+        fa2.state = c->d_af_state;
+        fa2.nframes = nframes, fa2.max_batch = c->max_batch, fa2.h = c->n / 2;
+        ProfScope ps(c, K_AUDIO_FILTER, c->side);
+        HIPCHK(audio_filter_launch(fa2, c->side));
     }
     hipStream_t last_user = c->side;
     if (chain)

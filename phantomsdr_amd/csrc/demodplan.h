@@ -14,6 +14,15 @@
 
 namespace psdr {
 
+// One section of a client's audio filter as the device table holds it (audiofilterplan.h): the f32 coefficients of
+// include/psdr.h's psdr_biquad and, for the blocked evaluation's scan, the powers P[k] = M^(2^k), k = 0..5, of M = A^16 with A =
+// [[-a1, 1], [-a2, 0]] the section's state matrix - row-major m00 m01 m10 m11, computed in double and rounded once
+struct AfSection {
+    float b0 = 0, b1 = 0, b2 = 0, a1 = 0, a2 = 0, pad[3] = {0, 0, 0};
+    float P[6][4] = {};
+};
+static_assert(sizeof(AfSection) == 128, "the device table's layout");
+
 struct AudioSlot {
     bool active = false;
     int l = 0, r = 0;
@@ -49,6 +58,11 @@ struct AudioSlot {
     float sq_t_open = 1.f, sq_t_close = 1.f;
     int sq_attack = 1, sq_hang = 0;
     bool b_sq_on = false, sq_fresh = false;
+    // psdr_client_set_audio_filter (audiofilterplan.h): af_n sections (0: off) as the table holds them; af_fresh: set since the
+    // slot's last filtered batch - the state starts from zero
+    int af_n = 0;
+    AfSection af_sec[PSDR_AUDIO_FILTER_SECTIONS];
+    bool af_fresh = false;
 };
 
 // The client parameter ring's slot.  [ClientParams x S][int x S]: the batch's list and, for the post chain, the list index of
