@@ -504,6 +504,56 @@ int psdr_client_set_audio_filter(psdr_ctx *ctx, int id, int nsections, const psd
 #define PSDR_AF_LOWPASS    2
 #define PSDR_AF_PEAK       3   /* band-pass with 0 dB at f0, bandwidth f0 / q */
 int psdr_audio_filter_design(int kind, double audio_rate, double f0, double q, psdr_biquad *out);    /* no context */
+/* AGC profile: speed, target, gain cap and manual gain per client.  The context's AGC is the reference's - target 0.2, attack
+ * 50 ms, release 300 ms (psdr_set_post_chain) - for every client; a profile replaces these numbers for one client: a fast AGC for
+ * CW, a slow one for broadcast, a bound on the gain a quiet channel is pumped up by, or no AGC at all and a fixed gain, which is
+ * what a digital-mode decoder behind the PCM needs.
+ *   The rule.  The reference's recurrence (src/utils/audioprocessing.cpp:40-66), every quantity and every operation as it is:
+ *     peak_t the maximum of |x| over the look-ahead window, the gain step g <- g + (w_t < g ? att : rel) * (w_t - g), the output
+ *     the sample delayed by L - 1 times g, zeros while the look-ahead fills.  Three things are the client's own, in f32:
+ *       att = (float)(1 - exp((double)(-1.0f / ((float)attack_ms * 0.001f * sr)))), sr = (float)audio_rate, exp in double;
+ *       rel   the same expression from release_ms - for 50 and 300 ms these are the context's own coefficients;
+ *       w_t = manual ? (float)manual_gain : fminf((float)desired / (peak_t + 1e-10f), cap),
+ *             cap = max_gain > 0 ? (float)max_gain : +Inf (fminf against +Inf is the identity);
+ *     each operation rounded once, nothing contracted; phantomsdr_amd/csrc/agcplan.h is the one definition of w_t, for the device
+ *     and for a host program alike.  In manual mode the gain therefore GLIDES from wherever the AGC left it to manual_gain with
+ *     the profile's own time constants and then stays: no click, and no time shift - the look-ahead's delay of L - 1 samples
+ *     stays.  The step moves g only while |c (w_t - g)| is at least half a unit in the last place of g, so the gain comes to
+ *     rest within 1 / (2 c) such units of manual_gain (c = att or rel): exactly on it for c > 0.5, within 600 units for a 100 ms
+ *     release at 12 kHz.  A gain that climbs to the cap rests below it by the same rule.
+ *   What does not move.  The look-ahead (200 ms), the DC blocker and the int16 conversion stay the context's.  A profile change
+ *     resets nothing: the gain, the look-ahead's fill count and the DC sums carry on, and AGC::reset remains what
+ *     psdr_client_set_audio_demodulation alone triggers.  Dropped, squelch-closed and paused frames are handled as before.  A
+ *     client with the profile {0.2, 50, 300, 0, 0, -} gives the bits of a client without one; other clients of the batch are not
+ *     affected by a bit; and a context in which no client ever had a profile allocates, uploads and launches exactly what a
+ *     library without these calls does.  An IQ client keeps its setting, which has no effect while the client is IQ.
+ * psdr_client_set_agc_profile: any thread; in force from the client's next batch, through the batch's snapshot (batches in
+ *   flight keep theirs: the chain runs up to three steps behind).  p = NULL: back to the context's AGC.  PSDR_ERR_INVALID, with
+ *   nothing changed, for an unknown id, a non-finite field (manual_gain is read only when manual = 1), desired outside (0, 1], a
+ *   time outside (0, 10000] ms, max_gain < 0, manual outside 0..1, manual_gain < 0 - in this order - and at last for a computed
+ *   att < rel: the gain step picks between its two candidates by min / max, which is the reference's pick only while attack is
+ *   at least as fast as release, as the context's own is.  PSDR_ERR_STATE if the context's audio_rate is not positive.  The
+ *   batches' table (256 bytes per client slot) is allocated with the context's first profile, all or none: PSDR_ERR_NOMEM and the
+ *   setting unchanged if that fails.
+ * psdr_agc_preset: needs no context.  PSDR_ERR_INVALID for an unknown kind or a null `out`.
+ * psdr_read_agc_gain: the gain the client's last chain batch left behind, the one its next batch starts from; synchronises.  A
+ *   paused client's stands still.  PSDR_ERR_STATE before psdr_set_post_chain, PSDR_ERR_NO_DATA for a client no chain batch has
+ *   listed yet.
+ * There is no psdr_group_* call: a group's clients run the context's AGC. */
+typedef struct psdr_agc_profile {
+    double desired;      /* target level, (0, 1] */
+    double attack_ms;    /* (0, 10000] */
+    double release_ms;   /* (0, 10000] */
+    double max_gain;     /* > 0: upper bound of the wanted gain; 0: none (the reference) */
+    int32_t manual;      /* 1: the wanted gain is manual_gain whatever the signal */
+    double manual_gain;  /* >= 0, finite (read only when manual = 1) */
+} psdr_agc_profile;
+int psdr_client_set_agc_profile(psdr_ctx *ctx, int id, const psdr_agc_profile *p);   /* NULL: back to the context's AGC */
+#define PSDR_AGC_REFERENCE 0   /* 0.2, 50, 300, no cap: the reference's constructor arguments */
+#define PSDR_AGC_FAST      1   /* 0.2,  5, 100 */
+#define PSDR_AGC_SLOW      2   /* 0.2, 50, 2000 */
+int psdr_agc_preset(int kind, psdr_agc_profile *out);   /* needs no context */
+int psdr_read_agc_gain(psdr_ctx *ctx, int id, float *gain);  /* the carried gain behind the client's last chain batch; synchronises */
 /* A client added after the last psdr_demod_batch has no results in it (the reference's frame loop would not
  * have posted a task for it either, src/websocket.cpp:156-185): psdr_read_audio / psdr_read_pcm / psdr_fetched_audio
  * return PSDR_ERR_NO_DATA for such a slot instead of the previous occupant's samples.
@@ -729,7 +779,8 @@ psdr_ctx *psdr_group_ctx(psdr_group *g, int rank);
  * flag: a group's clients are untuned, and a band migration carries the flag's value 0.  There is none for notches either
  * (psdr_client_set_notch, psdr_client_set_auto_notch): a group's clients have none, and a band migration carries none.  Nor
  * is there one for the squelch (psdr_client_set_squelch): a group's clients are always open, and a band migration carries
- * neither the setting nor the gate's state. */
+ * neither the setting nor the gate's state.  Nor for the AGC profile (psdr_client_set_agc_profile): a group's clients run the
+ * context's AGC. */
 int psdr_group_client_add(psdr_group *g, int l, double audio_mid, int r, int mode, int *gid_out);
 int psdr_group_client_remove(psdr_group *g, int gid);
 int psdr_group_client_set_audio_range(psdr_group *g, int gid, int l, double audio_mid, int r);

@@ -30,6 +30,12 @@ class psdr_biquad(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("b0", "b1", "b2", "a1", "a2")]
 
 
+class psdr_agc_profile(C.Structure):
+    """psdr_client_set_agc_profile: target, attack / release in ms, gain cap (0: none), manual flag and manual gain"""
+    _fields_ = [("desired", C.c_double), ("attack_ms", C.c_double), ("release_ms", C.c_double), ("max_gain", C.c_double),
+                ("manual", C.c_int32), ("manual_gain", C.c_double)]
+
+
 # every symbol include/psdr.h declares: (name, restype, argtypes)
 _vp, _i, _sz, _u64 = C.c_void_p, C.c_int, C.c_size_t, C.c_uint64
 _pp = C.POINTER(C.c_void_p)
@@ -84,6 +90,9 @@ SYMBOLS = [
     ("psdr_fetched_squelch", _i, [_vp, _i, _i, C.POINTER(C.c_int32)]),
     ("psdr_client_set_audio_filter", _i, [_vp, _i, _i, _vp]),
     ("psdr_audio_filter_design", _i, [_i, C.c_double, C.c_double, C.c_double, _vp]),
+    ("psdr_client_set_agc_profile", _i, [_vp, _i, C.POINTER(psdr_agc_profile)]),
+    ("psdr_agc_preset", _i, [_i, C.POINTER(psdr_agc_profile)]),
+    ("psdr_read_agc_gain", _i, [_vp, _i, C.POINTER(C.c_float)]),
     ("psdr_demod_batch", _i, [_vp, _u64]),
     ("psdr_demod_batch_from", _i, [_vp, _vp, _sz, _i, _u64]),
     ("psdr_pack_band", _i, [_vp, _i, C.c_uint32, C.c_uint32, _vp, _sz]),

@@ -37,7 +37,21 @@ AF_DEEMPHASIS, AF_HIGHPASS, AF_LOWPASS, AF_PEAK = 0, 1, 2, 3
 AF_KINDS = {"deemphasis": AF_DEEMPHASIS, "highpass": AF_HIGHPASS, "lowpass": AF_LOWPASS, "peak": AF_PEAK}
 AUDIO_FILTER_SECTIONS = 2
 
+# PSDR_AGC_* (include/psdr.h): the presets of psdr_agc_preset
+AGC_REFERENCE, AGC_FAST, AGC_SLOW = 0, 1, 2
+AGC_PRESETS = {"reference": AGC_REFERENCE, "fast": AGC_FAST, "slow": AGC_SLOW}
+
 FFTW_MEASURE, FFTW_DESTROY_INPUT, FFTW_ESTIMATE = 0, 1, 1 << 6  # accepted and ignored
+
+
+def agc_preset(kind):
+    """an AGC profile as a dict for AudioClient.set_agc_profile(**...) (psdr_agc_preset; needs no context): "reference" (0.2, 50 ms,
+    300 ms: the context's own), "fast" (5 / 100 ms) or "slow" (50 / 2000 ms), or an AGC_* constant"""
+    p = _lib.psdr_agc_profile()
+    k = AGC_PRESETS[kind] if isinstance(kind, str) else int(kind)
+    check(_lib.load().psdr_agc_preset(k, C.byref(p)))
+    return dict(desired=p.desired, attack_ms=p.attack_ms, release_ms=p.release_ms, max_gain=p.max_gain, manual=bool(p.manual),
+                manual_gain=p.manual_gain)
 
 
 def design_audio_filter(kind, rate, f0, q=math.sqrt(0.5)):
@@ -532,6 +546,31 @@ class AudioClient:
             raise ValueError("a section is (b0, b1, b2, a1, a2)")
         arr = (_lib.psdr_biquad * max(len(sections), 1))(*[_lib.psdr_biquad(*s) for s in sections])
         check(self.ctx.lib.psdr_client_set_audio_filter(self.ctx.h, self.id, len(sections), C.cast(arr, C.c_void_p) if sections else None))
+
+    def set_agc_profile(self, profile, **fields):
+        """the client's own AGC numbers in the post chain (psdr_client_set_agc_profile).  `profile`: None - back to the context's
+        AGC -, a preset name ("reference", "fast", "slow") or a dict like agc_preset()'s; keyword arguments replace single fields
+        of it: desired, attack_ms, release_ms, max_gain (a cap on the wanted gain, 0: none), manual (True: the gain glides to
+        manual_gain and stays).  Nothing of the chain's state is reset; in force from the client's next batch."""
+        if profile is None and not fields:
+            check(self.ctx.lib.psdr_client_set_agc_profile(self.ctx.h, self.id, None))
+            return
+        f = agc_preset(profile if isinstance(profile, (str, int)) else AGC_REFERENCE)
+        if isinstance(profile, dict):
+            f.update(profile)
+        unknown = set(fields) - set(f)
+        if unknown:
+            raise TypeError(f"unknown AGC profile fields {sorted(unknown)}")
+        f.update(fields)
+        p = _lib.psdr_agc_profile(float(f["desired"]), float(f["attack_ms"]), float(f["release_ms"]), float(f["max_gain"]),
+                                  int(f["manual"]), float(f["manual_gain"]))
+        check(self.ctx.lib.psdr_client_set_agc_profile(self.ctx.h, self.id, C.byref(p)))
+
+    def read_agc_gain(self):
+        """the gain the client's last post chain batch left behind (psdr_read_agc_gain); synchronises"""
+        g = C.c_float(0)
+        check(self.ctx.lib.psdr_read_agc_gain(self.ctx.h, self.id, C.byref(g)))
+        return np.float32(g.value)
 
     def on_window_message(self, l, m, r):
         """returns False where the reference silently returns (src/signal.cpp:302-311)."""

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/psdr.h"
+#include "agcplan.h"
 #include "audiofilterplan.h"
 #include "blankerplan.h"
 #include "butterfly.h"
@@ -306,6 +307,11 @@ struct psdr_ctx {
     DevBuf<float> d_af_state;
     HostBuf<AfEntry> h_af_tab;
     DevBuf<AfEntry> d_af_tab;
+    // AGC profiles (agcplan.h; postchain.h: k_pc_want_prof and the PcWithProfiles kernels): the batch's table, one image of [slots] entries per slot of
+    // client_ring like the squelch's - allocated with the context's first profile (under mtx), both images or none, and kept.
+    // The chain's carried state is the context's own: a profile adds none
+    HostBuf<AgcEntry> h_agc_tab;
+    DevBuf<AgcEntry> d_agc_tab;
     DevBuf<unsigned> d_ssb_mark;  // [slots] DemodArgs::ssb_mark (demod.h): USB / LSB batches that need the frame-ordered NaN guard
     ParamRing client_ring;
     int last_demod_frames = 0;
@@ -496,8 +502,9 @@ int launch_pass2_band(psdr_ctx *c, const Pass2Args &a, unsigned blocks);
 int launch_pass2_real(psdr_ctx *c, const Pass2Args &a);
 // postchain.hip: the chain's kernels for the batch demod_impl has just enqueued; *last_user = the last stream that reads
 // the client parameter block; d_drop: the flags [slots][max_batch] of the frames that stay out of the clients' streams - the
-// batch's NaN flags themselves, or (a batch with squelch clients) k_squelch's merged drop flags
+// batch's NaN flags themselves, or (a batch with squelch clients) k_squelch's merged drop flags; d_agc: the batch's table of AGC
+// profiles [slots], uploaded on `side`, or null (no client of the batch has one)
 int post_chain_enqueue(psdr_ctx *c, const ClientParams *d_clients, const int *d_slot_ci, int nact, int npaused, int nframes,
-                       const int *d_drop, hipStream_t *last_user);
+                       const int *d_drop, const AgcEntry *d_agc, hipStream_t *last_user);
 
 }  // namespace psdr

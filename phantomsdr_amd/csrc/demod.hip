@@ -100,6 +100,22 @@ static int audio_filter_alloc(psdr_ctx *c) {
     c->d_af_tab = std::move(d_tab);
     return PSDR_OK;
 }
+// the context's first AGC profile: the batches' table, host and device image or neither (a context that never sees a profile
+// allocates nothing); under mtx
+static int agc_profile_alloc(psdr_ctx *c) {
+    if (c->d_agc_tab) return PSDR_OK;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t S = c->aslots.size();
+    HostBuf<AgcEntry> h_tab;
+    DevBuf<AgcEntry> d_tab;
+    if (h_tab.alloc(S * ParamRing::K) || d_tab.alloc(S * ParamRing::K, true)) {
+        const std::string msg = psdr_last_error();
+        return fail(PSDR_ERR_NOMEM, "AGC profile table (%zu bytes): %s", S * ParamRing::K * sizeof(AgcEntry), msg.c_str());
+    }
+    c->h_agc_tab = std::move(h_tab);
+    c->d_agc_tab = std::move(d_tab);
+    return PSDR_OK;
+}
 int psdr::check_slot(psdr_ctx *c, int id) {
     if (id < 0 || id >= (int)c->aslots.size() || !c->aslots[id].active)
         return fail(PSDR_ERR_INVALID, "no audio client with id %d", id);
@@ -322,6 +338,40 @@ extern "C" int psdr_client_set_audio_filter(psdr_ctx *c, int id, int nsections, 
     audio_filter_apply(c->aslots[id], nsections, sections);
     return PSDR_OK;
 }
+extern "C" int psdr_client_set_agc_profile(psdr_ctx *c, int id, const psdr_agc_profile *p) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mtx);
+    const int rate = c->cfg.audio_rate;
+    switch (agc_profile_check(c->aslots.data(), c->aslots.size(), id, p, rate)) {
+    case AP_OK: break;
+    case AP_BAD_ID: return fail(PSDR_ERR_INVALID, "no audio client with id %d", id);
+    case AP_NONFINITE: return fail(PSDR_ERR_INVALID, "AGC profile: a field that is not a finite number");
+    case AP_BAD_DESIRED: return fail(PSDR_ERR_INVALID, "AGC profile: desired %g outside (0, 1]", p->desired);
+    case AP_BAD_TIME: return fail(PSDR_ERR_INVALID, "AGC profile: attack %g ms / release %g ms outside (0, %g]", p->attack_ms, p->release_ms, AGC_MS_MAX);
+    case AP_BAD_CAP: return fail(PSDR_ERR_INVALID, "AGC profile: max_gain %g below 0", p->max_gain);
+    case AP_BAD_MANUAL: return fail(PSDR_ERR_INVALID, "AGC profile: manual %d outside 0..1", (int)p->manual);
+    case AP_BAD_MANUAL_GAIN: return fail(PSDR_ERR_INVALID, "AGC profile: manual_gain %g below 0", p->manual_gain);
+    case AP_NO_RATE: return fail(PSDR_ERR_STATE, "AGC profile: the context's audio_rate %d is not positive", rate);
+    case AP_ATTACK_SLOWER:
+        return fail(PSDR_ERR_INVALID, "AGC profile: attack %g ms is slower than release %g ms (the gain step needs attack >= release)", p->attack_ms, p->release_ms);
+    }
+    if (p) PSDRCHK(agc_profile_alloc(c));
+    agc_profile_apply(c->aslots[id], p, rate);
+    return PSDR_OK;
+}
+extern "C" int psdr_agc_preset(int kind, psdr_agc_profile *out) {
+    if (!out) return fail(PSDR_ERR_INVALID, "null argument");
+    if (!agc_preset(kind, out)) return fail(PSDR_ERR_INVALID, "AGC preset: unknown kind %d", kind);
+    return PSDR_OK;
+}
+// (a debug entry, beside psdr_debug_notch_ptrs: exported for the tests, not part of include/psdr.h)  out[0]: the AGC profiles'
+// table (null until the context's first profile), out[1]: PostArgs::agc_tab of the last chain batch
+extern "C" int psdr_debug_agc_profile_ptrs(psdr_ctx *c, const void *out[2]) {
+    if (!c || !out) return fail(PSDR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mtx);
+    out[0] = c->d_agc_tab.get(), out[1] = c->post.agc_tab;
+    return PSDR_OK;
+}
 // (a debug entry, beside psdr_debug_notch_ptrs: exported for the tests, not part of include/psdr.h)  out[0..1]: the audio filter's
 // table and state (null until the context's first filter client)
 extern "C" int psdr_debug_audio_filter_ptrs(psdr_ctx *c, const void *out[2]) {
@@ -476,6 +526,8 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     SquelchEntry *h_sq = nullptr, *d_sq_list = nullptr;  // this ring slot's image of the squelch table
     AfPlan af;
     AfEntry *h_af = nullptr, *d_af_list = nullptr;  // this ring slot's image of the audio filter's table
+    AgcPlan ag;
+    AgcEntry *h_agc = nullptr, *d_agc_img = nullptr;  // this ring slot's image of the AGC profiles' table
     int4 *notch_tab = nullptr;
     cf *iq_rows[2] = {nullptr, nullptr}, *car_rows[2] = {nullptr, nullptr};
     {
@@ -498,6 +550,10 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
         if (c->d_af_tab) {  // (null until the context's first audio filter client)
             h_af = c->h_af_tab + (size_t)ring * c->aslots.size(), d_af_list = c->d_af_tab + (size_t)ring * c->aslots.size();
             af = audio_filter_plan(c->aslots.data(), c->aslots.size(), c->demod_seq, h_af);
+        }
+        if (c->d_agc_tab && f.post_on && p.nact > 0) {  // (null until the context's first AGC profile)
+            h_agc = c->h_agc_tab + (size_t)ring * c->aslots.size(), d_agc_img = c->d_agc_tab + (size_t)ring * c->aslots.size();
+            ag = agc_profile_plan(c->aslots.data(), c->aslots.size(), c->demod_seq, h_agc);
         }
     }
     c->last_demod_frames = nframes;
@@ -691,8 +747,11 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
         HIPCHK(audio_filter_launch(fa2, c->side));
     }
     hipStream_t last_user = c->side;
+    // the AGC profiles of the batch's snapshot, in front of the chain (whose stages all start behind `side`)
+    if (chain && ag.any) HIPCHK(hipMemcpyAsync(d_agc_img, h_agc, c->aslots.size() * sizeof(AgcEntry), hipMemcpyHostToDevice, c->side));
     if (chain)
-        PSDRCHK(post_chain_enqueue(c, a.clients, ring_at<int>(d_ring, p.slot_ci), p.nact, p.npaused, nframes, chain_drop, &last_user));
+        PSDRCHK(post_chain_enqueue(c, a.clients, ring_at<int>(d_ring, p.slot_ci), p.nact, p.npaused, nframes, chain_drop,
+                                   ag.any ? d_agc_img : nullptr, &last_user));
     HIPCHK(c->client_ring.release(ring, last_user));
     return side_done(c);
 }

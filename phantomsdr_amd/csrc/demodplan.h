@@ -63,6 +63,9 @@ struct AudioSlot {
     int af_n = 0;
     AfSection af_sec[PSDR_AUDIO_FILTER_SECTIONS];
     bool af_fresh = false;
+    // psdr_client_set_agc_profile (agcplan.h): the profile as the chain's table holds it, on = 0: none.  A setting and nothing
+    // else: no state of the chain starts over with it
+    AgcEntry agc = {0.f, 0.f, 0.f, HUGE_VALF, 0.f, 0, 0, 0};
 };
 
 // The client parameter ring's slot.  [ClientParams x S][int x S]: the batch's list and, for the post chain, the list index of

@@ -48,6 +48,7 @@
 
 #include <type_traits>
 
+#include "agcplan.h"
 #include "butterfly.h"
 #include "types.h"
 
@@ -130,6 +131,21 @@ __device__ __forceinline__ float pc_gain_step(float &gain, float w, float att, f
     const float ga = __fmaf_rn(att, d, gain), gr = __fmaf_rn(rel, d, gain);
     gain = ATT_FASTER ? fminf(ga, gr) : fmaxf(ga, gr);
     return gain;
+}
+// A lane's AGC numbers (agcplan.h), loaded ONCE ahead of the lane's loops: its slot's profile where the batch has a table and the
+// slot has one, else the context's own (no cap, not manual).  Only the kernels of a batch WITH a table call this, under
+// `if constexpr (PROF)`: the kernels a batch without a profile gets contain no trace of it, and are what they were before there
+// were profiles, instruction for instruction.
+struct PcWithProfiles {};  // the tag of a kernel that reads the table: k_pc_gain<., ., PcWithProfiles>, k_pc_agc<., ., PcWithProfiles>
+template <typename... WITH>
+constexpr bool pc_with_profiles = sizeof...(WITH) != 0;
+__device__ __forceinline__ AgcEntry pc_agc_entry(const PostArgs &a, int slot, bool listed) {
+    AgcEntry e = {a.desired, a.attack, a.release, __builtin_huge_valf(), 0.f, 0, 0, 0};
+    if (listed && a.agc_tab) {  // (listed: slot < a.slots, the table's length)
+        const AgcEntry t = a.agc_tab[slot];
+        if (t.on) e = t;
+    }
+    return e;
 }
 // one wave per client: where each surviving frame starts in the client's stream (a ballot per 64
 // frames: the count of surviving frames below a lane is a popcount)
@@ -728,9 +744,12 @@ __global__ __launch_bounds__(64) void k_pc_prefix(PostArgs a) {
 // w_t = desired / (peak_t + 1e-10) for the samples t = r of the sub-block (r < T), peak_t = max(S[t], P[t + L - 1]); w_t goes
 // to sample t's row (vo + L - 1 + t, where V1 keeps sample t and k_pc_gain will put g_t) of S.  (t + L - 1 is the
 // last row of the same block when t is the block's first row: S[t] is the whole block then, and so is that P.)
-__global__ __launch_bounds__(64) void k_pc_want(PostArgs a) {
+template <bool PROF>
+__device__ __forceinline__ void pc_want_body(const PostArgs &a) {
     const PcPiece p = pc_piece(a);
     if (!p.listed || p.r1 <= p.r0) return;
+    [[maybe_unused]] AgcEntry e;
+    if constexpr (PROF) e = pc_agc_entry(a, p.slot, true);
     const int T = a.len[p.slot], v0 = a.vo + a.L - 1;
     const float *v1 = a.V1 + pc_base(p.slot, a.pv);
     const float *P = a.P + pc_base(p.slot, a.pv);
@@ -749,10 +768,18 @@ __global__ __launch_bounds__(64) void k_pc_want(PostArgs a) {
         for (int i = 0; i < PC_PEAK_U; i++)
             if (r - i >= p.r0) {
                 run = fmaxf(run, fabsf(v[i]));
-                if (r - i < T) W[pc_el(v0 + r - i)] = __fdiv_rn(a.desired, __fadd_rn(fmaxf(run, q[i]), 1e-10f));
+                if (r - i < T) {
+                    if constexpr (PROF)
+                        W[pc_el(v0 + r - i)] = agc_want(e, fmaxf(run, q[i]));
+                    else
+                        W[pc_el(v0 + r - i)] = agc_ratio(a.desired, fmaxf(run, q[i]));
+                }
             }
     }
 }
+__global__ __launch_bounds__(64) void k_pc_want(PostArgs a) { pc_want_body<false>(a); }
+// ... of a batch with an AGC profile table (PostArgs::agc_tab)
+__global__ __launch_bounds__(64) void k_pc_want_prof(PostArgs a) { pc_want_body<true>(a); }
 
 // the gain recurrence (src/utils/audioprocessing.cpp:55-66); g_t -> sample t's row of P (0 while the
 // look-ahead buffer is still filling: the reference outputs 0 there and leaves the gain alone;
@@ -763,8 +790,12 @@ __global__ __launch_bounds__(64) void k_pc_want(PostArgs a) {
 // one-wave form took 2.2 - 3.0 ms per 512 frames against 1.5 ms with 16 lanes).
 constexpr int PC_GAIN_RING = 12;
 static_assert(16 * (PC_MA_RING + 4) <= PSDR_PC_PAD && 16 * (PC_GAIN_RING + 4) <= PSDR_PC_PAD, "the loader waves read ahead inside the padding");
-template <bool ATT_FASTER, bool OWN>
+// WITH: empty, or PcWithProfiles - the kernel of a batch with an AGC profile table (PostArgs::agc_tab).  A parameter PACK, so that
+// the kernel without profiles keeps its name, k_pc_gain<ATT_FASTER, OWN>, and - being the same text, not a wrapper around it - its
+// code, instruction for instruction (wrapped in a function both k_pc_gain and k_pc_agc came out in another order)
+template <bool ATT_FASTER, bool OWN, typename... WITH>
 __global__ __launch_bounds__(128) void k_pc_gain(PostArgs a) {
+    constexpr bool PROF = pc_with_profiles<WITH...>;
     __shared__ pc_f4 hand[2][4][64];  // [buffer][row group of the block][lane]: 8 KiB
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int wpg = 64 / a.lanes;  // (pc_wg_slot written out: through the function this kernel's instructions come out in another order)
@@ -836,8 +867,12 @@ __global__ __launch_bounds__(128) void k_pc_gain(PostArgs a) {
         __syncthreads();
         return;
     }
-    // ---- wave 1: the recurrence
-    const float att = a.attack, rel = a.release;
+    // ---- wave 1: the recurrence (att / rel are the lane's own where its slot has a profile: per-lane values either way)
+    float att = a.attack, rel = a.release;
+    if constexpr (PROF) {
+        const AgcEntry prof = pc_agc_entry(a, slot, listed);
+        att = prof.att, rel = prof.rel;
+    }
     auto step = [&](float w) -> float { return pc_gain_step<ATT_FASTER>(gain, w, att, rel); };
     for (int t = 0; t < tfill; t++) G[pc_el(t)] = 0.f;
     for (int t = tfill; t < t0; t++) G[pc_el(t)] = step(W[pc_el(t)]);
@@ -1046,8 +1081,10 @@ __global__ __launch_bounds__(256) void k_pc_zero(PostArgs a) {
     for (int j4 = threadIdx.x >> 6; j4 < (a.h >> 2); j4 += 4) dst[j4] = pc_i4{0, 0, 0, 0};
 }
 
-template <bool ATT_FASTER, bool PCM16 = false>
+// (WITH: empty or PcWithProfiles, as in k_pc_gain)
+template <bool ATT_FASTER, bool PCM16 = false, typename... WITH>
 __global__ __launch_bounds__(64 * (1 + PC_AGC_NP)) void k_pc_agc(PostArgs a) {
+    constexpr bool PROF = pc_with_profiles<WITH...>;
     constexpr int NP = PC_AGC_NP, AH = PC_AGC_AHEAD;
     // [buffer][chunk of the round (up to NP * 4)][row group][slot lane] - 16 floats per chunk and slot: NP * 64 * 16 floats per
     // round whatever a.lanes is (12 KiB), w and g, two buffers each: 48 KiB
@@ -1091,7 +1128,11 @@ __global__ __launch_bounds__(64 * (1 + PC_AGC_NP)) void k_pc_agc(PostArgs a) {
         // while the look-ahead buffer is filling (t < tfill: right after a reset / for a new client) the reference outputs 0
         // and leaves the gain alone (src/utils/audioprocessing.cpp:40-54)
         const int tfill = min(T, max(0, L - 1 - n0));
-        const float att = a.attack, rel = a.release;
+        float att = a.attack, rel = a.release;  // (per-lane values either way: the loop is the same)
+        if constexpr (PROF) {
+            const AgcEntry prof = pc_agc_entry(a, slot, listed);
+            att = prof.att, rel = prof.rel;
+        }
         auto step = [&](float w) -> float { return pc_gain_step<ATT_FASTER>(gain, w, att, rel); };
         const bool mine = sl < lanes;  // (the other lanes idle along, barriers included)
         // round r of the recurrence runs one barrier behind the producers' round r
@@ -1152,6 +1193,8 @@ __global__ __launch_bounds__(64 * (1 + PC_AGC_NP)) void k_pc_agc(PostArgs a) {
     const int ci = slot < a.slots ? a.slot_ci[slot] : -1;
     const bool listed = ci >= 0;
     const int T = listed ? a.len[slot] : 0;
+    [[maybe_unused]] AgcEntry prof;  // the producers form w: target, cap and the manual choice are theirs
+    if constexpr (PROF) prof = pc_agc_entry(a, slot, listed);
     const float *__restrict__ V = a.V1 + pc_base(min(slot, a.slots - 1), a.pv);
     const size_t cbase = ((size_t)g64 * a.nch) * 64 + (size_t)(sl0 + sl);
     const float *__restrict__ CS = a.CS + cbase;
@@ -1204,7 +1247,10 @@ __global__ __launch_bounds__(64 * (1 + PC_AGC_NP)) void k_pc_agc(PostArgs a) {
 #pragma unroll
         for (int i = 0; i < 16; i++) {
             const float peak = fmaxf(fmaxf(sf[i + 1], mid), pf[i]);
-            w[i >> 2][i & 3] = __fdiv_rn(a.desired, __fadd_rn(peak, 1e-10f));
+            if constexpr (PROF)
+                w[i >> 2][i & 3] = agc_want(prof, peak);
+            else
+                w[i >> 2][i & 3] = agc_ratio(a.desired, peak);
         }
         // (the chunk's first float is in no window of its own steps; without a use the compiler recycles its register right
         // behind the load - and waits for the load to land first, a round trip to memory in every round)

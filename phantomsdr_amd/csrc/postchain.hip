@@ -298,6 +298,22 @@ extern "C" int psdr_set_post_chain(psdr_ctx *c, int enable) {
     return PSDR_OK;
 }
 
+// the gain the client's last chain batch left behind (the one its next batch starts from, unless a mode change resets it)
+extern "C" int psdr_read_agc_gain(psdr_ctx *c, int id, float *gain) {
+    if (!c || !gain) return fail(PSDR_ERR_INVALID, "null argument");
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);
+        PSDRCHK(check_slot(c, id));
+        if (!c->post_ready) return fail(PSDR_ERR_STATE, "post chain not set up (psdr_set_post_chain)");
+        // (agc_reset 2: a fresh client no chain batch has listed yet - the slot holds its previous occupant's gain)
+        if (c->aslots[id].agc_reset == 2) return fail(PSDR_ERR_NO_DATA, "client %d has not been part of a post chain batch", id);
+    }
+    HIPCHK(hipSetDevice(c->device));
+    PSDRCHK(drain(c));
+    HIPCHK(hipMemcpy(gain, c->pc.agc_gain + id, sizeof(float), hipMemcpyDeviceToHost));
+    return PSDR_OK;
+}
+
 // run-time booleans -> template arguments: f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...)
 template <typename F>
 static auto pc_with_bools(F &&f) {
@@ -314,7 +330,7 @@ static auto pc_with_bools(F &&f, bool b, B... rest) {
 // every slot's client, -1 = not listed).  What is launched, where and with how much LDS is c->post_plan's business
 // (postplan.h); only what depends on nframes is worked out here.
 int psdr::post_chain_enqueue(psdr_ctx *c, const ClientParams *d_clients, const int *d_slot_ci, int nact, int npaused, int nframes,
-                             const int *d_drop, hipStream_t *last_user) {
+                             const int *d_drop, const AgcEntry *d_agc, hipStream_t *last_user) {
     constexpr int NS = psdr_ctx::PC_SETS;
     const PcPlan &p = c->post_plan;
     const int set = (int)(c->chain_seq % NS), nxt = (set + 1) % NS;
@@ -343,6 +359,10 @@ int psdr::post_chain_enqueue(psdr_ctx *c, const ClientParams *d_clients, const i
     pa.len = c->pc.len[set];
     pa.CM = c->pc.cm[set], pa.CP = c->pc.cp[set], pa.CS = c->pc.cs[set];
     pa.falive = c->pc.falive[set];
+    // the batch's AGC profiles: with a table the kernels that form w and step the gain are the forms with profiles (k_pc_want_prof, PcWithProfiles), which read each
+    // lane's entry once; without one the batch gets the kernels it always got
+    pa.agc_tab = c->post.agc_tab = d_agc;
+    const bool prof = d_agc != nullptr;
     c->post_direct = p.direct;
     const int nall = nact + npaused, skip = p.skip;
     const unsigned groups = p.groups, rgroups = p.rgroups;
@@ -431,10 +451,13 @@ int psdr::post_chain_enqueue(psdr_ctx *c, const ClientParams *d_clients, const i
         if (!(skip & 128)) hipLaunchKernelGGL(k_pc_zero, dim3(groups, nframes), dim3(256), 0, sc, pa);
         if (!(skip & 64))
             pc_with_bools(
-                [&](auto att, auto p16) {
-                    hipLaunchKernelGGL((k_pc_agc<decltype(att)::value, decltype(p16)::value>), dim3(rgroups), dim3(64 * (1 + PC_AGC_NP)), 0, sc, pa);
+                [&](auto att, auto p16, auto pr) {
+                    if constexpr (decltype(pr)::value)
+                        hipLaunchKernelGGL((k_pc_agc<decltype(att)::value, decltype(p16)::value, PcWithProfiles>), dim3(rgroups), dim3(64 * (1 + PC_AGC_NP)), 0, sc, pa);
+                    else
+                        hipLaunchKernelGGL((k_pc_agc<decltype(att)::value, decltype(p16)::value>), dim3(rgroups), dim3(64 * (1 + PC_AGC_NP)), 0, sc, pa);
                 },
-                p.att_faster, p.pcm16);
+                p.att_faster, p.pcm16, prof);
         HIPCHK(hipGetLastError());
         if ((rc = done(sc, 3))) return rc;
     } else {
@@ -452,7 +475,7 @@ int psdr::post_chain_enqueue(psdr_ctx *c, const ClientParams *d_clients, const i
             }
             {
                 ProfScope ps(c, K_POST, sp);
-                if (!(skip & 32)) hipLaunchKernelGGL(k_pc_want, dim3(groups, nblk * pa.nsub), dim3(64), 0, sp, pa);
+                if (!(skip & 32)) hipLaunchKernelGGL(prof ? k_pc_want_prof : k_pc_want, dim3(groups, nblk * pa.nsub), dim3(64), 0, sp, pa);
             }
             HIPCHK(hipGetLastError());
             if (!p.split_peak && (rc = done(sp, 2))) return rc;
@@ -462,10 +485,13 @@ int psdr::post_chain_enqueue(psdr_ctx *c, const ClientParams *d_clients, const i
             ProfScope ps(c, K_POST, sc);
             if (!(skip & 64))
                 pc_with_bools(
-                    [&](auto att, auto own) {
-                        hipLaunchKernelGGL((k_pc_gain<decltype(att)::value, decltype(own)::value>), dim3(rgroups), dim3(128), p.gain_lds, sc, pa);
+                    [&](auto att, auto own, auto pr) {
+                        if constexpr (decltype(pr)::value)
+                            hipLaunchKernelGGL((k_pc_gain<decltype(att)::value, decltype(own)::value, PcWithProfiles>), dim3(rgroups), dim3(128), p.gain_lds, sc, pa);
+                        else
+                            hipLaunchKernelGGL((k_pc_gain<decltype(att)::value, decltype(own)::value>), dim3(rgroups), dim3(128), p.gain_lds, sc, pa);
                     },
-                    p.att_faster, p.own);
+                    p.att_faster, p.own, prof);
             if ((rc = fetch_guard_wait(c, sc, c->guard_pcm[c->pcm_set]))) return rc;  // what read this PCM buffer two batches ago has landed
             c->guard_pcm[c->pcm_set] = nullptr;
             if (skip & 128)

@@ -87,6 +87,12 @@ struct PcPlan {
     int skip = 0;              // PcKnobs::skip
 };
 
+// The AGC's attack / release coefficient of a time constant in ms at the rate sr, 1 - exp(-1 / (ms * 0.001 * sr)) as
+// src/utils/audioprocessing.cpp:13-14 computes it: the products and the quotient in f32, exp() on a float argument is C's
+// double exp, and the double result narrows into the float member.  The context's own AGC (pc_resolve below) and every
+// per-client profile (agcplan.h) get their coefficients here.
+inline float pc_agc_coeff(float ms, float sr) { return (float)(1 - std::exp((double)(-1.0f / (ms * 0.001f * sr)))); }
+
 // look-ahead blocks of L rows that L - 1 history rows and T samples touch
 inline size_t pc_nblk(int L, size_t T) { return ((size_t)L - 1 + T + (size_t)L - 1) / (size_t)L; }
 
@@ -110,8 +116,8 @@ inline PcPlan pc_resolve(const PcFacts &f, const PcKnobs &k) {
     const float sr = (float)rate;
     p.L = (int)(size_t)(200.0f * sr / 1000.0f);
     p.desired = 0.2f;
-    p.attack = (float)(1 - std::exp((double)(-1.0f / (50.0f * 0.001f * sr))));
-    p.release = (float)(1 - std::exp((double)(-1.0f / (300.0f * 0.001f * sr))));
+    p.attack = pc_agc_coeff(50.0f, sr);
+    p.release = pc_agc_coeff(300.0f, sr);
     p.att_faster = p.attack >= p.release;
     // (D up to 12288 - audio rates up to 4.6 MHz; the AGC look-ahead L has no such limit: k_pc_submax / k_pc_prefix /
     // k_pc_want walk it in 256-row pieces)

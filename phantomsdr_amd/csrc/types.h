@@ -38,6 +38,17 @@ struct SbClient {
 // the stream's end (rings of 12 register sets: postchain.h PC_MA_RING, PC_GAIN_RING)
 #define PSDR_PC_PAD (16 * 20)
 
+// One slot's AGC profile as the chain's kernels read it (agcplan.h; include/psdr.h: psdr_client_set_agc_profile): the f32 numbers
+// of the rule, rounded once on the host.  The batch's table holds one entry per slot, `on` = 0 where the slot has no profile
+// (the kernels then take PostArgs::desired / attack / release).
+struct alignas(16) AgcEntry {
+    float desired, att, rel;  // target level, attack and release coefficients
+    float cap;                // upper bound of the wanted gain, +Inf: none
+    float manual_gain;        // the wanted gain of every sample where manual != 0
+    int on, manual, pad;
+};
+static_assert(sizeof(AgcEntry) == 32, "the device table's layout: two 16-byte loads per lane");
+
 struct PostArgs {
     const ClientParams *clients;  // this batch's list: the active clients, then the paused ones (empty streams)
     const int *slot_ci;           // [slots] index into `clients` of the slot's client, -1 = not listed in this batch
@@ -75,6 +86,9 @@ struct PostArgs {
     unsigned h_magic;     // ceil(2^32 / h): stream position / h by one multiplication
     int direct;           // k_pc_ma2 may read a work-group's new samples from `audio` itself (k_pc_gather4 then skips it)
     int32_t *pcm_dump;    // 16 bytes per thread of a k_pc_agc work-group: where its unconditional stores of row groups without a sample go
+    const AgcEntry *agc_tab;  // [slots] the batch's AGC profiles, null: no client of the batch has one (the kernels without the
+                              // table are launched: k_pc_want, k_pc_gain<., .>, k_pc_agc<., .> instead of k_pc_want_prof and the
+                              // PcWithProfiles instantiations)
 };
 
 struct WfClient {
