@@ -2,7 +2,9 @@
 // share.  context.hip (lifetime, Level 1, ingest ring, instrumentation), pass1.hip / pass2.hip (the FFT pass
 // launchers), forward.hip (the frame loop: passes + pyramid tails, spectrum / pyramid read-back, band layout,
 // waterfall), demod.hip (audio clients + demodulation), fetch.hip (the served end: results to host memory), postchain.hip
-// (DC blocker / AGC / int16), wire.hip (packets).
+// (DC blocker / AGC / int16), wire.hip (packets).  What a context allocates has one owner each (owned.h); what only some
+// contexts need - an optional per-client feature's buffers and tables - sits in one struct per feature that exists whole or
+// not at all (psdr_ctx: `iq` .. `agc_prof`; RingTable: a batch's table beside the client parameter ring).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -94,12 +96,36 @@ struct ParamRing {
         if (used[idx] && hipEventSynchronize(ev[idx]) != hipSuccess) return -1;
         return idx;
     }
+    // hands the slot acquire() has just returned back, unused
+    void unacquire() { idx = (idx + K - 1) % K; }
     void *host(int i) { return h + slot_bytes * i; }
     void *dev(int i) { return d + slot_bytes * i; }
     hipError_t release(int i, hipStream_t s) {
         const hipError_t e = hipEventRecord(ev[i], s);
         used[i] = e == hipSuccess;
         return e;
+    }
+};
+// A batch's table of S entries of T that travels beside a ParamRing: one host and one device image [ParamRing::K][S], image i
+// with the discipline of the ring's slot i (filled once the slot is acquired, read by the kernels the slot's event covers).
+template <typename T>
+struct RingTable {
+    HostBuf<T> h;
+    DevBuf<T> d;
+    size_t S = 0;
+    static size_t bytes(size_t entries) { return entries * ParamRing::K * sizeof(T); }  // (of one image)
+    int alloc(size_t entries) {
+        PSDRCHK(h.alloc(entries * ParamRing::K));
+        PSDRCHK(d.alloc(entries * ParamRing::K, true));
+        S = entries;
+        return PSDR_OK;
+    }
+    explicit operator bool() const { return (bool)d; }
+    T *host(int ring) const { return h + (size_t)ring * S; }
+    T *dev(int ring) const { return d + (size_t)ring * S; }
+    // the first `count` entries of the slot's host image to its device image
+    hipError_t upload(int ring, size_t count, hipStream_t s) const {
+        return hipMemcpyAsync(dev(ring), host(ring), count * sizeof(T), hipMemcpyHostToDevice, s);
     }
 };
 
@@ -267,51 +293,93 @@ struct psdr_ctx {
     DevBuf<float> audio_pool[2], pwr_pool[2];
     DevBuf<int> nan_pool[2];
     int out_set = 0, pcm_set = 0;
-    // PSDR_IQ clients' rows [slot][max_batch][n/2] complex64: two pools that alternate with out_set like audio_pool, allocated
-    // when a client is first set to PSDR_IQ (psdr_client_set_audio_demodulation, under mtx) and kept; d_iq: the last batch's
-    DevBuf<cf> iq_pool[2];
-    cf *d_iq = nullptr;
-    // PSDR_SAM clients (demod.h): the carrier tail [2][slots][n/2] beside bb_tail, and the carrier records
-    // [slot][max_batch] (level, offset_hz) in two pools that alternate with out_set; allocated together when a client is
-    // first set to PSDR_SAM (under mtx) and kept.  d_car: the last batch's records
-    DevBuf<cf> d_car_tail, car_pool[2];
-    cf *d_car = nullptr;
-    // tuned USB / LSB clients (demod.h): their own tail [2][slots][n/2], allocated with the context's first one (under mtx) and kept
-    DevBuf<cf> d_ft_tail;
+    // Optional per-client features.  Each struct below owns everything its feature allocates, and the context has it from the
+    // first client that uses the feature (demod.hip: first_use, under mtx): built whole from the context's sizes and then moved
+    // in - all of it or none - and kept.  A context that never sees such a client allocates nothing.  alloc(): non-zero if an
+    // allocation failed (psdr_last_error() says why); bytes(): the size the failure message names.
+    // PSDR_IQ clients' rows [slot][max_batch][n/2] complex64: two pools that alternate with out_set like audio_pool
+    struct IqRows {
+        DevBuf<cf> pool[2];
+        static size_t bytes(const psdr_ctx &c) { return c.aslots.size() * (size_t)c.max_batch * ((size_t)c.n / 2) * sizeof(cf); }  // (of one pool)
+        int alloc(const psdr_ctx &c) { return pool[0].alloc(bytes(c) / sizeof(cf)) || pool[1].alloc(bytes(c) / sizeof(cf)); }
+        explicit operator bool() const { return (bool)pool[1]; }
+    } iq;
+    cf *d_iq = nullptr;  // view: the last batch's pool (null until the context's first IQ client)
+    // PSDR_SAM clients (demod.h): the carrier tail [2][slots][n/2] beside bb_tail, and the carrier records [slot][max_batch]
+    // (level, offset_hz) in two pools that alternate with out_set
+    struct Sam {
+        DevBuf<cf> car_tail, pool[2];
+        static size_t bytes(const psdr_ctx &c) { return 2 * c.aslots.size() * ((size_t)c.n / 2 + (size_t)c.max_batch) * sizeof(cf); }
+        int alloc(const psdr_ctx &c) {
+            const size_t S = c.aslots.size(), recs = S * (size_t)c.max_batch;
+            return car_tail.alloc(2 * S * ((size_t)c.n / 2), true) || pool[0].alloc(recs, true) || pool[1].alloc(recs, true);
+        }
+        explicit operator bool() const { return (bool)pool[1]; }
+    } sam;
+    cf *d_car = nullptr;  // view: the last batch's records (null until the context's first SAM client)
+    // a family's own tail [2][slots][n/2] - ft: tuned USB / LSB clients (demod.h); sb: sideband SAM clients, the tail of their
+    // clipped baseband
+    struct Tails {
+        DevBuf<cf> tail;
+        static size_t bytes(const psdr_ctx &c) { return 2 * c.aslots.size() * ((size_t)c.n / 2) * sizeof(cf); }
+        int alloc(const psdr_ctx &c) { return tail.alloc(bytes(c) / sizeof(cf), true); }
+        explicit operator bool() const { return (bool)tail; }
+    } ft, sb;
     int opt_fine_tune = 0;  // PSDR_OPT_FINE_TUNE: the flag psdr_client_add hands a new client
-    // sideband SAM clients (demod.h): the tail of their clipped baseband [2][slots][n/2], allocated with the context's first one
-    // (under mtx) and kept
-    DevBuf<cf> d_sb_tail;
     int opt_sam_sideband = PSDR_SAM_BOTH;  // PSDR_OPT_SAM_SIDEBAND: the value psdr_client_add hands a new client
     // auto-notch (demod.h: k_notch_detect): per slot the power sums acc [slots][n], the frame counter and the table of the two
-    // automatic entries (DemodArgs::notch_auto) - all three allocated with the context's first auto-notch client (under mtx),
-    // or none, and kept.  Manual notches travel in the client ring and need no allocation.
-    DevBuf<float> d_notch_acc;
-    DevBuf<int> d_notch_cnt;
-    DevBuf<int4> d_notch_tab;
+    // automatic entries (DemodArgs::notch_auto).  Manual notches travel in the client ring and need no allocation.
+    struct Notch {
+        DevBuf<float> acc;
+        DevBuf<int> cnt;
+        DevBuf<int4> tab;
+        static size_t bytes(const psdr_ctx &c) { return c.aslots.size() * ((size_t)c.n * sizeof(float) + sizeof(int) + sizeof(int4)); }
+        int alloc(const psdr_ctx &c) {
+            const size_t S = c.aslots.size();
+            return acc.alloc(S * (size_t)c.n, true) || cnt.alloc(S, true) || tab.alloc(S, true);
+        }
+        explicit operator bool() const { return (bool)tab; }
+    } notch;
     int opt_auto_notch = 0;  // PSDR_OPT_AUTO_NOTCH: the value psdr_client_add hands a new client
     const void *dbg_notch_man = nullptr, *dbg_notch_auto = nullptr;  // DemodArgs::notch_man / notch_auto of the last batch (psdr_debug_notch_ptrs)
     // squelch (squelch.h: k_squelch): the frames' open flags [slots][max_batch] in two sets that alternate with out_set like
-    // nan_pool (d_sq: the last batch's), the post chain's drop flags [slots][max_batch] (written and read on `side` within one
-    // batch: one set), the gates' state [slots] and the batch's table (squelchplan.h) - one image of [slots] entries per slot of
-    // client_ring, with the ring's discipline: the manual notches' way is closed, the client ring's layout is pinned.  All of
-    // it is allocated with the context's first squelch client (under mtx), or none, and kept.
-    DevBuf<int> sq_pool[2], d_sq_drop;
-    int *d_sq = nullptr;
-    DevBuf<SquelchState> d_sq_state;
-    HostBuf<SquelchEntry> h_sq_tab;
-    DevBuf<SquelchEntry> d_sq_tab;
+    // nan_pool, the post chain's drop flags [slots][max_batch] (written and read on `side` within one batch: one set), the
+    // gates' state [slots] and the batch's table (squelchplan.h) - a RingTable beside client_ring: the manual notches' way is
+    // closed, the client ring's layout is pinned.
+    struct Squelch {
+        DevBuf<int> pool[2], drop;
+        DevBuf<SquelchState> state;
+        RingTable<SquelchEntry> tab;
+        static size_t bytes(const psdr_ctx &c) {
+            const size_t S = c.aslots.size();
+            return 3 * S * (size_t)c.max_batch * sizeof(int) + S * sizeof(SquelchState) + RingTable<SquelchEntry>::bytes(S);
+        }
+        int alloc(const psdr_ctx &c) {
+            const size_t S = c.aslots.size(), rows = S * (size_t)c.max_batch;
+            return pool[0].alloc(rows, true) || pool[1].alloc(rows, true) || drop.alloc(rows, true) || state.alloc(S, true) || tab.alloc(S);
+        }
+        explicit operator bool() const { return (bool)tab; }
+    } squelch;
+    int *d_sq = nullptr;  // view: the last batch's open flags (null until the context's first squelch client)
     // audio filter (audiofilter.h: k_audio_filter): the sections' carried state [slots][2 sections][2] and the batch's table
-    // (audiofilterplan.h), one image of [slots] entries per slot of client_ring like the squelch's - allocated with the context's
-    // first filter client (under mtx), both or none, and kept
-    DevBuf<float> d_af_state;
-    HostBuf<AfEntry> h_af_tab;
-    DevBuf<AfEntry> d_af_tab;
-    // AGC profiles (agcplan.h; postchain.h: k_pc_want_prof and the PcWithProfiles kernels): the batch's table, one image of [slots] entries per slot of
-    // client_ring like the squelch's - allocated with the context's first profile (under mtx), both images or none, and kept.
-    // The chain's carried state is the context's own: a profile adds none
-    HostBuf<AgcEntry> h_agc_tab;
-    DevBuf<AgcEntry> d_agc_tab;
+    // (audiofilterplan.h), a RingTable beside client_ring
+    struct AudioFilter {
+        DevBuf<float> state;
+        RingTable<AfEntry> tab;
+        static size_t bytes(const psdr_ctx &c) {
+            return c.aslots.size() * 2 * PSDR_AUDIO_FILTER_SECTIONS * sizeof(float) + RingTable<AfEntry>::bytes(c.aslots.size());
+        }
+        int alloc(const psdr_ctx &c) { return state.alloc(c.aslots.size() * 2 * PSDR_AUDIO_FILTER_SECTIONS, true) || tab.alloc(c.aslots.size()); }
+        explicit operator bool() const { return (bool)tab; }
+    } af;
+    // AGC profiles (agcplan.h; postchain.h: k_pc_want_prof and the PcWithProfiles kernels): the batch's table, a RingTable beside
+    // client_ring.  The chain's carried state is the context's own: a profile adds none
+    struct AgcProfiles {
+        RingTable<AgcEntry> tab;
+        static size_t bytes(const psdr_ctx &c) { return RingTable<AgcEntry>::bytes(c.aslots.size()); }
+        int alloc(const psdr_ctx &c) { return tab.alloc(c.aslots.size()); }
+        explicit operator bool() const { return (bool)tab; }
+    } agc_prof;
     DevBuf<unsigned> d_ssb_mark;  // [slots] DemodArgs::ssb_mark (demod.h): USB / LSB batches that need the frame-ordered NaN guard
     ParamRing client_ring;
     int last_demod_frames = 0;

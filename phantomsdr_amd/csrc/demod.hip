@@ -6,114 +6,29 @@
 #include "squelch.h"
 #include "audiofilter.h"
 
-// the context's first tuned USB / LSB client: its family's tails (a context that never sees one allocates nothing); under mtx
-static int ft_tail_alloc(psdr_ctx *c) {
-    if (c->d_ft_tail) return PSDR_OK;
+// The context's first client of an optional feature (ctx.h: the structs behind `iq`): what the feature allocates is built whole
+// and only then moved in, so a failed call leaves the context as it was.  msg: the failure's text, with the bytes and the
+// underlying error.  Under mtx.
+template <class Feature>
+static int first_use(psdr_ctx *c, Feature &have, const char *msg) {
+    if (have) return PSDR_OK;
     HIPCHK(hipSetDevice(c->device));
-    const size_t S = c->aslots.size(), h = (size_t)c->n / 2;
-    DevBuf<cf> tail;
-    if (tail.alloc(2 * S * h, true)) {
-        const std::string msg = psdr_last_error();
-        return fail(PSDR_ERR_NOMEM, "tuned USB / LSB tails (%zu bytes): %s", 2 * S * h * sizeof(cf), msg.c_str());
+    Feature fresh;
+    if (fresh.alloc(*c)) {
+        const std::string why = psdr_last_error();
+        return fail(PSDR_ERR_NOMEM, msg, Feature::bytes(*c), why.c_str());
     }
-    c->d_ft_tail = std::move(tail);
+    have = std::move(fresh);
     return PSDR_OK;
 }
-// the context's first sideband SAM client: the tails of its clipped baseband (a context that never sees one allocates
-// nothing); under mtx
-static int sb_tail_alloc(psdr_ctx *c) {
-    if (c->d_sb_tail) return PSDR_OK;
-    HIPCHK(hipSetDevice(c->device));
-    const size_t S = c->aslots.size(), h = (size_t)c->n / 2;
-    DevBuf<cf> tail;
-    if (tail.alloc(2 * S * h, true)) {
-        const std::string msg = psdr_last_error();
-        return fail(PSDR_ERR_NOMEM, "sideband SAM tails (%zu bytes): %s", 2 * S * h * sizeof(cf), msg.c_str());
-    }
-    c->d_sb_tail = std::move(tail);
-    return PSDR_OK;
-}
-// the context's first auto-notch client: the detector's sums, counters and table, all three or none (a context that never
-// sees one allocates nothing); under mtx
-static int notch_alloc(psdr_ctx *c) {
-    if (c->d_notch_tab) return PSDR_OK;
-    HIPCHK(hipSetDevice(c->device));
-    const size_t S = c->aslots.size(), n = (size_t)c->n;
-    DevBuf<float> acc;
-    DevBuf<int> cnt;
-    DevBuf<int4> tab;
-    if (acc.alloc(S * n, true) || cnt.alloc(S, true) || tab.alloc(S, true)) {
-        const std::string msg = psdr_last_error();
-        return fail(PSDR_ERR_NOMEM, "auto-notch state (%zu bytes): %s", S * (n * sizeof(float) + sizeof(int) + sizeof(int4)), msg.c_str());
-    }
-    c->d_notch_acc = std::move(acc);
-    c->d_notch_cnt = std::move(cnt);
-    c->d_notch_tab = std::move(tab);
-    return PSDR_OK;
-}
+static int first_tuned(psdr_ctx *c) { return first_use(c, c->ft, "tuned USB / LSB tails (%zu bytes): %s"); }
+static int first_sideband(psdr_ctx *c) { return first_use(c, c->sb, "sideband SAM tails (%zu bytes): %s"); }
+static int first_auto_notch(psdr_ctx *c) { return first_use(c, c->notch, "auto-notch state (%zu bytes): %s"); }
 // the detector's state of one slot back to zero: sums, counter, both automatic entries (stream-ordered on `side`)
 static int notch_zero(psdr_ctx *c, size_t slot) {
-    HIPCHK(hipMemsetAsync(c->d_notch_acc + slot * (size_t)c->n, 0, (size_t)c->n * sizeof(float), c->side));
-    HIPCHK(hipMemsetAsync(c->d_notch_cnt + slot, 0, sizeof(int), c->side));
-    HIPCHK(hipMemsetAsync(c->d_notch_tab + slot, 0, sizeof(int4), c->side));
-    return PSDR_OK;
-}
-// the context's first squelch client: flag rows, drop flags, state and the batch's table, all or none (a context that never sees
-// one allocates nothing); under mtx
-static int squelch_alloc(psdr_ctx *c) {
-    if (c->d_sq_tab) return PSDR_OK;
-    HIPCHK(hipSetDevice(c->device));
-    const size_t S = c->aslots.size(), rows = S * (size_t)c->max_batch;
-    DevBuf<int> pool[2], drop;
-    DevBuf<SquelchState> state;
-    HostBuf<SquelchEntry> h_tab;
-    DevBuf<SquelchEntry> d_tab;
-    if (pool[0].alloc(rows, true) || pool[1].alloc(rows, true) || drop.alloc(rows, true) || state.alloc(S, true) || h_tab.alloc(S * ParamRing::K) ||
-        d_tab.alloc(S * ParamRing::K, true)) {
-        const std::string msg = psdr_last_error();
-        return fail(PSDR_ERR_NOMEM, "squelch flags, state and table (%zu bytes): %s",
-                    3 * rows * sizeof(int) + S * sizeof(SquelchState) + S * ParamRing::K * sizeof(SquelchEntry), msg.c_str());
-    }
-    c->sq_pool[0] = std::move(pool[0]), c->sq_pool[1] = std::move(pool[1]);
-    c->d_sq_drop = std::move(drop);
-    c->d_sq_state = std::move(state);
-    c->h_sq_tab = std::move(h_tab);
-    c->d_sq_tab = std::move(d_tab);
-    return PSDR_OK;
-}
-// the context's first audio filter client: the sections' state and the batch's table, all or none (a context that never sees one
-// allocates nothing); under mtx
-static int audio_filter_alloc(psdr_ctx *c) {
-    if (c->d_af_tab) return PSDR_OK;
-    HIPCHK(hipSetDevice(c->device));
-    const size_t S = c->aslots.size();
-    DevBuf<float> state;
-    HostBuf<AfEntry> h_tab;
-    DevBuf<AfEntry> d_tab;
-    if (state.alloc(S * 2 * PSDR_AUDIO_FILTER_SECTIONS, true) || h_tab.alloc(S * ParamRing::K) || d_tab.alloc(S * ParamRing::K, true)) {
-        const std::string msg = psdr_last_error();
-        return fail(PSDR_ERR_NOMEM, "audio filter state and table (%zu bytes): %s",
-                    S * (2 * PSDR_AUDIO_FILTER_SECTIONS * sizeof(float) + ParamRing::K * sizeof(AfEntry)), msg.c_str());
-    }
-    c->d_af_state = std::move(state);
-    c->h_af_tab = std::move(h_tab);
-    c->d_af_tab = std::move(d_tab);
-    return PSDR_OK;
-}
-// the context's first AGC profile: the batches' table, host and device image or neither (a context that never sees a profile
-// allocates nothing); under mtx
-static int agc_profile_alloc(psdr_ctx *c) {
-    if (c->d_agc_tab) return PSDR_OK;
-    HIPCHK(hipSetDevice(c->device));
-    const size_t S = c->aslots.size();
-    HostBuf<AgcEntry> h_tab;
-    DevBuf<AgcEntry> d_tab;
-    if (h_tab.alloc(S * ParamRing::K) || d_tab.alloc(S * ParamRing::K, true)) {
-        const std::string msg = psdr_last_error();
-        return fail(PSDR_ERR_NOMEM, "AGC profile table (%zu bytes): %s", S * ParamRing::K * sizeof(AgcEntry), msg.c_str());
-    }
-    c->h_agc_tab = std::move(h_tab);
-    c->d_agc_tab = std::move(d_tab);
+    HIPCHK(hipMemsetAsync(c->notch.acc + slot * (size_t)c->n, 0, (size_t)c->n * sizeof(float), c->side));
+    HIPCHK(hipMemsetAsync(c->notch.cnt + slot, 0, sizeof(int), c->side));
+    HIPCHK(hipMemsetAsync(c->notch.tab + slot, 0, sizeof(int4), c->side));
     return PSDR_OK;
 }
 int psdr::check_slot(psdr_ctx *c, int id) {
@@ -129,9 +44,9 @@ extern "C" int psdr_client_add(psdr_ctx *c, int *id_out) {
     for (size_t i = 0; i < c->aslots.size(); i++)
         if (!c->aslots[i].active) {
             AudioSlot &s = c->aslots[i];
-            if (c->opt_fine_tune) PSDRCHK(ft_tail_alloc(c));  // (a new client is a USB client: a tuned one under PSDR_OPT_FINE_TUNE)
-            if (c->opt_auto_notch) PSDRCHK(notch_alloc(c));
-            if (c->d_notch_tab) PSDRCHK(notch_zero(c, i));  // (the previous occupant's automatic entries do not outlive it)
+            if (c->opt_fine_tune) PSDRCHK(first_tuned(c));  // (a new client is a USB client: a tuned one under PSDR_OPT_FINE_TUNE)
+            if (c->opt_auto_notch) PSDRCHK(first_auto_notch(c));
+            if (c->notch) PSDRCHK(notch_zero(c, i));  // (the previous occupant's automatic entries do not outlive it)
             s = AudioSlot();
             s.active = true;
             s.fine = c->opt_fine_tune;
@@ -155,16 +70,14 @@ extern "C" int psdr_client_add(psdr_ctx *c, int *id_out) {
 extern "C" int psdr_client_remove(psdr_ctx *c, int id) {
     if (!c) return fail(PSDR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mtx);
-    int rc = check_slot(c, id);
-    if (rc) return rc;
+    PSDRCHK(check_slot(c, id));
     c->aslots[id].active = false;
     return PSDR_OK;
 }
 extern "C" int psdr_client_set_audio_range(psdr_ctx *c, int id, int l, double mid, int r) {
     if (!c) return fail(PSDR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mtx);
-    int rc = check_slot(c, id);
-    if (rc) return rc;
+    PSDRCHK(check_slot(c, id));
     // the reference does not validate here (src/signal.cpp:81-94); a range outside the
     // spectrum would read out of bounds there, so it is refused here
     if (l < 0 || r < l || (size_t)r > c->R || r - l > c->n)
@@ -179,8 +92,7 @@ extern "C" int psdr_client_on_window_message(psdr_ctx *c, int id, int l, double 
     if (!c) return fail(PSDR_ERR_INVALID, "null argument");
     {
         std::lock_guard<std::mutex> lk(c->mtx);
-        int rc = check_slot(c, id);
-        if (rc) return rc;
+        PSDRCHK(check_slot(c, id));
     }
     const int R = (int)c->R;  // src/signal.cpp:305-311
     if (l < 0 || l >= R || r < 0 || r >= R || l > r)
@@ -194,48 +106,25 @@ extern "C" int psdr_client_on_window_message(psdr_ctx *c, int id, int l, double 
 extern "C" int psdr_client_set_paused(psdr_ctx *c, int id, int paused) {
     if (!c) return fail(PSDR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mtx);
-    int rc = check_slot(c, id);
-    if (rc) return rc;
+    PSDRCHK(check_slot(c, id));
     c->aslots[id].paused = paused != 0;
     return PSDR_OK;
 }
 extern "C" int psdr_client_set_audio_demodulation(psdr_ctx *c, int id, int mode) {
     if (!c) return fail(PSDR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mtx);
-    int rc = check_slot(c, id);
-    if (rc) return rc;
+    PSDRCHK(check_slot(c, id));
     if (mode < PSDR_USB || mode > PSDR_SAM) return fail(PSDR_ERR_INVALID, "unknown mode %d", mode);
     if (mode == PSDR_SAM && !sam_size_served(c->n))
         return fail(PSDR_ERR_UNSUPPORTED, "PSDR_SAM needs audio_fft_size < %d (this context: %d): the carrier's direct sum indexes its twiddles with a 32-bit product", PSDR_SAM_MAX_AUDIO_FFT, c->n);
-    if (mode == PSDR_IQ && !c->iq_pool[1]) {
-        // the first IQ client of the context: its rows' two pools (a context that never sees one allocates nothing); both
-        // exist before either is kept, and the mode changes only then
-        HIPCHK(hipSetDevice(c->device));
-        const size_t rows = c->aslots.size() * (size_t)c->max_batch * ((size_t)c->n / 2);
-        DevBuf<cf> pool[2];
-        if (pool[0].alloc(rows) || pool[1].alloc(rows)) {
-            const std::string msg = psdr_last_error();
-            return fail(PSDR_ERR_NOMEM, "IQ rows (2 x %zu bytes): %s", rows * sizeof(cf), msg.c_str());
-        }
-        c->iq_pool[0] = std::move(pool[0]);
-        c->iq_pool[1] = std::move(pool[1]);
-    }
-    if (mode == PSDR_SAM && !c->car_pool[1]) {
-        // the first SAM client of the context: the carrier tails and the two pools of carrier records, all three or none
+    // (the mode changes only once everything it needs exists)
+    if (mode == PSDR_IQ) PSDRCHK(first_use(c, c->iq, "IQ rows (2 x %zu bytes): %s"));
+    if (mode == PSDR_SAM && !c->sam) {
         if (c->cfg.audio_rate <= 0) return fail(PSDR_ERR_STATE, "PSDR_SAM needs audio_rate > 0 (the carrier low-pass is 500 Hz)");
-        HIPCHK(hipSetDevice(c->device));
-        const size_t S = c->aslots.size(), h = (size_t)c->n / 2, recs = S * (size_t)c->max_batch;
-        DevBuf<cf> tail, pool[2];
-        if (tail.alloc(2 * S * h, true) || pool[0].alloc(recs, true) || pool[1].alloc(recs, true)) {
-            const std::string msg = psdr_last_error();
-            return fail(PSDR_ERR_NOMEM, "carrier tails and records (%zu bytes): %s", (2 * S * h + 2 * recs) * sizeof(cf), msg.c_str());
-        }
-        c->d_car_tail = std::move(tail);
-        c->car_pool[0] = std::move(pool[0]);
-        c->car_pool[1] = std::move(pool[1]);
+        PSDRCHK(first_use(c, c->sam, "carrier tails and records (%zu bytes): %s"));
     }
-    if (tuned_mode(c->aslots[id].fine, mode) && mode != PSDR_IQ) PSDRCHK(ft_tail_alloc(c));
-    if (sb_sam(mode, c->aslots[id].sam_sb)) PSDRCHK(sb_tail_alloc(c));
+    if (tuned_mode(c->aslots[id].fine, mode) && mode != PSDR_IQ) PSDRCHK(first_tuned(c));
+    if (sb_sam(mode, c->aslots[id].sam_sb)) PSDRCHK(first_sideband(c));
     c->aslots[id].mode = mode;
     if (c->aslots[id].agc_reset == 0) c->aslots[id].agc_reset = 1;  // src/signal.cpp:316-328: resets the AGC
     return PSDR_OK;
@@ -243,21 +132,19 @@ extern "C" int psdr_client_set_audio_demodulation(psdr_ctx *c, int id, int mode)
 extern "C" int psdr_client_set_fine_tune(psdr_ctx *c, int id, int on) {
     if (!c) return fail(PSDR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mtx);
-    int rc = check_slot(c, id);
-    if (rc) return rc;
+    PSDRCHK(check_slot(c, id));
     AudioSlot &s = c->aslots[id];
-    if (tuned_mode(on, s.mode) && s.mode != PSDR_IQ) PSDRCHK(ft_tail_alloc(c));
+    if (tuned_mode(on, s.mode) && s.mode != PSDR_IQ) PSDRCHK(first_tuned(c));
     s.fine = on ? 1 : 0;
     return PSDR_OK;
 }
 extern "C" int psdr_client_set_sam_sideband(psdr_ctx *c, int id, int sideband) {
     if (!c) return fail(PSDR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mtx);
-    int rc = check_slot(c, id);
-    if (rc) return rc;
+    PSDRCHK(check_slot(c, id));
     if (sideband < PSDR_SAM_BOTH || sideband > PSDR_SAM_LOWER) return fail(PSDR_ERR_INVALID, "unknown SAM sideband %d", sideband);
     AudioSlot &s = c->aslots[id];
-    if (sb_sam(s.mode, sideband)) PSDRCHK(sb_tail_alloc(c));
+    if (sb_sam(s.mode, sideband)) PSDRCHK(first_sideband(c));
     s.sam_sb = sideband;
     return PSDR_OK;
 }
@@ -284,8 +171,7 @@ extern "C" int psdr_debug_notch_interval(double centre_bin, double width_bins, i
 extern "C" int psdr_client_set_notch(psdr_ctx *c, int id, int index, double centre_bin, double width_bins) {
     if (!c) return fail(PSDR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mtx);
-    int rc = check_slot(c, id);
-    if (rc) return rc;
+    PSDRCHK(check_slot(c, id));
     if (index < 0 || index >= PSDR_NOTCH_MANUAL) return fail(PSDR_ERR_INVALID, "notch index %d outside 0..%d", index, PSDR_NOTCH_MANUAL - 1);
     if (!std::isfinite(centre_bin) || !std::isfinite(width_bins)) return fail(PSDR_ERR_INVALID, "non-finite notch");
     if (width_bins > (double)c->n) return fail(PSDR_ERR_INVALID, "notch wider than audio_fft_size %d", c->n);
@@ -299,9 +185,8 @@ extern "C" int psdr_client_set_notch(psdr_ctx *c, int id, int index, double cent
 extern "C" int psdr_client_set_auto_notch(psdr_ctx *c, int id, int on) {
     if (!c) return fail(PSDR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mtx);
-    int rc = check_slot(c, id);
-    if (rc) return rc;
-    if (on) PSDRCHK(notch_alloc(c));
+    PSDRCHK(check_slot(c, id));
+    if (on) PSDRCHK(first_auto_notch(c));
     AudioSlot &s = c->aslots[id];
     if (on && !s.auto_notch) s.auto_fresh = true;
     s.auto_notch = on ? 1 : 0;
@@ -318,7 +203,7 @@ extern "C" int psdr_client_set_squelch(psdr_ctx *c, int id, int on, double open_
     case SQ_BAD_ATTACK: return fail(PSDR_ERR_INVALID, "squelch: attack_frames %d outside 1..%d", attack_frames, SQUELCH_FRAMES_MAX);
     case SQ_BAD_HANG: return fail(PSDR_ERR_INVALID, "squelch: hang_frames %d outside 0..%d", hang_frames, SQUELCH_FRAMES_MAX);
     }
-    if (on) PSDRCHK(squelch_alloc(c));
+    if (on) PSDRCHK(first_use(c, c->squelch, "squelch flags, state and table (%zu bytes): %s"));
     squelch_apply(c->aslots[id], on, open_db, close_db, attack_frames, hang_frames);
     return PSDR_OK;
 }
@@ -334,7 +219,7 @@ extern "C" int psdr_client_set_audio_filter(psdr_ctx *c, int id, int nsections, 
     case AF_UNSTABLE: return fail(PSDR_ERR_INVALID, "audio filter: a section that is not stable (|a2| < 1 and |a1| < 1 + a2)");
     case AF_POLE: return fail(PSDR_ERR_INVALID, "audio filter: a pole radius above %g", AF_POLE_MAX);
     }
-    if (nsections > 0) PSDRCHK(audio_filter_alloc(c));
+    if (nsections > 0) PSDRCHK(first_use(c, c->af, "audio filter state and table (%zu bytes): %s"));
     audio_filter_apply(c->aslots[id], nsections, sections);
     return PSDR_OK;
 }
@@ -355,7 +240,7 @@ extern "C" int psdr_client_set_agc_profile(psdr_ctx *c, int id, const psdr_agc_p
     case AP_ATTACK_SLOWER:
         return fail(PSDR_ERR_INVALID, "AGC profile: attack %g ms is slower than release %g ms (the gain step needs attack >= release)", p->attack_ms, p->release_ms);
     }
-    if (p) PSDRCHK(agc_profile_alloc(c));
+    if (p) PSDRCHK(first_use(c, c->agc_prof, "AGC profile table (%zu bytes): %s"));
     agc_profile_apply(c->aslots[id], p, rate);
     return PSDR_OK;
 }
@@ -369,7 +254,7 @@ extern "C" int psdr_agc_preset(int kind, psdr_agc_profile *out) {
 extern "C" int psdr_debug_agc_profile_ptrs(psdr_ctx *c, const void *out[2]) {
     if (!c || !out) return fail(PSDR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mtx);
-    out[0] = c->d_agc_tab.get(), out[1] = c->post.agc_tab;
+    out[0] = c->agc_prof.tab.d.get(), out[1] = c->post.agc_tab;
     return PSDR_OK;
 }
 // (a debug entry, beside psdr_debug_notch_ptrs: exported for the tests, not part of include/psdr.h)  out[0..1]: the audio filter's
@@ -377,7 +262,7 @@ extern "C" int psdr_debug_agc_profile_ptrs(psdr_ctx *c, const void *out[2]) {
 extern "C" int psdr_debug_audio_filter_ptrs(psdr_ctx *c, const void *out[2]) {
     if (!c || !out) return fail(PSDR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mtx);
-    out[0] = c->d_af_tab.get(), out[1] = c->d_af_state.get();
+    out[0] = c->af.tab.d.get(), out[1] = c->af.state.get();
     return PSDR_OK;
 }
 // (... and whether the last chain batch's moving averages read the audio rows themselves, k_pc_ma2 DIRECT: the form in which the
@@ -405,7 +290,7 @@ extern "C" int psdr_audio_filter_design(int kind, double audio_rate, double f0, 
 extern "C" int psdr_debug_notch_ptrs(psdr_ctx *c, const void *out[5]) {
     if (!c || !out) return fail(PSDR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mtx);
-    out[0] = c->d_notch_tab.get(), out[1] = c->d_notch_acc.get(), out[2] = c->d_notch_cnt.get();
+    out[0] = c->notch.tab.get(), out[1] = c->notch.acc.get(), out[2] = c->notch.cnt.get();
     out[3] = c->dbg_notch_man, out[4] = c->dbg_notch_auto;
     return PSDR_OK;
 }
@@ -508,177 +393,174 @@ static const T *ring_at(const unsigned char *d_ring, size_t off) {
     return (const T *)(d_ring + off);
 }
 
-// One batch: demod_plan (demodplan.h) says who is demodulated, in which list of the ring slot and from which state; this
-// copies, zeroes and launches what it names.
-static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nframes, uint64_t first_frame_num,
-                      const uint32_t *band = nullptr, bool band_tiled = false) {
-    if (c->n <= 0) return fail(PSDR_ERR_STATE, "context created with audio_fft_size 0");
-    HIPCHK(hipSetDevice(c->device));
-    const int ring = c->client_ring.acquire();
-    if (ring < 0) return fail(PSDR_ERR_HIP, "client parameter ring: event wait failed");
-    unsigned char *h_ring = (unsigned char *)c->client_ring.host(ring), *d_ring = (unsigned char *)c->client_ring.dev(ring);
+// One batch as it is fixed under mtx: demod_plan (demodplan.h) says who is demodulated, in which list of the ring slot and from
+// which state; the squelch's, the audio filter's and the AGC profiles' plans say what follows the demodulation, and fill the ring
+// slot's image of their tables.
+struct BatchPlan {
+    int ring = 0;
+    unsigned char *h_ring = nullptr, *d_ring = nullptr;  // the ring slot's two copies
+    DemodPlan p;
+    SquelchPlan sq;
+    AfPlan af;
+    AgcPlan ag;
+    bool chain = false;  // the post chain follows: it is on, and somebody is in it
+    // of the optional features: the rows of the result set this batch writes and the detector's table - null where the context has
+    // none yet (they appear under mtx, once, and stay)
+    cf *iq_rows = nullptr, *car_rows = nullptr;
+    int *sq_rows = nullptr;
+    int4 *notch_tab = nullptr;
+};
+static int batch_plan(psdr_ctx *c, int nframes, const uint32_t *band, BatchPlan &b) {
+    b.ring = c->client_ring.acquire();
+    if (b.ring < 0) return fail(PSDR_ERR_HIP, "client parameter ring: event wait failed");
+    b.h_ring = (unsigned char *)c->client_ring.host(b.ring), b.d_ring = (unsigned char *)c->client_ring.dev(b.ring);
     DemodFacts f;
     f.n = c->n, f.nframes = nframes;
     if (band) f.has_band = true, f.band_first = band[0], f.band_count = band[1];
-    DemodPlan p;
-    SquelchPlan sq;
-    int *sq_rows[2] = {nullptr, nullptr};
-    SquelchEntry *h_sq = nullptr, *d_sq_list = nullptr;  // this ring slot's image of the squelch table
-    AfPlan af;
-    AfEntry *h_af = nullptr, *d_af_list = nullptr;  // this ring slot's image of the audio filter's table
-    AgcPlan ag;
-    AgcEntry *h_agc = nullptr, *d_agc_img = nullptr;  // this ring slot's image of the AGC profiles' table
-    int4 *notch_tab = nullptr;
-    cf *iq_rows[2] = {nullptr, nullptr}, *car_rows[2] = {nullptr, nullptr};
-    {
-        std::lock_guard<std::mutex> lk(c->mtx);  // (the band is checked under the same lock that fixes the windows of the batch)
-        iq_rows[0] = c->iq_pool[0], iq_rows[1] = c->iq_pool[1];  // (allocated under this lock, once)
-        notch_tab = c->d_notch_tab;
-        car_rows[0] = c->car_pool[0], car_rows[1] = c->car_pool[1];
-        f.post_on = c->post_on, f.have_notch_tab = notch_tab != nullptr;
-        p = demod_plan(c->aslots.data(), c->aslots.size(), c->demod_seq, f, h_ring);
-        if (p.verdict == DP_BAND_OUTSIDE) {
-            c->client_ring.idx = (c->client_ring.idx + ParamRing::K - 1) % ParamRing::K;  // hand the slot back
-            return fail(PSDR_ERR_INVALID, "client %d: window [%d, %d) outside the band [%u, %u)", p.bad_slot, p.bad_l, p.bad_r, band[0],
-                        band[0] + band[1]);
-        }
-        if (c->d_sq_tab) {  // (null until the context's first squelch client)
-            sq_rows[0] = c->sq_pool[0], sq_rows[1] = c->sq_pool[1];
-            h_sq = c->h_sq_tab + (size_t)ring * c->aslots.size(), d_sq_list = c->d_sq_tab + (size_t)ring * c->aslots.size();
-            sq = squelch_plan(c->aslots.data(), c->aslots.size(), c->demod_seq, f.post_on && p.nact > 0, h_sq);
-        }
-        if (c->d_af_tab) {  // (null until the context's first audio filter client)
-            h_af = c->h_af_tab + (size_t)ring * c->aslots.size(), d_af_list = c->d_af_tab + (size_t)ring * c->aslots.size();
-            af = audio_filter_plan(c->aslots.data(), c->aslots.size(), c->demod_seq, h_af);
-        }
-        if (c->d_agc_tab && f.post_on && p.nact > 0) {  // (null until the context's first AGC profile)
-            h_agc = c->h_agc_tab + (size_t)ring * c->aslots.size(), d_agc_img = c->d_agc_tab + (size_t)ring * c->aslots.size();
-            ag = agc_profile_plan(c->aslots.data(), c->aslots.size(), c->demod_seq, h_agc);
-        }
+    std::lock_guard<std::mutex> lk(c->mtx);  // (the band is checked under the same lock that fixes the windows of the batch)
+    AudioSlot *slots = c->aslots.data();
+    const size_t S = c->aslots.size();
+    const int set = c->out_set ^ 1;
+    b.iq_rows = c->iq.pool[set], b.car_rows = c->sam.pool[set], b.sq_rows = c->squelch.pool[set], b.notch_tab = c->notch.tab;
+    f.post_on = c->post_on, f.have_notch_tab = b.notch_tab != nullptr;
+    b.p = demod_plan(slots, S, c->demod_seq, f, b.h_ring);
+    if (b.p.verdict == DP_BAND_OUTSIDE) {
+        c->client_ring.unacquire();
+        return fail(PSDR_ERR_INVALID, "client %d: window [%d, %d) outside the band [%u, %u)", b.p.bad_slot, b.p.bad_l, b.p.bad_r, band[0],
+                    band[0] + band[1]);
     }
-    c->last_demod_frames = nframes;
-    if (p.idle()) return PSDR_OK;
+    b.chain = f.post_on && b.p.nact > 0;
+    if (c->squelch) b.sq = squelch_plan(slots, S, c->demod_seq, b.chain, c->squelch.tab.host(b.ring));
+    if (c->af) b.af = audio_filter_plan(slots, S, c->demod_seq, c->af.tab.host(b.ring));
+    if (c->agc_prof && b.chain) b.ag = agc_profile_plan(slots, S, c->demod_seq, c->agc_prof.tab.host(b.ring));
+    return PSDR_OK;
+}
+// What `side` holds in front of the batch's first kernel: the states that start from zero, the flip to the other result set, the
+// ring slot and the tables.
+static int batch_begin(psdr_ctx *c, const BatchPlan &b) {
+    const DemodPlan &p = b.p;
     // the gates that start from (closed, 0): squelch_plan has taken sq_fresh off these slots, so the zeroing is enqueued before
     // anything below can fail the batch (`side` orders it behind the last batch's k_squelch and in front of this one's)
-    for (size_t slot : sq.zero) HIPCHK(hipMemsetAsync(c->d_sq_state + slot, 0, sizeof(SquelchState), c->side));
+    for (size_t slot : b.sq.zero) HIPCHK(hipMemsetAsync(c->squelch.state + slot, 0, sizeof(SquelchState), c->side));
     // ... and the audio filters that start from zero, by the same rule (audio_filter_plan has taken af_fresh off these slots)
-    for (size_t slot : af.zero)
-        HIPCHK(hipMemsetAsync(c->d_af_state + slot * 2 * PSDR_AUDIO_FILTER_SECTIONS, 0, 2 * PSDR_AUDIO_FILTER_SECTIONS * sizeof(float), c->side));
-    {  // this batch's results go to the OTHER set (the copies of the last batch to the host may still be reading theirs); what
-       // read this set two batches ago must have landed
-        c->out_set ^= 1;
-        c->d_audio = c->audio_pool[c->out_set], c->d_pwr = c->pwr_pool[c->out_set], c->d_nan = c->nan_pool[c->out_set];
-        c->d_iq = iq_rows[c->out_set];  // (null until the context's first IQ client)
-        c->d_car = car_rows[c->out_set];  // (... first SAM client)
-        c->d_sq = sq_rows[c->out_set];    // (... first squelch client)
-        int rc = fetch_guard_wait(c, c->side, c->guard_audio[c->out_set]);
-        if (rc) return rc;
-        c->guard_audio[c->out_set] = nullptr;
-        // ... and the post chain's moving averages of that batch, which read its audio rows themselves (postchain.h k_pc_ma2
-        // DIRECT) on a stream of their own, up to two steps behind the passes (psdr_set_post_chain drains: the chain has
-        // been on for every batch since chain_seq started to count)
-        if (c->post_on && c->post_direct && c->chain_seq >= 2 && c->pc_s[0] && c->side != c->stream)
-            HIPCHK(hipStreamWaitEvent(c->side, c->pc.ev[1][(c->chain_seq - 2) % psdr_ctx::PC_SETS], 0));
-    }
+    for (size_t slot : b.af.zero)
+        HIPCHK(hipMemsetAsync(c->af.state + slot * 2 * PSDR_AUDIO_FILTER_SECTIONS, 0, 2 * PSDR_AUDIO_FILTER_SECTIONS * sizeof(float), c->side));
+    // this batch's results go to the OTHER set (the copies of the last batch to the host may still be reading theirs); what
+    // read this set two batches ago must have landed
+    c->out_set ^= 1;
+    c->d_audio = c->audio_pool[c->out_set], c->d_pwr = c->pwr_pool[c->out_set], c->d_nan = c->nan_pool[c->out_set];
+    c->d_iq = b.iq_rows, c->d_car = b.car_rows, c->d_sq = b.sq_rows;
+    PSDRCHK(fetch_guard_wait(c, c->side, c->guard_audio[c->out_set]));
+    c->guard_audio[c->out_set] = nullptr;
+    // ... and the post chain's moving averages of that batch, which read its audio rows themselves (postchain.h k_pc_ma2
+    // DIRECT) on a stream of their own, up to two steps behind the passes (psdr_set_post_chain drains: the chain has
+    // been on for every batch since chain_seq started to count)
+    if (c->post_on && c->post_direct && c->chain_seq >= 2 && c->pc_s[0] && c->side != c->stream)
+        HIPCHK(hipStreamWaitEvent(c->side, c->pc.ev[1][(c->chain_seq - 2) % psdr_ctx::PC_SETS], 0));
     for (int i = 0; i < p.ncopies; i++)
-        HIPCHK(hipMemcpyAsync(d_ring + p.copies[i].off, h_ring + p.copies[i].off, p.copies[i].bytes, hipMemcpyHostToDevice, c->side));
+        HIPCHK(hipMemcpyAsync(b.d_ring + p.copies[i].off, b.h_ring + p.copies[i].off, p.copies[i].bytes, hipMemcpyHostToDevice, c->side));
     // what starts from zero (car_zero names the slots of both kinds of SAM client: they share the carrier tail)
-    if (p.ntssb > 0 && !c->d_ft_tail) return fail(PSDR_ERR_STATE, "tuned USB / LSB clients without their tails");
-    if (p.nsb > 0 && (!c->d_sb_tail || !c->d_car_tail)) return fail(PSDR_ERR_STATE, "sideband SAM clients without their tails");
+    if (p.ntssb > 0 && !c->ft) return fail(PSDR_ERR_STATE, "tuned USB / LSB clients without their tails");
+    if (p.nsb > 0 && (!c->sb || !c->sam)) return fail(PSDR_ERR_STATE, "sideband SAM clients without their tails");
     const size_t tail_bytes = ((size_t)c->n / 2) * sizeof(cf);
     for (size_t slot : p.det_zero) PSDRCHK(notch_zero(c, slot));
-    for (size_t off : p.car_zero) HIPCHK(hipMemsetAsync(c->d_car_tail + off, 0, tail_bytes, c->side));
-    for (size_t off : p.ft_zero) HIPCHK(hipMemsetAsync(c->d_ft_tail + off, 0, tail_bytes, c->side));
-    for (size_t off : p.sb_zero) HIPCHK(hipMemsetAsync(c->d_sb_tail + off, 0, tail_bytes, c->side));
-    if (sq.any()) HIPCHK(hipMemcpyAsync(d_sq_list, h_sq, (size_t)(sq.nsq + sq.ncopy) * sizeof(SquelchEntry), hipMemcpyHostToDevice, c->side));
-    if (af.any()) HIPCHK(hipMemcpyAsync(d_af_list, h_af, (size_t)af.n * sizeof(AfEntry), hipMemcpyHostToDevice, c->side));
-    DemodArgs a = demod_args(c, spec, spec_stride, nframes, first_frame_num, band, band_tiled);
-    a.clients = ring_at<ClientParams>(d_ring, p.plain.clients);
-    a.notch_man = p.any_manual ? ring_at<int4>(d_ring, p.notch) : nullptr;
-    a.notch_auto = notch_tab;
-    c->dbg_notch_man = a.notch_man, c->dbg_notch_auto = a.notch_auto;
-    // a list with launches of its own: the batch's arguments with its clients
-    auto of_list = [&](const RingList &l) {
-        DemodArgs al = a;
-        al.clients = ring_at<ClientParams>(d_ring, l.clients);
-        return al;
-    };
-    // the frame-ordered second walk of marked USB / LSB slots (demod.h: DemodArgs::ssb_mark) can only find work where
-    // non-finite values can arise: float input formats, or a spectrum that comes from the caller
-    const bool can_be_nonfinite = c->cfg.input_format >= PSDR_FMT_F32 || spec != c->d_spec;
+    for (size_t off : p.car_zero) HIPCHK(hipMemsetAsync(c->sam.car_tail + off, 0, tail_bytes, c->side));
+    for (size_t off : p.ft_zero) HIPCHK(hipMemsetAsync(c->ft.tail + off, 0, tail_bytes, c->side));
+    for (size_t off : p.sb_zero) HIPCHK(hipMemsetAsync(c->sb.tail + off, 0, tail_bytes, c->side));
+    if (b.sq.any()) HIPCHK(c->squelch.tab.upload(b.ring, (size_t)(b.sq.nsq + b.sq.ncopy), c->side));
+    if (b.af.any()) HIPCHK(c->af.tab.upload(b.ring, (size_t)b.af.n, c->side));
+    return PSDR_OK;
+}
+
+static bool fixed_plan(const psdr_ctx *c) { return c->n == 360 || c->n == 720; }
+// the transform alone, into ypost, of the `cnt` clients listed in aa.clients (every path but the chain kernels')
+static int launch_idft(psdr_ctx *c, const DemodArgs &aa, int cnt) {
+    if (fixed_plan(c)) {
+        // compile-time plans (demod.h): 360 = 8*9*5, 720 = 8*9*10; W items per work-group in
+        // the 15 KiB of LDS an FFT pass leaves free on a CU
+        const unsigned items = (unsigned)cnt * (unsigned)aa.nframes;
+        const unsigned W = c->n == 360 ? 4u : 1u;
+        const size_t lds = (size_t)(1 + W) * c->n * sizeof(cf);
+        if (c->n == 360)
+            hipLaunchKernelGGL((k_demod_idft_fixed<360, 8, 9, 5>), dim3((items + W - 1) / W), dim3(64 * W), lds,
+                               c->side, aa, cnt);
+        else
+            hipLaunchKernelGGL((k_demod_idft_fixed<720, 8, 9, 10>), dim3((items + W - 1) / W), dim3(64 * W), lds,
+                               c->side, aa, cnt);
+    } else if (c->n <= 512) {
+        // one wave per (client, frame), no work-group barriers (demod.h)
+        const unsigned items = (unsigned)cnt * (unsigned)aa.nframes;
+        const size_t lds = (size_t)(2 * PSDR_IDFT_WAVES + 1) * c->n * sizeof(cf);
+        hipLaunchKernelGGL(k_demod_idft_wave, dim3((items + PSDR_IDFT_WAVES - 1) / PSDR_IDFT_WAVES),
+                           dim3(64 * PSDR_IDFT_WAVES), lds, c->side, aa, cnt);
+    } else {
+        if (c->idft_lds > 64 * 1024 && c->lds_attr_done.insert((const void *)k_demod_idft).second)
+            HIPCHK(hipFuncSetAttribute((const void *)k_demod_idft, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->idft_lds));
+        hipLaunchKernelGGL(k_demod_idft, dim3(cnt, aa.nframes), dim3(c->idft_threads), c->idft_lds, c->side,
+                           aa);
+    }
+    return PSDR_OK;
+}
+// the plain list (USB, LSB, AM, FM): the `nold` clients listed in a.clients
+static int launch_plain(psdr_ctx *c, const DemodArgs &a, int nold, bool can_be_nonfinite) {
     bool ola_done = false;
-    const bool fixed_plan = c->n == 360 || c->n == 720;
-    // the transform alone, into ypost, of the `cnt` clients listed in aa.clients (every path but the chain kernels')
-    auto launch_idft = [&](const DemodArgs &aa, int cnt) -> int {
-        if (fixed_plan) {
-            // compile-time plans (demod.h): 360 = 8*9*5, 720 = 8*9*10; W items per work-group in
-            // the 15 KiB of LDS an FFT pass leaves free on a CU
-            const unsigned items = (unsigned)cnt * (unsigned)nframes;
-            const unsigned W = c->n == 360 ? 4u : 1u;
-            const size_t lds = (size_t)(1 + W) * c->n * sizeof(cf);
-            if (c->n == 360)
-                hipLaunchKernelGGL((k_demod_idft_fixed<360, 8, 9, 5>), dim3((items + W - 1) / W), dim3(64 * W), lds,
-                                   c->side, aa, cnt);
-            else
-                hipLaunchKernelGGL((k_demod_idft_fixed<720, 8, 9, 10>), dim3((items + W - 1) / W), dim3(64 * W), lds,
-                                   c->side, aa, cnt);
-        } else if (c->n <= 512) {
-            // one wave per (client, frame), no work-group barriers (demod.h)
-            const unsigned items = (unsigned)cnt * (unsigned)nframes;
-            const size_t lds = (size_t)(2 * PSDR_IDFT_WAVES + 1) * c->n * sizeof(cf);
-            hipLaunchKernelGGL(k_demod_idft_wave, dim3((items + PSDR_IDFT_WAVES - 1) / PSDR_IDFT_WAVES),
-                               dim3(64 * PSDR_IDFT_WAVES), lds, c->side, aa, cnt);
-        } else {
-            if (c->idft_lds > 64 * 1024 && c->lds_attr_done.insert((const void *)k_demod_idft).second)
-                HIPCHK(hipFuncSetAttribute((const void *)k_demod_idft, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->idft_lds));
-            hipLaunchKernelGGL(k_demod_idft, dim3(cnt, nframes), dim3(c->idft_threads), c->idft_lds, c->side,
-                               aa);
-        }
-        return PSDR_OK;
-    };
-    const int nold = p.nold;
-    if (nold > 0) {
+    {
         ProfScope ps(c, K_IDFT, c->side);
-        if (fixed_plan && c->demod_chain) {
+        if (fixed_plan(c) && c->demod_chain) {
             // transform + overlap-add + demodulation in one kernel, one wave per chain of K consecutive frames of a
             // client (demod.h)
             HIPCHK(launch_chain(c, CHAIN_FIXED, a, nold, 0, 4u, 0));
             if (can_be_nonfinite) {
                 DemodArgs ar = a;
                 ar.replay = 1;
-                HIPCHK(launch_chain(c, CHAIN_FIXED, ar, nold, nframes, 4u, 0));  // one chain = the whole batch
+                HIPCHK(launch_chain(c, CHAIN_FIXED, ar, nold, a.nframes, 4u, 0));  // one chain = the whole batch
             }
             ola_done = true;
         } else {
-            PSDRCHK(launch_idft(a, nold));
+            PSDRCHK(launch_idft(c, a, nold));
         }
         HIPCHK(hipGetLastError());
     }
-    if (nold > 0 && !ola_done) {
+    if (!ola_done) {
         ProfScope ps(c, K_OLA, c->side);
         HIPCHK(launch_ola(c, k_demod_ola, a, nold));
         if (can_be_nonfinite) hipLaunchKernelGGL(k_demod_ola_seq, dim3(((unsigned)nold + 3) / 4), dim3(256), 0, c->side, a, nold);
         HIPCHK(hipGetLastError());
     }
-    // a list with launches of its own (PSDR_SAM, PSDR_IQ): its chain kernel, or the transform and its overlap-add kernel
-    auto serve = [&](const auto &fam, auto ola, const DemodArgs &aa, int cnt, unsigned W360, size_t wave_lds, auto extra) -> int {
-        if (fixed_plan && c->demod_chain) {
-            ProfScope ps(c, K_IDFT, c->side);
-            HIPCHK(launch_chain(c, fam, aa, cnt, 0, W360, wave_lds, extra));
-            return PSDR_OK;
-        }
-        {
-            ProfScope ps(c, K_IDFT, c->side);
-            PSDRCHK(launch_idft(aa, cnt));
-            HIPCHK(hipGetLastError());
-        }
-        ProfScope ps(c, K_OLA, c->side);
-        HIPCHK(launch_ola(c, ola, aa, cnt, extra));
+    return PSDR_OK;
+}
+// a list with launches of its own (PSDR_SAM, PSDR_IQ, ...): its chain kernel, or the transform and its overlap-add kernel
+template <class Fam, class Ola, class Extra>
+static int serve(psdr_ctx *c, const Fam &fam, Ola ola, const DemodArgs &aa, int cnt, unsigned W360, size_t wave_lds, Extra extra) {
+    if (fixed_plan(c) && c->demod_chain) {
+        ProfScope ps(c, K_IDFT, c->side);
+        HIPCHK(launch_chain(c, fam, aa, cnt, 0, W360, wave_lds, extra));
         return PSDR_OK;
+    }
+    {
+        ProfScope ps(c, K_IDFT, c->side);
+        PSDRCHK(launch_idft(c, aa, cnt));
+        HIPCHK(hipGetLastError());
+    }
+    ProfScope ps(c, K_OLA, c->side);
+    HIPCHK(launch_ola(c, ola, aa, cnt, extra));
+    return PSDR_OK;
+}
+// The batch's lists in their order on `side`: plain, SAM, IQ, tuned SSB, tuned IQ, sideband SAM.  a: the batch's arguments with
+// the plain list's clients
+static int launch_lists(psdr_ctx *c, const BatchPlan &b, const DemodArgs &a, bool can_be_nonfinite) {
+    const DemodPlan &p = b.p;
+    // a list with launches of its own: the batch's arguments with its clients
+    auto of_list = [&](const RingList &l) {
+        DemodArgs al = a;
+        al.clients = ring_at<ClientParams>(b.d_ring, l.clients);
+        return al;
     };
+    if (p.nold > 0) PSDRCHK(launch_plain(c, a, p.nold, can_be_nonfinite));
+    const size_t tail_bytes = ((size_t)c->n / 2) * sizeof(cf);
     SamArgs sa{};
     if (p.nsam + p.nsb > 0) {
-        sa.car_tail = c->d_car_tail;
+        sa.car_tail = c->sam.car_tail;
         sa.car_rec = c->d_car;
         sa.cutoff = (int)((int64_t)500 * c->n / c->cfg.audio_rate);  // src/signal.cpp:217-220
         sa.hz_per_rad = (float)((double)c->cfg.audio_rate / (2.0 * M_PI));
@@ -686,76 +568,112 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     // the PSDR_SAM clients: the tail of the active list, launches of their own behind the others' (demod.h)
     // (a wave's carrier tail lives in n/2 words of LDS behind the transform buffers: two waves per work-group at
     // n = 360, 11.25 KiB, and one at 720, 14.1 KiB - inside the 15 KiB an FFT pass leaves free on a CU)
-    if (p.nsam > 0) PSDRCHK(serve(CHAIN_SAM, k_demod_ola_sam, of_list(p.sam), p.nsam, 2u, tail_bytes, sa));
+    if (p.nsam > 0) PSDRCHK(serve(c, CHAIN_SAM, k_demod_ola_sam, of_list(p.sam), p.nsam, 2u, tail_bytes, sa));
     // the PSDR_IQ clients: launches of their own behind the others', on the same stream (demod.h)
-    if (p.niq > 0) PSDRCHK(serve(p.iq_notched ? CHAIN_IQ_NZ : CHAIN_IQ, k_demod_ola_iq, of_list(p.iq), p.niq, 4u, 0, c->d_iq));
+    if (p.niq > 0) PSDRCHK(serve(c, p.iq_notched ? CHAIN_IQ_NZ : CHAIN_IQ, k_demod_ola_iq, of_list(p.iq), p.niq, 4u, 0, c->d_iq));
     // the tuned clients: their own list, launches of their own behind the others' (demod.h)
     FtArgs fa{};
-    fa.tail = c->d_ft_tail;
+    fa.tail = c->ft.tail;
     fa.iq = c->d_iq;
     if (p.ntssb > 0) {
-        fa.ft = ring_at<FtClient>(d_ring, p.tssb.side);
-        PSDRCHK(serve(CHAIN_FT_SSB, k_demod_ola_ft<true>, of_list(p.tssb), p.ntssb, 4u, 0, fa));
+        fa.ft = ring_at<FtClient>(b.d_ring, p.tssb.side);
+        PSDRCHK(serve(c, CHAIN_FT_SSB, k_demod_ola_ft<true>, of_list(p.tssb), p.ntssb, 4u, 0, fa));
     }
     if (p.ntiq > 0) {
-        fa.ft = ring_at<FtClient>(d_ring, p.tiq.side);
-        PSDRCHK(serve(CHAIN_FT_IQ, k_demod_ola_ft<false>, of_list(p.tiq), p.ntiq, 4u, 0, fa));
+        fa.ft = ring_at<FtClient>(b.d_ring, p.tiq.side);
+        PSDRCHK(serve(c, CHAIN_FT_IQ, k_demod_ola_ft<false>, of_list(p.tiq), p.ntiq, 4u, 0, fa));
     }
     if (p.nsb > 0) {
         // the sideband SAM clients: their own list, launches of their own behind all the others' (demod.h); LDS as SAM's
         SbArgs sba{};
         sba.sa = sa;
-        sba.sb = ring_at<SbClient>(d_ring, p.sb.side);
-        sba.tail = c->d_sb_tail;
-        PSDRCHK(serve(CHAIN_SBSAM, k_demod_ola_sbsam, of_list(p.sb), p.nsb, 2u, tail_bytes, sba));
+        sba.sb = ring_at<SbClient>(b.d_ring, p.sb.side);
+        sba.tail = c->sb.tail;
+        PSDRCHK(serve(c, CHAIN_SBSAM, k_demod_ola_sbsam, of_list(p.sb), p.nsb, 2u, tail_bytes, sba));
     }
-    if (p.ndet > 0) {
-        // the detector, behind the batch's last demodulation kernel: it writes the table those have just read (demod.h)
-        NotchArgs na{};
-        na.det = ring_at<ClientParams>(d_ring, p.det.clients);
-        na.acc = c->d_notch_acc;
-        na.cnt = c->d_notch_cnt;
-        na.tab = notch_tab;
-        na.period = std::max(1, c->cfg.audio_rate / c->n);
-        hipLaunchKernelGGL(k_notch_detect, dim3((unsigned)p.ndet), dim3(64), 0, c->side, a, p.ndet, na);
-        HIPCHK(hipGetLastError());
-    }
-    const bool chain = f.post_on && p.nact > 0;
-    const int *chain_drop = c->d_nan;  // what stays out of the chain's streams: the NaN guard's frames ...
-    if (sq.any()) {
-        // the squelch, behind the batch's last demodulation kernel and in front of the chain: it reads pwr and the NaN flags
-        SquelchArgs qa{};
-        qa.list = d_sq_list, qa.nlist = sq.nsq + sq.ncopy;
-        qa.pwr = c->d_pwr, qa.nan_flags = c->d_nan;
-        qa.open = c->d_sq, qa.drop = chain ? c->d_sq_drop.get() : nullptr;
-        qa.state = c->d_sq_state;
-        qa.nframes = nframes, qa.max_batch = c->max_batch;
-        ProfScope ps(c, K_SQUELCH, c->side);
-        hipLaunchKernelGGL(k_squelch, dim3((unsigned)qa.nlist), dim3(64), 0, c->side, qa);
-        HIPCHK(hipGetLastError());
-        if (chain) chain_drop = c->d_sq_drop;  // ... and the closed ones
-    }
-    if (af.any()) {
-        // the audio filter, behind the batch's last demodulation kernel and in front of the chain: it filters the listed clients'
-        // rows in place (k_squelch reads pwr and flags, not rows: their order does not matter)
-        AudioFilterArgs fa2{};
-        fa2.list = d_af_list, fa2.nlist = af.n;
-        fa2.audio = c->d_audio, fa2.nan_flags = c->d_nan;
-        fa2.state = c->d_af_state;
-        fa2.nframes = nframes, fa2.max_batch = c->max_batch, fa2.h = c->n / 2;
-        ProfScope ps(c, K_AUDIO_FILTER, c->side);
-        HIPCHK(audio_filter_launch(fa2, c->side));
-    }
+    return PSDR_OK;
+}
+// Behind the batch's last demodulation kernel - the auto-notch detector: it writes the table those have just read (demod.h)
+static int launch_detector(psdr_ctx *c, const BatchPlan &b, const DemodArgs &a) {
+    NotchArgs na{};
+    na.det = ring_at<ClientParams>(b.d_ring, b.p.det.clients);
+    na.acc = c->notch.acc;
+    na.cnt = c->notch.cnt;
+    na.tab = b.notch_tab;
+    na.period = std::max(1, c->cfg.audio_rate / c->n);
+    hipLaunchKernelGGL(k_notch_detect, dim3((unsigned)b.p.ndet), dim3(64), 0, c->side, a, b.p.ndet, na);
+    HIPCHK(hipGetLastError());
+    return PSDR_OK;
+}
+// ... the squelch, in front of the chain: it reads pwr and the NaN flags.  *chain_drop: what stays out of the chain's streams
+static int launch_squelch(psdr_ctx *c, const BatchPlan &b, int nframes, const int **chain_drop) {
+    SquelchArgs qa{};
+    qa.list = c->squelch.tab.dev(b.ring), qa.nlist = b.sq.nsq + b.sq.ncopy;
+    qa.pwr = c->d_pwr, qa.nan_flags = c->d_nan;
+    qa.open = c->d_sq, qa.drop = b.chain ? c->squelch.drop.get() : nullptr;
+    qa.state = c->squelch.state;
+    qa.nframes = nframes, qa.max_batch = c->max_batch;
+    ProfScope ps(c, K_SQUELCH, c->side);
+    hipLaunchKernelGGL(k_squelch, dim3((unsigned)qa.nlist), dim3(64), 0, c->side, qa);
+    HIPCHK(hipGetLastError());
+    if (b.chain) *chain_drop = c->squelch.drop;  // ... the NaN guard's frames and the closed ones
+    return PSDR_OK;
+}
+// ... the audio filter, in front of the chain: it filters the listed clients' rows in place (k_squelch reads pwr and flags, not
+// rows: their order does not matter)
+static int launch_audio_filter(psdr_ctx *c, const BatchPlan &b, int nframes) {
+    AudioFilterArgs fa{};
+    fa.list = c->af.tab.dev(b.ring), fa.nlist = b.af.n;
+    fa.audio = c->d_audio, fa.nan_flags = c->d_nan;
+    fa.state = c->af.state;
+    fa.nframes = nframes, fa.max_batch = c->max_batch, fa.h = c->n / 2;
+    ProfScope ps(c, K_AUDIO_FILTER, c->side);
+    HIPCHK(audio_filter_launch(fa, c->side));
+    return PSDR_OK;
+}
+// The batch's end: the post chain, if it follows, and the ring slot's release behind its last reader
+static int batch_end(psdr_ctx *c, const BatchPlan &b, const ClientParams *d_clients, int nframes, const int *chain_drop) {
     hipStream_t last_user = c->side;
-    // the AGC profiles of the batch's snapshot, in front of the chain (whose stages all start behind `side`)
-    if (chain && ag.any) HIPCHK(hipMemcpyAsync(d_agc_img, h_agc, c->aslots.size() * sizeof(AgcEntry), hipMemcpyHostToDevice, c->side));
-    if (chain)
-        PSDRCHK(post_chain_enqueue(c, a.clients, ring_at<int>(d_ring, p.slot_ci), p.nact, p.npaused, nframes, chain_drop,
-                                   ag.any ? d_agc_img : nullptr, &last_user));
-    HIPCHK(c->client_ring.release(ring, last_user));
+    if (b.chain) {
+        // the AGC profiles of the batch's snapshot, in front of the chain (whose stages all start behind `side`)
+        if (b.ag.any) HIPCHK(c->agc_prof.tab.upload(b.ring, c->aslots.size(), c->side));
+        PSDRCHK(post_chain_enqueue(c, d_clients, ring_at<int>(b.d_ring, b.p.slot_ci), b.p.nact, b.p.npaused, nframes, chain_drop,
+                                   b.ag.any ? c->agc_prof.tab.dev(b.ring) : nullptr, &last_user));
+    }
+    HIPCHK(c->client_ring.release(b.ring, last_user));
     return side_done(c);
 }
 
+// One batch: plans it, then copies, zeroes and launches what the plans name.
+static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nframes, uint64_t first_frame_num,
+                      const uint32_t *band = nullptr, bool band_tiled = false) {
+    if (c->n <= 0) return fail(PSDR_ERR_STATE, "context created with audio_fft_size 0");
+    HIPCHK(hipSetDevice(c->device));
+    BatchPlan b;
+    PSDRCHK(batch_plan(c, nframes, band, b));
+    c->last_demod_frames = nframes;
+    if (b.p.idle()) return PSDR_OK;
+    PSDRCHK(batch_begin(c, b));
+    DemodArgs a = demod_args(c, spec, spec_stride, nframes, first_frame_num, band, band_tiled);
+    a.clients = ring_at<ClientParams>(b.d_ring, b.p.plain.clients);
+    a.notch_man = b.p.any_manual ? ring_at<int4>(b.d_ring, b.p.notch) : nullptr;
+    a.notch_auto = b.notch_tab;
+    c->dbg_notch_man = a.notch_man, c->dbg_notch_auto = a.notch_auto;
+    // the frame-ordered second walk of marked USB / LSB slots (demod.h: DemodArgs::ssb_mark) can only find work where
+    // non-finite values can arise: float input formats, or a spectrum that comes from the caller
+    PSDRCHK(launch_lists(c, b, a, c->cfg.input_format >= PSDR_FMT_F32 || spec != c->d_spec));
+    if (b.p.ndet > 0) PSDRCHK(launch_detector(c, b, a));
+    const int *chain_drop = c->d_nan;  // what stays out of the chain's streams: the NaN guard's frames ...
+    if (b.sq.any()) PSDRCHK(launch_squelch(c, b, nframes, &chain_drop));
+    if (b.af.any()) PSDRCHK(launch_audio_filter(c, b, nframes));
+    return batch_end(c, b, a.clients, nframes, chain_drop);
+}
+
+static int check_nframes(const psdr_ctx *c, int nframes) {
+    if (nframes < 1 || nframes > c->max_batch)
+        return fail(PSDR_ERR_INVALID, "nframes %d outside [1, max_batch=%d]", nframes, c->max_batch);
+    return PSDR_OK;
+}
 extern "C" int psdr_demod_batch(psdr_ctx *c, uint64_t first_frame_num) {
     if (!c) return fail(PSDR_ERR_INVALID, "null argument");
     if (c->last_nframes < 1) return fail(PSDR_ERR_STATE, "demod_batch before process_batch/execute");
@@ -764,8 +682,7 @@ extern "C" int psdr_demod_batch(psdr_ctx *c, uint64_t first_frame_num) {
 extern "C" int psdr_demod_batch_from(psdr_ctx *c, const float *d_spec, size_t frame_stride_bins,
                                      int nframes, uint64_t first_frame_num) {
     if (!c || !d_spec) return fail(PSDR_ERR_INVALID, "null argument");
-    if (nframes < 1 || nframes > c->max_batch)
-        return fail(PSDR_ERR_INVALID, "nframes %d outside [1, max_batch=%d]", nframes, c->max_batch);
+    PSDRCHK(check_nframes(c, nframes));
     if (frame_stride_bins < (c->is_real ? c->N / 2 + 1 : c->N))
         return fail(PSDR_ERR_INVALID, "frame stride smaller than one spectrum");
     return demod_impl(c, (const cf *)d_spec, frame_stride_bins, nframes, first_frame_num);
@@ -773,8 +690,7 @@ extern "C" int psdr_demod_batch_from(psdr_ctx *c, const float *d_spec, size_t fr
 extern "C" int psdr_demod_batch_from_band(psdr_ctx *c, const float *d_band, size_t frame_stride_bins, uint32_t first_bin,
                                           uint32_t nbins, int nframes, uint64_t first_frame_num) {
     if (!c || !d_band) return fail(PSDR_ERR_INVALID, "null argument");
-    if (nframes < 1 || nframes > c->max_batch)
-        return fail(PSDR_ERR_INVALID, "nframes %d outside [1, max_batch=%d]", nframes, c->max_batch);
+    PSDRCHK(check_nframes(c, nframes));
     if (nbins < 1 || frame_stride_bins < nbins) return fail(PSDR_ERR_INVALID, "frame stride smaller than the band");
     const uint32_t band[2] = {first_bin, nbins};
     return demod_impl(c, (const cf *)d_band, frame_stride_bins, nframes, first_frame_num, band);
@@ -783,8 +699,7 @@ extern "C" int psdr_demod_batch_from_band_region(psdr_ctx *c, const float *d_reg
                                                  uint32_t nbins, int nframes, uint64_t first_frame_num) {
     if (!c || !d_region) return fail(PSDR_ERR_INVALID, "null argument");
     if (c->is_real || c->M2 != 1024) return fail(PSDR_ERR_UNSUPPORTED, "band regions: IQ frames with 1024-point rows only");
-    if (nframes < 1 || nframes > c->max_batch)
-        return fail(PSDR_ERR_INVALID, "nframes %d outside [1, max_batch=%d]", nframes, c->max_batch);
+    PSDRCHK(check_nframes(c, nframes));
     const uint32_t m1 = (uint32_t)c->M1;
     if (nbins < m1 || (nbins & (m1 - 1)) || (first_bin & (m1 - 1)) || first_bin >= (uint32_t)c->M)
         return fail(PSDR_ERR_INVALID, "band region [%u, +%u): whole columns of %u bins", first_bin, nbins, m1);

@@ -34,7 +34,7 @@ struct AudioSlot {
     uint64_t last_seq = 0;  // the demodulation batch (ctx->demod_seq) that last included this slot; 0: none yet
     int b_l = 0, b_r = 0;   // the window that batch was demodulated with (psdr_fetch_begin copies it into its FetchSet)
     double b_mid = 0;
-    int b_mode = PSDR_USB;  // ... and the mode: a batch demodulated as PSDR_IQ left complex rows (iq_pool) and no audio / PCM; one
+    int b_mode = PSDR_USB;  // ... and the mode: a batch demodulated as PSDR_IQ left complex rows (iq.pool) and no audio / PCM; one
                             // demodulated as PSDR_SAM left carrier records and a carrier tail the next SAM batch continues
     uint64_t born = 0;      // psdr_client_add's serial number: a fetched set answers only for the occupant it was filled with
     // psdr_client_set_fine_tune: with the flag on, a USB / LSB / IQ client is a TUNED client (demod.h: k_demod_chain_ft)

@@ -388,13 +388,13 @@ extern "C" int psdr_read_notches(psdr_ctx *c, int id, int first[4], int end[4]) 
     bool have_tab = false;
     PSDRCHK(read_begin(c, id, false, -1, nullptr, ROWS_ANY, false, &F, [&](const AudioSlot &s) {
         for (int k = 0; k < 4; k++) man[k] = s.b_notch[k];
-        have_tab = (bool)c->d_notch_tab;
+        have_tab = (bool)c->notch;
     }));
     int4 t = make_int4(0, 0, 0, 0);
     if (have_tab) {  // the table as the batch's detector left it: in force from the next batch on
         HIPCHK(hipSetDevice(c->device));
         PSDRCHK(drain(c));
-        HIPCHK(hipMemcpy(&t, c->d_notch_tab + id, sizeof(int4), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&t, c->notch.tab + id, sizeof(int4), hipMemcpyDeviceToHost));
     }
     first[0] = man[0], end[0] = man[1], first[1] = man[2], end[1] = man[3];
     first[2] = t.x, end[2] = t.y, first[3] = t.z, end[3] = t.w;

@@ -189,7 +189,7 @@ int main() {
             const psdr_biquad *ptr = null || sec.empty() ? nullptr : sec.data();
             const AfVerdict v = audio_filter_check(c.slots.data(), c.S, id, n, ptr);
             if (v == AF_OK) {
-                if (n > 0) have = true;  // (audio_filter_alloc)
+                if (n > 0) have = true;  // (first_use of the filter's state and table)
                 audio_filter_apply(c.slots[id], n, ptr);
             }
             printf("set id=%d verdict=%s\n", id, verdict_name(v));
