@@ -13,6 +13,9 @@
 //                       streams (one copy per root->peer link, ordered by events).  A device may then be listed more than
 //                       once (n ranks on fewer GPUs): the whole multi-rank logic - placement, band regions and halos,
 //                       migration, fetch - runs on a one-GPU box, only the transport differs.
+// What is DECIDED - the argument rules, transport and buffers per rank, a client's rank, and the ordered operations of a step
+// with their streams and events - is groupplan.h (host-only, tests/test_group_plan.py).  This file carries it out: it creates
+// what the layout names, walks a step's list (group_issue: one place per HIP / RCCL call) and keeps the client table.
 // Everything of one rank - its kernels and its side of the collective - is enqueued in order on ONE stream per device
 // (psdr_set_stream), so a step needs no host synchronisation; psdr_group_synchronize() drains all devices.
 // Threads: client calls arrive on the server's websocket threads while the frame loop steps the group.  A client is named
@@ -22,6 +25,7 @@
 #include <dlfcn.h>
 
 #include "ctx.h"
+#include "groupplan.h"
 
 namespace {
 
@@ -69,46 +73,53 @@ Rccl g_rccl;
         if (e_ != ncclSuccess) return fail(PSDR_ERR_HIP, "%s failed: %s", #expr, g_rccl.GetErrorString(e_));  \
     } while (0)
 
+// fails with `rc` and the message as it stands now: the clean-up in between must not overwrite it
+template <typename Cleanup>
+int fail_after(int rc, Cleanup cleanup) {
+    const std::string msg = psdr_last_error();
+    cleanup();
+    return fail(rc, "%s", msg.c_str());
+}
+// `count` elements on `device`; `what`: the message, which names the bytes and may name the device
+template <typename T>
+int alloc_on(int device, DevBuf<T> &b, size_t count, const char *what) {
+    if (hipSetDevice(device) == hipSuccess && !b.alloc(count)) return PSDR_OK;
+    return fail(PSDR_ERR_NOMEM, what, count * sizeof(T), device);
+}
+
 }  // namespace
 
 struct GroupClient {
     int rank = -1, id = -1;  // device rank and the slot of that rank's context; rank < 0: free entry
 };
 struct psdr_group {
-    int n = 0, shard = 0;
-    bool comm_on = false;           // RCCL collectives are issued (n > 1, or PSDR_SHARD_FORCE_COMM)
-    bool peer_copy = false;         // PSDR_SHARD_PEER_COPY: peers pull with hipMemcpyPeerAsync instead
+    GroupFacts facts;               // the create arguments and the root's shape
+    GroupLayout lay;                // transport, buffers per rank, bands (groupplan.h)
+    int n = 0;
     std::mutex mtx;                 // the client table, next_rr, and every enqueue on the ranks' streams
     std::vector<GroupClient> clients;  // gid -> (rank, slot): the gid a caller holds never changes
     std::vector<Event> ev_rank;        // per rank, on its device: migration hand-over / peer copy done
     std::vector<Event> ev_t0, ev_t1;   // peer copy: the copy's own duration on the peer's stream
     Event ev_x;                        // the root's data of this step is ready (peer copy; overlapped exchange)
-    bool copies_pending = false;       // peer copy: ev_rank[r] of the last step not yet waited for by the root
-    // The exchange of batch b beside the root's transform of batch b + 1 (PSDR_SHARD_CLIENTS, banded PSDR_SHARD_BAND): the
-    // root alternates its two result sets (psdr_ctx::alt_sets) and issues ITS side of the collective on a stream of its
-    // own (`xs`), behind ev_x; what it waits for - before it overwrites a set two steps later - is that set's exchange
+    // copies_pending, and - the exchange of batch b beside the root's transform of batch b + 1 (lay.overlap) - xpending: the
+    // root alternates its two result sets (psdr_ctx::alt_sets) and issues ITS side of the collective on a stream of its own
+    // (`xs`), behind ev_x; what it waits for - before it overwrites a set two steps later - is that set's exchange
     // (ev_xdone[set]; peer copies: ev_pull[set][r], recorded by the peers).  PSDR_SHARD_SERIAL switches it off (A/B, tests).
-    bool overlap = false;
+    GroupState state;
     Stream xs;
     Event ev_xdone[2];
-    bool xpending[2] = {false, false};
     std::vector<Event> ev_pull[2];
     std::vector<int> dev;
     std::vector<psdr_ctx *> ctx;
     std::vector<Stream> st;         // the one stream per device everything of that rank is ordered on
     std::vector<ncclComm_t> comm;
     std::vector<DevBuf<unsigned char>> rbuf;  // per rank: receive buffer (raw halves / band region), nullptr where unused
-    size_t rbuf_bytes = 0;
     std::vector<DevBuf<cf>> sbuf;   // band sharding with the pack pass: the root's send buffers, one per band
-    // band sharding
-    bool banded = false;            // the root writes band regions itself (no pack)
-    uint32_t band_first[16] = {0}, band_bins[16] = {0};
-    size_t band_stride = 0;         // bins between frames inside a band buffer
     int next_rr = 0;                // round-robin cursor of psdr_group_client_add
     // link accounting
     double link_bytes = 0;          // bytes that crossed ONE link (root -> one peer) in the last step
     Event ev0, ev1;
-    bool timed = false;
+    GroupStats stats = STATS_NONE;  // which events timed the last step's exchange
     uint64_t steps = 0;
 };
 
@@ -128,10 +139,10 @@ static int gid_new(psdr_group *g, int rank, int id) {
     g->clients.push_back(GroupClient{rank, id});
     return (int)g->clients.size() - 1;
 }
-static int band_of(const psdr_group *g, int l) {
-    const size_t R = g->ctx[0]->R, per = R / (size_t)g->n;
-    int b = (int)((size_t)std::max(l, 0) / per);
-    return std::min(b, g->n - 1);
+// rank `to` copies on its own stream what rank `from` holds: inside one device, or across two
+static hipError_t rank_copy(psdr_group *g, int to, void *d, int from, const void *s, size_t bytes) {
+    return g->dev[from] == g->dev[to] ? hipMemcpyAsync(d, s, bytes, hipMemcpyDeviceToDevice, g->st[to])
+                                      : hipMemcpyPeerAsync(d, g->dev[to], s, g->dev[from], bytes, g->st[to]);
 }
 
 extern "C" void psdr_group_destroy(psdr_group *g) {
@@ -151,36 +162,30 @@ extern "C" void psdr_group_destroy(psdr_group *g) {
 
 extern "C" int psdr_group_create(const psdr_config *cfg, const int *devices, int ndevices, int shard, psdr_group **out) {
     if (!cfg || !devices || !out) return fail(PSDR_ERR_INVALID, "null argument");
-    const bool force_comm = (shard & PSDR_SHARD_FORCE_COMM) != 0, peer_copy = (shard & PSDR_SHARD_PEER_COPY) != 0;
-    const bool serial = (shard & PSDR_SHARD_SERIAL) != 0;
-    shard &= ~(PSDR_SHARD_FORCE_COMM | PSDR_SHARD_PEER_COPY | PSDR_SHARD_SERIAL);
-    if (ndevices < 1 || ndevices > 16) return fail(PSDR_ERR_INVALID, "a group has 1..16 devices, not %d", ndevices);
-    if (shard < PSDR_SHARD_CLIENTS || shard > PSDR_SHARD_BAND) return fail(PSDR_ERR_INVALID, "unknown sharding %d", shard);
-    if (force_comm && peer_copy) return fail(PSDR_ERR_INVALID, "PSDR_SHARD_FORCE_COMM (RCCL) and PSDR_SHARD_PEER_COPY (no RCCL) exclude each other");
-    for (int i = 0; i < ndevices && !peer_copy; i++)
-        for (int j = 0; j < i; j++)
-            if (devices[i] == devices[j])
-                return fail(PSDR_ERR_INVALID, "device %d listed twice (RCCL wants one rank per device; PSDR_SHARD_PEER_COPY allows it)", devices[i]);
-    if (shard == PSDR_SHARD_BAND && (ndevices & (ndevices - 1))) return fail(PSDR_ERR_INVALID, "band sharding: a power-of-two number of devices, not %d", ndevices);
+    GroupFacts f = group_flags(ndevices, shard);
+    f.twice = group_listed_twice(devices, ndevices);
+    const GroupCheck chk = group_check(f);
+    switch (chk.what) {
+    case GROUP_BAD_COUNT: return fail(chk.code, "a group has 1..16 devices, not %d", chk.arg);
+    case GROUP_BAD_SHARD: return fail(chk.code, "unknown sharding %d", chk.arg);
+    case GROUP_EXCLUSIVE: return fail(chk.code, "PSDR_SHARD_FORCE_COMM (RCCL) and PSDR_SHARD_PEER_COPY (no RCCL) exclude each other");
+    case GROUP_TWICE: return fail(chk.code, "device %d listed twice (RCCL wants one rank per device; PSDR_SHARD_PEER_COPY allows it)", chk.arg);
+    case GROUP_BAND_POW2: return fail(chk.code, "band sharding: a power-of-two number of devices, not %d", chk.arg);
+    case GROUP_OK: break;
+    }
     psdr_group *g = new (std::nothrow) psdr_group();
     if (!g) return fail(PSDR_ERR_NOMEM, "out of memory");
     g->n = ndevices;
-    g->shard = shard;
-    g->peer_copy = peer_copy && ndevices > 1;
-    g->comm_on = !peer_copy && (ndevices > 1 || force_comm);
     g->dev.assign(devices, devices + ndevices);
     g->ctx.assign(ndevices, nullptr);
     g->st.resize(ndevices);
     g->comm.assign(ndevices, nullptr);
     g->rbuf.resize(ndevices);
+    g->sbuf.resize(ndevices);
     g->ev_rank.resize(ndevices);
     g->ev_t0.resize(ndevices);
     g->ev_t1.resize(ndevices);
-    auto bail = [&](int rc) {
-        const std::string msg = psdr_last_error();  // (the clean-up below must not overwrite it)
-        psdr_group_destroy(g);
-        return fail(rc, "%s", msg.c_str());
-    };
+    auto bail = [&](int rc) { return fail_after(rc, [&] { psdr_group_destroy(g); }); };
     for (int r = 0; r < ndevices; r++) {
         psdr_config c = *cfg;
         c.device = devices[r];
@@ -197,14 +202,19 @@ extern "C" int psdr_group_create(const psdr_config *cfg, const int *devices, int
             fail(PSDR_ERR_HIP, "event creation on device %d failed", devices[r]);
             return bail(PSDR_ERR_HIP);
         }
-        if (g->peer_copy && r > 0 && devices[r] != devices[0]) {
+        if (f.peer_copy && r > 0 && devices[r] != devices[0]) {
             (void)hipDeviceEnablePeerAccess(devices[0], 0);  // (direct xGMI reads; without it the copy is staged)
             (void)hipGetLastError();
         }
     }
     psdr_ctx *c0 = g->ctx[0];
-    const size_t F = (size_t)c0->max_batch;
-    if (g->comm_on) {
+    f.R = c0->R, f.is_real = c0->is_real, f.lay_mode = c0->lay.mode;
+    f.max_batch = (size_t)c0->max_batch, f.half_frame_bytes = psdr_half_frame_bytes(c0), f.spec_stride = c0->spec_stride;
+    f.audio_fft_size = cfg->audio_fft_size;
+    g->facts = f;
+    g->lay = group_layout(f);
+    const GroupLayout &L = g->lay;
+    if (L.comm_on) {
         int rc = g_rccl.load();
         if (rc) return bail(rc);
         const int e = g_rccl.CommInitAll(g->comm.data(), ndevices, devices);
@@ -214,58 +224,28 @@ extern "C" int psdr_group_create(const psdr_config *cfg, const int *devices, int
         }
     }
     // ---- per-sharding buffers
-    if (shard == PSDR_SHARD_RAW) {
-        g->rbuf_bytes = (F + 1) * psdr_half_frame_bytes(c0);
-        for (int r = 1; r < ndevices; r++) {
-            if (hipSetDevice(devices[r]) != hipSuccess || g->rbuf[r].alloc(g->rbuf_bytes)) {
-                fail(PSDR_ERR_NOMEM, "raw receive buffer of %zu bytes on device %d", g->rbuf_bytes, devices[r]);
-                return bail(PSDR_ERR_NOMEM);
-            }
+    if (L.banded) {  // the root's second pass writes the regions: the context is their owner
+        GroupBands own;
+        int rc = psdr_set_band_layout(c0, ndevices, L.halo);
+        for (int b = 0; b < ndevices && !rc; b++) {
+            const float *p;
+            rc = psdr_band_region(c0, b, &p, &own.stride, &own.first[b], &own.bins[b]);
         }
-    } else if (shard == PSDR_SHARD_BAND) {
-        const uint32_t halo = (uint32_t)std::max(cfg->audio_fft_size, 0);  // a window is at most audio_fft_size bins wide (src/signal.cpp:309-311)
-        const size_t R = c0->R;
-        g->banded = !c0->is_real && c0->lay.mode == 1 && ndevices > 1;
-        if (g->banded) {
-            int rc = psdr_set_band_layout(c0, ndevices, halo);
-            if (rc) return bail(rc);
-            for (int b = 0; b < ndevices; b++) {
-                const float *p;
-                rc = psdr_band_region(c0, b, &p, &g->band_stride, &g->band_first[b], &g->band_bins[b]);
-                if (rc) return bail(rc);
-            }
-        } else {
-            // linear band buffers filled by psdr_pack_band: [b R/n, (b+1) R/n + 1 + halo), the same count on every rank
-            const size_t per = (R + (size_t)ndevices - 1) / (size_t)ndevices;
-            const uint32_t cnt = (uint32_t)std::min(per + 1 + halo, R);
-            g->band_stride = cnt;
-            for (int b = 0; b < ndevices; b++) g->band_first[b] = (uint32_t)((size_t)b * (R / (size_t)ndevices)), g->band_bins[b] = cnt;
-            g->sbuf.resize(ndevices);
-            // (one device with the collectives forced: band 0 - the whole spectrum - is packed, sent to and received from
-            // oneself and demodulated from the received buffer, so that the pack + ncclSend / ncclRecv + band demodulation
-            // path runs on a single-GPU box)
-            for (int b = (ndevices == 1 && g->comm_on) ? 0 : 1; b < ndevices; b++) {
-                if (hipSetDevice(devices[0]) != hipSuccess || g->sbuf[b].alloc(F * g->band_stride)) {
-                    fail(PSDR_ERR_NOMEM, "band send buffer of %zu bytes", F * g->band_stride * sizeof(cf));
-                    return bail(PSDR_ERR_NOMEM);
-                }
-            }
-        }
-        g->rbuf_bytes = F * g->band_stride * sizeof(cf);
-        for (int r = (ndevices == 1 && g->comm_on) ? 0 : 1; r < ndevices; r++) {
-            if (hipSetDevice(devices[r]) != hipSuccess || g->rbuf[r].alloc(g->rbuf_bytes)) {
-                fail(PSDR_ERR_NOMEM, "band receive buffer of %zu bytes on device %d", g->rbuf_bytes, devices[r]);
-                return bail(PSDR_ERR_NOMEM);
-            }
-        }
+        if (rc) return bail(rc);
+        g->lay = group_layout(f, &own);
     }
+    for (int b = 0; b < ndevices; b++)
+        if (L.sbuf[b] && alloc_on(devices[0], g->sbuf[b], f.max_batch * L.band.stride, "band send buffer of %zu bytes")) return bail(PSDR_ERR_NOMEM);
+    for (int r = 0; r < ndevices; r++)
+        if (L.rbuf_bytes[r] && alloc_on(devices[r], g->rbuf[r], L.rbuf_bytes[r],
+                                        f.shard == PSDR_SHARD_RAW ? "raw receive buffer of %zu bytes on device %d" : "band receive buffer of %zu bytes on device %d"))
+            return bail(PSDR_ERR_NOMEM);
     if (hipSetDevice(devices[0]) != hipSuccess || g->ev0.create_timing() || g->ev1.create_timing() || g->ev_x.create()) {
         fail(PSDR_ERR_HIP, "event creation failed");
         return bail(PSDR_ERR_HIP);
     }
     // the exchange beside the next transform: spectrum broadcast, and band regions the root's second pass writes itself
-    g->overlap = !serial && (g->comm_on || g->peer_copy) && (shard == PSDR_SHARD_CLIENTS || (shard == PSDR_SHARD_BAND && g->banded));
-    if (g->overlap) {
+    if (L.overlap) {
         c0->alt_sets = true;
         bool ok = !g->xs.create();
         for (Event &e : g->ev_xdone) ok = ok && !e.create();
@@ -286,28 +266,29 @@ extern "C" int psdr_group_size(const psdr_group *g) { return g ? g->n : 0; }
 extern "C" psdr_ctx *psdr_group_ctx(psdr_group *g, int rank) { return (g && rank >= 0 && rank < g->n) ? g->ctx[rank] : nullptr; }
 
 // ---- audio clients: the group picks the GPU ---------------------------------------------------------------------
+// A client of the group on context c: untuned and without notches, whatever PSDR_OPT_FINE_TUNE and PSDR_OPT_AUTO_NOTCH of
+// the rank's context say (a migration carries the fine-tune flag as 0 and no notches); the slot is given back on failure
+static int place_client(psdr_ctx *c, int l, double audio_mid, int r, int mode, bool paused, int *id) {
+    int rc = psdr_client_add(c, id);
+    if (rc) return rc;
+    rc = psdr_client_set_fine_tune(c, *id, 0);
+    if (!rc) rc = psdr_client_set_auto_notch(c, *id, 0);
+    if (!rc) rc = psdr_client_set_audio_demodulation(c, *id, mode);
+    if (!rc) rc = psdr_client_set_audio_range(c, *id, l, audio_mid, r);
+    if (!rc && paused) rc = psdr_client_set_paused(c, *id, 1);
+    return rc ? fail_after(rc, [&] { psdr_client_remove(c, *id); }) : PSDR_OK;
+}
 extern "C" int psdr_group_client_add(psdr_group *g, int l, double audio_mid, int r, int mode, int *gid_out) {
     if (!g || !gid_out) return fail(PSDR_ERR_INVALID, "null argument");
     // (a group neither migrates nor fetches IQ rows: a context of its own serves such a client)
     if (mode == PSDR_IQ) return fail(PSDR_ERR_UNSUPPORTED, "PSDR_IQ clients are not served through a group");
     if (mode == PSDR_SAM) return fail(PSDR_ERR_UNSUPPORTED, "PSDR_SAM clients are not served through a group (the carrier tail is not migrated)");
     std::lock_guard<std::mutex> lk(g->mtx);
-    // clients / raw: round robin (client i on GPU i mod n, like assign_clients of distributed.py); band: the band the
-    // window STARTS in (it may end in the halo)
-    const int rank = g->shard == PSDR_SHARD_BAND ? band_of(g, l) : g->next_rr % g->n;
+    const int rank = group_rank_for(g->facts, l, g->next_rr);
     int id = -1;
-    int rc = psdr_client_add(g->ctx[rank], &id);
+    const int rc = place_client(g->ctx[rank], l, audio_mid, r, mode, false, &id);
     if (rc) return rc;
-    rc = psdr_client_set_fine_tune(g->ctx[rank], id, 0);  // a group's clients are untuned, whatever PSDR_OPT_FINE_TUNE of the rank's context says
-    if (!rc) rc = psdr_client_set_auto_notch(g->ctx[rank], id, 0);  // ... and without notches, whatever PSDR_OPT_AUTO_NOTCH says
-    if (!rc) rc = psdr_client_set_audio_demodulation(g->ctx[rank], id, mode);
-    if (!rc) rc = psdr_client_set_audio_range(g->ctx[rank], id, l, audio_mid, r);
-    if (rc) {
-        const std::string msg = psdr_last_error();
-        psdr_client_remove(g->ctx[rank], id);
-        return fail(rc, "%s", msg.c_str());
-    }
-    if (g->shard != PSDR_SHARD_BAND) g->next_rr++;
+    if (g->facts.shard != PSDR_SHARD_BAND) g->next_rr++;
     *gid_out = gid_new(g, rank, id);
     return PSDR_OK;
 }
@@ -353,7 +334,7 @@ extern "C" int psdr_group_client_set_audio_range(psdr_group *g, int gid, int l, 
     std::lock_guard<std::mutex> lk(g->mtx);
     int rank, id, rc = gid_split(g, gid, &rank, &id);
     if (rc) return rc;
-    const int want = g->shard == PSDR_SHARD_BAND ? band_of(g, l) : rank;
+    const int want = g->facts.shard == PSDR_SHARD_BAND ? group_rank_for(g->facts, l, 0) : rank;
     if (want == rank) return psdr_client_set_audio_range(g->ctx[rank], id, l, audio_mid, r);
     psdr_ctx *src = g->ctx[rank], *dst = g->ctx[want];
     int mode, nid = -1, src_par;
@@ -365,18 +346,8 @@ extern "C" int psdr_group_client_set_audio_range(psdr_group *g, int gid, int l, 
         paused = src->aslots[id].paused;
         src_par = src->aslots[id].state_cur;  // the parity the NEXT batch would read: what the last one wrote
     }
-    rc = psdr_client_add(dst, &nid);
+    rc = place_client(dst, l, audio_mid, r, mode, paused, &nid);
     if (rc) return rc;
-    rc = psdr_client_set_fine_tune(dst, nid, 0);  // the fine-tune flag travels as 0
-    if (!rc) rc = psdr_client_set_auto_notch(dst, nid, 0);  // notches do not travel
-    if (!rc) rc = psdr_client_set_audio_demodulation(dst, nid, mode);
-    if (!rc) rc = psdr_client_set_audio_range(dst, nid, l, audio_mid, r);
-    if (!rc && paused) rc = psdr_client_set_paused(dst, nid, 1);
-    if (rc) {
-        const std::string msg = psdr_last_error();
-        psdr_client_remove(dst, nid);
-        return fail(rc, "%s", msg.c_str());
-    }
     // the state rows: [parity][slot][n/2] (ctx.h); the fresh slot reads parity 0 first.  Ordered on the two ranks' streams:
     // after everything the old device has enqueued, before anything the new one enqueues from here on; the old slot may be
     // handed out again only after the copy has read it.
@@ -386,24 +357,17 @@ extern "C" int psdr_group_client_set_audio_range(psdr_group *g, int gid, int l, 
         HIPCHK(hipEventRecord(g->ev_rank[rank], g->st[rank]));
         HIPCHK(hipSetDevice(g->dev[want]));
         HIPCHK(hipStreamWaitEvent(g->st[want], g->ev_rank[rank], 0));
-        auto copy = [&](void *d, const void *sp, size_t bytes) -> hipError_t {
-            return g->dev[rank] == g->dev[want] ? hipMemcpyAsync(d, sp, bytes, hipMemcpyDeviceToDevice, g->st[want])
-                                                : hipMemcpyPeerAsync(d, g->dev[want], sp, g->dev[rank], bytes, g->st[want]);
-        };
-        HIPCHK(copy(dst->d_real_prev + ((size_t)0 * Sd + nid) * h, src->d_real_prev + ((size_t)src_par * Ss + id) * h, h * sizeof(float)));
-        HIPCHK(copy(dst->d_bb_tail + ((size_t)0 * Sd + nid) * h, src->d_bb_tail + ((size_t)src_par * Ss + id) * h, h * sizeof(cf)));
-        HIPCHK(copy(dst->d_bb_last + ((size_t)0 * Sd + nid), src->d_bb_last + ((size_t)src_par * Ss + id), sizeof(cf)));
+        HIPCHK(rank_copy(g, want, dst->d_real_prev + ((size_t)0 * Sd + nid) * h, rank, src->d_real_prev + ((size_t)src_par * Ss + id) * h, h * sizeof(float)));
+        HIPCHK(rank_copy(g, want, dst->d_bb_tail + ((size_t)0 * Sd + nid) * h, rank, src->d_bb_tail + ((size_t)src_par * Ss + id) * h, h * sizeof(cf)));
+        HIPCHK(rank_copy(g, want, dst->d_bb_last + ((size_t)0 * Sd + nid), rank, src->d_bb_last + ((size_t)src_par * Ss + id), sizeof(cf)));
         HIPCHK(hipEventRecord(g->ev_rank[want], g->st[want]));
         HIPCHK(hipSetDevice(g->dev[rank]));
         HIPCHK(hipStreamWaitEvent(g->st[rank], g->ev_rank[want], 0));
         return PSDR_OK;
     };
     rc = move_state();
-    if (rc) {  // the client stays where it was (gid -> src), the half-made slot on the new device is given back
-        const std::string msg = psdr_last_error();
-        psdr_client_remove(dst, nid);
-        return fail(rc, "%s", msg.c_str());
-    }
+    // (failed: the client stays where it was (gid -> src), the half-made slot on the new device is given back)
+    if (rc) return fail_after(rc, [&] { psdr_client_remove(dst, nid); });
     psdr_client_remove(src, id);
     g->clients[gid] = GroupClient{want, nid};
     return PSDR_OK;
@@ -411,262 +375,130 @@ extern "C" int psdr_group_client_set_audio_range(psdr_group *g, int gid, int l, 
 
 // ---- one batch ------------------------------------------------------------------------------------------------
 // raw_root: nframes + 1 raw half-frames on the root device (nullptr: the root's ingest ring from first_half on)
-static int group_step(psdr_group *g, const void *raw_root, uint64_t first_half, int nframes, uint64_t first_frame_num) {
-    psdr_ctx *c0 = g->ctx[0];
-    if (nframes < 1 || nframes > c0->max_batch) return fail(PSDR_ERR_INVALID, "nframes %d outside [1, max_batch=%d]", nframes, c0->max_batch);
-    const size_t F = (size_t)nframes;
-    const size_t hb = psdr_half_frame_bytes(c0);
-    int rc;
-    auto root_transform = [&]() -> int { return raw_root ? psdr_process_batch(c0, raw_root, nframes) : psdr_process_ring(c0, first_half, nframes); };
-    g->timed = false;
-    g->link_bytes = 0;
-    // PSDR_SHARD_PEER_COPY: what the root is about to overwrite (its spectrum / band regions / send buffers) was the source
-    // of the peers' copies of the previous step
-    auto root_waits_for_copies = [&]() -> int {
-        if (!g->copies_pending) return PSDR_OK;
-        HIPCHK(hipSetDevice(g->dev[0]));
-        for (int r = 1; r < g->n; r++) HIPCHK(hipStreamWaitEvent(g->st[0], g->ev_rank[r], 0));
-        g->copies_pending = false;
-        return PSDR_OK;
-    };
-    // ... and the pull itself: peer r copies `bytes` from the root's src[r] into dst[r] on ITS OWN stream, behind the
-    // root's "data ready" event - n - 1 independent copies, one per root -> peer link
-    auto peers_pull = [&](const std::vector<const void *> &src, const auto &dst, size_t bytes) -> int {
-        HIPCHK(hipSetDevice(g->dev[0]));
-        HIPCHK(hipEventRecord(g->ev_x, g->st[0]));
-        for (int r = 1; r < g->n; r++) {
-            HIPCHK(hipSetDevice(g->dev[r]));
-            HIPCHK(hipStreamWaitEvent(g->st[r], g->ev_x, 0));
-            HIPCHK(hipEventRecord(g->ev_t0[r], g->st[r]));
-            if (g->dev[r] == g->dev[0])
-                HIPCHK(hipMemcpyAsync(dst[r], src[r], bytes, hipMemcpyDeviceToDevice, g->st[r]));
-            else
-                HIPCHK(hipMemcpyPeerAsync(dst[r], g->dev[r], src[r], g->dev[0], bytes, g->st[r]));
-            HIPCHK(hipEventRecord(g->ev_t1[r], g->st[r]));
-            HIPCHK(hipEventRecord(g->ev_rank[r], g->st[r]));
-        }
-        g->copies_pending = true;
-        g->timed = true;
-        g->link_bytes = (double)bytes;
-        return PSDR_OK;
-    };
-    // overlapped exchange: the result set the root's transform is about to overwrite (the OTHER one: process_frames toggles)
-    // was the source of the exchange two steps ago - that, and only that, is waited for
-    auto root_waits_for_set = [&](int set) -> int {
-        HIPCHK(hipSetDevice(g->dev[0]));
-        if (g->xpending[set]) {
-            if (g->comm_on) HIPCHK(hipStreamWaitEvent(g->st[0], g->ev_xdone[set], 0));
-            if (g->peer_copy)
-                for (int r = 1; r < g->n; r++) HIPCHK(hipStreamWaitEvent(g->st[0], g->ev_pull[set][r], 0));
-            g->xpending[set] = false;
-        }
-        return PSDR_OK;
-    };
-    // ... its side of the collective goes to the exchange stream, behind the transform; the peers' sides stay on their streams
-    auto exchange_begin = [&]() -> int {
-        HIPCHK(hipSetDevice(g->dev[0]));
-        HIPCHK(hipEventRecord(g->ev_x, g->st[0]));
-        HIPCHK(hipStreamWaitEvent(g->xs, g->ev_x, 0));
-        HIPCHK(hipEventRecord(g->ev0, g->xs));
-        return PSDR_OK;
-    };
-    auto exchange_end = [&](int set, double bytes) -> int {
-        HIPCHK(hipSetDevice(g->dev[0]));
-        HIPCHK(hipEventRecord(g->ev1, g->xs));
-        HIPCHK(hipEventRecord(g->ev_xdone[set], g->xs));
-        g->xpending[set] = true;
-        g->timed = true;
-        g->link_bytes = bytes;
-        return PSDR_OK;
-    };
-    auto peers_pull_set = [&](int set, const std::vector<const void *> &src, const auto &dst, size_t bytes) -> int {
-        HIPCHK(hipSetDevice(g->dev[0]));
-        HIPCHK(hipEventRecord(g->ev_x, g->st[0]));
-        for (int r = 1; r < g->n; r++) {
-            HIPCHK(hipSetDevice(g->dev[r]));
-            HIPCHK(hipStreamWaitEvent(g->st[r], g->ev_x, 0));
-            HIPCHK(hipEventRecord(g->ev_t0[r], g->st[r]));
-            if (g->dev[r] == g->dev[0])
-                HIPCHK(hipMemcpyAsync(dst[r], src[r], bytes, hipMemcpyDeviceToDevice, g->st[r]));
-            else
-                HIPCHK(hipMemcpyPeerAsync(dst[r], g->dev[r], src[r], g->dev[0], bytes, g->st[r]));
-            HIPCHK(hipEventRecord(g->ev_t1[r], g->st[r]));
-            HIPCHK(hipEventRecord(g->ev_pull[set][r], g->st[r]));
-        }
-        g->xpending[set] = true;
-        g->timed = true;
-        g->link_bytes = (double)bytes;
-        return PSDR_OK;
-    };
-    rc = g->overlap ? root_waits_for_set(c0->cur_set ^ 1) : root_waits_for_copies();
-    if (rc) return rc;
-    if (g->shard == PSDR_SHARD_RAW) {
-        // the raw half-frames cross the links, every GPU transforms them itself
-        const unsigned char *src = (const unsigned char *)raw_root;
-        if (!src) {
-            if (!c0->ring.d) return fail(PSDR_ERR_STATE, "psdr_ring_create() on the root context first");
-            const int s0 = (int)(first_half % (uint64_t)c0->ring.nhalves);
-            if (s0 + nframes > c0->ring.nhalves) return fail(PSDR_ERR_INVALID, "frames cross the end of the ring: split the batch");
-            src = c0->ring.d + (size_t)s0 * hb;
-            for (int i = 0; i <= nframes; i++) {  // the copies of exactly the halves that are sent
-                const int slot = (s0 + i) % c0->ring.nhalves;
-                if (!c0->ring.ever_written[slot]) return fail(PSDR_ERR_STATE, "half-frame slot %d was never written", slot);
-                HIPCHK(hipStreamWaitEvent(g->st[0], c0->ring.ev_written[slot], 0));
-            }
-        }
-        const size_t bytes = (F + 1) * hb;
-        if (g->comm_on) {
-            HIPCHK(hipSetDevice(g->dev[0]));
-            HIPCHK(hipEventRecord(g->ev0, g->st[0]));
-            NCCLCHK(g_rccl.GroupStart());
-            for (int r = 0; r < g->n; r++) {
-                HIPCHK(hipSetDevice(g->dev[r]));
-                // (root: in place - its own transform reads the caller's buffer / the ring)
-                NCCLCHK(g_rccl.Broadcast(src, r == 0 ? (void *)src : g->rbuf[r], bytes, ncclChar, 0, g->comm[r], g->st[r]));
-            }
-            NCCLCHK(g_rccl.GroupEnd());
-            HIPCHK(hipSetDevice(g->dev[0]));
-            HIPCHK(hipEventRecord(g->ev1, g->st[0]));
-            g->timed = true;
-            g->link_bytes = (double)bytes;
-        } else if (g->peer_copy) {
-            rc = peers_pull(std::vector<const void *>(g->n, src), g->rbuf, bytes);
-            if (rc) return rc;
-            // the raw halves are the caller's (or the ingest ring's, whose slots are released by the root's first pass):
-            // the root's transform - and with it everything the caller orders behind it - comes after the pulls
-            rc = root_waits_for_copies();
-            if (rc) return rc;
-        }
-        rc = root_transform();
-        if (rc) return rc;
-        for (int r = 1; r < g->n; r++) {
-            rc = psdr_process_batch(g->ctx[r], g->rbuf[r], nframes);
-            if (rc) return rc;
-        }
-        for (int r = 0; r < g->n; r++) {
-            rc = psdr_demod_batch(g->ctx[r], first_frame_num);
-            if (rc) return rc;
-        }
-    } else {
-        rc = root_transform();
-        if (rc) return rc;
-        if (g->shard == PSDR_SHARD_CLIENTS) {
-            const size_t count = F * c0->spec_stride * 2;  // floats: the device layout, frames spec_stride bins apart
-            if (g->comm_on) {
-                // overlap: the root's side on the exchange stream (its own stream goes on with the demodulation and the next
-                // batch's transform into the other result set)
-                hipStream_t s0 = g->overlap ? g->xs : g->st[0];
-                if (g->overlap) {
-                    rc = exchange_begin();
-                    if (rc) return rc;
-                } else {
-                    HIPCHK(hipSetDevice(g->dev[0]));
-                    HIPCHK(hipEventRecord(g->ev0, g->st[0]));
-                }
-                NCCLCHK(g_rccl.GroupStart());
-                for (int r = 0; r < g->n; r++) {
-                    HIPCHK(hipSetDevice(g->dev[r]));
-                    // straight out of the root's spectrum buffer into every rank's own
-                    NCCLCHK(g_rccl.Broadcast(c0->d_spec, r == 0 ? (void *)c0->d_spec : (void *)g->ctx[r]->d_spec, count, ncclFloat, 0, g->comm[r], r == 0 ? s0 : g->st[r]));
-                }
-                NCCLCHK(g_rccl.GroupEnd());
-                if (g->overlap) {
-                    rc = exchange_end(c0->cur_set, (double)count * sizeof(float));
-                    if (rc) return rc;
-                } else {
-                    HIPCHK(hipSetDevice(g->dev[0]));
-                    HIPCHK(hipEventRecord(g->ev1, g->st[0]));
-                    g->timed = true;
-                    g->link_bytes = (double)count * sizeof(float);
-                }
-            } else if (g->peer_copy) {
-                std::vector<void *> dst(g->n, nullptr);
-                for (int r = 1; r < g->n; r++) dst[r] = g->ctx[r]->d_spec;
-                rc = g->overlap ? peers_pull_set(c0->cur_set, std::vector<const void *>(g->n, c0->d_spec), dst, count * sizeof(float))
-                                : peers_pull(std::vector<const void *>(g->n, c0->d_spec), dst, count * sizeof(float));
-                if (rc) return rc;
-            }
-            rc = psdr_demod_batch(c0, first_frame_num);
-            if (rc) return rc;
-            for (int r = 1; r < g->n; r++) {
-                rc = psdr_demod_batch_from(g->ctx[r], (const float *)g->ctx[r]->d_spec, g->ctx[r]->spec_stride, nframes, first_frame_num);
-                if (rc) return rc;
-            }
-        } else {  // PSDR_SHARD_BAND
-            const size_t count = F * g->band_stride * 2;  // floats per band
-            std::vector<const float *> send(g->n, nullptr);
-            for (int b = 1; b < g->n; b++) {
-                if (g->banded) {
-                    rc = psdr_band_region(c0, b, &send[b], nullptr, nullptr, nullptr);  // the region of THIS batch (the sets alternate)
-                } else {
-                    rc = psdr_pack_band(c0, nframes, g->band_first[b], g->band_bins[b], (float *)g->sbuf[b].get(), g->band_stride);
-                    send[b] = (const float *)g->sbuf[b].get();
-                }
-                if (rc) return rc;
-            }
-            const bool self_loop = g->comm_on && g->n == 1;  // forced on one device: band 0 goes through RCCL to oneself
-            if (self_loop) {
-                rc = psdr_pack_band(c0, nframes, g->band_first[0], g->band_bins[0], (float *)g->sbuf[0].get(), g->band_stride);
-                if (rc) return rc;
-                send[0] = (const float *)g->sbuf[0].get();
-            }
-            if (g->comm_on) {
-                hipStream_t s0 = g->overlap ? g->xs : g->st[0];  // (overlap: banded regions only - they alternate with the result sets)
-                if (g->overlap) {
-                    rc = exchange_begin();
-                    if (rc) return rc;
-                } else {
-                    HIPCHK(hipSetDevice(g->dev[0]));
-                    HIPCHK(hipEventRecord(g->ev0, g->st[0]));
-                }
-                NCCLCHK(g_rccl.GroupStart());
-                for (int b = self_loop ? 0 : 1; b < g->n; b++) {
-                    HIPCHK(hipSetDevice(g->dev[0]));
-                    NCCLCHK(g_rccl.Send(send[b], count, ncclFloat, b, g->comm[0], s0));
-                    HIPCHK(hipSetDevice(g->dev[b]));
-                    NCCLCHK(g_rccl.Recv(g->rbuf[b], count, ncclFloat, 0, g->comm[b], g->st[b]));
-                }
-                NCCLCHK(g_rccl.GroupEnd());
-                if (g->overlap) {
-                    rc = exchange_end(c0->cur_set, (double)count * sizeof(float));
-                    if (rc) return rc;
-                } else {
-                    HIPCHK(hipSetDevice(g->dev[0]));
-                    HIPCHK(hipEventRecord(g->ev1, g->st[0]));
-                    g->timed = true;
-                    g->link_bytes = (double)count * sizeof(float);
-                }
-            } else if (g->peer_copy) {
-                std::vector<const void *> src(g->n, nullptr);
-                for (int b = 1; b < g->n; b++) src[b] = send[b];
-                rc = g->overlap ? peers_pull_set(c0->cur_set, src, g->rbuf, count * sizeof(float)) : peers_pull(src, g->rbuf, count * sizeof(float));
-                if (rc) return rc;
-            }
-            // the root's own clients read its spectrum through SpecLayout::pos (self_loop: the band buffer that came back)
-            rc = self_loop ? psdr_demod_batch_from_band(c0, (const float *)g->rbuf[0].get(), g->band_stride, g->band_first[0], g->band_bins[0], nframes, first_frame_num)
-                           : psdr_demod_batch(c0, first_frame_num);
-            if (rc) return rc;
-            for (int b = 1; b < g->n; b++) {
-                rc = g->banded ? psdr_demod_batch_from_band_region(g->ctx[b], (const float *)g->rbuf[b].get(), g->band_stride, g->band_first[b], g->band_bins[b], nframes, first_frame_num)
-                               : psdr_demod_batch_from_band(g->ctx[b], (const float *)g->rbuf[b].get(), g->band_stride, g->band_first[b], g->band_bins[b], nframes, first_frame_num);
-                if (rc) return rc;
-            }
-        }
+struct StepArgs {
+    const void *raw_root;
+    uint64_t first_half;
+    int nframes;
+    uint64_t first_frame_num;
+};
+static hipEvent_t op_event(psdr_group *g, const GroupOp &o) {
+    switch (o.ev) {
+    case EV0: return g->ev0;
+    case EV1: return g->ev1;
+    case EV_X: return g->ev_x;
+    case EV_RANK: return g->ev_rank[o.ev_rank];
+    case EV_T0: return g->ev_t0[o.ev_rank];
+    case EV_T1: return g->ev_t1[o.ev_rank];
+    case EV_XDONE: return g->ev_xdone[o.ev_set];
+    case EV_PULL: return g->ev_pull[o.ev_set][o.ev_rank];
+    case EV_NONE: break;
     }
-    rc = psdr_waterfall_batch(c0, first_frame_num);  // waterfall clients stay on the root (they read only its pyramid)
-    if (rc) return rc;
+    return nullptr;
+}
+// raw from the ring: the copies of exactly the halves that are sent
+static int ring_wait(psdr_group *g, uint64_t first_half, int nhalves) {
+    psdr_ctx *c0 = g->ctx[0];
+    if (!c0->ring.d) return fail(PSDR_ERR_STATE, "psdr_ring_create() on the root context first");
+    const int s0 = (int)(first_half % (uint64_t)c0->ring.nhalves);
+    if (s0 + nhalves - 1 > c0->ring.nhalves) return fail(PSDR_ERR_INVALID, "frames cross the end of the ring: split the batch");
+    for (int i = 0; i < nhalves; i++) {
+        const int slot = (s0 + i) % c0->ring.nhalves;
+        if (!c0->ring.ever_written[slot]) return fail(PSDR_ERR_STATE, "half-frame slot %d was never written", slot);
+        HIPCHK(hipStreamWaitEvent(g->st[0], c0->ring.ev_written[slot], 0));
+    }
+    return PSDR_OK;
+}
+// rank r's share of the root's data of this step: where it lies on the root, and where the rank takes it
+static int share_of(psdr_group *g, const StepArgs &a, int r, const void **src, void **dst) {
+    psdr_ctx *c0 = g->ctx[0];
+    if (g->lay.shard == PSDR_SHARD_RAW) {  // (root: in place - its own transform reads the caller's buffer / the ring)
+        *src = a.raw_root ? a.raw_root : c0->ring.d + (size_t)(a.first_half % (uint64_t)c0->ring.nhalves) * g->lay.half_frame_bytes;
+        *dst = r == 0 ? (void *)*src : g->rbuf[r].get();
+    } else if (g->lay.shard == PSDR_SHARD_CLIENTS) {  // straight out of the root's spectrum buffer into every rank's own
+        *src = c0->d_spec;
+        *dst = g->ctx[r]->d_spec;
+    } else {
+        const float *region = (const float *)g->sbuf[r].get();
+        if (g->lay.banded) PSDRCHK(psdr_band_region(c0, r, &region, nullptr, nullptr, nullptr));  // the region of THIS batch (the sets alternate)
+        *src = region;
+        *dst = g->rbuf[r].get();
+    }
+    return PSDR_OK;
+}
+static int group_issue(psdr_group *g, const GroupOp &o, const StepArgs &a) {
+    psdr_ctx *c = g->ctx[o.rank];
+    const GroupBands &B = g->lay.band;
+    const float *band = (const float *)g->rbuf[o.rank].get();
+    switch (o.kind) {  // what a context does sets its own device
+    case OP_TRANSFORM:
+        return o.rank ? psdr_process_batch(c, g->rbuf[o.rank], a.nframes) : a.raw_root ? psdr_process_batch(c, a.raw_root, a.nframes) : psdr_process_ring(c, a.first_half, a.nframes);
+    case OP_PACK: return psdr_pack_band(c, a.nframes, B.first[o.band], B.bins[o.band], (float *)g->sbuf[o.band].get(), B.stride);
+    case OP_DEMOD_OWN: return psdr_demod_batch(c, a.first_frame_num);
+    case OP_DEMOD_FROM_SPEC: return psdr_demod_batch_from(c, (const float *)c->d_spec, c->spec_stride, a.nframes, a.first_frame_num);
+    case OP_DEMOD_FROM_BAND: return psdr_demod_batch_from_band(c, band, B.stride, B.first[o.rank], B.bins[o.rank], a.nframes, a.first_frame_num);
+    case OP_DEMOD_FROM_BAND_REGION: return psdr_demod_batch_from_band_region(c, band, B.stride, B.first[o.rank], B.bins[o.rank], a.nframes, a.first_frame_num);
+    case OP_WATERFALL: return psdr_waterfall_batch(c, a.first_frame_num);
+    default: break;
+    }
+    const hipStream_t s = o.xs ? (hipStream_t)g->xs : (hipStream_t)g->st[o.rank];
+    const void *src = nullptr;
+    void *dst = nullptr;
+    HIPCHK(hipSetDevice(g->dev[o.rank]));
+    switch (o.kind) {
+    case OP_WAIT: HIPCHK(hipStreamWaitEvent(s, op_event(g, o), 0)); break;
+    case OP_RECORD: HIPCHK(hipEventRecord(op_event(g, o), s)); break;
+    case OP_RING_WAIT: return ring_wait(g, a.first_half, (int)o.arg);
+    case OP_GROUP_START: NCCLCHK(g_rccl.GroupStart()); break;
+    case OP_GROUP_END: NCCLCHK(g_rccl.GroupEnd()); break;
+    case OP_BCAST_RAW:
+    case OP_BCAST_SPEC:
+        PSDRCHK(share_of(g, a, o.rank, &src, &dst));
+        NCCLCHK(g_rccl.Broadcast(src, dst, o.arg, o.kind == OP_BCAST_RAW ? ncclChar : ncclFloat, 0, g->comm[o.rank], s));
+        break;
+    case OP_SEND_BAND:
+        PSDRCHK(share_of(g, a, o.band, &src, &dst));
+        NCCLCHK(g_rccl.Send(src, o.arg, ncclFloat, o.band, g->comm[0], s));
+        break;
+    case OP_RECV_BAND:
+        PSDRCHK(share_of(g, a, o.rank, &src, &dst));
+        NCCLCHK(g_rccl.Recv(dst, o.arg, ncclFloat, 0, g->comm[o.rank], s));
+        break;
+    case OP_PULL:
+        PSDRCHK(share_of(g, a, o.rank, &src, &dst));
+        HIPCHK(rank_copy(g, o.rank, dst, 0, src, o.arg));
+        break;
+    default: break;
+    }
+    return PSDR_OK;
+}
+// One step is its plan (groupplan.h), issued in order.  The state moves as far as operations were issued: a failed step
+// leaves the events it has recorded pending, and nothing it has not.
+static int group_step(psdr_group *g, const StepArgs &a) {
+    psdr_ctx *c0 = g->ctx[0];
+    if (a.nframes < 1 || a.nframes > c0->max_batch) return fail(PSDR_ERR_INVALID, "nframes %d outside [1, max_batch=%d]", a.nframes, c0->max_batch);
+    g->state.cur_set = c0->cur_set;
+    const GroupStepPlan p = group_step_plan(g->lay, g->state, !a.raw_root, a.nframes);
+    g->stats = STATS_NONE;
+    g->link_bytes = 0;
+    for (int i = 0; i < p.n; i++) {
+        const GroupOp &o = p.op[i];
+        const int rc = group_issue(g, o, a);
+        if (rc) return rc;
+        group_commit(g->state, o.commit, p.set);
+        if (o.commit & GC_TIMED) g->stats = p.stats, g->link_bytes = (double)p.link_bytes;
+    }
     g->steps++;
     return PSDR_OK;
 }
 extern "C" int psdr_group_step(psdr_group *g, const void *d_halves_root, int nframes, uint64_t first_frame_num) {
     if (!g || !d_halves_root) return fail(PSDR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(g->mtx);  // (enqueue only: a step never waits for the device)
-    return group_step(g, d_halves_root, 0, nframes, first_frame_num);
+    return group_step(g, StepArgs{d_halves_root, 0, nframes, first_frame_num});
 }
 extern "C" int psdr_group_step_ring(psdr_group *g, uint64_t first_half, int nframes, uint64_t first_frame_num) {
     if (!g) return fail(PSDR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(g->mtx);
-    return group_step(g, nullptr, first_half, nframes, first_frame_num);
+    return group_step(g, StepArgs{nullptr, first_half, nframes, first_frame_num});
 }
 extern "C" int psdr_group_synchronize(psdr_group *g) {
     if (!g) return fail(PSDR_ERR_INVALID, "null argument");
@@ -687,7 +519,7 @@ extern "C" int psdr_group_link_stats(psdr_group *g, double *bytes_per_link, doub
     if (bytes_per_link) *bytes_per_link = g->link_bytes;
     if (exchange_ms) {
         *exchange_ms = 0;
-        if (g->timed && g->peer_copy) {  // the slowest peer's own copy
+        if (g->stats == STATS_T01) {  // the slowest peer's own copy
             for (int r = 1; r < g->n; r++) {
                 HIPCHK(hipSetDevice(g->dev[r]));
                 HIPCHK(hipEventSynchronize(g->ev_t1[r]));
@@ -695,7 +527,7 @@ extern "C" int psdr_group_link_stats(psdr_group *g, double *bytes_per_link, doub
                 HIPCHK(hipEventElapsedTime(&ms, g->ev_t0[r], g->ev_t1[r]));
                 *exchange_ms = std::max(*exchange_ms, (double)ms);
             }
-        } else if (g->timed) {
+        } else if (g->stats == STATS_EV01) {
             HIPCHK(hipSetDevice(g->dev[0]));
             HIPCHK(hipEventSynchronize(g->ev1));
             float ms = 0;

@@ -297,14 +297,62 @@ def test_multi_device_group_matches_a_plain_context(shard, N, is_real, n, ndev):
     assert links[-1][0] > 0 and links[-1][1] > 0
 
 
+@pytest.mark.parametrize("how,devices", [("peer_copy", [0, 0]), ("rccl_forced", [0])])
+@pytest.mark.parametrize("shard", ["clients", "raw", "band"])
+def test_link_stats_are_the_bytes_of_one_link(shard, how, devices):
+    """psdr_group_link_stats after a step: (F + 1) half-frames for raw, F frames of the spectrum one spec_stride apart for clients,
+    F frames of one band one band stride apart for band - 8 bytes a bin - and an exchange that took time"""
+    from phantomsdr_amd import Group
+    from phantomsdr_amd.distributed import band_bounds
+    N, n, F, R = 1 << 16, 248, 4, 1 << 16
+    raw = quantize_raw(synth_stream((F + 1) * (N // 2), False, seed=7, fft_size=N), "s16", False)
+    g = Group(devices, shard, N, False, levels_for(R), force_comm=how == "rccl_forced", peer_copy=how == "peer_copy", additional_size=n,
+              audio_fft_size=n, input_format="s16", max_batch=F, max_clients=8, max_waterfall_clients=1)
+    try:
+        root = g.root
+        d = root.dev_alloc(raw.nbytes)
+        root.h2d(d, raw)
+        for mode, l, m, r in _clients(N, R, n, 8):
+            g.client_add(l, m, r, mode)
+        g.step(d, F, 0)
+        g.fetch()
+        link, ms = g.link_stats()
+        p0, p1, nb = C.c_void_p(), C.c_void_p(), C.c_size_t()
+        assert root.lib.psdr_spectrum_device_ptr(root.h, 0, C.byref(p0), C.byref(nb)) == 0
+        assert root.lib.psdr_spectrum_device_ptr(root.h, 1, C.byref(p1), C.byref(nb)) == 0
+        spec_stride = (p1.value - p0.value) // 8
+        assert spec_stride == nb.value == N
+        band_stride = band_bounds(0, R, len(devices), n)[1]  # (a 2^16-point root packs its bands: the same count on every rank)
+        want = {"raw": (F + 1) * root.half_frame_bytes(), "clients": F * spec_stride * 8, "band": F * band_stride * 8}[shard]
+        assert link == want and ms > 0, (link, want, ms)
+        g.synchronize()
+        root.dev_free(d)
+    finally:
+        g.close()
+
+
 def test_group_argument_errors():
-    from phantomsdr_amd import Group, PsdrError
+    from phantomsdr_amd import Group, PsdrError, _lib
+    from phantomsdr_amd.core import Context
     with pytest.raises(PsdrError) as e:
         Group([0, 0], "clients", 1 << 16, False, 7, audio_fft_size=248, additional_size=248)
     assert e.value.code == -1 and "twice" in str(e.value)
+    assert "device 0 listed twice (RCCL wants one rank per device; PSDR_SHARD_PEER_COPY allows it)" in str(e.value)
     with pytest.raises(PsdrError) as e:  # RCCL forced and no RCCL at all exclude each other
         Group([0], "clients", 1 << 16, False, 7, force_comm=True, peer_copy=True, audio_fft_size=248, additional_size=248)
-    assert e.value.code == -1
+    assert e.value.code == -1 and "PSDR_SHARD_FORCE_COMM (RCCL) and PSDR_SHARD_PEER_COPY (no RCCL) exclude each other" in str(e.value)
+    with pytest.raises(PsdrError) as e:  # three ranks on the one device: band sharding wants a power of two
+        Group([0, 0, 0], "band", 1 << 16, False, 7, peer_copy=True, audio_fft_size=248, additional_size=248)
+    assert e.value.code == -1 and "band sharding: a power-of-two number of devices, not 3" in str(e.value)
+    # (the Python class sizes the list itself and knows the three shardings by name: these two go through the C entry)
+    lib = _lib.load()
+    cfg = Context._config(1 << 16, False, 7, audio_fft_size=248, additional_size=248)
+    for count, shard, text in ((0, 0, "a group has 1..16 devices, not 0"), (17, 0x200, "a group has 1..16 devices, not 17"), (1, 3, "unknown sharding 3"),
+                               (1, 0xFF, "unknown sharding 255")):
+        h = C.c_void_p()
+        with pytest.raises(PsdrError) as e:
+            _lib.check(lib.psdr_group_create(C.byref(cfg), (C.c_int * 17)(), count, shard, C.byref(h)))
+        assert e.value.code == -1 and text in str(e.value) and not h.value
     if _ndev() >= 3:
         with pytest.raises(PsdrError) as e:
             Group([0, 1, 2], "band", 1 << 16, False, 7, audio_fft_size=248, additional_size=248)
