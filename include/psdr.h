@@ -461,6 +461,56 @@ int psdr_read_notches(psdr_ctx *ctx, int id, int first[4], int end[4]);
 int psdr_client_set_squelch(psdr_ctx *ctx, int id, int on, double open_db, double close_db, int attack_frames, int hang_frames);
 int psdr_read_squelch(psdr_ctx *ctx, int id, int nframes, int32_t *open, int *nframes_out);
 int psdr_fetched_squelch(psdr_ctx *ctx, int id, int frame, int32_t *open);
+/* Noise floor: the noise power of a client's window, frame by frame - the reference an S-meter needs for an SNR and a squelch
+ * needs to be set in dB ABOVE THE NOISE (band noise moves by tens of dB over a day and from band to band; an absolute threshold is
+ * wrong an hour later).  Only the device can estimate it: the full-resolution spectrum never leaves it.  Opt-in per client;
+ * nothing changes for a client that does not ask for it.  For a noise-floor client with window [l, r), len = r - l, and
+ * period = max(1, audio_rate / audio_fft_size) frames (the auto-notch detector's period):
+ *   Bin power.  For window bin t of frame f: p = fmaf(re, re, im * im) of the raw spectrum bin l + t - un-notched, as the
+ *     auto-notch detector takes it, indexed as l and r are, on every spectrum layout.
+ *   Sums.  acc[t] += p, per bin, in frame order: the bits do not depend on how the stream is split into batches.
+ *   Evaluation, every `period` frames the client takes part in: k = (len - 1) / 4 (integer division); q = the k-th smallest
+ *     (0-based) of the len sums, ordered as unsigned 32-bit integers on the f32 bit pattern - numeric order for the non-negative
+ *     sums, +Inf above every finite value, NaN above +Inf; the order is total, ties need no rule.  e = q / (float)period, one
+ *     correctly rounded f32 division: the lower-quartile bin power per frame.  e goes into a ring of the last 8 evaluations; the
+ *     sums restart from zero.
+ *   Estimate.  m = +Inf; for each filled ring entry x: m = (x < m) ? x : m; n0 = (m < +Inf) ? m : 0.  A NaN or Inf entry is
+ *     never the minimum; before the first evaluation, and when all 8 entries are non-finite, n0 = 0.
+ *   Record.  W_f = n0 * (float)len, one f32 product, with n0 as it stands after frame f has been added and any evaluation it
+ *     completes has run: the window's noise power in the units of pwr, so pwr_f / W_f is the SNR.  Any split of the same
+ *     frames into batches gives the same W bits.
+ *   What n0 is not: the mean noise power.  The quartile and the minimum over the ring (4 s) bias it BELOW the mean; for
+ *     Gaussian noise the factor depends on `period`.  Thresholds and SNRs are relative to this number, not to the mean (the
+ *     blanker's threshold is relative to its own reference level in the same way).
+ *   State per client slot: the sums (audio_fft_size floats), the ring, its fill and position, the frame counter and the
+ *     previous [l, r).  Everything starts from zero when the feature is switched ON for the client (also while paused) and
+ *     whenever [l, r) differs from the client's previous batch.  A mode change, a change of audio_mid alone or a change of
+ *     notches does NOT reset it.  A paused client's state stands still.  len <= 0: nothing is added, W_f = 0.
+ *   Every client kind: USB, LSB, AM, FM, SAM, IQ, tuned, sideband SAM.  Audio rows, IQ rows, pwr, NaN flags, carrier records
+ *     and every piece of demodulation state are bit for bit those of the same client without the feature.
+ * psdr_client_set_noise_floor: any thread; in force from the client's next batch.  PSDR_ERR_INVALID for an unknown id, then
+ *   PSDR_ERR_STATE if the context's audio_rate is not positive, then PSDR_ERR_STATE for on = 0 while the client's squelch
+ *   reference is PSDR_SQ_NOISE; nothing changed in each case.  The device state (4 * audio_fft_size + 8 * max_batch + 176 bytes
+ *   per client slot) is allocated with the context's first on = 1, all or none: PSDR_ERR_NOMEM and the setting unchanged if
+ *   that fails.  A context that never has such a client allocates nothing, a batch without one launches nothing.
+ * psdr_client_set_squelch_reference: what the squelch's thresholds (psdr_client_set_squelch) are relative to.
+ *   PSDR_SQ_ABSOLUTE, the default: the squelch as described above, bit for bit.  PSDR_SQ_NOISE: the two comparisons of frame f
+ *   are P_f >= T_open * W_f and P_f >= T_close * W_f, each threshold one f32 product - open_db and close_db keep their range
+ *   and are dB above W; everything else of the gate (attack, hang, the post chain's view of a closed frame) stays.  W_f = 0 -
+ *   before the first estimate, digital silence - lets any power that is not NaN compare at or above the threshold: the gate is
+ *   open until there is an estimate.  PSDR_ERR_INVALID for an unknown id or value; PSDR_ERR_STATE for PSDR_SQ_NOISE on a client
+ *   whose noise floor is off.  The gate's state is not reset by a change of reference.  Any thread; in force from the next batch.
+ * psdr_read_noise: w[nframes], the W of every frame of the client's last batch, otherwise the contract of psdr_read_squelch.  A
+ *   client whose last batch ran with the feature off reads 0 for every frame.  PSDR_ERR_NO_DATA under psdr_read_audio's rule.
+ * psdr_fetched_noise answers from the fetched set: a fetch (with any of the audio bits) of a batch that had noise-floor clients
+ *   carries their rows as ONE extra copy, the span from the lowest to the highest such slot - the rule of the squelch flags and
+ *   the carrier records.  Clients without the feature read 0.  Errors as psdr_fetched_squelch.
+ * There is no psdr_group_* call: a group's clients have no noise floor. */
+enum { PSDR_SQ_ABSOLUTE = 0, PSDR_SQ_NOISE = 1 };
+int psdr_client_set_noise_floor(psdr_ctx *ctx, int id, int on);
+int psdr_client_set_squelch_reference(psdr_ctx *ctx, int id, int ref);
+int psdr_read_noise(psdr_ctx *ctx, int id, int nframes, float *w, int *nframes_out);
+int psdr_fetched_noise(psdr_ctx *ctx, int id, int frame, float *w);
 /* Audio filter: a cascade of 1 or 2 biquad sections per client on the audio BEHIND the detector - the one place the window
  * [l, r) cannot reach: FM de-emphasis, a cut against a sub-audible tone, hum on an AM carrier, a CW peak filter.
  *   Form.  Each section is in transposed direct form II with two f32 states, from sample to sample:

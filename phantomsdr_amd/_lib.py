@@ -88,6 +88,10 @@ SYMBOLS = [
     ("psdr_client_set_squelch", _i, [_vp, _i, _i, C.c_double, C.c_double, _i, _i]),
     ("psdr_read_squelch", _i, [_vp, _i, _i, _vp, C.POINTER(_i)]),
     ("psdr_fetched_squelch", _i, [_vp, _i, _i, C.POINTER(C.c_int32)]),
+    ("psdr_client_set_noise_floor", _i, [_vp, _i, _i]),
+    ("psdr_client_set_squelch_reference", _i, [_vp, _i, _i]),
+    ("psdr_read_noise", _i, [_vp, _i, _i, _vp, C.POINTER(_i)]),
+    ("psdr_fetched_noise", _i, [_vp, _i, _i, C.POINTER(C.c_float)]),
     ("psdr_client_set_audio_filter", _i, [_vp, _i, _i, _vp]),
     ("psdr_audio_filter_design", _i, [_i, C.c_double, C.c_double, C.c_double, _vp]),
     ("psdr_client_set_agc_profile", _i, [_vp, _i, C.POINTER(psdr_agc_profile)]),

@@ -28,6 +28,8 @@ MODES = {"USB": USB, "LSB": LSB, "AM": AM, "FM": FM, "IQ": IQ, "SAM": SAM}
 # psdr_sam_sideband (include/psdr.h): which sideband a SAM client detects against the recovered carrier
 SAM_BOTH, SAM_UPPER, SAM_LOWER = 0, 1, 2
 SAM_SIDEBANDS = {"both": SAM_BOTH, "upper": SAM_UPPER, "lower": SAM_LOWER}
+SQ_ABSOLUTE, SQ_NOISE = 0, 1  # psdr_client_set_squelch_reference
+SQUELCH_REFERENCES = {"absolute": SQ_ABSOLUTE, "noise": SQ_NOISE}
 # psdr_wf_detector (include/psdr.h): what a sent waterfall row shows of the frames since the previous one
 WF_SAMPLE, WF_PEAK, WF_MEAN = 0, 1, 2
 WF_DETECTORS = {"sample": WF_SAMPLE, "peak": WF_PEAK, "mean": WF_MEAN}
@@ -263,6 +265,13 @@ class Context:
         o = C.c_int32(0)
         check(self.lib.psdr_fetched_squelch(self.h, int(cid), int(frame), C.byref(o)))
         return o.value
+
+    def fetched_noise(self, cid, frame):
+        """the window's noise power W of one frame of the fetched batch (psdr.h: psdr_fetched_noise); 0.0 for a client without
+        the noise floor"""
+        w = C.c_float(0)
+        check(self.lib.psdr_fetched_noise(self.h, int(cid), int(frame), C.byref(w)))
+        return w.value
 
     def fetched_iq_span(self):
         """(first slot, slots, bytes) the fetched batch's IQ copy covered (psdr.h: psdr_fetched_iq_span)"""
@@ -536,6 +545,27 @@ class AudioClient:
         got = C.c_int(0)
         check(self.ctx.lib.psdr_read_squelch(self.ctx.h, self.id, F, _ptr(o), C.byref(got)))
         return o[:got.value]
+
+    def set_noise_floor(self, on):
+        """noise floor of the client's window (psdr_client_set_noise_floor): behind every batch the device estimates the
+        window's noise power W per frame - the lower quartile of the bins' power sums, the minimum over the last 8 evaluations -
+        for an SNR (pwr / W) and for a squelch set in dB above the noise.  Starts from zero when switched on and on a retune."""
+        check(self.ctx.lib.psdr_client_set_noise_floor(self.ctx.h, self.id, 1 if on else 0))
+
+    def set_squelch_reference(self, ref):
+        """what the squelch's thresholds are relative to (psdr_client_set_squelch_reference): "absolute" (default) or "noise" -
+        dB above the noise floor's W, for a client whose noise floor is on.  The gate's state is kept."""
+        ref = SQUELCH_REFERENCES[ref] if isinstance(ref, str) else int(ref)
+        check(self.ctx.lib.psdr_client_set_squelch_reference(self.ctx.h, self.id, ref))
+
+    def read_noise(self, nframes=None):
+        """W[F] (float32), the window's noise power per frame of the last demod batch (psdr.h: psdr_read_noise); all 0 for a
+        client without the noise floor"""
+        F = nframes or self.ctx.last_demod_frames or self.ctx.last_nframes
+        w = np.empty(F, np.float32)
+        got = C.c_int(0)
+        check(self.ctx.lib.psdr_read_noise(self.ctx.h, self.id, F, _ptr(w), C.byref(got)))
+        return w[:got.value]
 
     def set_audio_filter(self, sections):
         """biquad sections behind the detector (psdr_client_set_audio_filter): a list of one or two (b0, b1, b2, a1, a2), for

@@ -27,6 +27,7 @@
 #include "demodplan.h"
 #include "fetchplan.h"
 #include "forwardplan.h"
+#include "noiseplan.h"
 #include "owned.h"
 #include "postplan.h"
 #include "quantize.h"
@@ -361,6 +362,24 @@ struct psdr_ctx {
         explicit operator bool() const { return (bool)tab; }
     } squelch;
     int *d_sq = nullptr;  // view: the last batch's open flags (null until the context's first squelch client)
+    // noise floor (noise.h: k_noise_floor): per slot the power sums acc [slots][n] and the ring's record, the frames' noise power
+    // W [slots][max_batch] in two sets that alternate with out_set like the squelch flags, and the batch's table (noiseplan.h),
+    // a RingTable beside client_ring
+    struct NoiseFloor {
+        DevBuf<float> acc, pool[2];
+        DevBuf<NoiseState> state;
+        RingTable<NoiseEntry> tab;
+        static size_t bytes(const psdr_ctx &c) {
+            const size_t S = c.aslots.size();
+            return S * (((size_t)c.n + 2 * (size_t)c.max_batch) * sizeof(float) + sizeof(NoiseState)) + RingTable<NoiseEntry>::bytes(S);
+        }
+        int alloc(const psdr_ctx &c) {
+            const size_t S = c.aslots.size(), rows = S * (size_t)c.max_batch;
+            return acc.alloc(S * (size_t)c.n, true) || state.alloc(S, true) || pool[0].alloc(rows, true) || pool[1].alloc(rows, true) || tab.alloc(S);
+        }
+        explicit operator bool() const { return (bool)tab; }
+    } noise;
+    float *d_nf = nullptr;  // view: the last batch's W rows (null until the context's first noise-floor client)
     // audio filter (audiofilter.h: k_audio_filter): the sections' carried state [slots][2 sections][2] and the batch's table
     // (audiofilterplan.h), a RingTable beside client_ring
     struct AudioFilter {
@@ -407,6 +426,8 @@ struct psdr_ctx {
         size_t iq_bytes = 0;  // ... and the bytes the fetch's IQ copy moved
         Span<cf> car;         // the carrier records of the slots that were SAM
         Span<int32_t> sq;     // the squelch flags of the slots that ran with squelch
+        Span<float> nf;       // the noise power rows of the slots that ran with the noise floor (noiseplan.h: noise_fetch_span)
+        std::vector<char> nf_on;  // ... per audio slot: the batch ran with it (psdr_fetched_noise: 0 for every frame otherwise)
         Event done;                      // every copy of the fetch on the first copy stream has landed
         Event ev_pcm;                    // ... and the PCM (its own copy stream: it waits for the post chain, up to two steps late)
         bool has_pcm = false;

@@ -3,6 +3,7 @@
 // every frame of a batch.  (The read-back of its results: fetch.hip.)
 #include "ctx.h"
 #include "demod.h"
+#include "noise.h"
 #include "squelch.h"
 #include "audiofilter.h"
 
@@ -207,6 +208,31 @@ extern "C" int psdr_client_set_squelch(psdr_ctx *c, int id, int on, double open_
     squelch_apply(c->aslots[id], on, open_db, close_db, attack_frames, hang_frames);
     return PSDR_OK;
 }
+extern "C" int psdr_client_set_noise_floor(psdr_ctx *c, int id, int on) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mtx);
+    switch (noise_floor_check(c->aslots.data(), c->aslots.size(), id, on, c->cfg.audio_rate)) {
+    case NF_OK: break;
+    case NF_BAD_ID: return fail(PSDR_ERR_INVALID, "no audio client with id %d", id);
+    case NF_NO_RATE: return fail(PSDR_ERR_STATE, "noise floor: the context's audio_rate %d is not positive", c->cfg.audio_rate);
+    case NF_IN_USE: return fail(PSDR_ERR_STATE, "noise floor: client %d's squelch reference is PSDR_SQ_NOISE (psdr_client_set_squelch_reference first)", id);
+    }
+    if (on) PSDRCHK(first_use(c, c->noise, "noise floor sums, records, rows and table (%zu bytes): %s"));
+    noise_floor_apply(c->aslots[id], on);
+    return PSDR_OK;
+}
+extern "C" int psdr_client_set_squelch_reference(psdr_ctx *c, int id, int ref) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mtx);
+    switch (squelch_reference_check(c->aslots.data(), c->aslots.size(), id, ref)) {
+    case SR_OK: break;
+    case SR_BAD_ID: return fail(PSDR_ERR_INVALID, "no audio client with id %d", id);
+    case SR_BAD_VALUE: return fail(PSDR_ERR_INVALID, "unknown squelch reference %d", ref);
+    case SR_NOISE_OFF: return fail(PSDR_ERR_STATE, "PSDR_SQ_NOISE: client %d's noise floor is off (psdr_client_set_noise_floor first)", id);
+    }
+    squelch_reference_apply(c->aslots[id], ref);
+    return PSDR_OK;
+}
 extern "C" int psdr_client_set_audio_filter(psdr_ctx *c, int id, int nsections, const psdr_biquad *sections) {
     if (!c) return fail(PSDR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mtx);
@@ -400,6 +426,7 @@ struct BatchPlan {
     int ring = 0;
     unsigned char *h_ring = nullptr, *d_ring = nullptr;  // the ring slot's two copies
     DemodPlan p;
+    NoisePlan nf;
     SquelchPlan sq;
     AfPlan af;
     AgcPlan ag;
@@ -408,6 +435,7 @@ struct BatchPlan {
     // none yet (they appear under mtx, once, and stay)
     cf *iq_rows = nullptr, *car_rows = nullptr;
     int *sq_rows = nullptr;
+    float *nf_rows = nullptr;
     int4 *notch_tab = nullptr;
 };
 static int batch_plan(psdr_ctx *c, int nframes, const uint32_t *band, BatchPlan &b) {
@@ -421,7 +449,7 @@ static int batch_plan(psdr_ctx *c, int nframes, const uint32_t *band, BatchPlan 
     AudioSlot *slots = c->aslots.data();
     const size_t S = c->aslots.size();
     const int set = c->out_set ^ 1;
-    b.iq_rows = c->iq.pool[set], b.car_rows = c->sam.pool[set], b.sq_rows = c->squelch.pool[set], b.notch_tab = c->notch.tab;
+    b.iq_rows = c->iq.pool[set], b.car_rows = c->sam.pool[set], b.sq_rows = c->squelch.pool[set], b.nf_rows = c->noise.pool[set], b.notch_tab = c->notch.tab;
     f.post_on = c->post_on, f.have_notch_tab = b.notch_tab != nullptr;
     b.p = demod_plan(slots, S, c->demod_seq, f, b.h_ring);
     if (b.p.verdict == DP_BAND_OUTSIDE) {
@@ -430,6 +458,7 @@ static int batch_plan(psdr_ctx *c, int nframes, const uint32_t *band, BatchPlan 
                     band[0] + band[1]);
     }
     b.chain = f.post_on && b.p.nact > 0;
+    if (c->noise) b.nf = noise_plan(slots, S, c->demod_seq, c->noise.tab.host(b.ring));
     if (c->squelch) b.sq = squelch_plan(slots, S, c->demod_seq, b.chain, c->squelch.tab.host(b.ring));
     if (c->af) b.af = audio_filter_plan(slots, S, c->demod_seq, c->af.tab.host(b.ring));
     if (c->agc_prof && b.chain) b.ag = agc_profile_plan(slots, S, c->demod_seq, c->agc_prof.tab.host(b.ring));
@@ -445,11 +474,16 @@ static int batch_begin(psdr_ctx *c, const BatchPlan &b) {
     // ... and the audio filters that start from zero, by the same rule (audio_filter_plan has taken af_fresh off these slots)
     for (size_t slot : b.af.zero)
         HIPCHK(hipMemsetAsync(c->af.state + slot * 2 * PSDR_AUDIO_FILTER_SECTIONS, 0, 2 * PSDR_AUDIO_FILTER_SECTIONS * sizeof(float), c->side));
+    // ... and the noise floors that start from zero: sums and record (noise_plan has taken nf_fresh off these slots)
+    for (size_t slot : b.nf.zero) {
+        HIPCHK(hipMemsetAsync(c->noise.acc + slot * (size_t)c->n, 0, (size_t)c->n * sizeof(float), c->side));
+        HIPCHK(hipMemsetAsync(c->noise.state + slot, 0, sizeof(NoiseState), c->side));
+    }
     // this batch's results go to the OTHER set (the copies of the last batch to the host may still be reading theirs); what
     // read this set two batches ago must have landed
     c->out_set ^= 1;
     c->d_audio = c->audio_pool[c->out_set], c->d_pwr = c->pwr_pool[c->out_set], c->d_nan = c->nan_pool[c->out_set];
-    c->d_iq = b.iq_rows, c->d_car = b.car_rows, c->d_sq = b.sq_rows;
+    c->d_iq = b.iq_rows, c->d_car = b.car_rows, c->d_sq = b.sq_rows, c->d_nf = b.nf_rows;
     PSDRCHK(fetch_guard_wait(c, c->side, c->guard_audio[c->out_set]));
     c->guard_audio[c->out_set] = nullptr;
     // ... and the post chain's moving averages of that batch, which read its audio rows themselves (postchain.h k_pc_ma2
@@ -468,6 +502,7 @@ static int batch_begin(psdr_ctx *c, const BatchPlan &b) {
     for (size_t off : p.ft_zero) HIPCHK(hipMemsetAsync(c->ft.tail + off, 0, tail_bytes, c->side));
     for (size_t off : p.sb_zero) HIPCHK(hipMemsetAsync(c->sb.tail + off, 0, tail_bytes, c->side));
     if (b.sq.any()) HIPCHK(c->squelch.tab.upload(b.ring, (size_t)(b.sq.nsq + b.sq.ncopy), c->side));
+    if (b.nf.any()) HIPCHK(c->noise.tab.upload(b.ring, (size_t)b.nf.n, c->side));
     if (b.af.any()) HIPCHK(c->af.tab.upload(b.ring, (size_t)b.af.n, c->side));
     return PSDR_OK;
 }
@@ -605,6 +640,17 @@ static int launch_detector(psdr_ctx *c, const BatchPlan &b, const DemodArgs &a) 
     HIPCHK(hipGetLastError());
     return PSDR_OK;
 }
+// ... the noise floor: it reads the batch's raw spectrum and writes the frames' noise power, which the squelch behind it reads
+static int launch_noise_floor(psdr_ctx *c, const BatchPlan &b, const DemodArgs &a) {
+    NoiseArgs na{};
+    na.list = c->noise.tab.dev(b.ring), na.nlist = b.nf.n;
+    na.acc = c->noise.acc, na.state = c->noise.state;
+    na.W = c->d_nf;
+    na.period = noise_period(c->cfg.audio_rate, c->n);
+    hipLaunchKernelGGL(k_noise_floor, dim3((unsigned)na.nlist), dim3(64), 0, c->side, a, na);
+    HIPCHK(hipGetLastError());
+    return PSDR_OK;
+}
 // ... the squelch, in front of the chain: it reads pwr and the NaN flags.  *chain_drop: what stays out of the chain's streams
 static int launch_squelch(psdr_ctx *c, const BatchPlan &b, int nframes, const int **chain_drop) {
     SquelchArgs qa{};
@@ -612,6 +658,7 @@ static int launch_squelch(psdr_ctx *c, const BatchPlan &b, int nframes, const in
     qa.pwr = c->d_pwr, qa.nan_flags = c->d_nan;
     qa.open = c->d_sq, qa.drop = b.chain ? c->squelch.drop.get() : nullptr;
     qa.state = c->squelch.state;
+    qa.noise = b.sq.any_ref ? c->d_nf : nullptr;
     qa.nframes = nframes, qa.max_batch = c->max_batch;
     ProfScope ps(c, K_SQUELCH, c->side);
     hipLaunchKernelGGL(k_squelch, dim3((unsigned)qa.nlist), dim3(64), 0, c->side, qa);
@@ -664,6 +711,7 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     PSDRCHK(launch_lists(c, b, a, c->cfg.input_format >= PSDR_FMT_F32 || spec != c->d_spec));
     if (b.p.ndet > 0) PSDRCHK(launch_detector(c, b, a));
     const int *chain_drop = c->d_nan;  // what stays out of the chain's streams: the NaN guard's frames ...
+    if (b.nf.any()) PSDRCHK(launch_noise_floor(c, b, a));
     if (b.sq.any()) PSDRCHK(launch_squelch(c, b, nframes, &chain_drop));
     if (b.af.any()) PSDRCHK(launch_audio_filter(c, b, nframes));
     return batch_end(c, b, a.clients, nframes, chain_drop);

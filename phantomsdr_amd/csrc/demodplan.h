@@ -66,6 +66,13 @@ struct AudioSlot {
     // psdr_client_set_agc_profile (agcplan.h): the profile as the chain's table holds it, on = 0: none.  A setting and nothing
     // else: no state of the chain starts over with it
     AgcEntry agc = {0.f, 0.f, 0.f, HUGE_VALF, 0.f, 0, 0, 0};
+    // psdr_client_set_noise_floor (noiseplan.h): b_nf_on: the last batch ran with it (psdr_read_noise); nf_fresh: switched on
+    // since the slot's last batch; nf_l, nf_r: the window the estimator's state belongs to - it starts from zero when any of the
+    // three says so.  sq_ref: psdr_client_set_squelch_reference, what the squelch's thresholds are relative to
+    int nf_on = 0;
+    bool b_nf_on = false, nf_fresh = false;
+    int nf_l = 0, nf_r = 0;
+    int sq_ref = PSDR_SQ_ABSOLUTE;
 };
 
 // The client parameter ring's slot.  [ClientParams x S][int x S]: the batch's list and, for the post chain, the list index of

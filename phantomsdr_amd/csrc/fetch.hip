@@ -73,6 +73,13 @@ extern "C" int psdr_fetch_begin(psdr_ctx *c, unsigned what) {
             w.l = sl.b_l, w.r = sl.b_r, w.mid = sl.b_mid, w.mode = sl.b_mode;
             w.sq = fetch_in_span(what, fs.slots[i], SPAN_SQ);
         }
+        // the noise power rows travel as the squelch flags do, with any of the audio bits: one span, planned beside fetch_plan
+        fs.nf_on.assign(f.S, 0);
+        fs.nf.at = FetchSpan{};
+        if (want_audio && c->noise) {
+            noise_fetch_span(c->aslots.data(), f.S, c->demod_seq, &fs.nf.at.lo, &fs.nf.at.n);
+            for (size_t i = 0; i < f.S; i++) fs.nf_on[i] = c->aslots[i].active && c->aslots[i].last_seq == c->demod_seq && c->aslots[i].b_nf_on;
+        }
         fs.wfm.assign(c->wslots.begin(), c->wslots.end());
     }
     // 3. the copies
@@ -87,6 +94,7 @@ extern "C" int psdr_fetch_begin(psdr_ctx *c, unsigned what) {
     PSDRCHK(grow(fs.iq.buf, fs.iq.cap, (size_t)p.span[SPAN_IQ].n, f.mb * f.h));
     PSDRCHK(grow(fs.car.buf, fs.car.cap, (size_t)p.span[SPAN_CAR].n, f.mb));
     PSDRCHK(grow(fs.sq.buf, fs.sq.cap, (size_t)p.span[SPAN_SQ].n, f.mb));
+    PSDRCHK(grow(fs.nf.buf, fs.nf.cap, (size_t)fs.nf.at.n, f.mb));
     PSDRCHK(grow(fs.wf, fs.wf_cap, p.wf_bytes, 1));
     fs.iq.at = p.span[SPAN_IQ], fs.car.at = p.span[SPAN_CAR], fs.sq.at = p.span[SPAN_SQ];
     fs.iq_bytes = p.iq_bytes;
@@ -115,7 +123,16 @@ extern "C" int psdr_fetch_begin(psdr_ctx *c, unsigned what) {
     };
     HIPCHK(hipEventRecord(c->ev_fetch_src, c->side));
     HIPCHK(hipStreamWaitEvent(st[0], c->ev_fetch_src, 0));
-    for (int i = 0; i < p.n0; i++) PSDRCHK(enqueue(p.copy[i]));
+    for (int i = 0; i < p.n0; i++) {
+        if (p.copy[i].after == FE_AUDIO && fs.nf.at.n > 0) {  // in front of the last of the audio copies: ev_audio guards the W rows' pool too
+            const FetchCopy k = fetch_rows(f, FB_PWR, (size_t)fs.nf.at.lo, (size_t)fs.nf.at.n, 1, sizeof(float));
+            if (k.pitched)
+                HIPCHK(hipMemcpy2DAsync(fs.nf.buf.get(), k.pitch, c->d_nf + k.src_off, k.pitch, k.width, k.rows, hipMemcpyDeviceToHost, st[0]));
+            else
+                HIPCHK(hipMemcpyAsync(fs.nf.buf.get(), c->d_nf + k.src_off, k.rows * k.pitch, hipMemcpyDeviceToHost, st[0]));
+        }
+        PSDRCHK(enqueue(p.copy[i]));
+    }
     HIPCHK(hipEventRecord(fs.done, st[0]));
     fs.has_pcm = false;
     if (p.has_pcm) {
@@ -254,6 +271,16 @@ extern "C" int psdr_fetched_squelch(psdr_ctx *c, int id, int frame, int32_t *ope
     *open = have ? fs->sq.buf[span_row(fs->sq.at, id, (size_t)c->max_batch, frame)] : 1;
     return PSDR_OK;
 }
+extern "C" int psdr_fetched_noise(psdr_ctx *c, int id, int frame, float *w) {
+    if (!c || !w) return fail(PSDR_ERR_INVALID, "null argument");
+    const FetchSet *fs = nullptr;
+    PSDRCHK(fetched_begin(c, id, "audio (PSDR_FETCH_AUDIO / _PCM / _IQ)", 0, false, ROWS_ANY, &fs));
+    PSDRCHK(fetched_frame(fs, frame));
+    // (a slot that ran with the noise floor lies inside the span by construction; any other reads 0)
+    const bool have = (size_t)id < fs->nf_on.size() && fs->nf_on[id] && fs->nf.at.holds(id);
+    *w = have ? fs->nf.buf[span_row(fs->nf.at, id, (size_t)c->max_batch, frame)] : 0.f;
+    return PSDR_OK;
+}
 extern "C" int psdr_fetched_iq_span(psdr_ctx *c, int *first_slot, int *nslots, size_t *bytes) {
     if (!c) return fail(PSDR_ERR_INVALID, "null argument");
     const FetchSet *fs = nullptr;
@@ -379,6 +406,20 @@ extern "C" int psdr_read_squelch(psdr_ctx *c, int id, int nframes, int32_t *open
     HIPCHK(hipSetDevice(c->device));
     PSDRCHK(drain(c));
     HIPCHK(hipMemcpy(open, c->d_sq + fetch_row(id, (size_t)c->max_batch, 0), F * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return PSDR_OK;
+}
+extern "C" int psdr_read_noise(psdr_ctx *c, int id, int nframes, float *w, int *nframes_out) {
+    if (!c || !w) return fail(PSDR_ERR_INVALID, "null argument");
+    size_t F = 0;
+    bool on = false;
+    PSDRCHK(read_begin(c, id, false, nframes, nframes_out, ROWS_ANY, false, &F, [&](const AudioSlot &s) { on = s.b_nf_on; }));
+    if (!on) {  // the batch ran without the noise floor for this client (the host snapshot answers)
+        std::fill(w, w + F, 0.f);
+        return PSDR_OK;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    PSDRCHK(drain(c));
+    HIPCHK(hipMemcpy(w, c->d_nf + fetch_row(id, (size_t)c->max_batch, 0), F * sizeof(float), hipMemcpyDeviceToHost));
     return PSDR_OK;
 }
 extern "C" int psdr_read_notches(psdr_ctx *c, int id, int first[4], int end[4]) {

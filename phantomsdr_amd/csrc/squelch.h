@@ -1,7 +1,9 @@
 // squelch.h - k_squelch: the per-client level gate behind a batch's last demodulation kernel (include/psdr.h:
 // psdr_client_set_squelch).  It reads what the demodulation kernels left - pwr and the NaN flags - and writes the frames' open
 // flags, the gate's carried state and, for a post-chain batch, the drop flags the chain's k_pc_index reads in place of the NaN
-// flags.  The demodulator is not touched.  The rule itself is squelchplan.h's squelch_step, shared with the host.
+// flags.  The demodulator is not touched.  The rule itself is squelchplan.h's squelch_step, shared with the host.  A
+// noise-referenced client (psdr_client_set_squelch_reference) compares against its thresholds times the frame's noise power W,
+// which k_noise_floor (noise.h) has written in front of this kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,6 +19,7 @@ struct SquelchArgs {
     int *open;             // [slots][max_batch]: 1 = the frame is heard
     int *drop;             // [slots][max_batch]: nan | !open (a copy entry: nan); null: no post chain behind this batch
     SquelchState *state;   // [slots]
+    const float *noise;    // [slots][max_batch]: the batch's noise power rows W (noise.h); null: no client of the batch is noise-referenced
     int nframes, max_batch;
 };
 
@@ -38,12 +41,18 @@ __global__ __launch_bounds__(64) void k_squelch(SquelchArgs a) {
     SquelchState st = a.state[e.slot];
     st.open = __builtin_amdgcn_readfirstlane(st.open);
     st.cnt = __builtin_amdgcn_readfirstlane(st.cnt);
+    const bool relative = __builtin_amdgcn_readfirstlane(e.pad) != 0 && a.noise != nullptr;
     for (int f0 = 0; f0 < a.nframes; f0 += 64) {
         const int f = f0 + lane;
         const bool in = f < a.nframes;
         const float p = in ? a.pwr[row + f] : 0.f;
         const int nf = in ? a.nan_flags[row + f] : 0;
-        const unsigned long long ge_open = __ballot(in && squelch_ge(p, e.t_open)), ge_close = __ballot(in && squelch_ge(p, e.t_close));
+        float t_open = e.t_open, t_close = e.t_close;
+        if (relative) {  // (wave-uniform)
+            const float w = in ? a.noise[row + f] : 0.f;
+            t_open = squelch_relative(e.t_open, w), t_close = squelch_relative(e.t_close, w);
+        }
+        const unsigned long long ge_open = __ballot(in && squelch_ge(p, t_open)), ge_close = __ballot(in && squelch_ge(p, t_close));
         const unsigned long long heard = squelch_walk(st, ge_open, ge_close, min(64, a.nframes - f0), e.attack, e.hang);
         if (in) {
             const int o = (int)((heard >> lane) & 1ull);

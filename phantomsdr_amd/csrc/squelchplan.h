@@ -27,6 +27,8 @@ struct SquelchState {
 };
 // One entry of the batch's squelch table.  attack >= 1: a squelch client.  attack == 0: an audio client WITHOUT squelch in a
 // post-chain batch that has squelch clients - its drop flags are its NaN flags, copied (the chain reads one array).
+// pad: the squelch's reference (include/psdr.h: psdr_client_set_squelch_reference) - 0: the thresholds are absolute, 1:
+// relative to the frame's noise power W_f (noiseplan.h).
 struct SquelchEntry {
     int slot, attack, hang, pad;
     float t_open, t_close;
@@ -56,6 +58,12 @@ PSDR_HOST_DEVICE inline int squelch_step(SquelchState &s, bool ge_open, bool ge_
 }
 PSDR_HOST_DEVICE inline int squelch_frame(SquelchState &s, float p, const SquelchEntry &e) {
     return squelch_step(s, squelch_ge(p, e.t_open), squelch_ge(p, e.t_close), e.attack, e.hang);
+}
+// A noise-referenced entry's threshold of frame f: one f32 product with the frame's noise power.  W_f = 0 (before the first
+// estimate, digital silence): any power that is not NaN is at or above it.
+PSDR_HOST_DEVICE inline float squelch_relative(float t, float w) { return t * w; }
+PSDR_HOST_DEVICE inline int squelch_frame_relative(SquelchState &s, float p, float w, const SquelchEntry &e) {
+    return squelch_step(s, squelch_ge(p, squelch_relative(e.t_open, w)), squelch_ge(p, squelch_relative(e.t_close, w)), e.attack, e.hang);
 }
 
 // A chunk of up to 64 consecutive frames whose comparisons are two masks (bit j: frame j; k_squelch's ballots): the mask of the
@@ -108,6 +116,7 @@ struct SquelchPlan {
     int ncopy = 0;  // table[nsq, nsq + ncopy): the chain's other audio clients (attack == 0), in slot order
     std::vector<size_t> zero;  // slots whose state starts this batch from (closed, 0)
     int lo = 0, n = 0;         // the fetch's span: the n slots from the lowest to the highest squelch slot (n == 0: none)
+    bool any_ref = false;      // a squelch client of the batch is noise-referenced: k_squelch reads the batch's W rows
     bool any() const { return nsq > 0; }  // no squelch client in the batch: nothing is uploaded, zeroed or launched
 };
 
@@ -123,7 +132,9 @@ inline SquelchPlan squelch_plan(AudioSlot *slots, size_t S, uint64_t demod_seq, 
         if (!s.sq_on) continue;
         if (s.sq_fresh) p.zero.push_back(i);
         s.sq_fresh = false;
-        table[p.nsq++] = SquelchEntry{(int)i, s.sq_attack, s.sq_hang, 0, s.sq_t_open, s.sq_t_close};
+        const int ref = s.sq_ref == PSDR_SQ_NOISE ? 1 : 0;  // (PSDR_SQ_NOISE is only ever set on a noise-floor client)
+        p.any_ref |= ref != 0;
+        table[p.nsq++] = SquelchEntry{(int)i, s.sq_attack, s.sq_hang, ref, s.sq_t_open, s.sq_t_close};
         if (hi < 0) p.lo = (int)i;
         hi = (int)i;
     }
