@@ -80,22 +80,6 @@ int reset_kclock(psdr_ctx *c) {
     return PSDR_OK;
 }
 
-std::vector<cf> make_twiddles(size_t count, size_t mult, size_t period, int sign) {
-    // exp(sign * 2 pi i * (j*mult) / period), j < count, generated in double
-    std::vector<cf> w(count);
-    for (size_t j = 0; j < count; j++) {
-        const double a = (double)sign * 2.0 * M_PI * (double)((j * mult) % period) / (double)period;
-        w[j] = make_float2((float)std::cos(a), (float)std::sin(a));
-    }
-    return w;
-}
-
-template <typename T>
-int upload(DevBuf<T> &dst, const std::vector<T> &v) {
-    PSDRCHK(dst.alloc(v.size()));
-    HIPCHK(hipMemcpy(dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return PSDR_OK;
-}
 }  // namespace psdr
 
 namespace {
@@ -115,14 +99,62 @@ size_t fmt_bytes(int fmt) {
     }
 }
 
-int build(psdr_ctx *c) {
-    const psdr_config &g = c->cfg;
+// a table of twiddle_plan (a table it leaves out stays unallocated)
+int upload(DevBuf<cf> &dst, const Twiddles &t) {
+    if (!t.count) return PSDR_OK;
+    const std::vector<Twiddle> w = make_twiddles(t);
+    PSDRCHK(dst.alloc(w.size()));
+    HIPCHK(hipMemcpy(dst, w.data(), w.size() * sizeof(cf), hipMemcpyHostToDevice));
+    return PSDR_OK;
+}
+// a buffer of buffer_plan (one it leaves out stays unallocated)
+template <typename B>
+int alloc(B &dst, const Buf &b) {
+    return b.count ? dst.alloc(b.count) : PSDR_OK;
+}
+template <typename T>
+int alloc(DevBuf<T> &dst, const Buf &b) {
+    return b.count ? dst.alloc(b.count, b.zero) : PSDR_OK;
+}
+
+// the knobs of ctx.h and the device's size, read once
+int read_env(int device, CreateEnv &env) {
+    const char *e = getenv("PSDR_REAL_SPLIT");
+    env.real_split_2048x1024 = e && strcmp(e, "2048x1024") == 0;
+    env.real_3pass = getenv("PSDR_REAL_3PASS") != nullptr;
+    if ((e = getenv("PSDR_SEG_LEN"))) env.seg_len = atoi(e);
+    if ((e = getenv("PSDR_DEMOD_CHAIN"))) env.demod_chain = atoi(e) != 0;
+    if ((e = getenv("PSDR_DEMOD_K"))) env.demod_chain_k = std::max(1, atoi(e));
+    if ((e = psdr_tuning_env("PSDR_LOG2M2"))) env.log2M2 = atoi(e);  // tuning: split M = M1 * M2
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    env.num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    return PSDR_OK;
+}
+
+// the one place the context's create-time fields are assigned
+void adopt(psdr_ctx *c, const psdr_config &cfg, const CreateEnv &env, const ShapePlan &s, const IdftPlan &d) {
+    c->cfg = cfg;
+    c->cfg.skip_num = s.skip_num;
+    c->shape = s;
+    c->device = cfg.device;
+    c->num_cus = env.num_cus;
+    c->N = s.N, c->M = s.M, c->R = s.R, c->is_real = s.is_real;
+    c->log2M1 = s.log2M1, c->log2M2 = s.log2M2, c->M1 = s.M1, c->M2 = s.M2, c->T1 = s.T1, c->T2 = s.T2;
+    c->size_log2 = s.size_log2, c->levels = s.levels, c->max_batch = s.max_batch;
+    c->spec_stride = s.spec_stride, c->q_len = s.q_len, c->q_stride = s.q_stride, c->qt_stride = s.qt_stride, c->p_stride = s.p_stride;
+    c->real_fused = s.real_fused, c->tile_ch = s.tile_ch, c->LT = s.LT, c->tiled_lt = s.tiled_lt;
+    c->min_waterfall_fft = s.min_waterfall_fft, c->log2UB = s.log2UB;
+    c->recmap = s.recmap, c->lay = s.lay, c->seg_facts = s.seg;
+    c->tails = tails_plan(s.tail);  // the pyramid levels above the tile
+    c->n = d.n, c->idft_kind = d.kind, c->nstages = d.nstages;
+    std::copy(d.radix, d.radix + PSDR_MAX_STAGES, c->radix);
+    c->lds_mode = d.lds_mode, c->idft_lds = d.idft_lds, c->idft_threads = d.idft_threads;
+    c->demod_chain = env.demod_chain, c->demod_chain_k = env.demod_chain_k;
+}
+
+int build(psdr_ctx *c, const IdftPlan &idft) {
     HIPCHK(hipSetDevice(c->device));
-    {
-        hipDeviceProp_t prop;
-        HIPCHK(hipGetDeviceProperties(&prop, c->device));
-        c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
     PSDRCHK(c->own_stream.create());
     {
         // the consumers are short kernels that must squeeze in next to the persistent FFT
@@ -141,181 +173,79 @@ int build(psdr_ctx *c) {
     PSDRCHK(c->ev_side_done.create());
     PSDRCHK(c->t0.create_timing());
     PSDRCHK(c->t1.create_timing());
+    for (int s = 0; s < 2; s++) PSDRCHK(c->ev_set_done[s].create());
 
-    // The Hann window (build_hann_window, src/utils/dsp.cpp:6-11) is evaluated inside pass 1
-    // from the twiddle tables; only W_N^1 (odd real samples) is needed on top of them.
-    {
-        const double ang = -2.0 * M_PI / (double)c->N;
-        c->wdelta = make_float2((float)std::cos(ang), (float)std::sin(ang));
-    }
-    // ---- twiddles
-    {
-        int rc = upload(c->d_Wl1, make_twiddles((size_t)c->M1, 1, (size_t)c->M1, -1));
-        if (rc) return rc;
-        if (c->M2 == c->M1) {
-            c->d_Wl2 = c->d_Wl1;
-        } else {
-            rc = upload(c->own_Wl2, make_twiddles((size_t)c->M2, 1, (size_t)c->M2, -1));
-            if (rc) return rc;
-            c->d_Wl2 = c->own_Wl2;
-        }
-        // inter-pass twiddle W_M^e = W_M1^{e >> log2M2} * W_M^{e & (M2-1)}: the first factor
-        // is the pass-1 stage table, the second has M2 entries
-        rc = upload(c->d_TB, make_twiddles((size_t)c->M2, 1, c->M, -1));
-        if (rc) return rc;
-        if (c->is_real) {
-            c->log2UB = std::min(10, ilog2(c->N));
-            const size_t UB = (size_t)1 << c->log2UB;
-            rc = upload(c->d_UA, make_twiddles(c->N / UB + 1, UB, c->N, -1));
-            if (rc) return rc;
-            rc = upload(c->d_UB, make_twiddles(UB, 1, c->N, -1));
-            if (rc) return rc;
-            if (c->real_fused) {
-                rc = upload(c->d_UG, make_twiddles((size_t)(c->M1 / c->T2), (size_t)(c->T2 / 2), c->N, -1));  // W_N^{CP g}: the tile's factor
-                if (rc) return rc;
-            }
-        }
+    // ---- twiddles.  The Hann window (build_hann_window, src/utils/dsp.cpp:6-11) is evaluated inside pass 1 from these
+    // tables; only W_N^1 (odd real samples) is needed on top of them.
+    const Twiddle w1 = make_twiddles(Twiddles{2, 1, c->N, -1})[1];
+    c->wdelta = make_float2(w1.x, w1.y);
+    const TwiddlePlan tw = twiddle_plan(c->shape);
+    PSDRCHK(upload(c->d_Wl1, tw.Wl1));
+    PSDRCHK(upload(c->own_Wl2, tw.Wl2));
+    c->d_Wl2 = tw.Wl2.count ? c->own_Wl2 : c->d_Wl1;
+    PSDRCHK(upload(c->d_TB, tw.TB));
+    PSDRCHK(upload(c->d_UA, tw.UA));
+    PSDRCHK(upload(c->d_UB, tw.UB));
+    PSDRCHK(upload(c->d_UG, tw.UG));
+    PSDRCHK(upload(c->d_Wn, tw.Wn));
+    if (idft.nstages) {
+        std::vector<IdftEntry> tab((size_t)idft.nstages * idft.n);
+        idft_stage_table(idft, tab.data());
+        PSDRCHK(c->d_stage_tab.alloc(tab.size()));
+        HIPCHK(hipMemcpy(c->d_stage_tab, tab.data(), tab.size() * sizeof(int4), hipMemcpyHostToDevice));
     }
 #ifdef PSDR_TRACE_ON
     PSDRCHK(c->d_trace.alloc(4864, true));
 #endif
-    // ---- work buffers
-    const size_t F = (size_t)c->max_batch;
-    for (auto &t : c->d_tickets) PSDRCHK(t.alloc(TICKET_SLOTS * 8, true));
-    PSDRCHK(c->d_Y.alloc(F * c->M));
-    if (c->is_real && !c->real_fused) PSDRCHK(c->d_Z.alloc(F * c->M));
-    if (!c->is_real && c->lay.mode) PSDRCHK(c->d_Z.alloc(c->M + 2));  // k-order staging
-    if (c->real_fused) {
-        // one frame of k-order staging for psdr_read_spectrum / psdr_get_output_buffer
-        PSDRCHK(c->d_Z.alloc(c->M + 2));
-        c->seg_facts.G = c->M1 / c->T2;
-        c->seg_facts.num_cus = c->num_cus;
-        if (const char *e = getenv("PSDR_SEG_LEN")) c->seg_facts.seg_len_env = atoi(e);
-        const size_t cap = c->seg_cap = seg_cap(c->seg_facts, c->max_batch);  // (in hand-off mode any segment may fall back to a seam)
-        for (int st = 0; st < 2; st++) {  // part of the double-buffered result sets: k_real_seam is a consumer
-            PSDRCHK(c->seam_pool[st][0].alloc(cap * (size_t)c->M2 * (size_t)(c->T2 / 2)));  // [segment][M2][couples per tile]
-            PSDRCHK(c->seam_pool[st][1].alloc(cap * (size_t)c->M2));
-        }
-        // flags (inside a launch only), then the fallback marks - ONE ARRAY PER RESULT SET: k_real_seam is a consumer, it may
-        // run after the next batch's second pass has started writing its own marks
-        PSDRCHK(c->d_segflag.alloc(3 * cap, true));
-        {  // the plans of the two batch sizes every caller uses, now rather than in the first batch (a synchronous upload)
-            const psdr_ctx::SegPlan *sp;
-            int rc = seg_plan(c, c->max_batch, &sp);
-            if (!rc && c->max_batch > 1) rc = seg_plan(c, 1, &sp);
-            if (rc) return rc;
-        }
+    // ---- buffers
+    const BufferPlan b = buffer_plan(c->shape, c->cfg);
+    for (auto &t : c->d_tickets) PSDRCHK(alloc(t, b.tickets));
+    PSDRCHK(alloc(c->d_Y, b.Y));
+    PSDRCHK(alloc(c->d_Z, b.Z));
+    c->seg_cap = b.seg_cap;
+    for (int st = 0; st < 2; st++) {  // part of the double-buffered result sets: k_real_seam is a consumer
+        PSDRCHK(alloc(c->seam_pool[st][0], b.seamP));
+        PSDRCHK(alloc(c->seam_pool[st][1], b.seamC));
     }
+    // flags (inside a launch only), then the fallback marks - ONE ARRAY PER RESULT SET: k_real_seam is a consumer, it may
+    // run after the next batch's second pass has started writing its own marks
+    PSDRCHK(alloc(c->d_segflag, b.segflag));
     for (int s = 0; s < 2; s++) {
-        PSDRCHK(c->spec_pool[s].alloc(F * c->spec_stride, true));
-        PSDRCHK(c->q_pool[s].alloc(F * c->q_stride, true));
-        if (c->tiled_lt >= 0) PSDRCHK(c->qt_pool[s].alloc(F * c->qt_stride, true));
-        PSDRCHK(c->pscr_pool[s][0].alloc(F * c->p_stride));
-        PSDRCHK(c->pscr_pool[s][1].alloc(F * c->p_stride));
-        PSDRCHK(c->ev_set_done[s].create());
+        PSDRCHK(alloc(c->spec_pool[s], b.spec));
+        PSDRCHK(alloc(c->q_pool[s], b.q));
+        PSDRCHK(alloc(c->qt_pool[s], b.qt));
+        PSDRCHK(alloc(c->pscr_pool[s][0], b.pscr));
+        PSDRCHK(alloc(c->pscr_pool[s][1], b.pscr));
     }
     select_set(c, 0);
-    c->q_untiled.assign(F, 0);
-    {  // the pyramid levels above the tile
-        TailFacts t;
-        t.R = c->R, t.levels = c->levels, t.LT = c->LT, t.log2M2 = c->log2M2, t.M2 = c->M2, t.real_fused = c->real_fused;
-        t.mapped = c->recmap.mapped, t.l2gpt = c->recmap.l2gpt, t.pair = c->recmap.pair;
-        c->tails = tails_plan(t);
-    }
-    // ---- level-1 staging
-    PSDRCHK(c->d_stage.alloc(c->is_real ? c->N : 2 * c->N));
-    {
-        const size_t nb = c->is_real ? (c->N / 2 + 1) : (c->N + (size_t)g.additional_size);
-        PSDRCHK(c->h_out.alloc(nb));
-        PSDRCHK(c->h_q.alloc(c->q_len));
-    }
+    c->q_untiled.assign((size_t)c->max_batch, 0);
+    PSDRCHK(alloc(c->d_stage, b.stage));  // level-1 staging
+    PSDRCHK(alloc(c->h_out, b.h_out));
+    PSDRCHK(alloc(c->h_q, b.h_q));
     // ---- audio clients
-    c->n = g.audio_fft_size;
-    if (c->n > 0) {
-        const int n = c->n;
-        // factorise n, grouping prime factors into radices <= 16 (fewer barriers)
-        std::vector<int> primes;
-        int m = n;
-        for (int p = 2; (long long)p * p <= m; p++)
-            while (m % p == 0) {
-                primes.push_back(p);
-                m /= p;
-            }
-        if (m > 1) primes.push_back(m);
-        std::vector<int> rad;
-        int cur = 1;
-        for (int p : primes) {
-            if (cur * p <= 16)
-                cur *= p;
-            else {
-                if (cur > 1) rad.push_back(cur);
-                cur = p;
-            }
-        }
-        if (cur > 1) rad.push_back(cur);
-        if ((int)rad.size() > PSDR_MAX_STAGES)
-            return fail(PSDR_ERR_UNSUPPORTED, "audio_fft_size %d has too many factors", n);
-        c->nstages = (int)rad.size();
-        for (int i = 0; i < c->nstages; i++) c->radix[i] = rad[i];
-        const size_t cap = 144 * 1024;
-        if ((size_t)n * 24 <= cap) {
-            c->lds_mode = 0;
-            c->idft_lds = (size_t)n * 24;
-        } else if ((size_t)n * 16 <= cap) {
-            c->lds_mode = 1;
-            c->idft_lds = (size_t)n * 16;
-        } else {
-            c->lds_mode = 2;
-            c->idft_lds = 0;
-        }
-        int rc = upload(c->d_Wn, make_twiddles((size_t)n, 1, (size_t)n, +1));
-        if (rc) return rc;
-        {
-            // stage tables of the generic-radix Stockham: output o = s*(n/R) + i of a stage with
-            // radix R and p = product of the earlier radices reads x[i + q*n/R] and writes
-            // y[j + s*p], j = (i - i%p)*R + i%p, with twiddle exponent q*e1, e1 = (i%p + s*p)*n/(p*R)
-            std::vector<int4> tab((size_t)c->nstages * n);
-            int pp = 1;
-            for (int st = 0; st < c->nstages; st++) {
-                const int R = c->radix[st], tlen = n / R, step = n / (pp * R);
-                for (int o = 0; o < n; o++) {
-                    const int s = o / tlen, i = o - s * tlen, k = i % pp, j = (i - k) * R + k;
-                    const long long e1 = ((long long)(k + s * pp) * step) % n;
-                    tab[(size_t)st * n + o] = make_int4(i, j + s * pp, (int)e1, 0);
-                }
-                pp *= R;
-            }
-            rc = upload(c->d_stage_tab, tab);
-            if (rc) return rc;
-            c->idft_threads = n <= 512 ? 128 : 256;
-            if (const char *e = getenv("PSDR_DEMOD_CHAIN")) c->demod_chain = atoi(e) != 0;
-            if (const char *e = getenv("PSDR_DEMOD_K")) c->demod_chain_k = std::max(1, atoi(e));
-        }
-        const size_t S = (size_t)std::max(1, g.max_clients);
-        c->aslots.resize(S);
-        PSDRCHK(c->d_ypost.alloc(S * F * n));
-        for (int k = 0; k < 2; k++) {
-            PSDRCHK(c->pwr_pool[k].alloc(S * F, true));
-            PSDRCHK(c->audio_pool[k].alloc(S * F * (n / 2), true));
-            PSDRCHK(c->nan_pool[k].alloc(S * F, true));
-        }
-        c->d_pwr = c->pwr_pool[0], c->d_audio = c->audio_pool[0], c->d_nan = c->nan_pool[0];
-        PSDRCHK(c->d_real_prev.alloc(2 * S * (n / 2), true));
-        PSDRCHK(c->d_bb_tail.alloc(2 * S * (n / 2), true));
-        PSDRCHK(c->d_bb_last.alloc(2 * S, true));
-        PSDRCHK(c->d_ssb_mark.alloc(S, true));
-        if (c->lds_mode == 2) PSDRCHK(c->d_gscratch.alloc(S * F * 2 * n));
-        // the batch's client list + the slot -> list index table; behind them the tuned clients' list (ctx.h: ft_ring_off)
-        if (c->client_ring.init(client_ring_bytes(S)))
-            return fail(PSDR_ERR_HIP, "client parameter ring allocation failed");
+    c->aslots.resize(b.slots);
+    PSDRCHK(alloc(c->d_ypost, b.ypost));
+    for (int k = 0; k < 2; k++) {
+        PSDRCHK(alloc(c->pwr_pool[k], b.pwr));
+        PSDRCHK(alloc(c->audio_pool[k], b.audio));
+        PSDRCHK(alloc(c->nan_pool[k], b.nan));
     }
+    c->d_pwr = c->pwr_pool[0], c->d_audio = c->audio_pool[0], c->d_nan = c->nan_pool[0];
+    PSDRCHK(alloc(c->d_real_prev, b.real_prev));
+    PSDRCHK(alloc(c->d_bb_tail, b.bb_tail));
+    PSDRCHK(alloc(c->d_bb_last, b.bb_last));
+    PSDRCHK(alloc(c->d_ssb_mark, b.ssb_mark));
+    PSDRCHK(alloc(c->d_gscratch, b.gscratch));
+    // the batch's client list + the slot -> list index table; behind them the tuned clients' list (ctx.h: ft_ring_off)
+    if (b.client_ring && c->client_ring.init(b.client_ring)) return fail(PSDR_ERR_HIP, "client parameter ring allocation failed");
     // ---- waterfall clients
-    {
-        const size_t W = (size_t)std::max(1, g.max_waterfall_clients);
-        c->wslots.resize(W);
-        c->wf_sent_off = (W * sizeof(WfClient) + 63) & ~(size_t)63;
-        if (c->wf_ring.init(c->wf_sent_off + F * sizeof(int)))
-            return fail(PSDR_ERR_HIP, "waterfall parameter ring allocation failed");
+    c->wslots.resize(b.wslots);
+    c->wf_sent_off = b.wf_sent_off;
+    if (c->wf_ring.init(b.wf_ring)) return fail(PSDR_ERR_HIP, "waterfall parameter ring allocation failed");
+    if (c->real_fused) {  // the plans of the two batch sizes every caller uses, now rather than in the first batch (a synchronous upload)
+        const psdr_ctx::SegPlan *sp;
+        PSDRCHK(seg_plan(c, c->max_batch, &sp));
+        if (c->max_batch > 1) PSDRCHK(seg_plan(c, 1, &sp));
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipDeviceSynchronize());
@@ -335,100 +265,17 @@ extern "C" int psdr_create(const psdr_config *cfg, psdr_ctx **out) {
         return fail(PSDR_ERR_NO_DEVICE, "No HIP devices found");
     if (cfg->device < 0 || cfg->device >= count)
         return fail(PSDR_ERR_INVALID, "device %d out of range (%d devices)", cfg->device, count);
-    const size_t N = cfg->fft_size;
-    if (N == 0 || (N & (N - 1))) return fail(PSDR_ERR_INVALID, "fft_size must be a power of two");
-    const bool is_real = cfg->is_real != 0;
-    const size_t M = is_real ? N / 2 : N;
-    const int m = ilog2(M);
-    if (m < 12 || m > 22)
-        return fail(PSDR_ERR_UNSUPPORTED,
-                    "fft_size %zu unsupported: complex transform length must be 2^12..2^22", N);
-    if (cfg->downsample_levels < 1 || ((M >> (cfg->downsample_levels - 1)) < 1))
-        return fail(PSDR_ERR_INVALID, "downsample_levels %d invalid", cfg->downsample_levels);
-    if (cfg->audio_fft_size < 0 || (cfg->audio_fft_size % 4) != 0)
-        return fail(PSDR_ERR_INVALID, "audio_fft_size must be a non-negative multiple of 4");
-    if (cfg->input_format < PSDR_FMT_U8 || cfg->input_format > PSDR_FMT_F64)
-        return fail(PSDR_ERR_INVALID, "unknown input_format %d", cfg->input_format);
-    if (cfg->max_batch < 1) return fail(PSDR_ERR_INVALID, "max_batch must be >= 1");
-
+    const PlanStatus ok = create_check(*cfg);
+    if (ok.code) return fail(ok.code, "%s", ok.msg.c_str());
+    CreateEnv env;
+    PSDRCHK(read_env(cfg->device, env));
+    const ShapePlan shape = shape_plan(*cfg, env);
+    const IdftPlan idft = idft_plan(cfg->audio_fft_size);
+    if (idft.st.code) return fail(idft.st.code, "%s", idft.st.msg.c_str());
     psdr_ctx *c = new (std::nothrow) psdr_ctx();
     if (!c) return fail(PSDR_ERR_NOMEM, "out of memory");
-    c->cfg = *cfg;
-    c->device = cfg->device;
-    c->N = N;
-    c->M = M;
-    c->is_real = is_real;
-    c->R = M;  // fft_result_size: N (IQ) or N/2 (real), src/spectrumserver.cpp:99-105
-    c->log2M2 = m / 2;
-    // 2^22-point real frames (a 2^21-point packed transform): 1024 x 2048 - the first pass is then the 16-column kernel
-    // of the 2^20 / 2^21-point shapes (128-byte raw rows and Y rows: 5.3 TB/s against the 8-column 2048-point kernel's
-    // 4.1), the second pass walks tiles of FOUR (row, mirror row) couples of 2048-point rows (k_fft_pass2_real<2048, 8, 16>).
-    // PSDR_REAL_SPLIT=2048x1024 selects round 4's split.
-    if (is_real && m == 21) {
-        const char *e = getenv("PSDR_REAL_SPLIT");
-        if (!(e && strcmp(e, "2048x1024") == 0)) c->log2M2 = 11;
-    }
-    if (const char *e = psdr_tuning_env("PSDR_LOG2M2")) c->log2M2 = atoi(e);  // tuning: split M = M1 * M2
-    c->log2M1 = m - c->log2M2;
-    c->M1 = 1 << c->log2M1;
-    c->M2 = 1 << c->log2M2;
-    c->T1 = pick_T(c->M1, c->M2);
-    c->T2 = pick_T(c->M2, c->M1);
-    c->size_log2 = (int)std::lround(std::log2((double)N)) + cfg->brightness_offset;
-    c->levels = cfg->downsample_levels;
-    c->max_batch = cfg->max_batch;
-    c->spec_stride = is_real ? (M + 2) : N;
-    c->q_len = 0;
-    for (int i = 0; i < c->levels; i++) c->q_len += c->R >> i;
-    c->q_stride = (c->q_len + 127) & ~(size_t)127;
-    c->real_fused = is_real && ((c->M2 == 1024 && c->T2 == 16 && (c->M1 == 1024 || c->M1 == 2048)) || (c->M2 == 2048 && c->T2 == 8 && c->M1 == 1024 && c->T1 == 16)) &&
-                    getenv("PSDR_REAL_3PASS") == nullptr;
-    if (c->real_fused) {
-        const int cp = c->T2 / 2;  // (row, mirror row) couples per tile: 8 (octet records, levels 0..3) or 4 (quartets, levels 0..2)
-        c->tile_ch = cp;           // quantize.h, RecMap mode 2
-        c->LT = ilog2((size_t)cp);
-        c->tiled_lt = c->LT;
-        c->recmap.l2tpr = ilog2((size_t)(c->M1 / cp));
-        c->recmap.l2gpt = 0;
-        c->recmap.l2rows = c->log2M2;
-        c->recmap.mapped = 2;
-        c->recmap.pair = cp == 4 ? 1 : 0;  // quartets: a column's two records side by side (quantize.h)
-        c->qt_stride = 2 * c->R;
-        c->lay.mode = 2;
-        c->lay.m1 = c->M1;
-        c->lay.l2m1 = c->log2M1;
-        c->lay.L = c->M2;
-        c->lay.l2L = c->log2M2;
-        c->lay.l2cp = c->LT;
-    } else if (is_real) {
-        c->LT = 8;  // the untangle kernel finishes levels 0..8 (4 bins per lane, 64 lanes)
-        c->tiled_lt = -1;
-    } else {
-        c->tile_ch = (c->T2 >= 16) ? 16 : 8;
-        c->LT = (c->T2 >= 16) ? 4 : 3;
-        c->tiled_lt = c->LT;
-        c->recmap.l2tpr = ilog2((size_t)(c->M1 / c->tile_ch));
-        c->recmap.l2gpt = ilog2((size_t)(c->T2 / c->tile_ch));
-        c->recmap.l2rows = c->log2M2;
-        c->recmap.mapped = 1;
-        c->qt_stride = 2 * c->R;  // R/CH records of 2*CH bytes
-        if (c->M2 == 1024 && c->T2 == 16) {  // k_fft_pass2<1024, 16, true, *> writes tile-major lines
-            c->lay.mode = 1;
-            c->lay.m1 = c->M1;
-            c->lay.l2m1 = c->log2M1;
-            c->lay.L = c->M2;
-            c->lay.l2L = c->log2M2;
-        }
-    }
-    c->p_stride = std::max<size_t>(c->R >> c->LT, 64);
-    if (cfg->skip_num < 1) c->cfg.skip_num = 1;
-    if (cfg->waterfall_size < 0) {
-        delete c;
-        return fail(PSDR_ERR_INVALID, "waterfall_size must be >= 0");
-    }
-    c->min_waterfall_fft = cfg->waterfall_size > 0 ? cfg->waterfall_size : (int)(c->R >> (c->levels - 1));
-
-    int rc = build(c);
+    adopt(c, *cfg, env, shape, idft);
+    int rc = build(c, idft);
     if (rc) {
         delete c;
         return rc;

@@ -2,7 +2,9 @@
 // share.  context.hip (lifetime, Level 1, ingest ring, instrumentation), pass1.hip / pass2.hip (the FFT pass
 // launchers), forward.hip (the frame loop: passes + pyramid tails, spectrum / pyramid read-back, band layout,
 // waterfall), demod.hip (audio clients + demodulation), fetch.hip (the served end: results to host memory), postchain.hip
-// (DC blocker / AGC / int16), wire.hip (packets).  What a context allocates has one owner each (owned.h); what only some
+// (DC blocker / AGC / int16), wire.hip (packets).  What the host decides sits in plain C++17 headers of pure functions, one per
+// decision - createplan.h (what psdr_create accepts, the shape, the buffers, the twiddles, the audio IDFT, the band regions),
+// forwardplan.h, demodplan.h, fetchplan.h, postplan.h and the per-feature plans.  What a context allocates has one owner each (owned.h); what only some
 // contexts need - an optional per-client feature's buffers and tables - sits in one struct per feature that exists whole or
 // not at all (psdr_ctx: `iq` .. `agc_prof`; RingTable: a batch's table beside the client parameter ring).
 #pragma once
@@ -24,6 +26,7 @@
 #include "audiofilterplan.h"
 #include "blankerplan.h"
 #include "butterfly.h"
+#include "createplan.h"
 #include "demodplan.h"
 #include "fetchplan.h"
 #include "forwardplan.h"
@@ -135,17 +138,18 @@ static_assert(sizeof(int4) == NOTCH_ENTRY, "a slot's manual notches are one int4
 // the segment table's entry: forwardplan.h (host-only: it spells uint4 as four unsigneds)
 static_assert(sizeof(uint4) == sizeof(SegEntry), "a segment table entry is one uint4 (Pass2Args::segtab, SeamArgs::segtab)");
 
-inline int ilog2(size_t v) {
-    int l = 0;
-    while (((size_t)1 << l) < v) l++;
-    return l;
-}
+// the audio IDFT's stage table entry and a twiddle: createplan.h (host-only: it spells int4 as four ints, float2 as two floats)
+static_assert(sizeof(int4) == sizeof(IdftEntry), "a stage table entry is one int4 (DemodArgs::stage_tab)");
+static_assert(sizeof(float2) == sizeof(Twiddle), "a twiddle is one float2");
 
 }  // namespace psdr
 using namespace psdr;
 
+// What psdr_create resolves (createplan.h: shape_plan, idft_plan) it copies into the fields below in one place (context.hip:
+// adopt); `lay`, `spec_stride`, `nbands` and `band_H` start from the plan and move with psdr_set_band_layout.
 struct psdr_ctx {
     psdr_config cfg;
+    ShapePlan shape;  // the plan itself, as created (band_plan reads it)
     int device = 0;
     int num_cus = 256;
     size_t N = 0, M = 0, R = 0;
@@ -243,6 +247,7 @@ struct psdr_ctx {
     int nstages = 0;
     int radix[PSDR_MAX_STAGES];
     int lds_mode = 0;
+    IdftKind idft_kind = IDFT_NONE;  // which kernels transform (createplan.h): demod.hip switches on it
     bool demod_chain = true;  // PSDR_DEMOD_CHAIN=0: the two-kernel path (k_demod_idft_fixed + k_demod_ola) for n = 360 / 720 too
     int demod_chain_k = 0;    // PSDR_DEMOD_K: frames per chain (0: 8, 4 when there are few clients)
     size_t idft_lds = 0;
@@ -545,9 +550,6 @@ struct ProfScope {
     }
 };
 
-constexpr unsigned TICKET_SLOTS = 64;
-// tile widths: T = min(16384/L, other dimension)
-inline int pick_T(int L, int other) { return std::min(16384 / L, other); }
 // persistent launch: as many work-groups as the CUs hold (LDS-limited), a multiple of 8 (XCD
 // round-robin of the TileQueue), or one per tile when there are fewer tiles than that
 inline unsigned persistent_grid(psdr_ctx *c, unsigned blocks, size_t lds) {

@@ -352,11 +352,11 @@ static int chain_k(const psdr_ctx *c, int cnt, int nframes) {
 template <class... X>
 static hipError_t launch_chain(psdr_ctx *c, const ChainFamily<X...> &fam, DemodArgs aa, int cnt, int K, unsigned W360, size_t wave_lds, X... extra) {
     if (K <= 0) K = chain_k(c, cnt, aa.nframes);
-    const unsigned W = c->n == 360 ? W360 : 1u;
+    const unsigned W = c->idft_kind == IDFT_FIXED360 ? W360 : 1u;
     const unsigned items = (unsigned)cnt * (unsigned)((aa.nframes + K - 1) / K);
     const size_t lds = (size_t)(1 + W) * c->n * sizeof(cf) + W * wave_lds;
     void *args[] = {&aa, &cnt, &K, &extra...};
-    return hipLaunchKernel((const void *)(c->n == 360 ? fam.k360 : fam.k720), dim3((items + W - 1) / W), dim3(64 * W), args, lds, c->side);
+    return hipLaunchKernel((const void *)(c->idft_kind == IDFT_FIXED360 ? fam.k360 : fam.k720), dim3((items + W - 1) / W), dim3(64 * W), args, lds, c->side);
 }
 // The overlap-add behind the IDFT kernels: one wave per (client, group of PSDR_OLA_FG frames)
 template <class... X>
@@ -507,28 +507,33 @@ static int batch_begin(psdr_ctx *c, const BatchPlan &b) {
     return PSDR_OK;
 }
 
-static bool fixed_plan(const psdr_ctx *c) { return c->n == 360 || c->n == 720; }
+static bool fixed_plan(const psdr_ctx *c) { return c->idft_kind == IDFT_FIXED360 || c->idft_kind == IDFT_FIXED720; }
 // the transform alone, into ypost, of the `cnt` clients listed in aa.clients (every path but the chain kernels')
 static int launch_idft(psdr_ctx *c, const DemodArgs &aa, int cnt) {
-    if (fixed_plan(c)) {
+    const unsigned items = (unsigned)cnt * (unsigned)aa.nframes;
+    switch (c->idft_kind) {
+    case IDFT_FIXED360:
+    case IDFT_FIXED720: {
         // compile-time plans (demod.h): 360 = 8*9*5, 720 = 8*9*10; W items per work-group in
         // the 15 KiB of LDS an FFT pass leaves free on a CU
-        const unsigned items = (unsigned)cnt * (unsigned)aa.nframes;
-        const unsigned W = c->n == 360 ? 4u : 1u;
+        const unsigned W = c->idft_kind == IDFT_FIXED360 ? 4u : 1u;
         const size_t lds = (size_t)(1 + W) * c->n * sizeof(cf);
-        if (c->n == 360)
+        if (c->idft_kind == IDFT_FIXED360)
             hipLaunchKernelGGL((k_demod_idft_fixed<360, 8, 9, 5>), dim3((items + W - 1) / W), dim3(64 * W), lds,
                                c->side, aa, cnt);
         else
             hipLaunchKernelGGL((k_demod_idft_fixed<720, 8, 9, 10>), dim3((items + W - 1) / W), dim3(64 * W), lds,
                                c->side, aa, cnt);
-    } else if (c->n <= 512) {
+        break;
+    }
+    case IDFT_WAVE: {
         // one wave per (client, frame), no work-group barriers (demod.h)
-        const unsigned items = (unsigned)cnt * (unsigned)aa.nframes;
         const size_t lds = (size_t)(2 * PSDR_IDFT_WAVES + 1) * c->n * sizeof(cf);
         hipLaunchKernelGGL(k_demod_idft_wave, dim3((items + PSDR_IDFT_WAVES - 1) / PSDR_IDFT_WAVES),
                            dim3(64 * PSDR_IDFT_WAVES), lds, c->side, aa, cnt);
-    } else {
+        break;
+    }
+    default:
         if (c->idft_lds > 64 * 1024 && c->lds_attr_done.insert((const void *)k_demod_idft).second)
             HIPCHK(hipFuncSetAttribute((const void *)k_demod_idft, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->idft_lds));
         hipLaunchKernelGGL(k_demod_idft, dim3(cnt, aa.nframes), dim3(c->idft_threads), c->idft_lds, c->side,

@@ -392,41 +392,27 @@ extern "C" int psdr_pack_band(psdr_ctx *c, int nframes, uint32_t first_bin, uint
 // ---- band sharding without the pack: pass 2 writes band regions ------------------------------------------------
 extern "C" int psdr_set_band_layout(psdr_ctx *c, int nbands, uint32_t halo_bins) {
     if (!c) return fail(PSDR_ERR_INVALID, "null argument");
-    if (c->is_real || c->lay.mode == 0 || c->lay.mode == 2 || (c->M1 != 1024 && c->M1 != 2048) || c->M2 != 1024)
-        return fail(PSDR_ERR_UNSUPPORTED, "banded spectrum: 2^20- and 2^21-point IQ frames only (use psdr_pack_band)");
-    if (nbands < 1 || nbands > 16 || (nbands & (nbands - 1))) return fail(PSDR_ERR_INVALID, "nbands %d: a power of two <= 16", nbands);
-    if (halo_bins > (uint32_t)c->M) return fail(PSDR_ERR_INVALID, "halo of %u bins", halo_bins);
-    const int H = (int)((halo_bins + (uint32_t)c->M1 - 1) >> c->log2M1), Lb = c->M2 / nbands, Lw = Lb + H;
-    // k_band_halo repeats the first H columns of band b+1 behind band b: they must be band b+1's OWN columns (a halo
-    // longer than a band would reach into band b+2's, which band b+1's region only holds as its own halo - written
-    // by the same launch)
-    if (H > Lb)
-        return fail(PSDR_ERR_INVALID, "halo of %u bins = %d columns of %d bins exceeds a band of %d columns (%d bands)", halo_bins, H,
-                    c->M1, Lb, nbands);
+    const BandPlan b = band_plan(c->shape, c->lay, nbands, halo_bins, c->max_batch);
+    if (b.st.code) return fail(b.st.code, "%s", b.st.msg.c_str());
     HIPCHK(hipSetDevice(c->device));
     {
         int rc = drain(c);
         if (rc) return rc;
     }
     HIPCHK(hipDeviceSynchronize());
-    const size_t F = (size_t)c->max_batch, fs = (size_t)c->M1 * Lw;
     {  // the new buffers first: a failed allocation leaves the context as it was
         DevBuf<cf> fresh[2];
         for (auto &f : fresh)
-            if (f.alloc((size_t)nbands * F * fs, true)) {
+            if (f.alloc((size_t)nbands * b.region, true)) {
                 (void)hipGetLastError();
-                return fail(PSDR_ERR_NOMEM, "banded spectrum: %zu bytes per result set", (size_t)nbands * F * fs * sizeof(cf));
+                return fail(PSDR_ERR_NOMEM, "banded spectrum: %zu bytes per result set", (size_t)nbands * b.region * sizeof(cf));
             }
         for (int s = 0; s < 2; s++) c->spec_pool[s] = std::move(fresh[s]);
     }
     c->nbands = nbands;
-    c->band_H = H;
-    c->spec_stride = fs;  // frame to frame INSIDE a region
-    c->lay.mode = 3;
-    c->lay.l2Lb = ilog2((size_t)Lb);
-    c->lay.Lw = Lw;
-    c->lay.band_stride = F * fs;
-    c->lay.c2_0 = 0;
+    c->band_H = b.H;
+    c->spec_stride = b.frame_stride;
+    c->lay = b.lay;
     c->set_pending[0] = c->set_pending[1] = false;
     select_set(c, c->cur_set);
     c->last_nframes = 0;

@@ -13,6 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import create_plan_table as CT
 import forward_plan_table as T
 from conftest import ROOT
 
@@ -30,7 +31,7 @@ HANDOFF = {(64, 512): True, (128, 512): True, (64, 640): True, (16, 600): True, 
            (128, 7): False, (64, 320): True, (64, 160): False, (128, 160): False, (64, 128): False, (64, 192): False, (64, 96): False, (64, 384): True,
            (64, 257): True}
 
-# ---- tails: the nine shapes psdr_create accepts that differ here, as it resolves them (context.hip) -
+# ---- tails: the nine shapes psdr_create accepts that differ here, as it resolves them (createplan.h: test_shapes_are_what_create_plans) -
 # name: R, LT, log2M2, real_fused, RecMap mapped / l2gpt / pair, groups per output row when the column tail takes them (else 0)
 SHAPES = {
     "iq12": (1 << 12, 4, 6, 0, 1, 2, 0, 0),         # 64 x 64, tiles of 64 rows: four groups per tile
@@ -44,6 +45,22 @@ SHAPES = {
     "real22": (1 << 21, 2, 11, 1, 2, 0, 1, 256),    # fused, 1024 x 2048: quartets side by side
     "real22-2048x1024": (1 << 21, 3, 10, 1, 2, 0, 0, 256),  # fused, PSDR_REAL_SPLIT=2048x1024: octets
 }
+
+
+# the config each row of SHAPES names: (fft_size, is_real, PSDR_REAL_SPLIT=2048x1024)
+SHAPE_CONFIGS = {"iq12": (1 << 12, 0, 0), "iq16": (1 << 16, 0, 0), "iq20": (1 << 20, 0, 0), "iq21": (1 << 21, 0, 0), "iq22": (1 << 22, 0, 0), "real13": (1 << 13, 1, 0),
+                 "real20": (1 << 20, 1, 0), "real21": (1 << 21, 1, 0), "real22": (1 << 22, 1, 0), "real22-2048x1024": (1 << 22, 1, 1)}
+
+
+def test_shapes_are_what_create_plans():
+    """the hand table above against shape_plan (createplan.h) for the config each row names: the facts tails_plan is handed at create"""
+    assert set(SHAPE_CONFIGS) == set(SHAPES)
+    script = "".join("%s\n%s\n" % (CT.env(split=split), CT.cfg(N, r, levels=3)) for N, r, split in SHAPE_CONFIGS.values())
+    out = CT.blocks(CT.run(CT.program(), script))
+    for (name, (R, LT, l2m2, fused, mapped, l2gpt, pair, ng)), b in zip(SHAPES.items(), out):
+        t = b["tail"][0]
+        assert tuple(int(t[k]) for k in ("R", "LT", "l2M2", "M2", "fused", "mapped", "l2gpt", "pair")) == (R, LT, l2m2, 1 << l2m2, fused, mapped, l2gpt, pair), name
+        assert ((R >> LT) >> l2m2 if ng else 0) == ng, name  # groups per output row, where the column tail takes them
 
 
 def tail_levels(R, LT):

@@ -2,7 +2,7 @@
 every plan the inverse DFT has.  Their family files, test_gpu_layout_clients.py and test_gpu_mixed_clients.py run n = 360 / 720
 (the compile-time plans), 256 (k_demod_idft_wave, radices 16 16, h = 128) and 1024 (k_demod_idft in lds_mode 0, radices 16 16 4,
 h = 512): h a multiple of the wave size both times, no run-time radix, no transform outside LDS.  Here the same clients run where
-the code behind psdr_create and launch_idft changes branch:
+the plan behind psdr_create and launch_idft changes branch:
 
     n      plan           reaches
     8      (8)            k_demod_idft_wave, h = 4, carrier cutoff 0
@@ -12,8 +12,8 @@ the code behind psdr_create and launch_idft changes branch:
     6400   (16, 16, 5, 5) k_demod_idft lds_mode 1: buffers in LDS, twiddles from global memory
     10068  (12, 839)      k_demod_idft lds_mode 2: buffers in the per-work-group global scratch, run-time radix
 
-The library exposes no plan, so plan_of() restates context.hip's grouping rule and launch_idft's thresholds and the first test
-pins the table above to it: a changed grouping must not silently move a case onto another branch.
+plan_of() asks the library's own planner (createplan.h idft_plan, built host-only by tests/create_plan_table.py) and the first
+test pins the table above to it: a changed grouping must not silently move a case onto another branch.
 
 Rig: natural-order spectra (the layouts are test_gpu_layout_clients.py's), 2^15-point IQ and 2^16-point real (R = 32768 either
 way: the 10064-bin window fits), s16 input, audio_rate 12000, 5 frames as batches of 3 + 1 + 1 with max_batch = 3.  One context
@@ -47,6 +47,7 @@ import os
 import numpy as np
 import pytest
 
+import create_plan_table as T
 import test_gpu_fine_tune as FT
 import test_gpu_iq_mode as IQM
 import test_gpu_sam_mode as SAM
@@ -88,30 +89,8 @@ def keys_of(n):
 # ---- the plan an audio size gets -------------------------------------------------------------------------------------------
 
 def plan_of(n):
-    """context.hip (psdr_create) and demod.hip (launch_idft), restated: prime factors in ascending order, multiplied into one
-    radix while the product stays <= 16; n <= 512: one wave per item; else one work-group per item with both buffers and the
-    twiddles in LDS while 24 n bytes fit 144 KiB, the buffers alone while 16 n do, else the global scratch"""
-    primes, m, p = [], n, 2
-    while p * p <= m:
-        while m % p == 0:
-            primes.append(p)
-            m //= p
-        p += 1
-    if m > 1:
-        primes.append(m)
-    rad, cur = [], 1
-    for p in primes:
-        if cur * p <= 16:
-            cur *= p
-        else:
-            if cur > 1:
-                rad.append(cur)
-            cur = p
-    if cur > 1:
-        rad.append(cur)
-    cap = 144 * 1024
-    kernel = "fixed" if n in (360, 720) else "wave" if n <= 512 else "lds0" if 24 * n <= cap else "lds1" if 16 * n <= cap else "lds2"
-    return tuple(rad), kernel
+    """(radices, kernel) as the library plans them (createplan.h idft_plan, through tests/create_plan_table.py)"""
+    return T.idft(n)
 
 
 def test_every_size_gets_the_plan_it_is_here_for():
