@@ -554,6 +554,46 @@ int psdr_client_set_audio_filter(psdr_ctx *ctx, int id, int nsections, const psd
 #define PSDR_AF_LOWPASS    2
 #define PSDR_AF_PEAK       3   /* band-pass with 0 dB at f0, bandwidth f0 / q */
 int psdr_audio_filter_design(int kind, double audio_rate, double f0, double q, psdr_biquad *out);    /* no context */
+/* Noise reduction: a short-time spectral gain per client on the audio rows, BEHIND the detector and IN FRONT of the audio filter
+ * and the post chain (a de-emphasis or a CW peak filter sees the cleaned audio).
+ *   Rule.  The client's stream - its rows in frame order, a frame whose NaN flag is set entering as zeros - is cut into blocks of
+ *     256 samples at a hop of 128.  A block is multiplied by the periodic square-root Hann window and transformed (256 points, 129
+ *     bins).  Per bin and block, all in f32: the power P = re^2 + im^2; the smoothed power Ps += 0.5 (P - Ps); the noise track N,
+ *     which follows a falling Ps with N += 0.25 (Ps - N) and a rising one with a time constant of 3 s at the context's audio_rate;
+ *     the raw gain g = 1 - beta N / Ps (g_min where Ps <= 0), kept inside [g_min, 1], g_min = 10^(-depth_db / 20); the gain
+ *     smoothed in time, G += 0.5 (g - G) where g > G and G += 0.25 (g - G) otherwise (the faster rise keeps speech onsets); and
+ *     the applied gain (G[k-1] + 2 G[k] + G[k+1]) / 4 with the edge bins mirrored.  The stream's first block sets N = Ps = P and
+ *     G = g.  A bin whose P is not finite leaves its Ps, N and G alone and is given g_min.  The block goes back through the
+ *     inverse transform and the same window and is overlap-added.  phantomsdr_amd/csrc/nrplan.h is the one definition of all of
+ *     it - windows, butterflies, operation order - for the device and for a host program alike, bit for bit.
+ *     What the noise track cannot tell from noise: a power that stays.  A tone that lasts for seconds - a carrier, a long dash - is
+ *     followed up with the 3 s time constant and reduced like noise (the notches are the tool for a carrier); speech and keying,
+ *     shorter than that, keep their level.
+ *   Delay.  Output sample i of the stream is the overlap-added sample i - 256: a fixed delay of 256 samples, whatever the batch
+ *     lengths; the first 256 samples after a start from zero are +0.0.
+ *   Who.  Every client of a batch whose kind writes audio rows: USB / LSB / AM / FM, SAM, sideband SAM, tuned USB / LSB.  A PSDR_IQ
+ *     client is refused; a client that becomes one keeps its setting, is not listed and its state stands still; a paused
+ *     client's too.
+ *   What.  The rows are rewritten in place: psdr_read_audio, psdr_fetch_begin / psdr_fetch_end with the psdr_fetched_* calls,
+ *     psdr_audio_device_ptr, the audio filter and the post chain read the reduced rows.  pwr, NaN flags, carrier records, squelch
+ *     flags and noise records are untouched, and so is every piece of demodulation state.  The row of a flagged frame is left as
+ *     the demodulator wrote it; output that falls on it is dropped.
+ *   State.  3648 bytes per client slot.  It starts from zero when the call switches noise reduction on (again, too: new numbers
+ *     start over), on a mode change and on a retune - whenever the mode, [l, r) or floor(audio_mid) are not those of the client's
+ *     last batch with noise reduction.  It is carried across batches, pauses and dropped or flagged frames.
+ * psdr_client_set_noise_reduction: any thread; in force from the client's next batch; on = 0 switches it off and ignores the
+ *   numbers.  depth_db inside [0, 40], beta (the over-subtraction factor) inside [0.5, 4].  PSDR_ERR_INVALID, with nothing changed
+ *   and a text of its own each, for an id outside the slots, a slot without a client, (on != 0) a PSDR_IQ client, a value that is not
+ *   finite, depth_db outside its range, beta outside its range - in this order; PSDR_ERR_STATE for a context without a positive
+ *   audio_rate.  The device state and tables are allocated with the context's first such client, all or none: PSDR_ERR_NOMEM and
+ *   the setting unchanged if that fails.
+ * psdr_noise_reduction_preset: needs no context.  PSDR_ERR_INVALID for an unknown kind or a null pointer.
+ * There is no psdr_group_* call: a group's clients have no noise reduction. */
+#define PSDR_NR_LIGHT  1   /* depth  8 dB, beta 1 */
+#define PSDR_NR_NORMAL 2   /* depth 14 dB, beta 1.5 */
+#define PSDR_NR_STRONG 3   /* depth 22 dB, beta 2 */
+int psdr_client_set_noise_reduction(psdr_ctx *ctx, int id, int on, double depth_db, double beta);
+int psdr_noise_reduction_preset(int kind, double *depth_db, double *beta);   /* needs no context */
 /* AGC profile: speed, target, gain cap and manual gain per client.  The context's AGC is the reference's - target 0.2, attack
  * 50 ms, release 300 ms (psdr_set_post_chain) - for every client; a profile replaces these numbers for one client: a fast AGC for
  * CW, a slow one for broadcast, a bound on the gain a quiet channel is pumped up by, or no AGC at all and a fixed gain, which is
@@ -707,6 +747,8 @@ enum { PSDR_OPT_POST_CHAIN_STREAMS = 1, PSDR_OPT_POST_CHAIN_AGC = 2, PSDR_OPT_PO
 #define PSDR_OPT_FINE_TUNE 5
 #define PSDR_OPT_SAM_SIDEBAND 6   /* the value a client gets at psdr_client_add; existing clients keep theirs */
 #define PSDR_OPT_AUTO_NOTCH 7     /* 0 (default) or 1: the auto-notch flag a client gets at psdr_client_add; existing clients keep theirs */
+#define PSDR_OPT_NOISE_REDUCTION 9 /* 0 (default) or a PSDR_NR_* preset: the noise reduction a client gets at psdr_client_add; existing
+                                    * clients keep theirs.  PSDR_ERR_INVALID for any other value, PSDR_ERR_STATE without an audio_rate.  (8 stays free.) */
 int psdr_set_option(psdr_ctx *ctx, int option, int value);
 /* pcm: [frames of the last demod_batch][audio_fft_size/2]; nframes = rows pcm holds (as psdr_read_audio) */
 int psdr_read_pcm(psdr_ctx *ctx, int id, int nframes, int32_t *pcm, int *nframes_out);

@@ -39,6 +39,10 @@ AF_DEEMPHASIS, AF_HIGHPASS, AF_LOWPASS, AF_PEAK = 0, 1, 2, 3
 AF_KINDS = {"deemphasis": AF_DEEMPHASIS, "highpass": AF_HIGHPASS, "lowpass": AF_LOWPASS, "peak": AF_PEAK}
 AUDIO_FILTER_SECTIONS = 2
 
+# PSDR_NR_* (include/psdr.h): the presets of psdr_noise_reduction_preset
+NR_LIGHT, NR_NORMAL, NR_STRONG = 1, 2, 3
+NR_PRESETS = {"light": NR_LIGHT, "normal": NR_NORMAL, "strong": NR_STRONG}
+
 # PSDR_AGC_* (include/psdr.h): the presets of psdr_agc_preset
 AGC_REFERENCE, AGC_FAST, AGC_SLOW = 0, 1, 2
 AGC_PRESETS = {"reference": AGC_REFERENCE, "fast": AGC_FAST, "slow": AGC_SLOW}
@@ -54,6 +58,15 @@ def agc_preset(kind):
     check(_lib.load().psdr_agc_preset(k, C.byref(p)))
     return dict(desired=p.desired, attack_ms=p.attack_ms, release_ms=p.release_ms, max_gain=p.max_gain, manual=bool(p.manual),
                 manual_gain=p.manual_gain)
+
+
+def noise_reduction_preset(kind):
+    """(depth_db, beta) of a noise reduction preset for AudioClient.set_noise_reduction (psdr_noise_reduction_preset; needs no
+    context): "light" (8 dB, 1), "normal" (14 dB, 1.5) or "strong" (22 dB, 2), or an NR_* constant"""
+    d, b = C.c_double(0), C.c_double(0)
+    k = NR_PRESETS[kind] if isinstance(kind, str) else int(kind)
+    check(_lib.load().psdr_noise_reduction_preset(k, C.byref(d), C.byref(b)))
+    return d.value, b.value
 
 
 def design_audio_filter(kind, rate, f0, q=math.sqrt(0.5)):
@@ -196,6 +209,7 @@ class Context:
     OPT_FINE_TUNE = 5  # 0 (default) / 1: the fine-tune flag of audio clients added from now on (AudioClient.set_fine_tune)
     OPT_SAM_SIDEBAND = 6  # SAM_BOTH (default) / SAM_UPPER / SAM_LOWER: the SAM sideband of audio clients added from now on
     OPT_AUTO_NOTCH = 7  # 0 (default) / 1: the auto-notch flag of audio clients added from now on (AudioClient.set_auto_notch)
+    OPT_NOISE_REDUCTION = 9  # 0 (default) / NR_LIGHT / NR_NORMAL / NR_STRONG: the noise reduction of audio clients added from now on
 
     def set_option(self, option, value):
         check(self.lib.psdr_set_option(self.h, int(option), int(value)))
@@ -372,11 +386,11 @@ class Context:
         check(self.lib.psdr_reset_kernel_stats(self.h))
 
     def kernel_stats(self):
-        names = (C.c_char_p * 16)()
-        ms = (C.c_double * 16)()
-        cnt = (C.c_int64 * 16)()
+        names = (C.c_char_p * 32)()
+        ms = (C.c_double * 32)()
+        cnt = (C.c_int64 * 32)()
         n = C.c_int(0)
-        check(self.lib.psdr_get_kernel_stats(self.h, 16, names, ms, cnt, C.byref(n)))
+        check(self.lib.psdr_get_kernel_stats(self.h, 32, names, ms, cnt, C.byref(n)))
         return {names[i].decode(): (ms[i], cnt[i]) for i in range(n.value)}
 
     def timer_start(self):
@@ -576,6 +590,18 @@ class AudioClient:
             raise ValueError("a section is (b0, b1, b2, a1, a2)")
         arr = (_lib.psdr_biquad * max(len(sections), 1))(*[_lib.psdr_biquad(*s) for s in sections])
         check(self.ctx.lib.psdr_client_set_audio_filter(self.ctx.h, self.id, len(sections), C.cast(arr, C.c_void_p) if sections else None))
+
+    def set_noise_reduction(self, kind, depth_db=None, beta=None):
+        """spectral noise reduction on the client's audio rows, in front of the audio filter and the post chain
+        (psdr_client_set_noise_reduction).  `kind`: None - off -, a preset name ("light", "normal", "strong") or an NR_*
+        constant; depth_db (0..40, the deepest attenuation) and beta (0.5..4, the over-subtraction) replace the preset's
+        numbers.  The rows are delayed by 256 samples; the state starts from zero with every call that switches it on."""
+        if kind is None:
+            check(self.ctx.lib.psdr_client_set_noise_reduction(self.ctx.h, self.id, 0, 0.0, 0.0))
+            return
+        d, b = noise_reduction_preset(kind)
+        check(self.ctx.lib.psdr_client_set_noise_reduction(self.ctx.h, self.id, 1, float(d if depth_db is None else depth_db),
+                                                           float(b if beta is None else beta)))
 
     def set_agc_profile(self, profile, **fields):
         """the client's own AGC numbers in the post chain (psdr_client_set_agc_profile).  `profile`: None - back to the context's

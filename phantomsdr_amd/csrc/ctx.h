@@ -31,6 +31,7 @@
 #include "fetchplan.h"
 #include "forwardplan.h"
 #include "noiseplan.h"
+#include "nrplan.h"
 #include "owned.h"
 #include "postplan.h"
 #include "quantize.h"
@@ -69,7 +70,7 @@ inline const char *psdr_tuning_env(const char *name) {
 
 namespace psdr {
 
-enum KernelId { K_PASS1, K_PASS2, K_UNTANGLE, K_TAIL, K_IDFT, K_OLA, K_WFALL, K_POST, K_SEAM, K_BAND, K_WFHOLD, K_WFCARRY, K_SQUELCH, K_NB_SCAN, K_NB_APPLY, K_AUDIO_FILTER, K_COUNT };
+enum KernelId { K_PASS1, K_PASS2, K_UNTANGLE, K_TAIL, K_IDFT, K_OLA, K_WFALL, K_POST, K_SEAM, K_BAND, K_WFHOLD, K_WFCARRY, K_SQUELCH, K_NB_SCAN, K_NB_APPLY, K_AUDIO_FILTER, K_AUDIO_NR, K_COUNT };
 extern const char *kKernelNames[K_COUNT];
 
 struct PendingEvent {
@@ -396,6 +397,23 @@ struct psdr_ctx {
         int alloc(const psdr_ctx &c) { return state.alloc(c.aslots.size() * 2 * PSDR_AUDIO_FILTER_SECTIONS, true) || tab.alloc(c.aslots.size()); }
         explicit operator bool() const { return (bool)tab; }
     } af;
+    // noise reduction (nr.h: k_audio_nr): the clients' carried state [slots], the window and twiddle tables and the batch's table
+    // (nrplan.h), a RingTable beside client_ring
+    struct NoiseReduction {
+        DevBuf<NrState> state;
+        DevBuf<NrTables> plan;
+        RingTable<NrEntry> tab;
+        static size_t bytes(const psdr_ctx &c) { return c.aslots.size() * sizeof(NrState) + sizeof(NrTables) + RingTable<NrEntry>::bytes(c.aslots.size()); }
+        int alloc(const psdr_ctx &c) {
+            if (state.alloc(c.aslots.size(), true) || plan.alloc(1) || tab.alloc(c.aslots.size())) return 1;
+            NrTables t;
+            nr_tables(t);
+            const hipError_t e = hipMemcpy(plan.get(), &t, sizeof(t), hipMemcpyHostToDevice);
+            return e == hipSuccess ? 0 : psdr_fail(PSDR_ERR_HIP, "noise reduction tables: %s", hipGetErrorString(e));
+        }
+        explicit operator bool() const { return (bool)tab; }
+    } nr;
+    int opt_nr = 0;  // PSDR_OPT_NOISE_REDUCTION: the preset (0: none) a client gets at psdr_client_add
     // AGC profiles (agcplan.h; postchain.h: k_pc_want_prof and the PcWithProfiles kernels): the batch's table, a RingTable beside
     // client_ring.  The chain's carried state is the context's own: a profile adds none
     struct AgcProfiles {

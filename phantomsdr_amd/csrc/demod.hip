@@ -6,6 +6,7 @@
 #include "noise.h"
 #include "squelch.h"
 #include "audiofilter.h"
+#include "nr.h"
 
 // The context's first client of an optional feature (ctx.h: the structs behind `iq`): what the feature allocates is built whole
 // and only then moved in, so a failed call leaves the context as it was.  msg: the failure's text, with the bytes and the
@@ -25,6 +26,7 @@ static int first_use(psdr_ctx *c, Feature &have, const char *msg) {
 static int first_tuned(psdr_ctx *c) { return first_use(c, c->ft, "tuned USB / LSB tails (%zu bytes): %s"); }
 static int first_sideband(psdr_ctx *c) { return first_use(c, c->sb, "sideband SAM tails (%zu bytes): %s"); }
 static int first_auto_notch(psdr_ctx *c) { return first_use(c, c->notch, "auto-notch state (%zu bytes): %s"); }
+static int first_noise_reduction(psdr_ctx *c) { return first_use(c, c->nr, "noise reduction state and tables (%zu bytes): %s"); }
 // the detector's state of one slot back to zero: sums, counter, both automatic entries (stream-ordered on `side`)
 static int notch_zero(psdr_ctx *c, size_t slot) {
     HIPCHK(hipMemsetAsync(c->notch.acc + slot * (size_t)c->n, 0, (size_t)c->n * sizeof(float), c->side));
@@ -48,7 +50,13 @@ extern "C" int psdr_client_add(psdr_ctx *c, int *id_out) {
             if (c->opt_fine_tune) PSDRCHK(first_tuned(c));  // (a new client is a USB client: a tuned one under PSDR_OPT_FINE_TUNE)
             if (c->opt_auto_notch) PSDRCHK(first_auto_notch(c));
             if (c->notch) PSDRCHK(notch_zero(c, i));  // (the previous occupant's automatic entries do not outlive it)
+            double nr_depth = 0, nr_beta = 0;
+            if (c->opt_nr) {
+                nr_preset(c->opt_nr, &nr_depth, &nr_beta);
+                PSDRCHK(first_noise_reduction(c));
+            }
             s = AudioSlot();
+            if (c->opt_nr) nr_apply(s, 1, nr_depth, nr_beta);
             s.active = true;
             s.fine = c->opt_fine_tune;
             s.sam_sb = c->opt_sam_sideband;  // (a new client is a USB client: the value waits for PSDR_SAM)
@@ -249,6 +257,36 @@ extern "C" int psdr_client_set_audio_filter(psdr_ctx *c, int id, int nsections, 
     audio_filter_apply(c->aslots[id], nsections, sections);
     return PSDR_OK;
 }
+extern "C" int psdr_client_set_noise_reduction(psdr_ctx *c, int id, int on, double depth_db, double beta) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mtx);
+    switch (nr_check(c->aslots.data(), c->aslots.size(), id, on, depth_db, beta, c->cfg.audio_rate)) {
+    case NR_OK: break;
+    case NR_BAD_ID: return fail(PSDR_ERR_INVALID, "noise reduction: id %d outside 0..%d", id, (int)c->aslots.size() - 1);
+    case NR_INACTIVE: return fail(PSDR_ERR_INVALID, "no audio client with id %d", id);
+    case NR_IQ: return fail(PSDR_ERR_INVALID, "noise reduction: client %d is a PSDR_IQ client, which has no audio rows", id);
+    case NR_NONFINITE: return fail(PSDR_ERR_INVALID, "noise reduction: depth_db or beta is not a finite number");
+    case NR_BAD_DEPTH: return fail(PSDR_ERR_INVALID, "noise reduction: depth_db %g outside [%g, %g]", depth_db, NR_DEPTH_MIN, NR_DEPTH_MAX);
+    case NR_BAD_BETA: return fail(PSDR_ERR_INVALID, "noise reduction: beta %g outside [%g, %g]", beta, NR_BETA_MIN, NR_BETA_MAX);
+    case NR_NO_RATE: return fail(PSDR_ERR_STATE, "noise reduction: the context's audio_rate %d is not positive", c->cfg.audio_rate);
+    }
+    if (on) PSDRCHK(first_noise_reduction(c));
+    nr_apply(c->aslots[id], on, depth_db, beta);
+    return PSDR_OK;
+}
+extern "C" int psdr_noise_reduction_preset(int kind, double *depth_db, double *beta) {
+    if (!depth_db || !beta) return fail(PSDR_ERR_INVALID, "null argument");
+    if (!nr_preset(kind, depth_db, beta)) return fail(PSDR_ERR_INVALID, "noise reduction preset: unknown kind %d", kind);
+    return PSDR_OK;
+}
+// (a debug entry, beside psdr_debug_audio_filter_ptrs: exported for the tests, not part of include/psdr.h)  out[0..1]: the noise
+// reduction's table and state (null until the context's first such client)
+extern "C" int psdr_debug_noise_reduction_ptrs(psdr_ctx *c, const void *out[2]) {
+    if (!c || !out) return fail(PSDR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mtx);
+    out[0] = c->nr.tab.d.get(), out[1] = c->nr.state.get();
+    return PSDR_OK;
+}
 extern "C" int psdr_client_set_agc_profile(psdr_ctx *c, int id, const psdr_agc_profile *p) {
     if (!c) return fail(PSDR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mtx);
@@ -429,6 +467,7 @@ struct BatchPlan {
     NoisePlan nf;
     SquelchPlan sq;
     AfPlan af;
+    NrPlan nr;
     AgcPlan ag;
     bool chain = false;  // the post chain follows: it is on, and somebody is in it
     // of the optional features: the rows of the result set this batch writes and the detector's table - null where the context has
@@ -461,6 +500,7 @@ static int batch_plan(psdr_ctx *c, int nframes, const uint32_t *band, BatchPlan 
     if (c->noise) b.nf = noise_plan(slots, S, c->demod_seq, c->noise.tab.host(b.ring));
     if (c->squelch) b.sq = squelch_plan(slots, S, c->demod_seq, b.chain, c->squelch.tab.host(b.ring));
     if (c->af) b.af = audio_filter_plan(slots, S, c->demod_seq, c->af.tab.host(b.ring));
+    if (c->nr) b.nr = nr_plan(slots, S, c->demod_seq, c->nr.tab.host(b.ring), nr_a_up(c->cfg.audio_rate));
     if (c->agc_prof && b.chain) b.ag = agc_profile_plan(slots, S, c->demod_seq, c->agc_prof.tab.host(b.ring));
     return PSDR_OK;
 }
@@ -474,6 +514,8 @@ static int batch_begin(psdr_ctx *c, const BatchPlan &b) {
     // ... and the audio filters that start from zero, by the same rule (audio_filter_plan has taken af_fresh off these slots)
     for (size_t slot : b.af.zero)
         HIPCHK(hipMemsetAsync(c->af.state + slot * 2 * PSDR_AUDIO_FILTER_SECTIONS, 0, 2 * PSDR_AUDIO_FILTER_SECTIONS * sizeof(float), c->side));
+    // ... and the noise reductions that start from zero (nr_plan has taken nr_fresh off these slots)
+    for (size_t slot : b.nr.zero) HIPCHK(hipMemsetAsync(c->nr.state + slot, 0, sizeof(NrState), c->side));
     // ... and the noise floors that start from zero: sums and record (noise_plan has taken nf_fresh off these slots)
     for (size_t slot : b.nf.zero) {
         HIPCHK(hipMemsetAsync(c->noise.acc + slot * (size_t)c->n, 0, (size_t)c->n * sizeof(float), c->side));
@@ -504,6 +546,7 @@ static int batch_begin(psdr_ctx *c, const BatchPlan &b) {
     if (b.sq.any()) HIPCHK(c->squelch.tab.upload(b.ring, (size_t)(b.sq.nsq + b.sq.ncopy), c->side));
     if (b.nf.any()) HIPCHK(c->noise.tab.upload(b.ring, (size_t)b.nf.n, c->side));
     if (b.af.any()) HIPCHK(c->af.tab.upload(b.ring, (size_t)b.af.n, c->side));
+    if (b.nr.any()) HIPCHK(c->nr.tab.upload(b.ring, (size_t)b.nr.n, c->side));
     return PSDR_OK;
 }
 
@@ -671,6 +714,18 @@ static int launch_squelch(psdr_ctx *c, const BatchPlan &b, int nframes, const in
     if (b.chain) *chain_drop = c->squelch.drop;  // ... the NaN guard's frames and the closed ones
     return PSDR_OK;
 }
+// ... the noise reduction, in front of the audio filter and the chain: it works on the listed clients' rows in place
+static int launch_noise_reduction(psdr_ctx *c, const BatchPlan &b, int nframes) {
+    NrArgs na{};
+    na.list = c->nr.tab.dev(b.ring), na.nlist = b.nr.n;
+    na.tab = c->nr.plan;
+    na.audio = c->d_audio, na.nan_flags = c->d_nan;
+    na.state = c->nr.state;
+    na.nframes = nframes, na.max_batch = c->max_batch, na.h = c->n / 2;
+    ProfScope ps(c, K_AUDIO_NR, c->side);
+    HIPCHK(audio_nr_launch(na, c->side));
+    return PSDR_OK;
+}
 // ... the audio filter, in front of the chain: it filters the listed clients' rows in place (k_squelch reads pwr and flags, not
 // rows: their order does not matter)
 static int launch_audio_filter(psdr_ctx *c, const BatchPlan &b, int nframes) {
@@ -718,6 +773,7 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     const int *chain_drop = c->d_nan;  // what stays out of the chain's streams: the NaN guard's frames ...
     if (b.nf.any()) PSDRCHK(launch_noise_floor(c, b, a));
     if (b.sq.any()) PSDRCHK(launch_squelch(c, b, nframes, &chain_drop));
+    if (b.nr.any()) PSDRCHK(launch_noise_reduction(c, b, nframes));
     if (b.af.any()) PSDRCHK(launch_audio_filter(c, b, nframes));
     return batch_end(c, b, a.clients, nframes, chain_drop);
 }

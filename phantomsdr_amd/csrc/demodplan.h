@@ -73,6 +73,13 @@ struct AudioSlot {
     bool b_nf_on = false, nf_fresh = false;
     int nf_l = 0, nf_r = 0;
     int sq_ref = PSDR_SQ_ABSOLUTE;
+    // psdr_client_set_noise_reduction (nrplan.h): the rounded parameters as the table holds them; nr_fresh: switched on since the
+    // slot's last listed batch; nr_mode, nr_l, nr_r, nr_m: mode, window and floor(audio_mid) the state belongs to - it starts from
+    // zero when any of these says so
+    int nr_on = 0;
+    float nr_g_min = 1.f, nr_beta = 1.f;
+    bool nr_fresh = false;
+    int nr_mode = PSDR_USB, nr_l = 0, nr_r = 0, nr_m = 0;
 };
 
 // The client parameter ring's slot.  [ClientParams x S][int x S]: the batch's list and, for the post chain, the list index of

@@ -211,6 +211,13 @@ extern "C" int psdr_set_option(psdr_ctx *c, int option, int value) {
         c->opt_auto_notch = value;
         return PSDR_OK;
     }
+    case PSDR_OPT_NOISE_REDUCTION: {
+        if (value < 0 || value > PSDR_NR_STRONG) return fail(PSDR_ERR_INVALID, "PSDR_OPT_NOISE_REDUCTION: 0 or a PSDR_NR_* preset, not %d", value);
+        if (value && c->cfg.audio_rate <= 0) return fail(PSDR_ERR_STATE, "noise reduction: the context's audio_rate %d is not positive", c->cfg.audio_rate);
+        std::lock_guard<std::mutex> lk(c->mtx);
+        c->opt_nr = value;
+        return PSDR_OK;
+    }
     default:
         return fail(PSDR_ERR_INVALID, "unknown option %d", option);
     }
