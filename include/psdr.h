@@ -594,6 +594,50 @@ int psdr_audio_filter_design(int kind, double audio_rate, double f0, double q, p
 #define PSDR_NR_STRONG 3   /* depth 22 dB, beta 2 */
 int psdr_client_set_noise_reduction(psdr_ctx *ctx, int id, int on, double depth_db, double beta);
 int psdr_noise_reduction_preset(int kind, double *depth_db, double *beta);   /* needs no context */
+/* Audio blanker: an impulse blanker per client on the audio rows, BEHIND the detector and IN FRONT of the noise reduction, the
+ * audio filter and the post chain.  (psdr_ring_set_blanker is the wideband one on the ingest ring, one threshold for the whole
+ * band; this one sees an impulse that is large inside one listener's window only, and is set per listener.)
+ *   Rule.  The client's stream - its rows in frame order, a frame whose NaN flag is set entering as zeros, zeros before its start -
+ *     is cut into blocks of 256 samples.  A block reads the INPUT samples of itself and of 24 samples on either side, never a
+ *     repaired one, so every block is a function of the input alone.  All in f32: (1) the autocorrelation R[0..10] over the block,
+ *     both factors of a product inside it; (2) Levinson-Durbin for the prediction-error filter a[0..10], a[0] = 1 - a block whose
+ *     R[0] is not finite or not above 1e-20 has no detections; where the recursion's error stops being positive and finite the
+ *     filter of the order before stands, the higher coefficients 0; (3) the residual e[n] = sum a[j] x[n - j] and the zero-phase
+ *     matched filter m[n] = sum a[j] e[n + j]; (4) T = threshold * sqrt(var m), the mean-removed variance of m over the block,
+ *     and no other factor; (5) n ascending, |m[n]| > T (strictly) makes n an impulse centre and the scan goes on at
+ *     n + PL + 1, PL = (width - 1) / 2, at most 16 centres per block; (6) the gap [c - PL, c + PL] of centre c is replaced:
+ *     the forward prediction f[i] = -sum a[j] f[i - j] from the 10 input samples in front of the gap, the backward one b[i] from
+ *     the 10 behind it, gap sample i = (1 - w) f[i] + w b[i] with w = i / (width - 1), the f32 quotient, and 1 - w the f32
+ *     difference; the block's own a also where the gap reaches into a neighbouring block; (7) a sample in more than one gap takes
+ *     the value of the gap with the later centre, every other sample passes through.  phantomsdr_amd/csrc/anbplan.h is the one
+ *     definition of all of it - the order of every sum included - for the device and for a host program alike, bit for bit.
+ *   Delay.  Output sample i of the stream is processed sample i - 536 (two blocks and the 24 samples), whatever the batch lengths;
+ *     the first 536 samples after a start from zero are +0.0.
+ *   Who, What.  As the noise reduction: every client of a batch whose kind writes audio rows, a PSDR_IQ client is refused, a
+ *     client that becomes one or is paused keeps its setting and its state stands still; the rows are rewritten in place and
+ *     every later reader sees them; pwr, NaN flags, carrier, squelch and noise records are untouched; the row of a flagged frame
+ *     is left as the demodulator wrote it.
+ *   State.  6624 bytes per client slot: the last 824 input samples twice over (one half is read while the other is written), the
+ *     position, two totals.  It starts from zero when the call
+ *     switches the blanker on (again, too), on a mode change and on a retune, as the noise reduction's does.
+ * psdr_client_set_audio_blanker: any thread; in force from the client's next batch; on = 0 switches it off and ignores the
+ *   numbers.  threshold inside [2, 12], width odd in 3..15.  PSDR_ERR_INVALID, with nothing changed and a text of its own each, for
+ *   an id outside the slots, a slot without a client, (on != 0) a PSDR_IQ client, a threshold that is not finite, threshold
+ *   outside its range, a width that is not odd in 3..15 - in this order.  The device state is allocated with the context's first
+ *   such client, all or none: PSDR_ERR_NOMEM and the setting unchanged if that fails.
+ * psdr_audio_blanker_preset: needs no context.  PSDR_ERR_INVALID for an unknown kind or a null pointer.
+ * psdr_read_audio_blanker: what an "NB active" indicator reads; synchronises.  impulses: the centres found, samples: the samples
+ *   their gaps hold (a sample in two gaps counts twice; samples before the stream's start do not count), both over the blocks
+ *   whose input is complete - block b once 256 (b + 1) + 24 samples are in - and cumulative since the state last started from
+ *   zero.  PSDR_ERR_NO_DATA where psdr_read_audio has none - the client was not part of the last demodulation batch, or as
+ *   PSDR_IQ - and for a client whose last batch ran without the blanker.  No per-frame record goes through psdr_fetch_*.
+ * There is no psdr_group_* call: a group's clients have no audio blanker. */
+#define PSDR_ANB_LIGHT  1   /* threshold 6,   width 5 */
+#define PSDR_ANB_NORMAL 2   /* threshold 4.5, width 7 */
+#define PSDR_ANB_STRONG 3   /* threshold 3.5, width 11 */
+int psdr_client_set_audio_blanker(psdr_ctx *ctx, int id, int on, double threshold, int width);
+int psdr_audio_blanker_preset(int kind, double *threshold, int *width);      /* needs no context */
+int psdr_read_audio_blanker(psdr_ctx *ctx, int id, uint64_t *impulses, uint64_t *samples); /* cumulative since the state last started; synchronises */
 /* AGC profile: speed, target, gain cap and manual gain per client.  The context's AGC is the reference's - target 0.2, attack
  * 50 ms, release 300 ms (psdr_set_post_chain) - for every client; a profile replaces these numbers for one client: a fast AGC for
  * CW, a slow one for broadcast, a bound on the gain a quiet channel is pumped up by, or no AGC at all and a fixed gain, which is
@@ -749,6 +793,8 @@ enum { PSDR_OPT_POST_CHAIN_STREAMS = 1, PSDR_OPT_POST_CHAIN_AGC = 2, PSDR_OPT_PO
 #define PSDR_OPT_AUTO_NOTCH 7     /* 0 (default) or 1: the auto-notch flag a client gets at psdr_client_add; existing clients keep theirs */
 #define PSDR_OPT_NOISE_REDUCTION 9 /* 0 (default) or a PSDR_NR_* preset: the noise reduction a client gets at psdr_client_add; existing
                                     * clients keep theirs.  PSDR_ERR_INVALID for any other value, PSDR_ERR_STATE without an audio_rate.  (8 stays free.) */
+#define PSDR_OPT_AUDIO_BLANKER 10  /* 0 (default) or a PSDR_ANB_* preset: the audio blanker a client gets at psdr_client_add; existing
+                                    * clients keep theirs.  PSDR_ERR_INVALID for any other value */
 int psdr_set_option(psdr_ctx *ctx, int option, int value);
 /* pcm: [frames of the last demod_batch][audio_fft_size/2]; nframes = rows pcm holds (as psdr_read_audio) */
 int psdr_read_pcm(psdr_ctx *ctx, int id, int nframes, int32_t *pcm, int *nframes_out);

@@ -96,6 +96,9 @@ SYMBOLS = [
     ("psdr_audio_filter_design", _i, [_i, C.c_double, C.c_double, C.c_double, _vp]),
     ("psdr_client_set_noise_reduction", _i, [_vp, _i, _i, C.c_double, C.c_double]),
     ("psdr_noise_reduction_preset", _i, [_i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("psdr_client_set_audio_blanker", _i, [_vp, _i, _i, C.c_double, _i]),
+    ("psdr_audio_blanker_preset", _i, [_i, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    ("psdr_read_audio_blanker", _i, [_vp, _i, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("psdr_client_set_agc_profile", _i, [_vp, _i, C.POINTER(psdr_agc_profile)]),
     ("psdr_agc_preset", _i, [_i, C.POINTER(psdr_agc_profile)]),
     ("psdr_read_agc_gain", _i, [_vp, _i, C.POINTER(C.c_float)]),

@@ -43,6 +43,10 @@ AUDIO_FILTER_SECTIONS = 2
 NR_LIGHT, NR_NORMAL, NR_STRONG = 1, 2, 3
 NR_PRESETS = {"light": NR_LIGHT, "normal": NR_NORMAL, "strong": NR_STRONG}
 
+# PSDR_ANB_* (include/psdr.h): the presets of psdr_audio_blanker_preset
+ANB_LIGHT, ANB_NORMAL, ANB_STRONG = 1, 2, 3
+ANB_PRESETS = {"light": ANB_LIGHT, "normal": ANB_NORMAL, "strong": ANB_STRONG}
+
 # PSDR_AGC_* (include/psdr.h): the presets of psdr_agc_preset
 AGC_REFERENCE, AGC_FAST, AGC_SLOW = 0, 1, 2
 AGC_PRESETS = {"reference": AGC_REFERENCE, "fast": AGC_FAST, "slow": AGC_SLOW}
@@ -67,6 +71,15 @@ def noise_reduction_preset(kind):
     k = NR_PRESETS[kind] if isinstance(kind, str) else int(kind)
     check(_lib.load().psdr_noise_reduction_preset(k, C.byref(d), C.byref(b)))
     return d.value, b.value
+
+
+def audio_blanker_preset(kind):
+    """(threshold, width) of an audio blanker preset for AudioClient.set_audio_blanker (psdr_audio_blanker_preset; needs no
+    context): "light" (6, 5), "normal" (4.5, 7) or "strong" (3.5, 11), or an ANB_* constant"""
+    t, w = C.c_double(0), C.c_int(0)
+    k = ANB_PRESETS[kind] if isinstance(kind, str) else int(kind)
+    check(_lib.load().psdr_audio_blanker_preset(k, C.byref(t), C.byref(w)))
+    return t.value, w.value
 
 
 def design_audio_filter(kind, rate, f0, q=math.sqrt(0.5)):
@@ -210,6 +223,7 @@ class Context:
     OPT_SAM_SIDEBAND = 6  # SAM_BOTH (default) / SAM_UPPER / SAM_LOWER: the SAM sideband of audio clients added from now on
     OPT_AUTO_NOTCH = 7  # 0 (default) / 1: the auto-notch flag of audio clients added from now on (AudioClient.set_auto_notch)
     OPT_NOISE_REDUCTION = 9  # 0 (default) / NR_LIGHT / NR_NORMAL / NR_STRONG: the noise reduction of audio clients added from now on
+    OPT_AUDIO_BLANKER = 10  # 0 (default) / ANB_LIGHT / ANB_NORMAL / ANB_STRONG: the audio blanker of audio clients added from now on
 
     def set_option(self, option, value):
         check(self.lib.psdr_set_option(self.h, int(option), int(value)))
@@ -602,6 +616,26 @@ class AudioClient:
         d, b = noise_reduction_preset(kind)
         check(self.ctx.lib.psdr_client_set_noise_reduction(self.ctx.h, self.id, 1, float(d if depth_db is None else depth_db),
                                                            float(b if beta is None else beta)))
+
+    def set_audio_blanker(self, kind, threshold=None, width=None):
+        """impulse blanker on the client's audio rows, in front of the noise reduction, the audio filter and the post chain
+        (psdr_client_set_audio_blanker).  `kind`: None - off -, a preset name ("light", "normal", "strong") or an ANB_* constant;
+        threshold (2..12, in standard deviations of the whitened block) and width (odd, 3..15, the samples cut out per impulse)
+        replace the preset's numbers.  The rows are delayed by 536 samples; the state starts from zero with every call that
+        switches it on."""
+        if kind is None:
+            check(self.ctx.lib.psdr_client_set_audio_blanker(self.ctx.h, self.id, 0, 0.0, 0))
+            return
+        t, w = audio_blanker_preset(kind)
+        check(self.ctx.lib.psdr_client_set_audio_blanker(self.ctx.h, self.id, 1, float(t if threshold is None else threshold),
+                                                         int(w if width is None else width)))
+
+    def audio_blanker_counts(self):
+        """(impulses, samples): what the client's audio blanker found and rewrote since its state last started from zero
+        (psdr_read_audio_blanker); synchronises"""
+        n, s = C.c_uint64(0), C.c_uint64(0)
+        check(self.ctx.lib.psdr_read_audio_blanker(self.ctx.h, self.id, C.byref(n), C.byref(s)))
+        return n.value, s.value
 
     def set_agc_profile(self, profile, **fields):
         """the client's own AGC numbers in the post chain (psdr_client_set_agc_profile).  `profile`: None - back to the context's

@@ -23,6 +23,7 @@
 
 #include "../../include/psdr.h"
 #include "agcplan.h"
+#include "anbplan.h"
 #include "audiofilterplan.h"
 #include "blankerplan.h"
 #include "butterfly.h"
@@ -70,7 +71,7 @@ inline const char *psdr_tuning_env(const char *name) {
 
 namespace psdr {
 
-enum KernelId { K_PASS1, K_PASS2, K_UNTANGLE, K_TAIL, K_IDFT, K_OLA, K_WFALL, K_POST, K_SEAM, K_BAND, K_WFHOLD, K_WFCARRY, K_SQUELCH, K_NB_SCAN, K_NB_APPLY, K_AUDIO_FILTER, K_AUDIO_NR, K_COUNT };
+enum KernelId { K_PASS1, K_PASS2, K_UNTANGLE, K_TAIL, K_IDFT, K_OLA, K_WFALL, K_POST, K_SEAM, K_BAND, K_WFHOLD, K_WFCARRY, K_SQUELCH, K_NB_SCAN, K_NB_APPLY, K_AUDIO_FILTER, K_AUDIO_NR, K_AUDIO_NB, K_COUNT };
 extern const char *kKernelNames[K_COUNT];
 
 struct PendingEvent {
@@ -414,6 +415,16 @@ struct psdr_ctx {
         explicit operator bool() const { return (bool)tab; }
     } nr;
     int opt_nr = 0;  // PSDR_OPT_NOISE_REDUCTION: the preset (0: none) a client gets at psdr_client_add
+    // audio blanker (anb.h: k_audio_nb): the clients' carried state [slots] and the batch's table (anbplan.h), a RingTable beside
+    // client_ring
+    struct AudioBlanker {
+        DevBuf<AnbState> state;
+        RingTable<AnbEntry> tab;
+        static size_t bytes(const psdr_ctx &c) { return c.aslots.size() * sizeof(AnbState) + RingTable<AnbEntry>::bytes(c.aslots.size()); }
+        int alloc(const psdr_ctx &c) { return state.alloc(c.aslots.size(), true) || tab.alloc(c.aslots.size()); }
+        explicit operator bool() const { return (bool)tab; }
+    } anb;
+    int opt_anb = 0;  // PSDR_OPT_AUDIO_BLANKER: the preset (0: none) a client gets at psdr_client_add
     // AGC profiles (agcplan.h; postchain.h: k_pc_want_prof and the PcWithProfiles kernels): the batch's table, a RingTable beside
     // client_ring.  The chain's carried state is the context's own: a profile adds none
     struct AgcProfiles {

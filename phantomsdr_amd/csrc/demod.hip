@@ -7,6 +7,7 @@
 #include "squelch.h"
 #include "audiofilter.h"
 #include "nr.h"
+#include "anb.h"
 
 // The context's first client of an optional feature (ctx.h: the structs behind `iq`): what the feature allocates is built whole
 // and only then moved in, so a failed call leaves the context as it was.  msg: the failure's text, with the bytes and the
@@ -27,6 +28,7 @@ static int first_tuned(psdr_ctx *c) { return first_use(c, c->ft, "tuned USB / LS
 static int first_sideband(psdr_ctx *c) { return first_use(c, c->sb, "sideband SAM tails (%zu bytes): %s"); }
 static int first_auto_notch(psdr_ctx *c) { return first_use(c, c->notch, "auto-notch state (%zu bytes): %s"); }
 static int first_noise_reduction(psdr_ctx *c) { return first_use(c, c->nr, "noise reduction state and tables (%zu bytes): %s"); }
+static int first_audio_blanker(psdr_ctx *c) { return first_use(c, c->anb, "audio blanker state (%zu bytes): %s"); }
 // the detector's state of one slot back to zero: sums, counter, both automatic entries (stream-ordered on `side`)
 static int notch_zero(psdr_ctx *c, size_t slot) {
     HIPCHK(hipMemsetAsync(c->notch.acc + slot * (size_t)c->n, 0, (size_t)c->n * sizeof(float), c->side));
@@ -55,8 +57,15 @@ extern "C" int psdr_client_add(psdr_ctx *c, int *id_out) {
                 nr_preset(c->opt_nr, &nr_depth, &nr_beta);
                 PSDRCHK(first_noise_reduction(c));
             }
+            double anb_thr = 0;
+            int anb_width = 0;
+            if (c->opt_anb) {
+                anb_preset(c->opt_anb, &anb_thr, &anb_width);
+                PSDRCHK(first_audio_blanker(c));
+            }
             s = AudioSlot();
             if (c->opt_nr) nr_apply(s, 1, nr_depth, nr_beta);
+            if (c->opt_anb) anb_apply(s, 1, anb_thr, anb_width);
             s.active = true;
             s.fine = c->opt_fine_tune;
             s.sam_sb = c->opt_sam_sideband;  // (a new client is a USB client: the value waits for PSDR_SAM)
@@ -287,6 +296,54 @@ extern "C" int psdr_debug_noise_reduction_ptrs(psdr_ctx *c, const void *out[2]) 
     out[0] = c->nr.tab.d.get(), out[1] = c->nr.state.get();
     return PSDR_OK;
 }
+extern "C" int psdr_client_set_audio_blanker(psdr_ctx *c, int id, int on, double threshold, int width) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mtx);
+    switch (anb_check(c->aslots.data(), c->aslots.size(), id, on, threshold, width)) {
+    case ANB_OK: break;
+    case ANB_BAD_ID: return fail(PSDR_ERR_INVALID, "audio blanker: id %d outside 0..%d", id, (int)c->aslots.size() - 1);
+    case ANB_INACTIVE: return fail(PSDR_ERR_INVALID, "no audio client with id %d", id);
+    case ANB_IQ: return fail(PSDR_ERR_INVALID, "audio blanker: client %d is a PSDR_IQ client, which has no audio rows", id);
+    case ANB_NONFINITE: return fail(PSDR_ERR_INVALID, "audio blanker: threshold is not a finite number");
+    case ANB_BAD_THRESHOLD: return fail(PSDR_ERR_INVALID, "audio blanker: threshold %g outside [%g, %g]", threshold, ANB_THR_MIN, ANB_THR_MAX);
+    case ANB_BAD_WIDTH: return fail(PSDR_ERR_INVALID, "audio blanker: width %d is not an odd number in %d..%d", width, ANB_WIDTH_MIN, ANB_WMAX);
+    }
+    if (on) PSDRCHK(first_audio_blanker(c));
+    anb_apply(c->aslots[id], on, threshold, width);
+    return PSDR_OK;
+}
+extern "C" int psdr_audio_blanker_preset(int kind, double *threshold, int *width) {
+    if (!threshold || !width) return fail(PSDR_ERR_INVALID, "null argument");
+    if (!anb_preset(kind, threshold, width)) return fail(PSDR_ERR_INVALID, "audio blanker preset: unknown kind %d", kind);
+    return PSDR_OK;
+}
+// the totals of the client's blanker state; psdr_read_audio's rule for who has something to read
+extern "C" int psdr_read_audio_blanker(psdr_ctx *c, int id, uint64_t *impulses, uint64_t *samples) {
+    if (!c || !impulses || !samples) return fail(PSDR_ERR_INVALID, "null argument");
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);
+        if (id < 0 || (size_t)id >= c->aslots.size()) return fail(PSDR_ERR_INVALID, "audio blanker: id %d outside 0..%d", id, (int)c->aslots.size() - 1);
+        const AudioSlot &s = c->aslots[id];
+        if (!s.active) return fail(PSDR_ERR_INVALID, "no audio client with id %d", id);
+        if (c->demod_seq == 0 || s.last_seq != c->demod_seq) return fail(PSDR_ERR_NO_DATA, "client %d was not part of the last demodulation batch", id);
+        if (s.b_mode == PSDR_IQ) return fail(PSDR_ERR_NO_DATA, "client %d was demodulated as PSDR_IQ in the last batch", id);
+        if (!s.anb_on || s.anb_fresh || !c->anb) return fail(PSDR_ERR_NO_DATA, "client %d had no audio blanker in the last demodulation batch", id);
+    }
+    HIPCHK(hipSetDevice(c->device));
+    PSDRCHK(drain(c));
+    uint64_t v[2] = {0, 0};
+    HIPCHK(hipMemcpy(v, &(c->anb.state + (size_t)id)->impulses, sizeof(v), hipMemcpyDeviceToHost));
+    *impulses = v[0], *samples = v[1];
+    return PSDR_OK;
+}
+// (a debug entry, beside psdr_debug_noise_reduction_ptrs: exported for the tests, not part of include/psdr.h)  out[0..1]: the audio
+// blanker's table and state (null until the context's first such client)
+extern "C" int psdr_debug_audio_blanker_ptrs(psdr_ctx *c, const void *out[2]) {
+    if (!c || !out) return fail(PSDR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mtx);
+    out[0] = c->anb.tab.d.get(), out[1] = c->anb.state.get();
+    return PSDR_OK;
+}
 extern "C" int psdr_client_set_agc_profile(psdr_ctx *c, int id, const psdr_agc_profile *p) {
     if (!c) return fail(PSDR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mtx);
@@ -468,6 +525,7 @@ struct BatchPlan {
     SquelchPlan sq;
     AfPlan af;
     NrPlan nr;
+    AnbPlan anb;
     AgcPlan ag;
     bool chain = false;  // the post chain follows: it is on, and somebody is in it
     // of the optional features: the rows of the result set this batch writes and the detector's table - null where the context has
@@ -501,6 +559,7 @@ static int batch_plan(psdr_ctx *c, int nframes, const uint32_t *band, BatchPlan 
     if (c->squelch) b.sq = squelch_plan(slots, S, c->demod_seq, b.chain, c->squelch.tab.host(b.ring));
     if (c->af) b.af = audio_filter_plan(slots, S, c->demod_seq, c->af.tab.host(b.ring));
     if (c->nr) b.nr = nr_plan(slots, S, c->demod_seq, c->nr.tab.host(b.ring), nr_a_up(c->cfg.audio_rate));
+    if (c->anb) b.anb = anb_plan(slots, S, c->demod_seq, c->anb.tab.host(b.ring));
     if (c->agc_prof && b.chain) b.ag = agc_profile_plan(slots, S, c->demod_seq, c->agc_prof.tab.host(b.ring));
     return PSDR_OK;
 }
@@ -516,6 +575,8 @@ static int batch_begin(psdr_ctx *c, const BatchPlan &b) {
         HIPCHK(hipMemsetAsync(c->af.state + slot * 2 * PSDR_AUDIO_FILTER_SECTIONS, 0, 2 * PSDR_AUDIO_FILTER_SECTIONS * sizeof(float), c->side));
     // ... and the noise reductions that start from zero (nr_plan has taken nr_fresh off these slots)
     for (size_t slot : b.nr.zero) HIPCHK(hipMemsetAsync(c->nr.state + slot, 0, sizeof(NrState), c->side));
+    // ... and the audio blankers (anb_plan has taken anb_fresh off these slots)
+    for (size_t slot : b.anb.zero) HIPCHK(hipMemsetAsync(c->anb.state + slot, 0, sizeof(AnbState), c->side));
     // ... and the noise floors that start from zero: sums and record (noise_plan has taken nf_fresh off these slots)
     for (size_t slot : b.nf.zero) {
         HIPCHK(hipMemsetAsync(c->noise.acc + slot * (size_t)c->n, 0, (size_t)c->n * sizeof(float), c->side));
@@ -547,6 +608,7 @@ static int batch_begin(psdr_ctx *c, const BatchPlan &b) {
     if (b.nf.any()) HIPCHK(c->noise.tab.upload(b.ring, (size_t)b.nf.n, c->side));
     if (b.af.any()) HIPCHK(c->af.tab.upload(b.ring, (size_t)b.af.n, c->side));
     if (b.nr.any()) HIPCHK(c->nr.tab.upload(b.ring, (size_t)b.nr.n, c->side));
+    if (b.anb.any()) HIPCHK(c->anb.tab.upload(b.ring, (size_t)b.anb.n, c->side));
     return PSDR_OK;
 }
 
@@ -714,6 +776,18 @@ static int launch_squelch(psdr_ctx *c, const BatchPlan &b, int nframes, const in
     if (b.chain) *chain_drop = c->squelch.drop;  // ... the NaN guard's frames and the closed ones
     return PSDR_OK;
 }
+// ... the audio blanker, in front of the noise reduction, the audio filter and the chain: it works on the listed clients' rows in
+// place
+static int launch_audio_blanker(psdr_ctx *c, const BatchPlan &b, int nframes) {
+    AnbArgs ba{};
+    ba.list = c->anb.tab.dev(b.ring), ba.nlist = b.anb.n;
+    ba.audio = c->d_audio, ba.nan_flags = c->d_nan;
+    ba.state = c->anb.state;
+    ba.nframes = nframes, ba.max_batch = c->max_batch, ba.h = c->n / 2;
+    ProfScope ps(c, K_AUDIO_NB, c->side);
+    HIPCHK(audio_nb_launch(ba, c->side));
+    return PSDR_OK;
+}
 // ... the noise reduction, in front of the audio filter and the chain: it works on the listed clients' rows in place
 static int launch_noise_reduction(psdr_ctx *c, const BatchPlan &b, int nframes) {
     NrArgs na{};
@@ -773,6 +847,7 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     const int *chain_drop = c->d_nan;  // what stays out of the chain's streams: the NaN guard's frames ...
     if (b.nf.any()) PSDRCHK(launch_noise_floor(c, b, a));
     if (b.sq.any()) PSDRCHK(launch_squelch(c, b, nframes, &chain_drop));
+    if (b.anb.any()) PSDRCHK(launch_audio_blanker(c, b, nframes));
     if (b.nr.any()) PSDRCHK(launch_noise_reduction(c, b, nframes));
     if (b.af.any()) PSDRCHK(launch_audio_filter(c, b, nframes));
     return batch_end(c, b, a.clients, nframes, chain_drop);

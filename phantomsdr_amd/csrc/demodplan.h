@@ -80,6 +80,13 @@ struct AudioSlot {
     float nr_g_min = 1.f, nr_beta = 1.f;
     bool nr_fresh = false;
     int nr_mode = PSDR_USB, nr_l = 0, nr_r = 0, nr_m = 0;
+    // psdr_client_set_audio_blanker (anbplan.h): the parameters as the table holds them; anb_fresh, anb_mode, anb_l, anb_r, anb_m:
+    // as the noise reduction's
+    int anb_on = 0;
+    float anb_threshold = 4.5f;
+    int anb_width = 7;
+    bool anb_fresh = false;
+    int anb_mode = PSDR_USB, anb_l = 0, anb_r = 0, anb_m = 0;
 };
 
 // The client parameter ring's slot.  [ClientParams x S][int x S]: the batch's list and, for the post chain, the list index of

@@ -274,6 +274,7 @@ static int place_client(psdr_ctx *c, int l, double audio_mid, int r, int mode, b
     rc = psdr_client_set_fine_tune(c, *id, 0);
     if (!rc) rc = psdr_client_set_auto_notch(c, *id, 0);
     if (!rc) rc = psdr_client_set_noise_reduction(c, *id, 0, 0.0, 0.0);  // (... nor PSDR_OPT_NOISE_REDUCTION: its state is not migrated)
+    if (!rc) rc = psdr_client_set_audio_blanker(c, *id, 0, 0.0, 0);  // (... nor PSDR_OPT_AUDIO_BLANKER, for the same reason)
     if (!rc) rc = psdr_client_set_audio_demodulation(c, *id, mode);
     if (!rc) rc = psdr_client_set_audio_range(c, *id, l, audio_mid, r);
     if (!rc && paused) rc = psdr_client_set_paused(c, *id, 1);

@@ -218,6 +218,12 @@ extern "C" int psdr_set_option(psdr_ctx *c, int option, int value) {
         c->opt_nr = value;
         return PSDR_OK;
     }
+    case PSDR_OPT_AUDIO_BLANKER: {
+        if (value < 0 || value > PSDR_ANB_STRONG) return fail(PSDR_ERR_INVALID, "PSDR_OPT_AUDIO_BLANKER: 0 or a PSDR_ANB_* preset, not %d", value);
+        std::lock_guard<std::mutex> lk(c->mtx);
+        c->opt_anb = value;
+        return PSDR_OK;
+    }
     default:
         return fail(PSDR_ERR_INVALID, "unknown option %d", option);
     }
