@@ -3,111 +3,17 @@ tests/nb_model.py.  Shapes: the smallest the library accepts - IQ at N = 2^12 (2
 formats, real at N = 2^13 (4096 samples, 16 blocks) in s16 and f32; a ring of 8 halves, max_batch 4, 24 halves of stream, so
 the ring wraps twice and the slot-0 half is blanked through its mirror once per turn.  tests/test_blanker_host.py shows that
 the model blanks every planted impulse of these streams with its full guard and nothing else: both sides cannot be idle."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import nb_model as M
+from nb_rig import Rig, run_blanked, run_plain, same
 
 pytestmark = pytest.mark.gpu
 
 CASES = [(f, False) for f in ("u8", "s8", "u16", "s16", "f32", "f64")] + [("s16", True), ("f32", True)]
 IDS = ["%s-%s" % (f, "real" if r else "iq") for f, r in CASES]
 GUARDS = [0, 7, 255]
-
-
-class Rig:
-    """one context with a ring of NHALVES halves; feed() writes the halves a call needs, then processes"""
-
-    def __init__(self, fmt, is_real):
-        from phantomsdr_amd import Context
-        self.fmt, self.is_real = fmt, is_real
-        self.ctx = Context(M.shape(is_real), is_real, 3, input_format=fmt, max_batch=M.MAX_BATCH, max_clients=1)
-        self.hb = self.ctx.half_frame_bytes()
-        self.ctx.ring_create(M.NHALVES)
-        self.pinned = [self.ctx.pinned_array(self.hb) for _ in range(M.NHALVES)]
-        self.written = -1  # the highest half written so far
-
-    def close(self):
-        self.ctx.close()
-
-    def call(self, halves, first, n):
-        """-> (spectra, pyramids) of the call's frames, as bytes"""
-        for h in range(max(first, self.written + 1), first + n + 1):
-            self.ctx.ring_wait(h)  # (the pinned buffer of the slot is free again)
-            self.ctx.synchronize()
-            self.pinned[h % M.NHALVES][:] = halves[h].view(np.uint8)
-            self.ctx.ring_write_async(h, self.pinned[h % M.NHALVES])
-            self.written = h
-        self.ctx.process_ring(first, n)
-        return ([self.ctx.read_spectrum(f).view(np.uint8).copy() for f in range(n)], [self.ctx.read_quantized(f).copy() for f in range(n)])
-
-    def ring_half(self, h):
-        return self.ctx.ring_read(h, M.DTYPE[self.fmt])
-
-    def mirror(self):
-        ptrs = (C.c_void_p * 6)()
-        assert self.ctx.lib.psdr_debug_blanker_ptrs(self.ctx.h, ptrs) == 0
-        out = np.empty(self.hb, np.uint8)
-        self.ctx.d2h(out, C.c_void_p(ptrs[5]))
-        return out.view(M.DTYPE[self.fmt])
-
-    def blanker_ptrs(self):
-        ptrs = (C.c_void_p * 6)()
-        assert self.ctx.lib.psdr_debug_blanker_ptrs(self.ctx.h, ptrs) == 0
-        return [ptrs[k] for k in range(5)]
-
-
-def same(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
-
-
-def run_blanked(fmt, is_real, guard, calls, db=M.THRESHOLD_DB, planted=True):
-    """the stream through a context with the blanker on, call by call against the model: ring bytes, counts, levels.
-    -> (frames' spectra and pyramids, the model-blanked stream, counts)"""
-    halves, _ = M.fixture(fmt, is_real, guard, planted=planted)
-    model, nb = [h.copy() for h in halves], M.Blanker(fmt, is_real, db, guard)
-    rig = Rig(fmt, is_real)
-    frames, counts = {}, {}
-    try:
-        rig.ctx.ring_set_blanker(True, db, guard)
-        for first, n in calls:
-            want = nb.process(model, first, n)
-            spec, q = rig.call(halves, first, n)
-            for f in range(n):
-                frames[first + f] = (spec[f], q[f])
-            for h in range(first, first + n + 1):
-                assert same(rig.ring_half(h), model[h]), (first, n, h)
-                got = rig.ctx.ring_read_blanker(h)
-                if h in want:
-                    assert got is not None and got[0] == want[h][0] and same(got[1], want[h][1]), (h, got, want[h])
-                    counts[h] = got[0]
-                else:
-                    assert got is None, (h, got)  # blanked by an earlier call: PSDR_ERR_NO_DATA
-                if h % M.NHALVES == 0:
-                    assert same(rig.mirror(), model[h]), (first, n, h)  # both copies of the slot-0 half
-            assert rig.ctx.ring_read_blanker(first + n + 1) is None
-    finally:
-        rig.close()
-    return frames, model, counts
-
-
-def run_plain(fmt, is_real, halves, calls):
-    """a context that never heard of the blanker, fed `halves`"""
-    rig = Rig(fmt, is_real)
-    frames = {}
-    try:
-        for first, n in calls:
-            spec, q = rig.call(halves, first, n)
-            for f in range(n):
-                frames[first + f] = (spec[f], q[f])
-            for h in range(first, first + n + 1):
-                assert same(rig.ring_half(h), halves[h])
-        assert not any(rig.blanker_ptrs())  # assertion 8: no blanker allocation
-    finally:
-        rig.close()
-    return frames
 
 
 @pytest.mark.parametrize("guard", GUARDS)
