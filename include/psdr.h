@@ -848,6 +848,60 @@ int psdr_waterfall_batch(psdr_ctx *ctx, uint64_t first_frame_num);
 int psdr_read_waterfall(psdr_ctx *ctx, int id, int8_t *out, size_t out_cap, int *nsent_out, int *level_out,
                         int *l_out, int *r_out);
 
+/* Band scan: a smoothed spectrum trace, the noise floor of the band by segments and a list of the signals on it - for markers
+ * on the waterfall, "next signal up / down" tuning, an automatic colour scale and an occupancy display.  Context-wide and
+ * opt-in: a context that never switches it on allocates nothing, a batch without a psdr_scan_batch launches nothing, and every
+ * other output is bit for bit the same with the scan on or off.  Only the device can do this: the int8 pyramid of EVERY frame
+ * is there, and the frames between two sent waterfall rows never leave it.
+ *   The rule.  Every quantity is an integer; phantomsdr_amd/csrc/scanplan.h is the one definition of every step, for the device
+ *   and for a host program alike.
+ *   Values.  For scan level v, n = R >> v (R: the bins of level 0) and q_t[j], j in [0, n), is frame t's int8 value at level v -
+ *     exactly what psdr_read_quantized delivers, indexed as a waterfall client's l and r are at that level.  u = q + 128 is in
+ *     0..255.  One count of q is 0.5 dB: q = 20 log10(P) + 127 with P the bin's POWER scaled by the level's power offset
+ *     (quantize.h), so q rises by 20 per decade of power, 10 log10 of a power ratio = (difference of q) / 2.
+ *   Trace.  s[j], a uint32 in units of 1/256 count above -128.  The first frame of a run sets s = u << 8; every later frame, in
+ *     frame order, d = (int)(u << 8) - (int)s; s += d >> a, the shift arithmetic (floor), a = avg_shift in 0..8 (0: the trace
+ *     is the last frame).  s stays inside [0, 255 * 256], and the trace after frame f does not depend on how the frames were
+ *     split into batches.
+ *   Runs of frames.  psdr_waterfall_batch's rule: a psdr_scan_batch whose first_frame_num equals the previous call's
+ *     first_frame_num plus its number of frames continues the run; any other call starts a new run, and so does the first call
+ *     behind a psdr_scan_set.
+ *   Evaluation, once per psdr_scan_batch, on the trace as it stands after the batch's last frame:
+ *     Segments.  A segment is 256 bins, G = n / 256 of them.  Q_g is the 63rd smallest (0-based) of the segment's 256 trace
+ *       values, the lower quartile; F_g = min(Q_{g-1}, Q_g, Q_{g+1}) over the neighbours that exist, so that a crowded segment
+ *       does not lift its own floor.
+ *     Hot bins.  hot[j] = s[j] >= F_{j >> 8} + (threshold << 8); threshold in 1..255, in counts (0.5 dB each).
+ *     Runs of bins.  gap in 0..64.  Bin j starts a run if it is hot and no bin of [j - gap - 1, j - 1] is hot; hot bin j ends a
+ *       run, with end = j + 1, if no bin of [j + 1, j + 1 + gap] is hot; bins outside [0, n) are not hot; segment borders do not
+ *       cut runs.  Each run gives one psdr_signal: first, end, peak_bin (the lowest bin of [first, end) with the largest s - a
+ *       cold bin inside the run counts), peak = s[peak_bin], floor = F_{peak_bin >> 8}.
+ *     List.  The first PSDR_SCAN_MAX_SIGNALS runs in ascending order of first are kept, and the total number of runs, which
+ *       is not truncated.
+ * psdr_scan_set: any thread; in force from the next psdr_scan_batch, which starts a new run; NULL switches the scan off.  What
+ *   the read calls deliver is gone until the next evaluation.  PSDR_ERR_INVALID, with nothing changed and a text of its own each,
+ *   in this order: level outside [0, downsample_levels); R >> level < 256; avg_shift outside 0..8; threshold outside 1..255; gap
+ *   outside 0..64.  The first call that switches the scan on allocates its device state - trace, bit mask, floors, list and
+ *   scratch, sized for level 0 (about 2.6 bytes per bin of R) - all or none: PSDR_ERR_NOMEM leaves the setting unchanged.
+ * psdr_scan_batch: frame-loop thread; speaks for the batch processed just before it, like psdr_waterfall_batch, and is ordered
+ *   against the passes in the same way (the records it reads are overwritten by the next batch): call it before the next
+ *   psdr_process_*.  PSDR_ERR_STATE while the scan is off, and (scan on) before any batch was processed.
+ * The read calls synchronise; PSDR_ERR_NO_DATA before the first evaluation (and behind a psdr_scan_set until the next one).
+ *   psdr_read_signals: the signals of the list with end - first >= min_width, in the list's order; at most cap of them are
+ *     copied to out, *n_out says how many passed (it may exceed cap), *total_out is the device's untruncated number of runs,
+ *     *frame_num_out the number of the last frame in the trace.  Any out pointer may be NULL.  PSDR_ERR_INVALID for cap < 0.
+ *   psdr_read_scan_floor: F_g, G values; psdr_read_scan_trace: s[j] as uint16, n values.  *nseg_out / *n_out say how many there
+ *     are; a NULL buffer only queries; PSDR_ERR_INVALID, nothing written, for a buffer that holds fewer.
+ * There is no PSDR_FETCH_* bit and no psdr_group_* call for the scan: a group's caller runs it on the root,
+ * psdr_group_ctx(g, 0), which transforms every frame. */
+#define PSDR_SCAN_MAX_SIGNALS 8192
+typedef struct psdr_scan_config { int level, avg_shift, threshold, gap; } psdr_scan_config;
+typedef struct psdr_signal { uint32_t first, end, peak_bin; uint32_t peak, floor; } psdr_signal; /* peak, floor: 1/256 count above -128 */
+int psdr_scan_set(psdr_ctx *ctx, const psdr_scan_config *cfg);      /* NULL: off */
+int psdr_scan_batch(psdr_ctx *ctx, uint64_t first_frame_num);       /* speaks for the batch processed just before it */
+int psdr_read_signals(psdr_ctx *ctx, int min_width, psdr_signal *out, int cap, int *n_out, int *total_out, uint64_t *frame_num_out);
+int psdr_read_scan_floor(psdr_ctx *ctx, uint32_t *F, int cap, int *nseg_out);
+int psdr_read_scan_trace(psdr_ctx *ctx, uint16_t *s, size_t cap, size_t *n_out);
+
 /* last batch, raw device-side results (for consumers that stay on the GPU, and tests) */
 /* spectrum of frame f, normalised by 1/N exactly like src/fft_impl.cpp:34-35.  IQ: N complex bins
  * indexed by the CLIENT coordinate c (bin k = (c+N/2+1) mod N); real: N/2+1 bins indexed by k.

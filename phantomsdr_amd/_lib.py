@@ -36,6 +36,11 @@ class psdr_agc_profile(C.Structure):
                 ("manual", C.c_int32), ("manual_gain", C.c_double)]
 
 
+class psdr_scan_config(C.Structure):
+    """psdr_scan_set: scan level, trace shift 0..8, threshold in counts 1..255, gap in bins 0..64"""
+    _fields_ = [(n, C.c_int) for n in ("level", "avg_shift", "threshold", "gap")]
+
+
 # every symbol include/psdr.h declares: (name, restype, argtypes)
 _vp, _i, _sz, _u64 = C.c_void_p, C.c_int, C.c_size_t, C.c_uint64
 _pp = C.POINTER(C.c_void_p)
@@ -132,6 +137,11 @@ SYMBOLS = [
     ("psdr_quantized_device_ptr", _i, [_vp, _i, _pp, C.POINTER(_sz)]),
     ("psdr_read_spectrum", _i, [_vp, _i, _vp]),
     ("psdr_read_quantized", _i, [_vp, _i, _vp]),
+    ("psdr_scan_set", _i, [_vp, C.POINTER(psdr_scan_config)]),
+    ("psdr_scan_batch", _i, [_vp, _u64]),
+    ("psdr_read_signals", _i, [_vp, _i, _vp, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_u64)]),
+    ("psdr_read_scan_floor", _i, [_vp, _vp, _i, C.POINTER(_i)]),
+    ("psdr_read_scan_trace", _i, [_vp, _vp, _sz, C.POINTER(_sz)]),
     ("psdr_set_profiling", _i, [_vp, _i]),
     ("psdr_get_kernel_stats", _i,
      [_vp, _i, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(_i)]),

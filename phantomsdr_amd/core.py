@@ -47,6 +47,10 @@ NR_PRESETS = {"light": NR_LIGHT, "normal": NR_NORMAL, "strong": NR_STRONG}
 ANB_LIGHT, ANB_NORMAL, ANB_STRONG = 1, 2, 3
 ANB_PRESETS = {"light": ANB_LIGHT, "normal": ANB_NORMAL, "strong": ANB_STRONG}
 
+# psdr_signal (include/psdr.h): one signal of the band scan's list; peak and floor in 1/256 count above -128
+SIGNAL_DTYPE = np.dtype([("first", np.uint32), ("end", np.uint32), ("peak_bin", np.uint32), ("peak", np.uint32), ("floor", np.uint32)])
+SCAN_MAX_SIGNALS = 8192  # PSDR_SCAN_MAX_SIGNALS
+
 # PSDR_AGC_* (include/psdr.h): the presets of psdr_agc_preset
 AGC_REFERENCE, AGC_FAST, AGC_SLOW = 0, 1, 2
 AGC_PRESETS = {"reference": AGC_REFERENCE, "fast": AGC_FAST, "slow": AGC_SLOW}
@@ -365,6 +369,48 @@ class Context:
 
     def waterfall_batch(self, first_frame_num):
         check(self.lib.psdr_waterfall_batch(self.h, first_frame_num))
+
+    # --- band scan (psdr_scan_*): smoothed trace, segment noise floor, list of signals ----------
+    def scan_set(self, level=None, avg_shift=3, threshold=12, gap=2):
+        """the context's band scan (psdr.h: psdr_scan_set).  level None: off.  avg_shift 0..8: the trace's time constant is
+        2^avg_shift frames; threshold 1..255 in counts of the int8 scale (0.5 dB each) above the segment floor; gap 0..64: cold
+        bins that do not split a signal.  In force from the next scan_batch, which starts a new run."""
+        if level is None:
+            check(self.lib.psdr_scan_set(self.h, None))
+            return
+        cfg = _lib.psdr_scan_config(int(level), int(avg_shift), int(threshold), int(gap))
+        check(self.lib.psdr_scan_set(self.h, C.byref(cfg)))
+
+    def scan_batch(self, first_frame_num):
+        """folds the batch processed just before into the trace and evaluates floors and signals (psdr_scan_batch)"""
+        check(self.lib.psdr_scan_batch(self.h, first_frame_num))
+
+    def read_signals(self, min_width=1):
+        """(signals, total, frame_num): the kept signals at least min_width bins wide as a structured array (first, end,
+        peak_bin, peak, floor; SIGNAL_DTYPE), the untruncated number of runs and the number of the last frame in the trace
+        (psdr_read_signals); synchronises"""
+        n, total, fn = C.c_int(0), C.c_int(0), C.c_uint64(0)
+        check(self.lib.psdr_read_signals(self.h, int(min_width), None, 0, C.byref(n), C.byref(total), C.byref(fn)))
+        out = np.zeros(n.value, SIGNAL_DTYPE)
+        if n.value:
+            check(self.lib.psdr_read_signals(self.h, int(min_width), _ptr(out), n.value, C.byref(n), C.byref(total), C.byref(fn)))
+        return out, total.value, fn.value
+
+    def read_scan_floor(self):
+        """uint32[G]: the segments' floors F_g in 1/256 count above -128 (psdr_read_scan_floor)"""
+        g = C.c_int(0)
+        check(self.lib.psdr_read_scan_floor(self.h, None, 0, C.byref(g)))
+        out = np.empty(g.value, np.uint32)
+        check(self.lib.psdr_read_scan_floor(self.h, _ptr(out), g.value, C.byref(g)))
+        return out
+
+    def read_scan_trace(self):
+        """uint16[n]: the trace s[j] in 1/256 count above -128 (psdr_read_scan_trace)"""
+        n = C.c_size_t(0)
+        check(self.lib.psdr_read_scan_trace(self.h, None, 0, C.byref(n)))
+        out = np.empty(n.value, np.uint16)
+        check(self.lib.psdr_read_scan_trace(self.h, _ptr(out), n.value, C.byref(n)))
+        return out
 
     def read_spectrum(self, frame):
         """complex64[nbins] in the reference's k order."""

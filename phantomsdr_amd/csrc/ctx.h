@@ -36,6 +36,7 @@
 #include "owned.h"
 #include "postplan.h"
 #include "quantize.h"
+#include "scanplan.h"
 #include "squelchplan.h"
 #include "types.h"
 
@@ -71,7 +72,7 @@ inline const char *psdr_tuning_env(const char *name) {
 
 namespace psdr {
 
-enum KernelId { K_PASS1, K_PASS2, K_UNTANGLE, K_TAIL, K_IDFT, K_OLA, K_WFALL, K_POST, K_SEAM, K_BAND, K_WFHOLD, K_WFCARRY, K_SQUELCH, K_NB_SCAN, K_NB_APPLY, K_AUDIO_FILTER, K_AUDIO_NR, K_AUDIO_NB, K_COUNT };
+enum KernelId { K_PASS1, K_PASS2, K_UNTANGLE, K_TAIL, K_IDFT, K_OLA, K_WFALL, K_POST, K_SEAM, K_BAND, K_WFHOLD, K_WFCARRY, K_SQUELCH, K_NB_SCAN, K_NB_APPLY, K_AUDIO_FILTER, K_AUDIO_NR, K_AUDIO_NB, K_SCAN_TRACE, K_SCAN_FLOOR, K_SCAN_HOT, K_SCAN_MARK, K_SCAN_EMIT, K_COUNT };
 extern const char *kKernelNames[K_COUNT];
 
 struct PendingEvent {
@@ -500,6 +501,27 @@ struct psdr_ctx {
     DevBuf<uint32_t> d_wf_sum;
     WfCarryLayout wf_lay;              // which bytes of a frame's record buffers the carry mirrors (forwardplan.h)
     WfCarry wf_carry;                  // the run the carry belongs to
+    // band scan (scan.h; psdr_scan_set): the trace [R] of 1/256 counts, the hot bins' mask and the start words [R / 64], the
+    // segments' quartiles and floors [R / 256], the list with its head, and the scratch of the run index (the starts in front of
+    // every mask word) - sized for level 0, allocated by the first psdr_scan_set that switches the scan on, all or none, and
+    // kept.  Touched on `side` only.  scan_on / scan_cfg: under mtx; scan_st: the run of frames the trace belongs to (scanplan.h)
+    struct BandScan {
+        DevBuf<uint16_t> trace;
+        DevBuf<uint64_t> hot, starts;
+        DevBuf<uint32_t> Q, F, base;
+        DevBuf<ScanRun> list;
+        DevBuf<ScanHead> head;
+        static size_t bytes(const psdr_ctx &c) { return scan_bytes(c.R); }
+        int alloc(const psdr_ctx &c) {
+            const size_t R = c.R;
+            return trace.alloc(R, true) || hot.alloc(R / 64, true) || starts.alloc(R / 64, true) || Q.alloc(R / SCAN_SEG, true) ||
+                   F.alloc(R / SCAN_SEG, true) || base.alloc(R / 64, true) || list.alloc(SCAN_CAP, true) || head.alloc(1, true);
+        }
+        explicit operator bool() const { return (bool)head; }
+    } scan;
+    bool scan_on = false;
+    psdr_scan_config scan_cfg{};
+    ScanState scan_st;
 
     // streaming ingest ring (psdr_ring_*)
     struct IngestRing {
