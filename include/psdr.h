@@ -638,6 +638,65 @@ int psdr_noise_reduction_preset(int kind, double *depth_db, double *beta);   /* 
 int psdr_client_set_audio_blanker(psdr_ctx *ctx, int id, int on, double threshold, int width);
 int psdr_audio_blanker_preset(int kind, double *threshold, int *width);      /* needs no context */
 int psdr_read_audio_blanker(psdr_ctx *ctx, int id, uint64_t *impulses, uint64_t *samples); /* cumulative since the state last started; synchronises */
+/* Tone decoder: which sub-audible (CTCSS) tone a client's audio carries, per client on the audio rows, and a tone squelch: the
+ * channel stays shut unless the transmission carries the right tone.  It READS the rows as the demodulator wrote them - in front
+ * of the audio blanker, the noise reduction and the audio filter, which would damage or remove the tone - and never writes them.
+ *   Tones.  The 50 standard tones, numbered 0..49 in ascending order, 67.0 Hz .. 254.1 Hz (psdr_tone_table).
+ *   Rule.  The client's stream is its rows in frame order, a NaN-flagged frame entering as zeros, sample t counting from the state's
+ *     start.  Tone k has the phase increment inc_k = round(f_k / audio_rate * 2^32), in double; the phase of sample t is the low 32
+ *     bits of inc_k t, exact at any stream position.  Blocks hold 256 samples; block b gives per tone
+ *     C[b][k] = sum_n x[256 b + n] conj(w_k(256 b + n)), n ascending in one f32 accumulator, where the twiddle w_k starts each block
+ *     from two 4096-entry tables over bits 31..20 and 19..8 of the phase (computed in double, rounded once) and is turned once per
+ *     sample by exp(2 pi i inc_k / 2^32).  The window is NB = ceil(0.4 audio_rate / 256) blocks (13 at 8 kHz, 19 at 12 kHz, 75 at
+ *     48 kHz) with weights h_j = 0.5 - 0.5 cos(2 pi (j + 0.5) / NB); every block b >= NB - 1 gives S_k = sum_j h_j C[b - NB + 1 + j][k],
+ *     j ascending, P_k = |S_k|^2, and a decision: best = the lowest k with the largest P_k; ref = the 12th smallest (0-based) of
+ *     the 50 powers, ordered as unsigned integers on the f32 bit pattern; level = P_best * 4 / (256 sum h)^2, the squared amplitude
+ *     of the tone in the units of the rows; hit = P_best >= ratio * ref && level >= min_level && (want < 0 || best == want) with
+ *     ratio = (float)pow(10, snr_db / 10).  A power that is not finite gives no hit and level 0.  phantomsdr_amd/csrc/toneplan.h is
+ *     the one definition of all of it - the order of every sum included - for the device and for a host program alike, bit for bit.
+ *   Gate.  The squelch's state machine in units of blocks: closed, attack_blocks consecutive hits open it; open, more than
+ *     hang_blocks consecutive misses close it; it starts at (closed, 0).
+ *   Records.  Frame f's record is what stands behind the last block that is complete at the frame's last sample (block b once
+ *     256 (b + 1) samples are in): tone = best if the last decision was a hit, else -1; level = the last decision's; open = the
+ *     gate; before the first decision -1, 0, closed.  Any split of the same frames into batches gives the same bits.
+ *   gate = 1.  With the post chain on, a frame whose record says closed stays out of the chain's stream like a NaN-flagged one
+ *     (together with what the level squelch drops: nan | !squelch_open | !tone_open); rows, pwr, NaN flags, psdr_read_squelch's
+ *     flags and every other state are those of a client without the decoder.  gate = 0: records only.
+ *   Who.  Every client of a batch whose kind writes audio rows; a PSDR_IQ client is refused, a client that becomes one keeps its
+ *     setting and is not listed.  The state is carried across batches and across dropped or flagged frames and stands still while
+ *     the client is paused.
+ *   State.  Per client slot 1048 bytes (the unfinished block's samples, the position, the gate, the last decision) and the block
+ *     correlations of the last NB + 3 blocks, 512 bytes each (64 lanes' worth): 12.3 KB in all at 12 kHz, 41 KB at 48 kHz; 16 bytes per
+ *     slot and frame of a batch for the records.  It starts from zero when the call switches the decoder on (again, too), on a mode
+ *     change and on a retune, as the noise reduction's does.
+ *   The default snr_db = 22 is a design constant between what tones in white noise reach and what noise alone reaches (DESIGN.md
+ *     3.20); nobody has tried it on off-air FM audio.
+ * psdr_client_set_tone_decoder: any thread; in force from the client's next batch; cfg = NULL switches it off.  PSDR_ERR_INVALID,
+ *   with nothing changed and a text of its own each, for an id outside the slots, a slot without a client, (cfg != NULL) a PSDR_IQ
+ *   client, want outside -1..49, gate outside 0..1, snr_db not finite or outside [6, 60], min_level not finite or below 0,
+ *   attack_blocks outside 1..1024, hang_blocks outside 0..1024; then PSDR_ERR_STATE for a context whose audio_rate is outside
+ *   [2000, 48000] (below, the top tone is not under Nyquist with room to spare; above, the window needs more than 75 blocks and the state per slot, 41 KB at 48 kHz, grows further) - in
+ *   this order.  The device state is allocated with the context's first such client, all or none: PSDR_ERR_NOMEM and the setting
+ *   unchanged if that fails.  A context without such a client allocates nothing, a batch without one launches nothing.
+ * psdr_tone_defaults, psdr_tone_table: need no context.  PSDR_ERR_INVALID for a null pointer or an audio_rate outside [2000, 48000].
+ * psdr_read_tone: psdr_read_squelch's contract - the records of the last demodulation batch, nframes the room of the arrays (any
+ *   of which may be null), synchronises - but a client whose last batch ran without the decoder reads PSDR_ERR_NO_DATA, as does one
+ *   that was not part of the batch or was demodulated as PSDR_IQ.
+ * Nothing of it goes through psdr_fetch_* yet, and there is no psdr_group_* call: a group's clients have no tone decoder. */
+#define PSDR_TONE_COUNT 50
+#define PSDR_TONE_ANY (-1)
+typedef struct {
+    int want;          /* 0..49, or PSDR_TONE_ANY (-1) */
+    int gate;          /* 1: a closed frame stays out of the post chain; 0: records only */
+    double snr_db;     /* [6, 60], default 22 */
+    double min_level;  /* >= 0, finite; default 0 */
+    int attack_blocks; /* 1..1024, default 2 */
+    int hang_blocks;   /* 0..1024, default NB */
+} psdr_tone_config;
+int psdr_tone_defaults(double audio_rate, psdr_tone_config *out);          /* needs no context */
+int psdr_tone_table(const double **hz, int *n);                            /* needs no context */
+int psdr_client_set_tone_decoder(psdr_ctx *ctx, int id, const psdr_tone_config *cfg);   /* NULL: off */
+int psdr_read_tone(psdr_ctx *ctx, int id, int nframes, int32_t *tone, float *level, int32_t *open, int *nframes_out);
 /* AGC profile: speed, target, gain cap and manual gain per client.  The context's AGC is the reference's - target 0.2, attack
  * 50 ms, release 300 ms (psdr_set_post_chain) - for every client; a profile replaces these numbers for one client: a fast AGC for
  * CW, a slow one for broadcast, a bound on the gain a quiet channel is pumped up by, or no AGC at all and a fixed gain, which is

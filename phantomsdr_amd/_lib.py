@@ -36,6 +36,12 @@ class psdr_agc_profile(C.Structure):
                 ("manual", C.c_int32), ("manual_gain", C.c_double)]
 
 
+class psdr_tone_config(C.Structure):
+    """psdr_client_set_tone_decoder: wanted tone (-1: any), gate flag, snr_db, min_level, attack and hang in blocks"""
+    _fields_ = [("want", C.c_int), ("gate", C.c_int), ("snr_db", C.c_double), ("min_level", C.c_double), ("attack_blocks", C.c_int),
+                ("hang_blocks", C.c_int)]
+
+
 class psdr_scan_config(C.Structure):
     """psdr_scan_set: scan level, trace shift 0..8, threshold in counts 1..255, gap in bins 0..64"""
     _fields_ = [(n, C.c_int) for n in ("level", "avg_shift", "threshold", "gap")]
@@ -104,6 +110,10 @@ SYMBOLS = [
     ("psdr_client_set_audio_blanker", _i, [_vp, _i, _i, C.c_double, _i]),
     ("psdr_audio_blanker_preset", _i, [_i, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     ("psdr_read_audio_blanker", _i, [_vp, _i, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("psdr_client_set_tone_decoder", _i, [_vp, _i, C.POINTER(psdr_tone_config)]),
+    ("psdr_tone_defaults", _i, [C.c_double, C.POINTER(psdr_tone_config)]),
+    ("psdr_tone_table", _i, [C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int)]),
+    ("psdr_read_tone", _i, [_vp, _i, _i, _vp, _vp, _vp, C.POINTER(_i)]),
     ("psdr_client_set_agc_profile", _i, [_vp, _i, C.POINTER(psdr_agc_profile)]),
     ("psdr_agc_preset", _i, [_i, C.POINTER(psdr_agc_profile)]),
     ("psdr_read_agc_gain", _i, [_vp, _i, C.POINTER(C.c_float)]),

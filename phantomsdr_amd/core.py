@@ -68,6 +68,24 @@ def agc_preset(kind):
                 manual_gain=p.manual_gain)
 
 
+TONE_ANY = -1  # PSDR_TONE_ANY
+
+
+def tone_table():
+    """the 50 standard sub-audible tones in Hz, ascending: index = the tone's number (psdr_tone_table; needs no context)"""
+    hz, n = C.POINTER(C.c_double)(), C.c_int(0)
+    check(_lib.load().psdr_tone_table(C.byref(hz), C.byref(n)))
+    return [hz[k] for k in range(n.value)]
+
+
+def tone_defaults(audio_rate):
+    """the tone decoder's defaults at `audio_rate` as a dict for AudioClient.set_tone_decoder(**...) (psdr_tone_defaults; needs no
+    context): any tone, gate on, snr_db 22, min_level 0, attack 2 blocks, hang one window of blocks"""
+    p = _lib.psdr_tone_config()
+    check(_lib.load().psdr_tone_defaults(float(audio_rate), C.byref(p)))
+    return dict(want=p.want, gate=p.gate, snr_db=p.snr_db, min_level=p.min_level, attack_blocks=p.attack_blocks, hang_blocks=p.hang_blocks)
+
+
 def noise_reduction_preset(kind):
     """(depth_db, beta) of a noise reduction preset for AudioClient.set_noise_reduction (psdr_noise_reduction_preset; needs no
     context): "light" (8 dB, 1), "normal" (14 dB, 1.5) or "strong" (22 dB, 2), or an NR_* constant"""
@@ -682,6 +700,33 @@ class AudioClient:
         n, s = C.c_uint64(0), C.c_uint64(0)
         check(self.ctx.lib.psdr_read_audio_blanker(self.ctx.h, self.id, C.byref(n), C.byref(s)))
         return n.value, s.value
+
+    def set_tone_decoder(self, on=True, **fields):
+        """sub-audible tone detection and tone squelch on the client's audio rows as the demodulator wrote them
+        (psdr_client_set_tone_decoder).  on false or None: off.  Keyword arguments replace single fields of tone_defaults() at
+        the context's audio_rate: want (0..49 or TONE_ANY), gate (1: a closed frame stays out of the post chain), snr_db,
+        min_level, attack_blocks, hang_blocks.  The state starts from zero with every call that switches it on."""
+        if not on:
+            check(self.ctx.lib.psdr_client_set_tone_decoder(self.ctx.h, self.id, None))
+            return
+        p = _lib.psdr_tone_config(want=TONE_ANY, gate=1, snr_db=22.0, min_level=0.0, attack_blocks=2, hang_blocks=0)
+        # (a rate outside the decoder's range is the call's refusal to make, not the defaults')
+        if self.ctx.lib.psdr_tone_defaults(float(self.ctx.cfg.audio_rate), C.byref(p)) != 0:
+            p.hang_blocks = 0
+        for k, v in fields.items():
+            if k not in ("want", "gate", "snr_db", "min_level", "attack_blocks", "hang_blocks"):
+                raise TypeError("set_tone_decoder: unknown field %r" % k)
+            setattr(p, k, float(v) if k in ("snr_db", "min_level") else int(v))
+        check(self.ctx.lib.psdr_client_set_tone_decoder(self.ctx.h, self.id, C.byref(p)))
+
+    def read_tone(self, nframes=None):
+        """(tone[F] int32, level[F] float32, open[F] int32) of the last demod batch (psdr.h: psdr_read_tone): per frame the tone's
+        number or -1, the squared amplitude the last decision measured, and the tone gate"""
+        F = nframes or self.ctx.last_demod_frames or self.ctx.last_nframes
+        t, lv, o = np.empty(F, np.int32), np.empty(F, np.float32), np.empty(F, np.int32)
+        got = C.c_int(0)
+        check(self.ctx.lib.psdr_read_tone(self.ctx.h, self.id, F, _ptr(t), _ptr(lv), _ptr(o), C.byref(got)))
+        return t[:got.value], lv[:got.value], o[:got.value]
 
     def set_agc_profile(self, profile, **fields):
         """the client's own AGC numbers in the post chain (psdr_client_set_agc_profile).  `profile`: None - back to the context's

@@ -38,6 +38,7 @@
 #include "quantize.h"
 #include "scanplan.h"
 #include "squelchplan.h"
+#include "toneplan.h"
 #include "types.h"
 
 // sets psdr_last_error() of the calling thread and returns `code`
@@ -72,7 +73,7 @@ inline const char *psdr_tuning_env(const char *name) {
 
 namespace psdr {
 
-enum KernelId { K_PASS1, K_PASS2, K_UNTANGLE, K_TAIL, K_IDFT, K_OLA, K_WFALL, K_POST, K_SEAM, K_BAND, K_WFHOLD, K_WFCARRY, K_SQUELCH, K_NB_SCAN, K_NB_APPLY, K_AUDIO_FILTER, K_AUDIO_NR, K_AUDIO_NB, K_SCAN_TRACE, K_SCAN_FLOOR, K_SCAN_HOT, K_SCAN_MARK, K_SCAN_EMIT, K_COUNT };
+enum KernelId { K_PASS1, K_PASS2, K_UNTANGLE, K_TAIL, K_IDFT, K_OLA, K_WFALL, K_POST, K_SEAM, K_BAND, K_WFHOLD, K_WFCARRY, K_SQUELCH, K_NB_SCAN, K_NB_APPLY, K_AUDIO_FILTER, K_AUDIO_NR, K_AUDIO_NB, K_SCAN_TRACE, K_SCAN_FLOOR, K_SCAN_HOT, K_SCAN_MARK, K_SCAN_EMIT, K_AUDIO_TONE, K_COUNT };
 extern const char *kKernelNames[K_COUNT];
 
 struct PendingEvent {
@@ -426,6 +427,36 @@ struct psdr_ctx {
         explicit operator bool() const { return (bool)tab; }
     } anb;
     int opt_anb = 0;  // PSDR_OPT_AUDIO_BLANKER: the preset (0: none) a client gets at psdr_client_add
+    // tone decoder (tone.h: k_audio_tone): the clients' carried state [slots] and history ring [slots][ring][64], the plan's
+    // tables for the context's audio_rate, the frames' records [slots][max_batch] and the chain's drop flags [slots][max_batch]
+    // (both written and read on `side` within one batch or behind a drain: one set), and the batch's table (toneplan.h), a
+    // RingTable beside client_ring
+    struct ToneDecoder {
+        DevBuf<ToneState> state;
+        DevBuf<ToneC> hist;
+        DevBuf<ToneTables> plan;
+        DevBuf<ToneRec> rec;
+        DevBuf<int> drop;
+        RingTable<ToneEntry> tab;
+        int ring = 0;  // rows of a slot's history ring
+        static size_t ring_rows(const psdr_ctx &c) { return (size_t)tone_ring(tone_nb((double)c.cfg.audio_rate)); }
+        static size_t bytes(const psdr_ctx &c) {
+            const size_t S = c.aslots.size();
+            return S * (sizeof(ToneState) + ring_rows(c) * TONE_LANES * sizeof(ToneC) + (size_t)c.max_batch * (sizeof(ToneRec) + sizeof(int))) + sizeof(ToneTables) +
+                   RingTable<ToneEntry>::bytes(S);
+        }
+        int alloc(const psdr_ctx &c) {
+            const size_t S = c.aslots.size(), rows = S * (size_t)c.max_batch;
+            ring = (int)ring_rows(c);
+            if (state.alloc(S, true) || hist.alloc(S * (size_t)ring * TONE_LANES, true) || plan.alloc(1) || rec.alloc(rows, true) || drop.alloc(rows, true) || tab.alloc(S))
+                return 1;
+            std::vector<ToneTables> t(1);
+            tone_tables(t[0], (double)c.cfg.audio_rate);
+            const hipError_t e = hipMemcpy(plan.get(), t.data(), sizeof(ToneTables), hipMemcpyHostToDevice);
+            return e == hipSuccess ? 0 : psdr_fail(PSDR_ERR_HIP, "tone decoder tables: %s", hipGetErrorString(e));
+        }
+        explicit operator bool() const { return (bool)tab; }
+    } tone;
     // AGC profiles (agcplan.h; postchain.h: k_pc_want_prof and the PcWithProfiles kernels): the batch's table, a RingTable beside
     // client_ring.  The chain's carried state is the context's own: a profile adds none
     struct AgcProfiles {

@@ -8,6 +8,7 @@
 #include "audiofilter.h"
 #include "nr.h"
 #include "anb.h"
+#include "tone.h"
 
 // The context's first client of an optional feature (ctx.h: the structs behind `iq`): what the feature allocates is built whole
 // and only then moved in, so a failed call leaves the context as it was.  msg: the failure's text, with the bytes and the
@@ -29,6 +30,7 @@ static int first_sideband(psdr_ctx *c) { return first_use(c, c->sb, "sideband SA
 static int first_auto_notch(psdr_ctx *c) { return first_use(c, c->notch, "auto-notch state (%zu bytes): %s"); }
 static int first_noise_reduction(psdr_ctx *c) { return first_use(c, c->nr, "noise reduction state and tables (%zu bytes): %s"); }
 static int first_audio_blanker(psdr_ctx *c) { return first_use(c, c->anb, "audio blanker state (%zu bytes): %s"); }
+static int first_tone_decoder(psdr_ctx *c) { return first_use(c, c->tone, "tone decoder state, records and tables (%zu bytes): %s"); }
 // the detector's state of one slot back to zero: sums, counter, both automatic entries (stream-ordered on `side`)
 static int notch_zero(psdr_ctx *c, size_t slot) {
     HIPCHK(hipMemsetAsync(c->notch.acc + slot * (size_t)c->n, 0, (size_t)c->n * sizeof(float), c->side));
@@ -344,6 +346,36 @@ extern "C" int psdr_debug_audio_blanker_ptrs(psdr_ctx *c, const void *out[2]) {
     out[0] = c->anb.tab.d.get(), out[1] = c->anb.state.get();
     return PSDR_OK;
 }
+extern "C" int psdr_client_set_tone_decoder(psdr_ctx *c, int id, const psdr_tone_config *cfg) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mtx);
+    switch (tone_check(c->aslots.data(), c->aslots.size(), id, cfg, c->cfg.audio_rate)) {
+    case TONE_OK: break;
+    case TONE_BAD_ID: return fail(PSDR_ERR_INVALID, "tone decoder: id %d outside 0..%d", id, (int)c->aslots.size() - 1);
+    case TONE_INACTIVE: return fail(PSDR_ERR_INVALID, "no audio client with id %d", id);
+    case TONE_IQ: return fail(PSDR_ERR_INVALID, "tone decoder: client %d is a PSDR_IQ client, which has no audio rows", id);
+    case TONE_BAD_WANT: return fail(PSDR_ERR_INVALID, "tone decoder: want %d outside %d..%d", cfg->want, PSDR_TONE_ANY, TONE_N - 1);
+    case TONE_BAD_GATE: return fail(PSDR_ERR_INVALID, "tone decoder: gate %d outside 0..1", cfg->gate);
+    case TONE_BAD_SNR: return fail(PSDR_ERR_INVALID, "tone decoder: snr_db %g is not a finite number inside [%g, %g]", cfg->snr_db, TONE_SNR_MIN, TONE_SNR_MAX);
+    case TONE_BAD_LEVEL: return fail(PSDR_ERR_INVALID, "tone decoder: min_level %g is not a finite number at or above 0", cfg->min_level);
+    case TONE_BAD_ATTACK: return fail(PSDR_ERR_INVALID, "tone decoder: attack_blocks %d outside 1..%d", cfg->attack_blocks, TONE_BLOCKS_MAX);
+    case TONE_BAD_HANG: return fail(PSDR_ERR_INVALID, "tone decoder: hang_blocks %d outside 0..%d", cfg->hang_blocks, TONE_BLOCKS_MAX);
+    case TONE_BAD_RATE: return fail(PSDR_ERR_STATE, "tone decoder: the context's audio_rate %d is outside [%d, %d]", c->cfg.audio_rate, TONE_RATE_MIN, TONE_RATE_MAX);
+    }
+    if (cfg) PSDRCHK(first_tone_decoder(c));
+    tone_apply(c->aslots[id], cfg);
+    return PSDR_OK;
+}
+extern "C" int psdr_tone_defaults(double audio_rate, psdr_tone_config *out) {
+    if (!out) return fail(PSDR_ERR_INVALID, "null argument");
+    if (!tone_defaults(audio_rate, out)) return fail(PSDR_ERR_INVALID, "tone decoder defaults: audio_rate %g outside [%d, %d]", audio_rate, TONE_RATE_MIN, TONE_RATE_MAX);
+    return PSDR_OK;
+}
+extern "C" int psdr_tone_table(const double **hz, int *n) {
+    if (!hz || !n) return fail(PSDR_ERR_INVALID, "null argument");
+    *hz = TONE_HZ, *n = TONE_N;
+    return PSDR_OK;
+}
 extern "C" int psdr_client_set_agc_profile(psdr_ctx *c, int id, const psdr_agc_profile *p) {
     if (!c) return fail(PSDR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mtx);
@@ -526,6 +558,7 @@ struct BatchPlan {
     AfPlan af;
     NrPlan nr;
     AnbPlan anb;
+    TonePlan tone;
     AgcPlan ag;
     bool chain = false;  // the post chain follows: it is on, and somebody is in it
     // of the optional features: the rows of the result set this batch writes and the detector's table - null where the context has
@@ -560,6 +593,7 @@ static int batch_plan(psdr_ctx *c, int nframes, const uint32_t *band, BatchPlan 
     if (c->af) b.af = audio_filter_plan(slots, S, c->demod_seq, c->af.tab.host(b.ring));
     if (c->nr) b.nr = nr_plan(slots, S, c->demod_seq, c->nr.tab.host(b.ring), nr_a_up(c->cfg.audio_rate));
     if (c->anb) b.anb = anb_plan(slots, S, c->demod_seq, c->anb.tab.host(b.ring));
+    if (c->tone) b.tone = tone_plan(slots, S, c->demod_seq, b.chain, c->tone.tab.host(b.ring));
     if (c->agc_prof && b.chain) b.ag = agc_profile_plan(slots, S, c->demod_seq, c->agc_prof.tab.host(b.ring));
     return PSDR_OK;
 }
@@ -577,6 +611,11 @@ static int batch_begin(psdr_ctx *c, const BatchPlan &b) {
     for (size_t slot : b.nr.zero) HIPCHK(hipMemsetAsync(c->nr.state + slot, 0, sizeof(NrState), c->side));
     // ... and the audio blankers (anb_plan has taken anb_fresh off these slots)
     for (size_t slot : b.anb.zero) HIPCHK(hipMemsetAsync(c->anb.state + slot, 0, sizeof(AnbState), c->side));
+    // ... and the tone decoders: state and history ring (tone_plan has taken tone_fresh off these slots)
+    for (size_t slot : b.tone.zero) {
+        HIPCHK(hipMemsetAsync(c->tone.state + slot, 0, sizeof(ToneState), c->side));
+        HIPCHK(hipMemsetAsync(c->tone.hist + slot * (size_t)c->tone.ring * TONE_LANES, 0, (size_t)c->tone.ring * TONE_LANES * sizeof(ToneC), c->side));
+    }
     // ... and the noise floors that start from zero: sums and record (noise_plan has taken nf_fresh off these slots)
     for (size_t slot : b.nf.zero) {
         HIPCHK(hipMemsetAsync(c->noise.acc + slot * (size_t)c->n, 0, (size_t)c->n * sizeof(float), c->side));
@@ -609,6 +648,7 @@ static int batch_begin(psdr_ctx *c, const BatchPlan &b) {
     if (b.af.any()) HIPCHK(c->af.tab.upload(b.ring, (size_t)b.af.n, c->side));
     if (b.nr.any()) HIPCHK(c->nr.tab.upload(b.ring, (size_t)b.nr.n, c->side));
     if (b.anb.any()) HIPCHK(c->anb.tab.upload(b.ring, (size_t)b.anb.n, c->side));
+    if (b.tone.any()) HIPCHK(c->tone.tab.upload(b.ring, (size_t)(b.tone.n + b.tone.ncopy), c->side));
     return PSDR_OK;
 }
 
@@ -776,6 +816,22 @@ static int launch_squelch(psdr_ctx *c, const BatchPlan &b, int nframes, const in
     if (b.chain) *chain_drop = c->squelch.drop;  // ... the NaN guard's frames and the closed ones
     return PSDR_OK;
 }
+// ... the tone decoder, behind the squelch and in front of everything that rewrites rows: it reads the listed clients' rows as the
+// demodulator left them and writes the frames' records.  *chain_drop: with gated clients in a chain batch the chain reads the
+// decoder's drop flags - what it would have read, and the closed frames
+static int launch_tone_decoder(psdr_ctx *c, const BatchPlan &b, int nframes, const int **chain_drop) {
+    ToneArgs ta{};
+    ta.list = c->tone.tab.dev(b.ring), ta.nlist = b.tone.n + b.tone.ncopy;
+    ta.tab = c->tone.plan;
+    ta.audio = c->d_audio, ta.nan_flags = c->d_nan;
+    ta.state = c->tone.state, ta.hist = c->tone.hist, ta.rec = c->tone.rec;
+    ta.prev_drop = *chain_drop, ta.drop = b.tone.gated ? c->tone.drop.get() : nullptr;
+    ta.nframes = nframes, ta.max_batch = c->max_batch, ta.h = c->n / 2, ta.ring = c->tone.ring;
+    ProfScope ps(c, K_AUDIO_TONE, c->side);
+    HIPCHK(audio_tone_launch(ta, c->side));
+    if (b.tone.gated) *chain_drop = c->tone.drop;
+    return PSDR_OK;
+}
 // ... the audio blanker, in front of the noise reduction, the audio filter and the chain: it works on the listed clients' rows in
 // place
 static int launch_audio_blanker(psdr_ctx *c, const BatchPlan &b, int nframes) {
@@ -847,6 +903,7 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     const int *chain_drop = c->d_nan;  // what stays out of the chain's streams: the NaN guard's frames ...
     if (b.nf.any()) PSDRCHK(launch_noise_floor(c, b, a));
     if (b.sq.any()) PSDRCHK(launch_squelch(c, b, nframes, &chain_drop));
+    if (b.tone.any()) PSDRCHK(launch_tone_decoder(c, b, nframes, &chain_drop));
     if (b.anb.any()) PSDRCHK(launch_audio_blanker(c, b, nframes));
     if (b.nr.any()) PSDRCHK(launch_noise_reduction(c, b, nframes));
     if (b.af.any()) PSDRCHK(launch_audio_filter(c, b, nframes));

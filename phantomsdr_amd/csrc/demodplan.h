@@ -87,6 +87,13 @@ struct AudioSlot {
     int anb_width = 7;
     bool anb_fresh = false;
     int anb_mode = PSDR_USB, anb_l = 0, anb_r = 0, anb_m = 0;
+    // psdr_client_set_tone_decoder (toneplan.h): the parameters as the table holds them; b_tone_on: the last batch ran with it
+    // (psdr_read_tone); tone_fresh, tone_mode, tone_l, tone_r, tone_m: as the noise reduction's
+    int tone_on = 0;
+    int tone_want = -1, tone_gate = 0, tone_attack = 2, tone_hang = 0;
+    float tone_ratio = 1.f, tone_min_level = 0.f;
+    bool b_tone_on = false, tone_fresh = false;
+    int tone_mode = PSDR_USB, tone_l = 0, tone_r = 0, tone_m = 0;
 };
 
 // The client parameter ring's slot.  [ClientParams x S][int x S]: the batch's list and, for the post chain, the list index of

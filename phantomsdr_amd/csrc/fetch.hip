@@ -408,6 +408,24 @@ extern "C" int psdr_read_squelch(psdr_ctx *c, int id, int nframes, int32_t *open
     HIPCHK(hipMemcpy(open, c->d_sq + fetch_row(id, (size_t)c->max_batch, 0), F * sizeof(int32_t), hipMemcpyDeviceToHost));
     return PSDR_OK;
 }
+// the tone decoder's records of the last batch; any of the three arrays may be null
+extern "C" int psdr_read_tone(psdr_ctx *c, int id, int nframes, int32_t *tone, float *level, int32_t *open, int *nframes_out) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    size_t F = 0;
+    bool on = false;
+    PSDRCHK(read_begin(c, id, false, nframes, nframes_out, ROWS_AUDIO, false, &F, [&](const AudioSlot &s) { on = s.b_tone_on && (bool)c->tone; }));
+    if (!on) return fail(PSDR_ERR_NO_DATA, "client %d had no tone decoder in the last demodulation batch", id);
+    HIPCHK(hipSetDevice(c->device));
+    PSDRCHK(drain(c));
+    std::vector<ToneRec> rec(F);
+    HIPCHK(hipMemcpy(rec.data(), c->tone.rec + fetch_row(id, (size_t)c->max_batch, 0), F * sizeof(ToneRec), hipMemcpyDeviceToHost));
+    for (size_t f = 0; f < F; f++) {
+        if (tone) tone[f] = rec[f].tone;
+        if (level) level[f] = rec[f].level;
+        if (open) open[f] = rec[f].open;
+    }
+    return PSDR_OK;
+}
 extern "C" int psdr_read_noise(psdr_ctx *c, int id, int nframes, float *w, int *nframes_out) {
     if (!c || !w) return fail(PSDR_ERR_INVALID, "null argument");
     size_t F = 0;
