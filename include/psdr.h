@@ -697,6 +697,69 @@ int psdr_tone_defaults(double audio_rate, psdr_tone_config *out);          /* ne
 int psdr_tone_table(const double **hz, int *n);                            /* needs no context */
 int psdr_client_set_tone_decoder(psdr_ctx *ctx, int id, const psdr_tone_config *cfg);   /* NULL: off */
 int psdr_read_tone(psdr_ctx *ctx, int id, int nframes, int32_t *tone, float *level, int32_t *open, int *nframes_out);
+/* CW decoder: Morse text, speed and pitch of the signal a client's audio carries, per client on the audio rows.  It READS the rows
+ * as the demodulator wrote them - the tone decoder's reading point: behind the squelch, in front of the audio blanker, the noise
+ * reduction and the audio filter - and never writes them: every other output of the client is that of a client without it.
+ *   Stream.  The client's rows in frame order, a NaN-flagged frame entering as zeros, sample t counting from the state's start.
+ *   Hop.  H samples: 32 below audio_rate 8000, 64 below 16000, 128 below 32000, else 256 - 4 to 8 ms.
+ *   Lanes.  Lane k = 0..63 listens at f_k = 250 + 25 k Hz.  Phase increment, the seed from the two 4096-entry tables at the exact
+ *     32-bit phase of the hop's first sample, one rotation per sample and the single f32 accumulator are the tone decoder's, over
+ *     H samples: C[b][k].  E[b][k] = |C[b][k] + C[b-1][k]|^2 (C[-1] = 0), a rectangular window of 2 H samples whose first nulls lie
+ *     62 to 125 Hz off: lanes 25 Hz apart lose under 1 dB between them.  An E that is not finite enters as 0.
+ *   Pitch.  A_k <- A_k + (E_k - A_k) / 64 per hop.  The candidates are the lanes with |f_k - pitch_hz| <= search_hz and always the
+ *     lane nearest to pitch_hz (a tie goes up), where the followed lane p starts.  Behind the A update of a hop, q = the lowest
+ *     candidate with the largest A (on the bit patterns); p becomes q only when A_q > 2 A_p.  e = E[b][p] with the new p.
+ *   Levels.  hi <- max(e, hi - hi / 128); lo = the 16th smallest (0-based, ordered as unsigned integers on the f32 bit patterns) of
+ *     the last 128 values of e.  The signal is present when 128 hops are in, hi is finite and above 0 (silence keys nothing) and hi >= ratio * lo with
+ *     ratio = (float)pow(10, snr_db / 10).  Raw key = present && e >= hi / 4 - half the amplitude, so a mark reads as long as it was
+ *     sent, to a hop.  For noise alone lo is 0.134 of the mean power and hi about 5 times the mean, some 16 dB apart; the
+ *     default 22 dB means about 13 dB of signal over the mean noise in the window's bandwidth.  Nobody has tried it on off-air CW.
+ *   Keying and timing, integers, in hops.  u is the dot length in 1/16 hop; it starts at round(16 * 1.2 / wpm * audio_rate / H) and
+ *     stays inside what 40 and 10 WPM give.  A raw key change is taken once it has held g = max(1, u / 64) hops; the run it starts
+ *     counts from its first hop, the run it ends stops in front of it.  A mark of len hops that ends is a dit if 16 len < 2 u, else
+ *     a dah; the code starts at 1 and is shifted left, the low bit 1 for a dah; more than 7 elements stay "too long".  With
+ *     track_speed, u <- u + floor((16 len - u) / 4) behind a dit and u + floor((floor(16 len / 3) - u) / 4) behind a dah.  When a
+ *     space reaches 2 u the code's character is appended - the ITU-R M.1677 letters, figures and . , : ? ' - / ( ) " = + @, an
+ *     unknown or too long code gives '*' -; when it reaches 5 u one ' ' is appended, once per gap and only behind a character.
+ *   Records.  Frame f's record is the state behind the last hop that is complete at the frame's last sample: nchars = the text's
+ *     length modulo 2^32, wpm = 1.2 audio_rate / (H u / 16), pitch_hz = f_p, level = hi / H^2 - the squared amplitude of a steady
+ *     tone in the units of the rows -, key = the debounced key; before the first hop all zero but pitch_hz, the starting lane's.
+ *     wpm and the scale are computed in double and rounded once.  Any split of the same frames into batches gives the same bits,
+ *     records and text.  phantomsdr_amd/csrc/cwplan.h is the one definition of all of it, for the device and a host program alike.
+ *   Who.  Every client of a batch whose kind writes audio rows; a PSDR_IQ client is refused, a client that becomes one keeps its
+ *     setting and is not listed.  The state is carried across batches and across dropped or flagged frames and stands still while
+ *     the client is paused.  It starts from zero when the call switches the decoder on (again, too), on a mode change and on a
+ *     retune.  Per client slot 2352 bytes of state, 1024 bytes of text and 24 bytes per frame of a batch for the records.
+ * psdr_client_set_cw_decoder: any thread; in force from the client's next batch; cfg = NULL switches it off.  PSDR_ERR_INVALID,
+ *   with nothing changed and a text of its own each, for an id outside the slots, a slot without a client, (cfg != NULL) a PSDR_IQ
+ *   client, pitch_hz outside [300, 1800], search_hz outside [0, 800], wpm outside [10, 40] (or any of them not finite),
+ *   track_speed outside 0..1, snr_db not finite or outside [6, 40]; then PSDR_ERR_STATE for a context whose audio_rate is outside
+ *   [4000, 48000] - in this order.  The device state is allocated with the context's first such client, all or none:
+ *   PSDR_ERR_NOMEM and the setting unchanged if that fails.  A context without such a client allocates nothing, a batch without one
+ *   launches nothing.
+ * psdr_cw_defaults: needs no context.  PSDR_ERR_INVALID for a null pointer or an audio_rate outside [4000, 48000].
+ * psdr_read_cw: psdr_read_tone's contract - the records of the last demodulation batch, nframes the room of the arrays (any of
+ *   which may be null), synchronises; a client whose last batch ran without the decoder reads PSDR_ERR_NO_DATA, as does one that
+ *   was not part of the batch or was demodulated as PSDR_IQ.
+ * psdr_read_cw_text: characters from .. total - 1 of the client's text since the state last started - the first cap of them, cap
+ *   being the room of out; no terminator is written -, their number in *n_out, total in *total_out (out with cap 0, n_out and
+ *   total_out may be null); synchronises.  The device keeps the last 1024 characters per slot in a byte ring: a `from` older than
+ *   that returns PSDR_ERR_NO_DATA; from == total returns PSDR_OK with 0 characters; from beyond total PSDR_ERR_INVALID.  A client
+ *   without the decoder reads PSDR_ERR_NO_DATA; a start that is pending (the call came, no batch since) reads total 0.
+ * Nothing of it goes through psdr_fetch_* yet, and there is no psdr_group_* call: a group's clients have no CW decoder. */
+#define PSDR_CW_LANES 64
+typedef struct {
+    double pitch_hz;   /* [300, 1800], default 700: where the listener put the signal in the audio */
+    double search_hz;  /* [0, 800], default 100: lanes within it may be followed; 0: the nearest lane only */
+    double wpm;        /* [10, 40], default 20: the speed the dot length starts from */
+    int track_speed;   /* 1 (default): the dot length follows the sender; 0: it stays at wpm */
+    double snr_db;     /* [6, 40], default 22: keying is recognised only while peak >= ratio * floor */
+} psdr_cw_config;
+int psdr_cw_defaults(double audio_rate, psdr_cw_config *out);                 /* needs no context */
+int psdr_client_set_cw_decoder(psdr_ctx *ctx, int id, const psdr_cw_config *cfg);   /* NULL: off */
+int psdr_read_cw(psdr_ctx *ctx, int id, int nframes, uint32_t *nchars, float *wpm, float *pitch_hz, float *level, int32_t *key,
+                 int *nframes_out);
+int psdr_read_cw_text(psdr_ctx *ctx, int id, uint64_t from, char *out, size_t cap, size_t *n_out, uint64_t *total_out);
 /* AGC profile: speed, target, gain cap and manual gain per client.  The context's AGC is the reference's - target 0.2, attack
  * 50 ms, release 300 ms (psdr_set_post_chain) - for every client; a profile replaces these numbers for one client: a fast AGC for
  * CW, a slow one for broadcast, a bound on the gain a quiet channel is pumped up by, or no AGC at all and a fixed gain, which is

@@ -86,6 +86,17 @@ def tone_defaults(audio_rate):
     return dict(want=p.want, gate=p.gate, snr_db=p.snr_db, min_level=p.min_level, attack_blocks=p.attack_blocks, hang_blocks=p.hang_blocks)
 
 
+CW_FIELDS = ("pitch_hz", "search_hz", "wpm", "track_speed", "snr_db")
+
+
+def cw_defaults(audio_rate):
+    """the CW decoder's defaults at `audio_rate` as a dict for AudioClient.set_cw_decoder(**...) (psdr_cw_defaults; needs no
+    context): pitch 700 Hz, search 100 Hz, 20 WPM, speed tracking on, snr_db 22"""
+    p = _lib.psdr_cw_config()
+    check(_lib.load().psdr_cw_defaults(float(audio_rate), C.byref(p)))
+    return {k: getattr(p, k) for k in CW_FIELDS}
+
+
 def noise_reduction_preset(kind):
     """(depth_db, beta) of a noise reduction preset for AudioClient.set_noise_reduction (psdr_noise_reduction_preset; needs no
     context): "light" (8 dB, 1), "normal" (14 dB, 1.5) or "strong" (22 dB, 2), or an NR_* constant"""
@@ -727,6 +738,39 @@ class AudioClient:
         got = C.c_int(0)
         check(self.ctx.lib.psdr_read_tone(self.ctx.h, self.id, F, _ptr(t), _ptr(lv), _ptr(o), C.byref(got)))
         return t[:got.value], lv[:got.value], o[:got.value]
+
+    def set_cw_decoder(self, on=True, **fields):
+        """Morse text, speed and pitch from the client's audio rows as the demodulator wrote them (psdr_client_set_cw_decoder).
+        on false or None: off.  Keyword arguments replace single fields of cw_defaults(): pitch_hz, search_hz, wpm, track_speed,
+        snr_db.  The state and the text start from zero with every call that switches it on."""
+        if not on:
+            check(self.ctx.lib.psdr_client_set_cw_decoder(self.ctx.h, self.id, None))
+            return
+        p = _lib.psdr_cw_config(pitch_hz=700.0, search_hz=100.0, wpm=20.0, track_speed=1, snr_db=22.0)
+        for k, v in fields.items():
+            if k not in CW_FIELDS:
+                raise TypeError("set_cw_decoder: unknown field %r" % k)
+            setattr(p, k, int(v) if k == "track_speed" else float(v))
+        check(self.ctx.lib.psdr_client_set_cw_decoder(self.ctx.h, self.id, C.byref(p)))
+
+    def read_cw(self, nframes=None):
+        """(nchars[F] uint32, wpm[F] float32, pitch_hz[F] float32, level[F] float32, key[F] int32) of the last demod batch (psdr.h:
+        psdr_read_cw): per frame the text's length so far, the speed the dot length stands at, the followed lane's pitch, the
+        squared amplitude of the peak, and the debounced key"""
+        F = nframes or self.ctx.last_demod_frames or self.ctx.last_nframes
+        n, w, p, lv, k = np.empty(F, np.uint32), np.empty(F, np.float32), np.empty(F, np.float32), np.empty(F, np.float32), np.empty(F, np.int32)
+        got = C.c_int(0)
+        check(self.ctx.lib.psdr_read_cw(self.ctx.h, self.id, F, _ptr(n), _ptr(w), _ptr(p), _ptr(lv), _ptr(k), C.byref(got)))
+        g = got.value
+        return n[:g], w[:g], p[:g], lv[:g], k[:g]
+
+    def read_cw_text(self, since=0):
+        """(text, total): the characters since .. total - 1 of the client's text since the decoder's state last started
+        (psdr_read_cw_text); the device keeps the last 1024"""
+        buf = C.create_string_buffer(1024)
+        n, total = C.c_size_t(0), C.c_uint64(0)
+        check(self.ctx.lib.psdr_read_cw_text(self.ctx.h, self.id, int(since), buf, 1024, C.byref(n), C.byref(total)))
+        return buf.raw[:n.value].decode("ascii"), total.value
 
     def set_agc_profile(self, profile, **fields):
         """the client's own AGC numbers in the post chain (psdr_client_set_agc_profile).  `profile`: None - back to the context's

@@ -9,6 +9,7 @@
 #include "nr.h"
 #include "anb.h"
 #include "tone.h"
+#include "cw.h"
 
 // The context's first client of an optional feature (ctx.h: the structs behind `iq`): what the feature allocates is built whole
 // and only then moved in, so a failed call leaves the context as it was.  msg: the failure's text, with the bytes and the
@@ -31,6 +32,7 @@ static int first_auto_notch(psdr_ctx *c) { return first_use(c, c->notch, "auto-n
 static int first_noise_reduction(psdr_ctx *c) { return first_use(c, c->nr, "noise reduction state and tables (%zu bytes): %s"); }
 static int first_audio_blanker(psdr_ctx *c) { return first_use(c, c->anb, "audio blanker state (%zu bytes): %s"); }
 static int first_tone_decoder(psdr_ctx *c) { return first_use(c, c->tone, "tone decoder state, records and tables (%zu bytes): %s"); }
+static int first_cw_decoder(psdr_ctx *c) { return first_use(c, c->cw, "CW decoder state, text, records and tables (%zu bytes): %s"); }
 // the detector's state of one slot back to zero: sums, counter, both automatic entries (stream-ordered on `side`)
 static int notch_zero(psdr_ctx *c, size_t slot) {
     HIPCHK(hipMemsetAsync(c->notch.acc + slot * (size_t)c->n, 0, (size_t)c->n * sizeof(float), c->side));
@@ -376,6 +378,30 @@ extern "C" int psdr_tone_table(const double **hz, int *n) {
     *hz = TONE_HZ, *n = TONE_N;
     return PSDR_OK;
 }
+extern "C" int psdr_client_set_cw_decoder(psdr_ctx *c, int id, const psdr_cw_config *cfg) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mtx);
+    switch (cw_check(c->aslots.data(), c->aslots.size(), id, cfg, c->cfg.audio_rate)) {
+    case CW_OK: break;
+    case CW_BAD_ID: return fail(PSDR_ERR_INVALID, "CW decoder: id %d outside 0..%d", id, (int)c->aslots.size() - 1);
+    case CW_INACTIVE: return fail(PSDR_ERR_INVALID, "no audio client with id %d", id);
+    case CW_IQ: return fail(PSDR_ERR_INVALID, "CW decoder: client %d is a PSDR_IQ client, which has no audio rows", id);
+    case CW_BAD_PITCH: return fail(PSDR_ERR_INVALID, "CW decoder: pitch_hz %g is not a finite number inside [%g, %g]", cfg->pitch_hz, CW_PITCH_MIN, CW_PITCH_MAX);
+    case CW_BAD_SEARCH: return fail(PSDR_ERR_INVALID, "CW decoder: search_hz %g is not a finite number inside [%g, %g]", cfg->search_hz, CW_SEARCH_MIN, CW_SEARCH_MAX);
+    case CW_BAD_WPM: return fail(PSDR_ERR_INVALID, "CW decoder: wpm %g is not a finite number inside [%g, %g]", cfg->wpm, CW_WPM_MIN, CW_WPM_MAX);
+    case CW_BAD_TRACK: return fail(PSDR_ERR_INVALID, "CW decoder: track_speed %d outside 0..1", cfg->track_speed);
+    case CW_BAD_SNR: return fail(PSDR_ERR_INVALID, "CW decoder: snr_db %g is not a finite number inside [%g, %g]", cfg->snr_db, CW_SNR_MIN, CW_SNR_MAX);
+    case CW_BAD_RATE: return fail(PSDR_ERR_STATE, "CW decoder: the context's audio_rate %d is outside [%d, %d]", c->cfg.audio_rate, CW_RATE_MIN, CW_RATE_MAX);
+    }
+    if (cfg) PSDRCHK(first_cw_decoder(c));
+    cw_apply(c->aslots[id], cfg, c->cfg.audio_rate);
+    return PSDR_OK;
+}
+extern "C" int psdr_cw_defaults(double audio_rate, psdr_cw_config *out) {
+    if (!out) return fail(PSDR_ERR_INVALID, "null argument");
+    if (!cw_defaults(audio_rate, out)) return fail(PSDR_ERR_INVALID, "CW decoder defaults: audio_rate %g outside [%d, %d]", audio_rate, CW_RATE_MIN, CW_RATE_MAX);
+    return PSDR_OK;
+}
 extern "C" int psdr_client_set_agc_profile(psdr_ctx *c, int id, const psdr_agc_profile *p) {
     if (!c) return fail(PSDR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mtx);
@@ -559,6 +585,7 @@ struct BatchPlan {
     NrPlan nr;
     AnbPlan anb;
     TonePlan tone;
+    CwPlan cw;
     AgcPlan ag;
     bool chain = false;  // the post chain follows: it is on, and somebody is in it
     // of the optional features: the rows of the result set this batch writes and the detector's table - null where the context has
@@ -594,6 +621,7 @@ static int batch_plan(psdr_ctx *c, int nframes, const uint32_t *band, BatchPlan 
     if (c->nr) b.nr = nr_plan(slots, S, c->demod_seq, c->nr.tab.host(b.ring), nr_a_up(c->cfg.audio_rate));
     if (c->anb) b.anb = anb_plan(slots, S, c->demod_seq, c->anb.tab.host(b.ring));
     if (c->tone) b.tone = tone_plan(slots, S, c->demod_seq, b.chain, c->tone.tab.host(b.ring));
+    if (c->cw) b.cw = cw_plan(slots, S, c->demod_seq, c->cw.tab.host(b.ring));
     if (c->agc_prof && b.chain) b.ag = agc_profile_plan(slots, S, c->demod_seq, c->agc_prof.tab.host(b.ring));
     return PSDR_OK;
 }
@@ -615,6 +643,11 @@ static int batch_begin(psdr_ctx *c, const BatchPlan &b) {
     for (size_t slot : b.tone.zero) {
         HIPCHK(hipMemsetAsync(c->tone.state + slot, 0, sizeof(ToneState), c->side));
         HIPCHK(hipMemsetAsync(c->tone.hist + slot * (size_t)c->tone.ring * TONE_LANES, 0, (size_t)c->tone.ring * TONE_LANES * sizeof(ToneC), c->side));
+    }
+    // ... and the CW decoders: state and text ring (cw_plan has taken cw_fresh off these slots)
+    for (size_t slot : b.cw.zero) {
+        HIPCHK(hipMemsetAsync(c->cw.state + slot, 0, sizeof(CwState), c->side));
+        HIPCHK(hipMemsetAsync(c->cw.text + slot * (size_t)CW_TEXT, 0, CW_TEXT, c->side));
     }
     // ... and the noise floors that start from zero: sums and record (noise_plan has taken nf_fresh off these slots)
     for (size_t slot : b.nf.zero) {
@@ -649,6 +682,7 @@ static int batch_begin(psdr_ctx *c, const BatchPlan &b) {
     if (b.nr.any()) HIPCHK(c->nr.tab.upload(b.ring, (size_t)b.nr.n, c->side));
     if (b.anb.any()) HIPCHK(c->anb.tab.upload(b.ring, (size_t)b.anb.n, c->side));
     if (b.tone.any()) HIPCHK(c->tone.tab.upload(b.ring, (size_t)(b.tone.n + b.tone.ncopy), c->side));
+    if (b.cw.any()) HIPCHK(c->cw.tab.upload(b.ring, (size_t)b.cw.n, c->side));
     return PSDR_OK;
 }
 
@@ -832,6 +866,19 @@ static int launch_tone_decoder(psdr_ctx *c, const BatchPlan &b, int nframes, con
     if (b.tone.gated) *chain_drop = c->tone.drop;
     return PSDR_OK;
 }
+// ... the CW decoder, at the tone decoder's reading point: it reads the listed clients' rows as the demodulator left them and
+// writes the frames' records and the clients' text
+static int launch_cw_decoder(psdr_ctx *c, const BatchPlan &b, int nframes) {
+    CwArgs ca{};
+    ca.list = c->cw.tab.dev(b.ring), ca.nlist = b.cw.n;
+    ca.tab = c->cw.plan;
+    ca.audio = c->d_audio, ca.nan_flags = c->d_nan;
+    ca.state = c->cw.state, ca.text = c->cw.text, ca.rec = c->cw.rec;
+    ca.nframes = nframes, ca.max_batch = c->max_batch, ca.h = c->n / 2;
+    ProfScope ps(c, K_AUDIO_CW, c->side);
+    HIPCHK(audio_cw_launch(ca, c->side));
+    return PSDR_OK;
+}
 // ... the audio blanker, in front of the noise reduction, the audio filter and the chain: it works on the listed clients' rows in
 // place
 static int launch_audio_blanker(psdr_ctx *c, const BatchPlan &b, int nframes) {
@@ -904,6 +951,7 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     if (b.nf.any()) PSDRCHK(launch_noise_floor(c, b, a));
     if (b.sq.any()) PSDRCHK(launch_squelch(c, b, nframes, &chain_drop));
     if (b.tone.any()) PSDRCHK(launch_tone_decoder(c, b, nframes, &chain_drop));
+    if (b.cw.any()) PSDRCHK(launch_cw_decoder(c, b, nframes));
     if (b.anb.any()) PSDRCHK(launch_audio_blanker(c, b, nframes));
     if (b.nr.any()) PSDRCHK(launch_noise_reduction(c, b, nframes));
     if (b.af.any()) PSDRCHK(launch_audio_filter(c, b, nframes));

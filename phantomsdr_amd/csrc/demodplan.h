@@ -94,6 +94,15 @@ struct AudioSlot {
     float tone_ratio = 1.f, tone_min_level = 0.f;
     bool b_tone_on = false, tone_fresh = false;
     int tone_mode = PSDR_USB, tone_l = 0, tone_r = 0, tone_m = 0;
+    // psdr_client_set_cw_decoder (cwplan.h): the parameters as the table holds them - the starting lane, the candidate lanes, the
+    // starting dot length, track_speed, the ratio; b_cw_on: the last batch ran with it (psdr_read_cw); cw_fresh, cw_mode, cw_l,
+    // cw_r, cw_m: as the tone decoder's
+    int cw_on = 0;
+    int cw_p0 = 18, cw_u0 = 180, cw_track = 1;
+    uint64_t cw_cand = 0;
+    float cw_ratio = 1.f;
+    bool b_cw_on = false, cw_fresh = false;
+    int cw_mode = PSDR_USB, cw_l = 0, cw_r = 0, cw_m = 0;
 };
 
 // The client parameter ring's slot.  [ClientParams x S][int x S]: the batch's list and, for the post chain, the list index of

@@ -426,6 +426,60 @@ extern "C" int psdr_read_tone(psdr_ctx *c, int id, int nframes, int32_t *tone, f
     }
     return PSDR_OK;
 }
+// the CW decoder's records of the last batch; any of the five arrays may be null
+extern "C" int psdr_read_cw(psdr_ctx *c, int id, int nframes, uint32_t *nchars, float *wpm, float *pitch_hz, float *level, int32_t *key, int *nframes_out) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    size_t F = 0;
+    bool on = false;
+    PSDRCHK(read_begin(c, id, false, nframes, nframes_out, ROWS_AUDIO, false, &F, [&](const AudioSlot &s) { on = s.b_cw_on && (bool)c->cw; }));
+    if (!on) return fail(PSDR_ERR_NO_DATA, "client %d had no CW decoder in the last demodulation batch", id);
+    HIPCHK(hipSetDevice(c->device));
+    PSDRCHK(drain(c));
+    std::vector<CwRec> rec(F);
+    HIPCHK(hipMemcpy(rec.data(), c->cw.rec + fetch_row(id, (size_t)c->max_batch, 0), F * sizeof(CwRec), hipMemcpyDeviceToHost));
+    for (size_t f = 0; f < F; f++) {
+        if (nchars) nchars[f] = rec[f].nchars;
+        if (wpm) wpm[f] = rec[f].wpm;
+        if (pitch_hz) pitch_hz[f] = rec[f].pitch_hz;
+        if (level) level[f] = rec[f].level;
+        if (key) key[f] = rec[f].key;
+    }
+    return PSDR_OK;
+}
+// the CW decoder's text since the state last started, from the slot's ring
+extern "C" int psdr_read_cw_text(psdr_ctx *c, int id, uint64_t from, char *out, size_t cap, size_t *n_out, uint64_t *total_out) {
+    if (!c || (!out && cap)) return fail(PSDR_ERR_INVALID, "null argument");
+    bool pending = false;
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);
+        if (id < 0 || (size_t)id >= c->aslots.size()) return fail(PSDR_ERR_INVALID, "CW text: id %d outside 0..%d", id, (int)c->aslots.size() - 1);
+        const AudioSlot &s = c->aslots[id];
+        if (!s.active) return fail(PSDR_ERR_INVALID, "no audio client with id %d", id);
+        if (!s.cw_on || !c->cw) return fail(PSDR_ERR_NO_DATA, "client %d has no CW decoder", id);
+        pending = s.cw_fresh;
+    }
+    uint64_t total = 0;
+    std::vector<uint8_t> ring;
+    if (!pending) {
+        HIPCHK(hipSetDevice(c->device));
+        PSDRCHK(drain(c));
+        CwState st;
+        HIPCHK(hipMemcpy(&st, c->cw.state + (size_t)id, sizeof(CwState), hipMemcpyDeviceToHost));
+        total = st.nchars;
+        if (from < total && total - from <= (uint64_t)CW_TEXT) {
+            ring.resize(CW_TEXT);
+            HIPCHK(hipMemcpy(ring.data(), c->cw.text + (size_t)id * CW_TEXT, CW_TEXT, hipMemcpyDeviceToHost));
+        }
+    }
+    if (from > total) return fail(PSDR_ERR_INVALID, "CW text: from %llu is beyond the text's %llu characters", (unsigned long long)from, (unsigned long long)total);
+    if (total - from > (uint64_t)CW_TEXT)
+        return fail(PSDR_ERR_NO_DATA, "CW text: from %llu is older than the last %d of %llu characters", (unsigned long long)from, CW_TEXT, (unsigned long long)total);
+    const size_t n = std::min((size_t)(total - from), cap);
+    for (size_t j = 0; j < n; j++) out[j] = (char)ring[(from + j) % CW_TEXT];
+    if (n_out) *n_out = n;
+    if (total_out) *total_out = total;
+    return PSDR_OK;
+}
 extern "C" int psdr_read_noise(psdr_ctx *c, int id, int nframes, float *w, int *nframes_out) {
     if (!c || !w) return fail(PSDR_ERR_INVALID, "null argument");
     size_t F = 0;

@@ -69,18 +69,24 @@ struct ToneTables {
     int nb;
     float lscale;
 };
-inline void tone_tables(ToneTables &t, double audio_rate) {
-    memset(&t, 0, sizeof(t));
+// the two seed tables and one lane's increment and rotation (hz <= 0: a lane without a tone, 0 and 1): the CW decoder's lanes
+// (cwplan.h) are made by the same two functions
+inline void tone_seed_tables(ToneTables &t) {
     for (int j = 0; j < TONE_TAB; j++) {
         const double a = 2.0 * M_PI * j / 4096.0, b = 2.0 * M_PI * j / 16777216.0;
         t.coarse[j][0] = (float)std::cos(a), t.coarse[j][1] = (float)std::sin(a);
         t.fine[j][0] = (float)std::cos(b), t.fine[j][1] = (float)std::sin(b);
     }
-    for (int k = 0; k < TONE_LANES; k++) {
-        t.inc[k] = k < TONE_N ? (uint32_t)std::floor(TONE_HZ[k] / audio_rate * 4294967296.0 + 0.5) : 0u;
-        const double a = 2.0 * M_PI * (double)t.inc[k] / 4294967296.0;
-        t.rot[k][0] = (float)std::cos(a), t.rot[k][1] = (float)std::sin(a);
-    }
+}
+inline void tone_lane(ToneTables &t, int k, double hz, double audio_rate) {
+    t.inc[k] = hz > 0 ? (uint32_t)std::floor(hz / audio_rate * 4294967296.0 + 0.5) : 0u;
+    const double a = 2.0 * M_PI * (double)t.inc[k] / 4294967296.0;
+    t.rot[k][0] = (float)std::cos(a), t.rot[k][1] = (float)std::sin(a);
+}
+inline void tone_tables(ToneTables &t, double audio_rate) {
+    memset(&t, 0, sizeof(t));
+    tone_seed_tables(t);
+    for (int k = 0; k < TONE_LANES; k++) tone_lane(t, k, k < TONE_N ? TONE_HZ[k] : 0.0, audio_rate);
     t.nb = tone_nb(audio_rate);
     double sum = 0;
     for (int j = 0; j < t.nb; j++) {
