@@ -10,7 +10,7 @@ import pytest
 import cw_model as M
 from conftest import ROOT
 
-RATES = (4000, 8000, 12000, 48000)
+RATES = (4000, 8000, 12000, 16000, 48000)
 TEXT = "PARIS CQ DE K1ABC 599 = ? /"
 # the lowest signal-to-noise ratio, in the 2 H window's bandwidth (rate / 2 H: SNR = a^2 H / (2 sigma^2)) and in 3 dB steps, at which
 # decode64() still reads TEXT at 20 WPM exactly with the seed below: measured 24 dB (21 dB gives `5OI*` for `599`); DESIGN 3.21
@@ -198,6 +198,14 @@ def test_defaults_and_tables(exe):
         morse = bytes.fromhex(d["morse"])
         assert {c: chr(b) for c, b in enumerate(morse) if b != ord("*")} == M.BY_CODE and len(M.BY_CODE) == 49
     assert M.lane_hz(63) == 1825.0 < 4000 / 2
+    # the hop length's class boundaries, on both sides
+    edges = {15999: 64, 16000: 128, 31999: 128, 32000: 256}
+    out = M.run_script(exe, "".join(f"tables {r}\n" for r in edges)).splitlines()
+    assert len(out) == len(edges)
+    for line, (rate, H) in zip(out, edges.items()):
+        d = dict(kv.split("=", 1) for kv in line.split()[1:])
+        assert float(d["rate"]) == rate and int(d["H"]) == H == M.hop_of(rate), line
+    assert M.hop_of(15999) == 64 and M.hop_of(16000) == 128 and M.hop_of(31999) == 128 and M.hop_of(32000) == 256
 
 
 def test_every_listed_character_round_trips_through_a_synthetic_keying(exe):

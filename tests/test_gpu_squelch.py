@@ -63,11 +63,11 @@ def window(shape):
 
 
 class Ctx:
-    def __init__(self, shape, n, max_clients, maxb=MAXB, post=False, agc=1, pcm16=0, raw=None):
+    def __init__(self, shape, n, max_clients, maxb=MAXB, post=False, agc=1, pcm16=0, raw=None, rate=RATE):
         from phantomsdr_amd import Context
         is_real, N, _ = SHAPES[shape]
         self.shape, self.n = shape, n
-        self.ctx = Context(N, is_real, LEVELS, additional_size=n, audio_fft_size=n, audio_rate=RATE, input_format="f32", max_batch=maxb,
+        self.ctx = Context(N, is_real, LEVELS, additional_size=n, audio_fft_size=n, audio_rate=rate, input_format="f32", max_batch=maxb,
                            max_clients=max_clients)
         raw = stream(shape) if raw is None else raw
         self.d = self.ctx.dev_alloc(raw.nbytes)

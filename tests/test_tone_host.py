@@ -10,10 +10,11 @@ import squelch_model
 import tone_model as M
 from conftest import ROOT
 
-RATES = (8000, 12000, 48000)
+RATES = (2000, 8000, 12000, 48000)
 SNR_DB = 22.0
-# the level against a float64 evaluation with exact phases, measured once on tone_inputs() at the three rates: worst relative error
-# 7.82e-6 (the f32 sum over up to 19 200 samples); the bound is four times that, for other seeds
+# the level against a float64 evaluation with exact phases, measured once on tone_inputs() at 8000, 12000 and 48000: worst relative
+# error 7.82e-6 (the f32 sum over up to 19 200 samples); the bound is four times that, for other seeds.  Rate 2000, added to RATES
+# later, shows 9.04e-6 - the worst of the four now - under the same bound
 LEVEL_ERR_MEASURED = 7.82e-6
 LEVEL_ERR_BOUND = 4 * LEVEL_ERR_MEASURED
 
