@@ -760,6 +760,93 @@ int psdr_client_set_cw_decoder(psdr_ctx *ctx, int id, const psdr_cw_config *cfg)
 int psdr_read_cw(psdr_ctx *ctx, int id, int nframes, uint32_t *nchars, float *wpm, float *pitch_hz, float *level, int32_t *key,
                  int *nframes_out);
 int psdr_read_cw_text(psdr_ctx *ctx, int id, uint64_t from, char *out, size_t cap, size_t *n_out, uint64_t *total_out);
+/* RTTY decoder: Baudot text and tuning offset of the radioteletype signal a client's audio carries, per client on the audio rows.
+ * It READS the rows as the demodulator wrote them - the tone and CW decoders' reading point: behind the squelch, in front of the audio
+ * blanker, the noise reduction and the audio filter - and never writes them: every other output of the client is that of a client
+ * without it.
+ *   Stream.  The client's rows in frame order, a NaN-flagged frame entering as zeros, sample t counting from the state's start.
+ *   Hop.  H samples: 8 below audio_rate 8000, 16 below 16000, 32 below 32000, else 64 - 1 to 2 ms, 6.7 hops per bit at least.
+ *   Lanes.  32 lanes in 16 pairs; pair j = 0..15 sits d_j = 20 (j - 8) Hz off the configured tones: lane 2 j listens at
+ *     mark_hz + d_j, lane 2 j + 1 at mark_hz + shift_hz + d_j.  Phase increment round(f / audio_rate * 2^32) in double, the seed from
+ *     the two 4096-entry tables at the exact 32-bit phase of the hop's first sample, one rotation per sample and the single f32
+ *     accumulator, n ascending, are the tone decoder's, over H samples: C[b][k].  A signal half-way between two pairs loses 0.7 dB
+ *     in a bit-long window at 45.45 baud.
+ *   Bit window.  Wn = max(2, round(audio_rate / (baud H))) hops (7 to 22); S[b][k] = sum_{j < Wn} C[b - Wn + 1 + j][k], j ascending,
+ *     hops before the start counting as 0, summed anew from the kept correlations every hop (no running sum: nothing drifts);
+ *     E[b][k] = |S|^2, an E that is not finite entering as 0.
+ *   Follower.  A_j <- A_j + ((E_2j + E_2j+1) - A_j) / 64 per hop.  The candidates are the pairs with |d_j| <= search_hz and always
+ *     pair 8, where the followed pair p starts; q = the lowest candidate with the largest A (on the bit patterns); p becomes q only
+ *     when A_q > 2 A_p.  m = E[2 p], s = E[2 p + 1] with the new p.
+ *   Slicer with threshold correction.  pm = max(m, em - em / 256), ps = max(s, es - es / 256); em <- max(pm, ps / 16),
+ *     es <- max(ps, pm / 16): a peak is held at 1/16 of the other at least, so that the tone that was not sent during a long idle
+ *     is not sliced at its own leakage (without the floor the first start bit behind an idle of a second is taken half a bit
+ *     early and the character is lost).  The bit is mark iff m es >= s em, in f32 products: a faded tone still slices at its own
+ *     half, and silence reads as mark.
+ *   Presence.  t = max(m, s), n = min(m, s); T <- T + (t - T) / 256, Nn <- Nn + (n - Nn) / 256.  The signal is present when 256
+ *     hops are in, T is finite and above 0 and T >= ratio Nn, ratio = (float)pow(10, snr_db / 10).  line = present ? bit : mark:
+ *     an absent signal is an idle line and prints nothing.  (Alternating bits keep the window across a transition all the time:
+ *     T / Nn falls to 8 dB there at any signal-to-noise ratio; with a weight of 1/64 noise alone reached 8.3 dB within 60 s, with
+ *     1/256 it stays under 6.4 dB - DESIGN.md 3.22.)
+ *   Framing, integers in 1/16 hop.  u = round(16 audio_rate / (baud H)), in double.  When idle, a hop whose line is space directly
+ *     behind a hop whose line is mark starts a character at t0 = 16 (that hop).  The sample points are c_i = t0 + floor(u / 2) + i u,
+ *     i = 0..6, each read at the hop b with 16 b <= c_i < 16 (b + 1): i = 0 the start bit - mark there is a false start: back to
+ *     idle, nothing counted -, i = 1..5 the data bits, least significant first, mark = 1, i = 6 the stop bit: mark and the code is
+ *     taken, space and one framing error is counted and the code dropped.  Idle again from the hop behind the stop sample.  The
+ *     window trails by half a bit, so the sample is the integral over the whole sent bit.
+ *   Baudot.  ITA2 with the US-TTY figures.  Code 31 switches to letters, code 27 to figures, both print nothing, as does code 0;
+ *     code 4 prints ' ' and with usos returns to letters; code 8 prints CR, code 2 LF, figures-S 0x07.  The state starts in letters.
+ *   Records.  Frame f's record is the state behind the last hop that is complete at the frame's last sample: nchars = the text's
+ *     length modulo 2^32, errors = the framing errors modulo 2^32, offset_hz = d_p, level = 4 max(em, es) / (Wn H)^2 - the squared
+ *     amplitude of a steady tone in the units of the rows, the scale computed in double and rounded once -, quality = T / Nn as
+ *     one f32 division, 0 when Nn is 0 or the quotient is not finite, present = the presence flag; before the first hop all zero.
+ *     Any split of the same frames into batches gives the same bits, records and text.  phantomsdr_amd/csrc/rttyplan.h is the one
+ *     definition of all of it, for the device and a host program alike.
+ *   Who.  Every client of a batch whose kind writes audio rows; a PSDR_IQ client is refused, a client that becomes one keeps its
+ *     setting and is not listed.  The state is carried across batches and across dropped or flagged frames (a flagged frame inside
+ *     a transmission can cost the characters up to the next idle) and stands still while the client is paused.  It starts from
+ *     zero when the call switches the decoder on (again, too), on a mode change and on a retune.  Per client slot 6536 bytes of
+ *     state - the last 24 hops' correlations of the 32 lanes (6144), the unfinished hop (256), the followers (64), levels and
+ *     framing (72) -, 1024 bytes of text and 24 bytes per frame of a batch for the records; 416 bytes per listed client in the
+ *     batch's table.
+ *   The default snr_db = 7.5 is measured on the host model: half-way between the 6.4 dB noise alone reaches in
+ *     60 s and the 8.6 dB the quality keeps while the test text is read at 15 dB in the bit window's bandwidth, the lowest ratio
+ *     in 3 dB steps at which it is read exactly.  Nobody has tried it on off-air RTTY.
+ * psdr_client_set_rtty_decoder: any thread; in force from the client's next batch; cfg = NULL switches it off.  PSDR_ERR_INVALID,
+ *   with nothing changed and a text of its own each, for an id outside the slots, a slot without a client, (cfg != NULL) a PSDR_IQ
+ *   client, mark_hz outside [300, 3000], shift_hz of a magnitude outside [85, 1000], baud outside [45, 75] (or any of them not
+ *   finite), usos outside 0..1, search_hz not finite or outside [0, 160], snr_db not finite or outside [3, 30]; then PSDR_ERR_STATE
+ *   for a context whose audio_rate is outside [4000, 48000]; then PSDR_ERR_STATE when the higher tone + 160 Hz lies above
+ *   0.45 audio_rate or the lower tone - 160 Hz below 100 Hz - in this order.  The device state is allocated with the context's
+ *   first such client, all or none: PSDR_ERR_NOMEM and the setting unchanged if that fails.  A context without such a client
+ *   allocates nothing, a batch without one launches nothing.
+ * psdr_rtty_defaults: needs no context; mark_hz is 915 where 2125 + 170 + 160 Hz does not stay under 0.45 audio_rate.
+ *   PSDR_ERR_INVALID for a null pointer or an audio_rate outside [4000, 48000].
+ * psdr_read_rtty: psdr_read_cw's contract - the records of the last demodulation batch, nframes the room of the arrays (any of
+ *   which may be null), synchronises; a client whose last batch ran without the decoder reads PSDR_ERR_NO_DATA, as does one that
+ *   was not part of the batch or was demodulated as PSDR_IQ.
+ * psdr_read_rtty_text: psdr_read_cw_text's contract to the letter: characters from .. total - 1 of the client's text since the state
+ *   last started - the first cap of them, no terminator -, their number in *n_out, total in *total_out (out with cap 0, n_out and
+ *   total_out may be null); synchronises.  The device keeps the last 1024 characters per slot: a `from` older than that returns
+ *   PSDR_ERR_NO_DATA; from == total returns PSDR_OK with 0 characters; from beyond total PSDR_ERR_INVALID.  A client without the
+ *   decoder reads PSDR_ERR_NO_DATA; a start that is pending (the call came, no batch since) reads total 0.
+ * Nothing of it goes through psdr_fetch_* yet, and there is no psdr_group_* call: a group's clients have no RTTY decoder.  Out of
+ * scope: the 100-baud SITOR-B / NAVTEX framing (its demodulator is this one; its 7-bit code and time diversity are not here) and
+ * automatic detection of speed or shift. */
+#define PSDR_RTTY_LANES 32
+#define PSDR_RTTY_SNR_DEFAULT 7.5
+typedef struct {
+    double mark_hz;    /* [300, 3000], default 2125 (915 at an audio_rate that has no room for it): the mark tone in the audio */
+    double shift_hz;   /* 85 <= |shift_hz| <= 1000, default 170: space = mark + shift; negative: the other sideband ("reverse") */
+    double baud;       /* [45, 75], default 45.45 */
+    int usos;          /* 1 (default): a space returns to letters (unshift on space); 0: it does not */
+    double search_hz;  /* [0, 160], default 60: pairs within it may be followed; 0: the configured tones only */
+    double snr_db;     /* [3, 30], default PSDR_RTTY_SNR_DEFAULT: the line is read only while T >= ratio * Nn */
+} psdr_rtty_config;
+int psdr_rtty_defaults(double audio_rate, psdr_rtty_config *out);               /* needs no context */
+int psdr_client_set_rtty_decoder(psdr_ctx *ctx, int id, const psdr_rtty_config *cfg);   /* NULL: off */
+int psdr_read_rtty(psdr_ctx *ctx, int id, int nframes, uint32_t *nchars, uint32_t *errors, float *offset_hz, float *level, float *quality,
+                   int32_t *present, int *nframes_out);
+int psdr_read_rtty_text(psdr_ctx *ctx, int id, uint64_t from, char *out, size_t cap, size_t *n_out, uint64_t *total_out);
 /* AGC profile: speed, target, gain cap and manual gain per client.  The context's AGC is the reference's - target 0.2, attack
  * 50 ms, release 300 ms (psdr_set_post_chain) - for every client; a profile replaces these numbers for one client: a fast AGC for
  * CW, a slow one for broadcast, a bound on the gain a quiet channel is pumped up by, or no AGC at all and a fixed gain, which is

@@ -47,6 +47,12 @@ class psdr_cw_config(C.Structure):
     _fields_ = [("pitch_hz", C.c_double), ("search_hz", C.c_double), ("wpm", C.c_double), ("track_speed", C.c_int), ("snr_db", C.c_double)]
 
 
+class psdr_rtty_config(C.Structure):
+    """psdr_client_set_rtty_decoder: mark_hz, shift_hz, baud, usos flag, search_hz, snr_db"""
+    _fields_ = [("mark_hz", C.c_double), ("shift_hz", C.c_double), ("baud", C.c_double), ("usos", C.c_int), ("search_hz", C.c_double),
+                ("snr_db", C.c_double)]
+
+
 class psdr_scan_config(C.Structure):
     """psdr_scan_set: scan level, trace shift 0..8, threshold in counts 1..255, gap in bins 0..64"""
     _fields_ = [(n, C.c_int) for n in ("level", "avg_shift", "threshold", "gap")]
@@ -123,6 +129,10 @@ SYMBOLS = [
     ("psdr_cw_defaults", _i, [C.c_double, C.POINTER(psdr_cw_config)]),
     ("psdr_read_cw", _i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i)]),
     ("psdr_read_cw_text", _i, [_vp, _i, C.c_uint64, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
+    ("psdr_client_set_rtty_decoder", _i, [_vp, _i, C.POINTER(psdr_rtty_config)]),
+    ("psdr_rtty_defaults", _i, [C.c_double, C.POINTER(psdr_rtty_config)]),
+    ("psdr_read_rtty", _i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i)]),
+    ("psdr_read_rtty_text", _i, [_vp, _i, C.c_uint64, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
     ("psdr_client_set_agc_profile", _i, [_vp, _i, C.POINTER(psdr_agc_profile)]),
     ("psdr_agc_preset", _i, [_i, C.POINTER(psdr_agc_profile)]),
     ("psdr_read_agc_gain", _i, [_vp, _i, C.POINTER(C.c_float)]),

@@ -97,6 +97,18 @@ def cw_defaults(audio_rate):
     return {k: getattr(p, k) for k in CW_FIELDS}
 
 
+RTTY_FIELDS = ("mark_hz", "shift_hz", "baud", "usos", "search_hz", "snr_db")
+
+
+def rtty_defaults(audio_rate):
+    """the RTTY decoder's defaults at `audio_rate` as a dict for AudioClient.set_rtty_decoder(**...) (psdr_rtty_defaults; needs no
+    context): mark 2125 Hz (915 Hz where the audio_rate has no room for it), shift 170 Hz, 45.45 baud, unshift on space, search
+    60 Hz, the measured snr_db"""
+    p = _lib.psdr_rtty_config()
+    check(_lib.load().psdr_rtty_defaults(float(audio_rate), C.byref(p)))
+    return {k: getattr(p, k) for k in RTTY_FIELDS}
+
+
 def noise_reduction_preset(kind):
     """(depth_db, beta) of a noise reduction preset for AudioClient.set_noise_reduction (psdr_noise_reduction_preset; needs no
     context): "light" (8 dB, 1), "normal" (14 dB, 1.5) or "strong" (22 dB, 2), or an NR_* constant"""
@@ -770,6 +782,44 @@ class AudioClient:
         buf = C.create_string_buffer(1024)
         n, total = C.c_size_t(0), C.c_uint64(0)
         check(self.ctx.lib.psdr_read_cw_text(self.ctx.h, self.id, int(since), buf, 1024, C.byref(n), C.byref(total)))
+        return buf.raw[:n.value].decode("ascii"), total.value
+
+    def set_rtty_decoder(self, on=True, **fields):
+        """Baudot text and tuning offset from the client's audio rows as the demodulator wrote them (psdr_client_set_rtty_decoder).
+        on false or None: off.  Keyword arguments replace single fields of rtty_defaults() at the context's audio_rate: mark_hz,
+        shift_hz (negative: reverse), baud, usos, search_hz, snr_db.  The state and the text start from zero with every call that
+        switches it on."""
+        if not on:
+            check(self.ctx.lib.psdr_client_set_rtty_decoder(self.ctx.h, self.id, None))
+            return
+        p = _lib.psdr_rtty_config(mark_hz=2125.0, shift_hz=170.0, baud=45.45, usos=1, search_hz=60.0, snr_db=0.0)
+        # (a rate outside the decoder's range is the call's refusal to make, not the defaults')
+        if self.ctx.lib.psdr_rtty_defaults(float(self.ctx.cfg.audio_rate), C.byref(p)) != 0:
+            p.snr_db = 7.5
+        for k, v in fields.items():
+            if k not in RTTY_FIELDS:
+                raise TypeError("set_rtty_decoder: unknown field %r" % k)
+            setattr(p, k, int(v) if k == "usos" else float(v))
+        check(self.ctx.lib.psdr_client_set_rtty_decoder(self.ctx.h, self.id, C.byref(p)))
+
+    def read_rtty(self, nframes=None):
+        """(nchars[F] uint32, errors[F] uint32, offset_hz[F] float32, level[F] float32, quality[F] float32, present[F] int32) of the
+        last demod batch (psdr.h: psdr_read_rtty): per frame the text's length so far, the framing errors so far, the followed
+        pair's offset from the configured tones, the squared amplitude of the stronger tone, T / Nn, and the presence flag"""
+        F = nframes or self.ctx.last_demod_frames or self.ctx.last_nframes
+        n, e, o = np.empty(F, np.uint32), np.empty(F, np.uint32), np.empty(F, np.float32)
+        lv, q, pr = np.empty(F, np.float32), np.empty(F, np.float32), np.empty(F, np.int32)
+        got = C.c_int(0)
+        check(self.ctx.lib.psdr_read_rtty(self.ctx.h, self.id, F, _ptr(n), _ptr(e), _ptr(o), _ptr(lv), _ptr(q), _ptr(pr), C.byref(got)))
+        g = got.value
+        return n[:g], e[:g], o[:g], lv[:g], q[:g], pr[:g]
+
+    def read_rtty_text(self, since=0):
+        """(text, total): the characters since .. total - 1 of the client's text since the decoder's state last started
+        (psdr_read_rtty_text); the device keeps the last 1024"""
+        buf = C.create_string_buffer(1024)
+        n, total = C.c_size_t(0), C.c_uint64(0)
+        check(self.ctx.lib.psdr_read_rtty_text(self.ctx.h, self.id, int(since), buf, 1024, C.byref(n), C.byref(total)))
         return buf.raw[:n.value].decode("ascii"), total.value
 
     def set_agc_profile(self, profile, **fields):

@@ -10,6 +10,7 @@
 #include "anb.h"
 #include "tone.h"
 #include "cw.h"
+#include "rtty.h"
 
 // The context's first client of an optional feature (ctx.h: the structs behind `iq`): what the feature allocates is built whole
 // and only then moved in, so a failed call leaves the context as it was.  msg: the failure's text, with the bytes and the
@@ -33,6 +34,7 @@ static int first_noise_reduction(psdr_ctx *c) { return first_use(c, c->nr, "nois
 static int first_audio_blanker(psdr_ctx *c) { return first_use(c, c->anb, "audio blanker state (%zu bytes): %s"); }
 static int first_tone_decoder(psdr_ctx *c) { return first_use(c, c->tone, "tone decoder state, records and tables (%zu bytes): %s"); }
 static int first_cw_decoder(psdr_ctx *c) { return first_use(c, c->cw, "CW decoder state, text, records and tables (%zu bytes): %s"); }
+static int first_rtty_decoder(psdr_ctx *c) { return first_use(c, c->rtty, "RTTY decoder state, text, records and tables (%zu bytes): %s"); }
 // the detector's state of one slot back to zero: sums, counter, both automatic entries (stream-ordered on `side`)
 static int notch_zero(psdr_ctx *c, size_t slot) {
     HIPCHK(hipMemsetAsync(c->notch.acc + slot * (size_t)c->n, 0, (size_t)c->n * sizeof(float), c->side));
@@ -402,6 +404,32 @@ extern "C" int psdr_cw_defaults(double audio_rate, psdr_cw_config *out) {
     if (!cw_defaults(audio_rate, out)) return fail(PSDR_ERR_INVALID, "CW decoder defaults: audio_rate %g outside [%d, %d]", audio_rate, CW_RATE_MIN, CW_RATE_MAX);
     return PSDR_OK;
 }
+extern "C" int psdr_client_set_rtty_decoder(psdr_ctx *c, int id, const psdr_rtty_config *cfg) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mtx);
+    switch (rtty_check(c->aslots.data(), c->aslots.size(), id, cfg, c->cfg.audio_rate)) {
+    case RTTY_OK: break;
+    case RTTY_BAD_ID: return fail(PSDR_ERR_INVALID, "RTTY decoder: id %d outside 0..%d", id, (int)c->aslots.size() - 1);
+    case RTTY_INACTIVE: return fail(PSDR_ERR_INVALID, "no audio client with id %d", id);
+    case RTTY_IQ: return fail(PSDR_ERR_INVALID, "RTTY decoder: client %d is a PSDR_IQ client, which has no audio rows", id);
+    case RTTY_BAD_MARK: return fail(PSDR_ERR_INVALID, "RTTY decoder: mark_hz %g is not a finite number inside [%g, %g]", cfg->mark_hz, RTTY_MARK_MIN, RTTY_MARK_MAX);
+    case RTTY_BAD_SHIFT: return fail(PSDR_ERR_INVALID, "RTTY decoder: shift_hz %g is not a finite number of magnitude inside [%g, %g]", cfg->shift_hz, RTTY_SHIFT_MIN, RTTY_SHIFT_MAX);
+    case RTTY_BAD_BAUD: return fail(PSDR_ERR_INVALID, "RTTY decoder: baud %g is not a finite number inside [%g, %g]", cfg->baud, RTTY_BAUD_MIN, RTTY_BAUD_MAX);
+    case RTTY_BAD_USOS: return fail(PSDR_ERR_INVALID, "RTTY decoder: usos %d outside 0..1", cfg->usos);
+    case RTTY_BAD_SEARCH: return fail(PSDR_ERR_INVALID, "RTTY decoder: search_hz %g is not a finite number inside [%g, %g]", cfg->search_hz, RTTY_SEARCH_MIN, RTTY_SEARCH_MAX);
+    case RTTY_BAD_SNR: return fail(PSDR_ERR_INVALID, "RTTY decoder: snr_db %g is not a finite number inside [%g, %g]", cfg->snr_db, RTTY_SNR_MIN, RTTY_SNR_MAX);
+    case RTTY_BAD_RATE: return fail(PSDR_ERR_STATE, "RTTY decoder: the context's audio_rate %d is outside [%d, %d]", c->cfg.audio_rate, RTTY_RATE_MIN, RTTY_RATE_MAX);
+    case RTTY_BAD_BAND: return fail(PSDR_ERR_STATE, "RTTY decoder: the tones %g and %g Hz with %g Hz to either side do not lie inside [%g Hz, %g of the audio_rate %d]", cfg->mark_hz, cfg->mark_hz + cfg->shift_hz, RTTY_EDGE, RTTY_BOTTOM, RTTY_TOP, c->cfg.audio_rate);
+    }
+    if (cfg) PSDRCHK(first_rtty_decoder(c));
+    rtty_apply(c->aslots[id], cfg, c->cfg.audio_rate);
+    return PSDR_OK;
+}
+extern "C" int psdr_rtty_defaults(double audio_rate, psdr_rtty_config *out) {
+    if (!out) return fail(PSDR_ERR_INVALID, "null argument");
+    if (!rtty_defaults(audio_rate, out)) return fail(PSDR_ERR_INVALID, "RTTY decoder defaults: audio_rate %g outside [%d, %d]", audio_rate, RTTY_RATE_MIN, RTTY_RATE_MAX);
+    return PSDR_OK;
+}
 extern "C" int psdr_client_set_agc_profile(psdr_ctx *c, int id, const psdr_agc_profile *p) {
     if (!c) return fail(PSDR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mtx);
@@ -586,6 +614,7 @@ struct BatchPlan {
     AnbPlan anb;
     TonePlan tone;
     CwPlan cw;
+    RttyPlan rtty;
     AgcPlan ag;
     bool chain = false;  // the post chain follows: it is on, and somebody is in it
     // of the optional features: the rows of the result set this batch writes and the detector's table - null where the context has
@@ -622,6 +651,7 @@ static int batch_plan(psdr_ctx *c, int nframes, const uint32_t *band, BatchPlan 
     if (c->anb) b.anb = anb_plan(slots, S, c->demod_seq, c->anb.tab.host(b.ring));
     if (c->tone) b.tone = tone_plan(slots, S, c->demod_seq, b.chain, c->tone.tab.host(b.ring));
     if (c->cw) b.cw = cw_plan(slots, S, c->demod_seq, c->cw.tab.host(b.ring));
+    if (c->rtty) b.rtty = rtty_plan(slots, S, c->demod_seq, c->rtty.tab.host(b.ring));
     if (c->agc_prof && b.chain) b.ag = agc_profile_plan(slots, S, c->demod_seq, c->agc_prof.tab.host(b.ring));
     return PSDR_OK;
 }
@@ -648,6 +678,11 @@ static int batch_begin(psdr_ctx *c, const BatchPlan &b) {
     for (size_t slot : b.cw.zero) {
         HIPCHK(hipMemsetAsync(c->cw.state + slot, 0, sizeof(CwState), c->side));
         HIPCHK(hipMemsetAsync(c->cw.text + slot * (size_t)CW_TEXT, 0, CW_TEXT, c->side));
+    }
+    // ... and the RTTY decoders: state and text ring (rtty_plan has taken rtty_fresh off these slots)
+    for (size_t slot : b.rtty.zero) {
+        HIPCHK(hipMemsetAsync(c->rtty.state + slot, 0, sizeof(RttyState), c->side));
+        HIPCHK(hipMemsetAsync(c->rtty.text + slot * (size_t)RTTY_TEXT, 0, RTTY_TEXT, c->side));
     }
     // ... and the noise floors that start from zero: sums and record (noise_plan has taken nf_fresh off these slots)
     for (size_t slot : b.nf.zero) {
@@ -683,6 +718,7 @@ static int batch_begin(psdr_ctx *c, const BatchPlan &b) {
     if (b.anb.any()) HIPCHK(c->anb.tab.upload(b.ring, (size_t)b.anb.n, c->side));
     if (b.tone.any()) HIPCHK(c->tone.tab.upload(b.ring, (size_t)(b.tone.n + b.tone.ncopy), c->side));
     if (b.cw.any()) HIPCHK(c->cw.tab.upload(b.ring, (size_t)b.cw.n, c->side));
+    if (b.rtty.any()) HIPCHK(c->rtty.tab.upload(b.ring, (size_t)b.rtty.n, c->side));
     return PSDR_OK;
 }
 
@@ -879,6 +915,19 @@ static int launch_cw_decoder(psdr_ctx *c, const BatchPlan &b, int nframes) {
     HIPCHK(audio_cw_launch(ca, c->side));
     return PSDR_OK;
 }
+// ... the RTTY decoder, at the same reading point: it reads the listed clients' rows as the demodulator left them and writes the
+// frames' records and the clients' text
+static int launch_rtty_decoder(psdr_ctx *c, const BatchPlan &b, int nframes) {
+    RttyArgs ra{};
+    ra.list = c->rtty.tab.dev(b.ring), ra.nlist = b.rtty.n;
+    ra.tab = c->rtty.plan;
+    ra.audio = c->d_audio, ra.nan_flags = c->d_nan;
+    ra.state = c->rtty.state, ra.text = c->rtty.text, ra.rec = c->rtty.rec;
+    ra.nframes = nframes, ra.max_batch = c->max_batch, ra.h = c->n / 2;
+    ProfScope ps(c, K_AUDIO_RTTY, c->side);
+    HIPCHK(audio_rtty_launch(ra, c->side));
+    return PSDR_OK;
+}
 // ... the audio blanker, in front of the noise reduction, the audio filter and the chain: it works on the listed clients' rows in
 // place
 static int launch_audio_blanker(psdr_ctx *c, const BatchPlan &b, int nframes) {
@@ -952,6 +1001,7 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     if (b.sq.any()) PSDRCHK(launch_squelch(c, b, nframes, &chain_drop));
     if (b.tone.any()) PSDRCHK(launch_tone_decoder(c, b, nframes, &chain_drop));
     if (b.cw.any()) PSDRCHK(launch_cw_decoder(c, b, nframes));
+    if (b.rtty.any()) PSDRCHK(launch_rtty_decoder(c, b, nframes));
     if (b.anb.any()) PSDRCHK(launch_audio_blanker(c, b, nframes));
     if (b.nr.any()) PSDRCHK(launch_noise_reduction(c, b, nframes));
     if (b.af.any()) PSDRCHK(launch_audio_filter(c, b, nframes));

@@ -103,6 +103,17 @@ struct AudioSlot {
     float cw_ratio = 1.f;
     bool b_cw_on = false, cw_fresh = false;
     int cw_mode = PSDR_USB, cw_l = 0, cw_r = 0, cw_m = 0;
+    // psdr_client_set_rtty_decoder (rttyplan.h): the parameters as the table holds them - the bit window in hops, the bit length
+    // in 1/16 hop, usos, the candidate pairs, the ratio, the level's scale, the 32 lanes' increments and rotations; b_rtty_on: the
+    // last batch ran with it (psdr_read_rtty); rtty_fresh, rtty_mode, rtty_l, rtty_r, rtty_m: as the tone decoder's
+    int rtty_on = 0;
+    int rtty_wn = 17, rtty_u = 264, rtty_usos = 1;
+    uint32_t rtty_cand = 0;
+    float rtty_ratio = 1.f, rtty_lscale = 0.f;
+    uint32_t rtty_inc[32] = {};
+    float rtty_rot[32][2] = {};
+    bool b_rtty_on = false, rtty_fresh = false;
+    int rtty_mode = PSDR_USB, rtty_l = 0, rtty_r = 0, rtty_m = 0;
 };
 
 // The client parameter ring's slot.  [ClientParams x S][int x S]: the batch's list and, for the post chain, the list index of

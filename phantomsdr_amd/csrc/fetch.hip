@@ -480,6 +480,62 @@ extern "C" int psdr_read_cw_text(psdr_ctx *c, int id, uint64_t from, char *out, 
     if (total_out) *total_out = total;
     return PSDR_OK;
 }
+// the RTTY decoder's records of the last batch; any of the six arrays may be null
+extern "C" int psdr_read_rtty(psdr_ctx *c, int id, int nframes, uint32_t *nchars, uint32_t *errors, float *offset_hz, float *level, float *quality, int32_t *present,
+                              int *nframes_out) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    size_t F = 0;
+    bool on = false;
+    PSDRCHK(read_begin(c, id, false, nframes, nframes_out, ROWS_AUDIO, false, &F, [&](const AudioSlot &s) { on = s.b_rtty_on && (bool)c->rtty; }));
+    if (!on) return fail(PSDR_ERR_NO_DATA, "client %d had no RTTY decoder in the last demodulation batch", id);
+    HIPCHK(hipSetDevice(c->device));
+    PSDRCHK(drain(c));
+    std::vector<RttyRec> rec(F);
+    HIPCHK(hipMemcpy(rec.data(), c->rtty.rec + fetch_row(id, (size_t)c->max_batch, 0), F * sizeof(RttyRec), hipMemcpyDeviceToHost));
+    for (size_t f = 0; f < F; f++) {
+        if (nchars) nchars[f] = rec[f].nchars;
+        if (errors) errors[f] = rec[f].errors;
+        if (offset_hz) offset_hz[f] = rec[f].offset_hz;
+        if (level) level[f] = rec[f].level;
+        if (quality) quality[f] = rec[f].quality;
+        if (present) present[f] = rec[f].present;
+    }
+    return PSDR_OK;
+}
+// the RTTY decoder's text since the state last started, from the slot's ring
+extern "C" int psdr_read_rtty_text(psdr_ctx *c, int id, uint64_t from, char *out, size_t cap, size_t *n_out, uint64_t *total_out) {
+    if (!c || (!out && cap)) return fail(PSDR_ERR_INVALID, "null argument");
+    bool pending = false;
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);
+        if (id < 0 || (size_t)id >= c->aslots.size()) return fail(PSDR_ERR_INVALID, "RTTY text: id %d outside 0..%d", id, (int)c->aslots.size() - 1);
+        const AudioSlot &s = c->aslots[id];
+        if (!s.active) return fail(PSDR_ERR_INVALID, "no audio client with id %d", id);
+        if (!s.rtty_on || !c->rtty) return fail(PSDR_ERR_NO_DATA, "client %d has no RTTY decoder", id);
+        pending = s.rtty_fresh;
+    }
+    uint64_t total = 0;
+    std::vector<uint8_t> ring;
+    if (!pending) {
+        HIPCHK(hipSetDevice(c->device));
+        PSDRCHK(drain(c));
+        std::vector<RttyState> st(1);
+        HIPCHK(hipMemcpy(st.data(), c->rtty.state + (size_t)id, sizeof(RttyState), hipMemcpyDeviceToHost));
+        total = st[0].nchars;
+        if (from < total && total - from <= (uint64_t)RTTY_TEXT) {
+            ring.resize(RTTY_TEXT);
+            HIPCHK(hipMemcpy(ring.data(), c->rtty.text + (size_t)id * RTTY_TEXT, RTTY_TEXT, hipMemcpyDeviceToHost));
+        }
+    }
+    if (from > total) return fail(PSDR_ERR_INVALID, "RTTY text: from %llu is beyond the text's %llu characters", (unsigned long long)from, (unsigned long long)total);
+    if (total - from > (uint64_t)RTTY_TEXT)
+        return fail(PSDR_ERR_NO_DATA, "RTTY text: from %llu is older than the last %d of %llu characters", (unsigned long long)from, RTTY_TEXT, (unsigned long long)total);
+    const size_t n = std::min((size_t)(total - from), cap);
+    for (size_t j = 0; j < n; j++) out[j] = (char)ring[(from + j) % RTTY_TEXT];
+    if (n_out) *n_out = n;
+    if (total_out) *total_out = total;
+    return PSDR_OK;
+}
 extern "C" int psdr_read_noise(psdr_ctx *c, int id, int nframes, float *w, int *nframes_out) {
     if (!c || !w) return fail(PSDR_ERR_INVALID, "null argument");
     size_t F = 0;

@@ -78,11 +78,13 @@ inline void tone_seed_tables(ToneTables &t) {
         t.fine[j][0] = (float)std::cos(b), t.fine[j][1] = (float)std::sin(b);
     }
 }
-inline void tone_lane(ToneTables &t, int k, double hz, double audio_rate) {
-    t.inc[k] = hz > 0 ? (uint32_t)std::floor(hz / audio_rate * 4294967296.0 + 0.5) : 0u;
-    const double a = 2.0 * M_PI * (double)t.inc[k] / 4294967296.0;
-    t.rot[k][0] = (float)std::cos(a), t.rot[k][1] = (float)std::sin(a);
+// (the RTTY decoder's lanes are the client's own: rttyplan.h keeps them in the batch's table, made by tone_inc_rot)
+inline void tone_inc_rot(double hz, double audio_rate, uint32_t &inc, float *rot) {
+    inc = hz > 0 ? (uint32_t)std::floor(hz / audio_rate * 4294967296.0 + 0.5) : 0u;
+    const double a = 2.0 * M_PI * (double)inc / 4294967296.0;
+    rot[0] = (float)std::cos(a), rot[1] = (float)std::sin(a);
 }
+inline void tone_lane(ToneTables &t, int k, double hz, double audio_rate) { tone_inc_rot(hz, audio_rate, t.inc[k], t.rot[k]); }
 inline void tone_tables(ToneTables &t, double audio_rate) {
     memset(&t, 0, sizeof(t));
     tone_seed_tables(t);
