@@ -1,6 +1,7 @@
 """The band scan's rule (include/psdr.h: psdr_scan_set) in numpy integers, written from the header's words - sort for the quartile,
 a walk over the hot bins for the runs - and the driver of tests/scan_plan_table.cpp, the host program that runs the kernels' own
-steps (phantomsdr_amd/csrc/scanplan.h).  Shared by tests/test_scan_host.py and tests/test_gpu_band_scan.py."""
+steps (phantomsdr_amd/csrc/scanplan.h).  Shared by tests/test_scan_host.py, tests/test_gpu_band_scan.py
+and the mask tests (tests/band_scan_masks.py)."""
 import os
 import struct
 import subprocess

@@ -89,10 +89,14 @@ class Rig:
         self.ctx.process_batch(self.d, nf, offset_bytes=start * self.ctx.half_frame_bytes())
         self.nf = nf
 
-    def scan(self, first):
-        """psdr_scan_batch for the batch just processed, and the model's step from the GPU's own int8 values"""
+    def scan(self, first, read=True):
+        """psdr_scan_batch for the batch just processed, and the model's step from the GPU's own int8 values.  read=False: the
+        call alone - nothing is read back, no stream is waited for and the model's trace stays as it is (the caller's matter)"""
         level, a, _, _ = self.cfg
         self.ctx.scan_batch(first)
+        if not read:
+            self.next, self.last = first + self.nf, first + self.nf - 1
+            return None
         q = np.stack([self.ctx.quantized_level(self.ctx.read_quantized(f), level) for f in range(self.nf)])
         fresh = self.next is None or first != self.next
         self.s = M.trace(self.s, q, fresh, a)
