@@ -847,6 +847,89 @@ int psdr_client_set_rtty_decoder(psdr_ctx *ctx, int id, const psdr_rtty_config *
 int psdr_read_rtty(psdr_ctx *ctx, int id, int nframes, uint32_t *nchars, uint32_t *errors, float *offset_hz, float *level, float *quality,
                    int32_t *present, int *nframes_out);
 int psdr_read_rtty_text(psdr_ctx *ctx, int id, uint64_t from, char *out, size_t cap, size_t *n_out, uint64_t *total_out);
+/* PSK31 decoder: varicode text and tuning offset of the BPSK31 or BPSK63 signal a client's audio carries, per client on the audio
+ * rows.  It READS the rows as the demodulator wrote them - the tone, CW and RTTY decoders' reading point: behind the squelch, in
+ * front of the audio blanker, the noise reduction and the audio filter - and never writes them: every other output of the client is
+ * that of a client without it.
+ *   Stream, hop.  The RTTY decoder's: the client's rows in frame order, a NaN-flagged frame entering as zeros, sample t counting
+ *     from the state's start; H = 8 samples below audio_rate 8000, 16 below 16000, 32 below 32000, else 64.
+ *   Lanes.  16 lanes; lane j = 0..15 listens at carrier_hz + (j - 8) baud / 8: 3.90625 Hz apart at 31.25 baud, so a signal half-way
+ *     between two lanes turns 22.5 degrees per symbol.  Phase increment round(f / audio_rate * 2^32) in double, the seed from the
+ *     two 4096-entry tables at the exact 32-bit phase of the hop's first sample, one rotation per sample and the single f32
+ *     accumulator, n ascending, are the tone decoder's, over H samples: C[b][j].
+ *   Symbol window.  Wn = round(audio_rate / (baud H)) hops (8 to 32); S[b][j] = sum_{i < Wn} C[b - Wn + 1 + i][j], i ascending, hops
+ *     before the start counting as 0, summed anew from the kept correlations every hop; E[b][j] = |S|^2, an E that is not finite
+ *     entering as 0.
+ *   Symbol clock, integers in 1/16 hop.  u = round(16 audio_rate / (baud H)), in double.  Every hop c <- (c + 16) mod u, from 0.
+ *     Sixteen timing bins hold followers G_i; the hop's bin is floor(16 c / u) and G_bin <- G_bin + (T[b] - G_bin) / 32, T[b] the
+ *     sum of the candidate lanes' E[b][j], j ascending (the followed lane's alone loses the clock on a lane that sits on one of the
+ *     idle's two tones: DESIGN.md 3.23).  g = the lowest bin with the largest G (on the bit patterns), tau = floor(g u / 16).  The
+ *     hop is a sample point when ((c - tau) mod u) < floor(u / 2) - the clock is within half a symbol behind tau - and
+ *     floor(3 u / 4) at least has passed since the last sample point (counted in steps of 16 from 0 at the start).  The dips of the
+ *     phase reversals make E peak where the window covers one whole symbol; a steady carrier leaves the bins level and g where
+ *     it was.
+ *   Differential detection, at a sample point, every lane: d_j = S_j conj(prev_j), then prev_j <- S_j; Re q_j = (Re d_j)^2 -
+ *     (Im d_j)^2 - the square takes the keying out - and |d_j|^2, either entering as 0 when it is not finite;
+ *     Qre_j <- Qre_j + (Re q_j - Qre_j) / 32.
+ *   Carrier follower.  M_j = max(Qre_j, +0): a lane 3.9 Hz off turns q by 90 degrees and reads 0, one 2 Hz off reads 0.7 - the
+ *     energy alone would differ by 0.2 dB.  The candidates are the lanes with |(j - 8) baud / 8| <= search_hz and always lane 8,
+ *     where the followed lane p starts; q = the lowest candidate with the largest M (on the bit patterns); p becomes q only when
+ *     M_q > 2 M_p, and a move clears the shift register.  search_hz stays below baud / 2: a lane half the baud rate off sees the same q - the false lock every PSK31
+ *     program knows - and nothing here could tell the two apart.
+ *   Presence.  A symbol's own coherence is Re q_p / |d_p|^2 as one f32 division, 0 when |d_p|^2 is 0 or the quotient is not
+ *     finite: the cosine of twice its turn.  coherence <- coherence + (it - coherence) / 32 per sample point, with the new p: near
+ *     1 for a clean signal, scattered about 0 for noise.  The signal is present when 32 sample points are in and
+ *     coherence >= quality.  (The quotient of two energy-weighted followers reached 0.70 on noise alone: DESIGN.md 3.23.)
+ *   Bit and varicode.  bit = Re d_p >= 0 ? 1 : 0 - a reversal is 0.  While the signal is absent nothing is shifted and the register
+ *     is cleared: an absent signal prints nothing.  Else sr <- sr << 1 | bit; when its low two bits are 00, code = sr >> 2 and
+ *     sr <- 0: code 0 is nothing, a code of G3PLX's 128-entry table appends its character (NUL is dropped), any other code counts
+ *     one error.  A register that passes 12 bits without 00 is cleared and counts one error - unless it holds ones only: that is
+ *     the steady carrier behind a transmission, which is no fault of the line.
+ *   Records.  Frame f's record is the state behind the last hop that is complete at the frame's last sample: nchars = the text's
+ *     length modulo 2^32, errors modulo 2^32, offset_hz = (p - 8) baud / 8, level = 4 A / (Wn H)^2 with A <- A + (E[b][p] - A) / 32
+ *     per sample point - the squared amplitude of a steady carrier in the units of the rows, the scale computed in double and
+ *     rounded once; idle reversals read (2 / pi)^2 of theirs -, quality = the coherence as of the last sample point, present = the presence flag; before the first hop all zero.
+ *     Any split of the same frames into batches gives the same bits, records and text.  phantomsdr_amd/csrc/pskplan.h is the one
+ *     definition of all of it, for the device and a host program alike.
+ *   Who.  Every client of a batch whose kind writes audio rows; a PSDR_IQ client is refused, a client that becomes one keeps its
+ *     setting and is not listed.  The state is carried across batches and across dropped or flagged frames and stands still while
+ *     the client is paused.  It starts from zero when the call switches the decoder on (again, too), on a mode change and on a
+ *     retune.  Per client slot 4664 bytes of state - the last 32 hops' correlations of the 16 lanes (4096), the unfinished hop
+ *     (256), prev, Qre and the bins (256), clock and register (56) -, 1024 bytes of text and 24 bytes per frame of a batch for
+ *     the records; 224 bytes per listed client in the batch's table.
+ *   The default quality is measured on the host model: half-way between the largest coherence noise alone
+ *     reaches in 60 s and the smallest it keeps while the test text is read at the lowest ratio, in 3 dB steps, at which it is
+ *     read exactly: 0.405, 0.616 at 12 dB in a bandwidth equal to the baud rate, 0.51.  Behind the end of a signal the coherence
+ *     needs some twenty symbols to fall under that: a transmission that ends without its carrier tail can print noise
+ *     meanwhile.  Nobody has tried it on off-air PSK31.
+ * psdr_client_set_psk_decoder: any thread; in force from the client's next batch; cfg = NULL switches it off.  PSDR_ERR_INVALID,
+ *   with nothing changed and a text of its own each, for an id outside the slots, a slot without a client, (cfg != NULL) a PSDR_IQ
+ *   client, carrier_hz not finite or outside [300, 3000], a baud that is neither 31.25 nor 62.5, search_hz not finite or outside
+ *   [0, baud / 2), quality not finite or outside (0, 1); then PSDR_ERR_STATE for a context whose audio_rate is outside
+ *   [4000, 48000]; then PSDR_ERR_STATE when lane 15 lies above 0.45 audio_rate or lane 0 below 100 Hz - in this order.  The device
+ *   state is allocated with the context's first such client, all or none: PSDR_ERR_NOMEM and the setting unchanged if that fails.
+ *   A context without such a client allocates nothing, a batch without one launches nothing.
+ * psdr_psk_defaults: needs no context; 1000 Hz, 31.25 baud, three lanes to either side (11.71875 Hz), the measured quality.
+ *   PSDR_ERR_INVALID for a null pointer or an audio_rate outside [4000, 48000].
+ * psdr_read_psk: psdr_read_rtty's contract - the records of the last demodulation batch, nframes the room of the arrays (any of
+ *   which may be null), synchronises; a client whose last batch ran without the decoder reads PSDR_ERR_NO_DATA, as does one that
+ *   was not part of the batch or was demodulated as PSDR_IQ.
+ * psdr_read_psk_text: psdr_read_rtty_text's contract to the letter; the device keeps the last 1024 characters per slot.
+ * Nothing of it goes through psdr_fetch_* yet, and there is no psdr_group_* call: a group's clients have no PSK decoder.  Out of
+ * scope: QPSK31 (it needs a Viterbi decoder), PSK125 and automatic detection of the speed. */
+#define PSDR_PSK_LANES 16
+#define PSDR_PSK_QUALITY_DEFAULT 0.51
+typedef struct {
+    double carrier_hz;  /* [300, 3000], default 1000: where the listener put the signal in the audio */
+    double baud;        /* 31.25 (default) or 62.5, nothing else */
+    double search_hz;   /* [0, baud / 2), default 3 baud / 8: lanes within it may be followed; 0: the configured carrier only */
+    double quality;     /* (0, 1), default PSDR_PSK_QUALITY_DEFAULT: the line is read only while coherence >= quality */
+} psdr_psk_config;
+int psdr_psk_defaults(double audio_rate, psdr_psk_config *out);               /* needs no context */
+int psdr_client_set_psk_decoder(psdr_ctx *ctx, int id, const psdr_psk_config *cfg);   /* NULL: off */
+int psdr_read_psk(psdr_ctx *ctx, int id, int nframes, uint32_t *nchars, uint32_t *errors, float *offset_hz, float *level, float *quality,
+                  int32_t *present, int *nframes_out);
+int psdr_read_psk_text(psdr_ctx *ctx, int id, uint64_t from, char *out, size_t cap, size_t *n_out, uint64_t *total_out);
 /* AGC profile: speed, target, gain cap and manual gain per client.  The context's AGC is the reference's - target 0.2, attack
  * 50 ms, release 300 ms (psdr_set_post_chain) - for every client; a profile replaces these numbers for one client: a fast AGC for
  * CW, a slow one for broadcast, a bound on the gain a quiet channel is pumped up by, or no AGC at all and a fixed gain, which is

@@ -53,6 +53,11 @@ class psdr_rtty_config(C.Structure):
                 ("snr_db", C.c_double)]
 
 
+class psdr_psk_config(C.Structure):
+    """psdr_client_set_psk_decoder: carrier_hz, baud (31.25 or 62.5), search_hz, quality"""
+    _fields_ = [("carrier_hz", C.c_double), ("baud", C.c_double), ("search_hz", C.c_double), ("quality", C.c_double)]
+
+
 class psdr_scan_config(C.Structure):
     """psdr_scan_set: scan level, trace shift 0..8, threshold in counts 1..255, gap in bins 0..64"""
     _fields_ = [(n, C.c_int) for n in ("level", "avg_shift", "threshold", "gap")]
@@ -133,6 +138,10 @@ SYMBOLS = [
     ("psdr_rtty_defaults", _i, [C.c_double, C.POINTER(psdr_rtty_config)]),
     ("psdr_read_rtty", _i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i)]),
     ("psdr_read_rtty_text", _i, [_vp, _i, C.c_uint64, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
+    ("psdr_client_set_psk_decoder", _i, [_vp, _i, C.POINTER(psdr_psk_config)]),
+    ("psdr_psk_defaults", _i, [C.c_double, C.POINTER(psdr_psk_config)]),
+    ("psdr_read_psk", _i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i)]),
+    ("psdr_read_psk_text", _i, [_vp, _i, C.c_uint64, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
     ("psdr_client_set_agc_profile", _i, [_vp, _i, C.POINTER(psdr_agc_profile)]),
     ("psdr_agc_preset", _i, [_i, C.POINTER(psdr_agc_profile)]),
     ("psdr_read_agc_gain", _i, [_vp, _i, C.POINTER(C.c_float)]),

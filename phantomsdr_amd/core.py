@@ -109,6 +109,17 @@ def rtty_defaults(audio_rate):
     return {k: getattr(p, k) for k in RTTY_FIELDS}
 
 
+PSK_FIELDS = ("carrier_hz", "baud", "search_hz", "quality")
+
+
+def psk_defaults(audio_rate):
+    """the PSK31 decoder's defaults at `audio_rate` as a dict for AudioClient.set_psk_decoder(**...) (psdr_psk_defaults; needs no
+    context): carrier 1000 Hz, 31.25 baud, search 11.71875 Hz (three lanes to either side), the measured quality"""
+    p = _lib.psdr_psk_config()
+    check(_lib.load().psdr_psk_defaults(float(audio_rate), C.byref(p)))
+    return {k: getattr(p, k) for k in PSK_FIELDS}
+
+
 def noise_reduction_preset(kind):
     """(depth_db, beta) of a noise reduction preset for AudioClient.set_noise_reduction (psdr_noise_reduction_preset; needs no
     context): "light" (8 dB, 1), "normal" (14 dB, 1.5) or "strong" (22 dB, 2), or an NR_* constant"""
@@ -820,6 +831,46 @@ class AudioClient:
         buf = C.create_string_buffer(1024)
         n, total = C.c_size_t(0), C.c_uint64(0)
         check(self.ctx.lib.psdr_read_rtty_text(self.ctx.h, self.id, int(since), buf, 1024, C.byref(n), C.byref(total)))
+        return buf.raw[:n.value].decode("ascii"), total.value
+
+    def set_psk_decoder(self, on=True, **fields):
+        """varicode text and tuning offset of a BPSK31 / BPSK63 signal from the client's audio rows as the demodulator wrote them
+        (psdr_client_set_psk_decoder).  on false or None: off.  Keyword arguments replace single fields of psk_defaults() at the
+        context's audio_rate: carrier_hz, baud (31.25 or 62.5), search_hz, quality; a baud without a search_hz searches three lanes
+        to either side at that speed.  The state and the text start from zero with every call that switches it on."""
+        if not on:
+            check(self.ctx.lib.psdr_client_set_psk_decoder(self.ctx.h, self.id, None))
+            return
+        p = _lib.psdr_psk_config(carrier_hz=1000.0, baud=31.25, search_hz=11.71875, quality=0.0)
+        # (a rate outside the decoder's range is the call's refusal to make, not the defaults')
+        if self.ctx.lib.psdr_psk_defaults(float(self.ctx.cfg.audio_rate), C.byref(p)) != 0:
+            p.quality = 0.51
+        for k, v in fields.items():
+            if k not in PSK_FIELDS:
+                raise TypeError("set_psk_decoder: unknown field %r" % k)
+            setattr(p, k, float(v))
+        if "baud" in fields and "search_hz" not in fields:
+            p.search_hz = 3.0 * p.baud / 8.0
+        check(self.ctx.lib.psdr_client_set_psk_decoder(self.ctx.h, self.id, C.byref(p)))
+
+    def read_psk(self, nframes=None):
+        """(nchars[F] uint32, errors[F] uint32, offset_hz[F] float32, level[F] float32, quality[F] float32, present[F] int32) of the
+        last demod batch (psdr.h: psdr_read_psk): per frame the text's length so far, the varicode errors so far, the followed
+        lane's offset from the configured carrier, the squared amplitude at the sample points, the coherence, and the presence flag"""
+        F = nframes or self.ctx.last_demod_frames or self.ctx.last_nframes
+        n, e, o = np.empty(F, np.uint32), np.empty(F, np.uint32), np.empty(F, np.float32)
+        lv, q, pr = np.empty(F, np.float32), np.empty(F, np.float32), np.empty(F, np.int32)
+        got = C.c_int(0)
+        check(self.ctx.lib.psdr_read_psk(self.ctx.h, self.id, F, _ptr(n), _ptr(e), _ptr(o), _ptr(lv), _ptr(q), _ptr(pr), C.byref(got)))
+        g = got.value
+        return n[:g], e[:g], o[:g], lv[:g], q[:g], pr[:g]
+
+    def read_psk_text(self, since=0):
+        """(text, total): the characters since .. total - 1 of the client's text since the decoder's state last started
+        (psdr_read_psk_text); the device keeps the last 1024"""
+        buf = C.create_string_buffer(1024)
+        n, total = C.c_size_t(0), C.c_uint64(0)
+        check(self.ctx.lib.psdr_read_psk_text(self.ctx.h, self.id, int(since), buf, 1024, C.byref(n), C.byref(total)))
         return buf.raw[:n.value].decode("ascii"), total.value
 
     def set_agc_profile(self, profile, **fields):

@@ -30,6 +30,7 @@
 #include "createplan.h"
 #include "cwplan.h"
 #include "rttyplan.h"
+#include "pskplan.h"
 #include "demodplan.h"
 #include "fetchplan.h"
 #include "forwardplan.h"
@@ -75,7 +76,7 @@ inline const char *psdr_tuning_env(const char *name) {
 
 namespace psdr {
 
-enum KernelId { K_PASS1, K_PASS2, K_UNTANGLE, K_TAIL, K_IDFT, K_OLA, K_WFALL, K_POST, K_SEAM, K_BAND, K_WFHOLD, K_WFCARRY, K_SQUELCH, K_NB_SCAN, K_NB_APPLY, K_AUDIO_FILTER, K_AUDIO_NR, K_AUDIO_NB, K_SCAN_TRACE, K_SCAN_FLOOR, K_SCAN_HOT, K_SCAN_MARK, K_SCAN_EMIT, K_AUDIO_TONE, K_AUDIO_CW, K_AUDIO_RTTY, K_COUNT };
+enum KernelId { K_PASS1, K_PASS2, K_UNTANGLE, K_TAIL, K_IDFT, K_OLA, K_WFALL, K_POST, K_SEAM, K_BAND, K_WFHOLD, K_WFCARRY, K_SQUELCH, K_NB_SCAN, K_NB_APPLY, K_AUDIO_FILTER, K_AUDIO_NR, K_AUDIO_NB, K_SCAN_TRACE, K_SCAN_FLOOR, K_SCAN_HOT, K_SCAN_MARK, K_SCAN_EMIT, K_AUDIO_TONE, K_AUDIO_CW, K_AUDIO_RTTY, K_AUDIO_PSK, K_COUNT };
 extern const char *kKernelNames[K_COUNT];
 
 struct PendingEvent {
@@ -505,6 +506,29 @@ struct psdr_ctx {
         }
         explicit operator bool() const { return (bool)tab; }
     } rtty;
+    // PSK31 decoder (psk.h: k_audio_psk): the clients' carried state [slots] and text ring [slots][1024], the seed tables and the
+    // varicode by code for the context's audio_rate, the frames' records [slots][max_batch] (written and read on `side` within one
+    // batch or behind a drain: one set), and the batch's table (pskplan.h), a RingTable beside client_ring
+    struct PskDecoder {
+        DevBuf<PskState> state;
+        DevBuf<uint8_t> text;
+        DevBuf<PskTables> plan;
+        DevBuf<PskRec> rec;
+        RingTable<PskEntry> tab;
+        static size_t bytes(const psdr_ctx &c) {
+            const size_t S = c.aslots.size();
+            return S * (sizeof(PskState) + PSK_TEXT + (size_t)c.max_batch * sizeof(PskRec)) + sizeof(PskTables) + RingTable<PskEntry>::bytes(S);
+        }
+        int alloc(const psdr_ctx &c) {
+            const size_t S = c.aslots.size();
+            if (state.alloc(S, true) || text.alloc(S * PSK_TEXT, true) || plan.alloc(1) || rec.alloc(S * (size_t)c.max_batch, true) || tab.alloc(S)) return 1;
+            std::vector<PskTables> t(1);
+            psk_tables(t[0], (double)c.cfg.audio_rate);
+            const hipError_t e = hipMemcpy(plan.get(), t.data(), sizeof(PskTables), hipMemcpyHostToDevice);
+            return e == hipSuccess ? 0 : psdr_fail(PSDR_ERR_HIP, "PSK decoder tables: %s", hipGetErrorString(e));
+        }
+        explicit operator bool() const { return (bool)tab; }
+    } psk;
     // AGC profiles (agcplan.h; postchain.h: k_pc_want_prof and the PcWithProfiles kernels): the batch's table, a RingTable beside
     // client_ring.  The chain's carried state is the context's own: a profile adds none
     struct AgcProfiles {

@@ -11,6 +11,7 @@
 #include "tone.h"
 #include "cw.h"
 #include "rtty.h"
+#include "psk.h"
 
 // The context's first client of an optional feature (ctx.h: the structs behind `iq`): what the feature allocates is built whole
 // and only then moved in, so a failed call leaves the context as it was.  msg: the failure's text, with the bytes and the
@@ -35,6 +36,7 @@ static int first_audio_blanker(psdr_ctx *c) { return first_use(c, c->anb, "audio
 static int first_tone_decoder(psdr_ctx *c) { return first_use(c, c->tone, "tone decoder state, records and tables (%zu bytes): %s"); }
 static int first_cw_decoder(psdr_ctx *c) { return first_use(c, c->cw, "CW decoder state, text, records and tables (%zu bytes): %s"); }
 static int first_rtty_decoder(psdr_ctx *c) { return first_use(c, c->rtty, "RTTY decoder state, text, records and tables (%zu bytes): %s"); }
+static int first_psk_decoder(psdr_ctx *c) { return first_use(c, c->psk, "PSK decoder state, text, records and tables (%zu bytes): %s"); }
 // the detector's state of one slot back to zero: sums, counter, both automatic entries (stream-ordered on `side`)
 static int notch_zero(psdr_ctx *c, size_t slot) {
     HIPCHK(hipMemsetAsync(c->notch.acc + slot * (size_t)c->n, 0, (size_t)c->n * sizeof(float), c->side));
@@ -430,6 +432,30 @@ extern "C" int psdr_rtty_defaults(double audio_rate, psdr_rtty_config *out) {
     if (!rtty_defaults(audio_rate, out)) return fail(PSDR_ERR_INVALID, "RTTY decoder defaults: audio_rate %g outside [%d, %d]", audio_rate, RTTY_RATE_MIN, RTTY_RATE_MAX);
     return PSDR_OK;
 }
+extern "C" int psdr_client_set_psk_decoder(psdr_ctx *c, int id, const psdr_psk_config *cfg) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mtx);
+    switch (psk_check(c->aslots.data(), c->aslots.size(), id, cfg, c->cfg.audio_rate)) {
+    case PSK_OK: break;
+    case PSK_BAD_ID: return fail(PSDR_ERR_INVALID, "PSK decoder: id %d outside 0..%d", id, (int)c->aslots.size() - 1);
+    case PSK_INACTIVE: return fail(PSDR_ERR_INVALID, "no audio client with id %d", id);
+    case PSK_IQ: return fail(PSDR_ERR_INVALID, "PSK decoder: client %d is a PSDR_IQ client, which has no audio rows", id);
+    case PSK_BAD_CARRIER: return fail(PSDR_ERR_INVALID, "PSK decoder: carrier_hz %g is not a finite number inside [%g, %g]", cfg->carrier_hz, PSK_CARRIER_MIN, PSK_CARRIER_MAX);
+    case PSK_BAD_BAUD: return fail(PSDR_ERR_INVALID, "PSK decoder: baud %g is neither %g nor %g", cfg->baud, PSK_BAUD_31, PSK_BAUD_63);
+    case PSK_BAD_SEARCH: return fail(PSDR_ERR_INVALID, "PSK decoder: search_hz %g is not a finite number inside [0, %g), half the baud rate", cfg->search_hz, cfg->baud / 2);
+    case PSK_BAD_QUALITY: return fail(PSDR_ERR_INVALID, "PSK decoder: quality %g is not a finite number inside (0, 1)", cfg->quality);
+    case PSK_BAD_RATE: return fail(PSDR_ERR_STATE, "PSK decoder: the context's audio_rate %d is outside [%d, %d]", c->cfg.audio_rate, PSK_RATE_MIN, PSK_RATE_MAX);
+    case PSK_BAD_BAND: return fail(PSDR_ERR_STATE, "PSK decoder: the lanes from %g to %g Hz do not lie inside [%g Hz, %g of the audio_rate %d]", cfg->carrier_hz + psk_lane_hz(0, cfg->baud), cfg->carrier_hz + psk_lane_hz(PSK_LANES - 1, cfg->baud), PSK_BOTTOM, PSK_TOP, c->cfg.audio_rate);
+    }
+    if (cfg) PSDRCHK(first_psk_decoder(c));
+    psk_apply(c->aslots[id], cfg, c->cfg.audio_rate);
+    return PSDR_OK;
+}
+extern "C" int psdr_psk_defaults(double audio_rate, psdr_psk_config *out) {
+    if (!out) return fail(PSDR_ERR_INVALID, "null argument");
+    if (!psk_defaults(audio_rate, out)) return fail(PSDR_ERR_INVALID, "PSK decoder defaults: audio_rate %g outside [%d, %d]", audio_rate, PSK_RATE_MIN, PSK_RATE_MAX);
+    return PSDR_OK;
+}
 extern "C" int psdr_client_set_agc_profile(psdr_ctx *c, int id, const psdr_agc_profile *p) {
     if (!c) return fail(PSDR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mtx);
@@ -615,6 +641,7 @@ struct BatchPlan {
     TonePlan tone;
     CwPlan cw;
     RttyPlan rtty;
+    PskPlan psk;
     AgcPlan ag;
     bool chain = false;  // the post chain follows: it is on, and somebody is in it
     // of the optional features: the rows of the result set this batch writes and the detector's table - null where the context has
@@ -652,6 +679,7 @@ static int batch_plan(psdr_ctx *c, int nframes, const uint32_t *band, BatchPlan 
     if (c->tone) b.tone = tone_plan(slots, S, c->demod_seq, b.chain, c->tone.tab.host(b.ring));
     if (c->cw) b.cw = cw_plan(slots, S, c->demod_seq, c->cw.tab.host(b.ring));
     if (c->rtty) b.rtty = rtty_plan(slots, S, c->demod_seq, c->rtty.tab.host(b.ring));
+    if (c->psk) b.psk = psk_plan(slots, S, c->demod_seq, c->psk.tab.host(b.ring));
     if (c->agc_prof && b.chain) b.ag = agc_profile_plan(slots, S, c->demod_seq, c->agc_prof.tab.host(b.ring));
     return PSDR_OK;
 }
@@ -683,6 +711,11 @@ static int batch_begin(psdr_ctx *c, const BatchPlan &b) {
     for (size_t slot : b.rtty.zero) {
         HIPCHK(hipMemsetAsync(c->rtty.state + slot, 0, sizeof(RttyState), c->side));
         HIPCHK(hipMemsetAsync(c->rtty.text + slot * (size_t)RTTY_TEXT, 0, RTTY_TEXT, c->side));
+    }
+    // ... and the PSK decoders: state and text ring (psk_plan has taken psk_fresh off these slots)
+    for (size_t slot : b.psk.zero) {
+        HIPCHK(hipMemsetAsync(c->psk.state + slot, 0, sizeof(PskState), c->side));
+        HIPCHK(hipMemsetAsync(c->psk.text + slot * (size_t)PSK_TEXT, 0, PSK_TEXT, c->side));
     }
     // ... and the noise floors that start from zero: sums and record (noise_plan has taken nf_fresh off these slots)
     for (size_t slot : b.nf.zero) {
@@ -719,6 +752,7 @@ static int batch_begin(psdr_ctx *c, const BatchPlan &b) {
     if (b.tone.any()) HIPCHK(c->tone.tab.upload(b.ring, (size_t)(b.tone.n + b.tone.ncopy), c->side));
     if (b.cw.any()) HIPCHK(c->cw.tab.upload(b.ring, (size_t)b.cw.n, c->side));
     if (b.rtty.any()) HIPCHK(c->rtty.tab.upload(b.ring, (size_t)b.rtty.n, c->side));
+    if (b.psk.any()) HIPCHK(c->psk.tab.upload(b.ring, (size_t)b.psk.n, c->side));
     return PSDR_OK;
 }
 
@@ -928,6 +962,19 @@ static int launch_rtty_decoder(psdr_ctx *c, const BatchPlan &b, int nframes) {
     HIPCHK(audio_rtty_launch(ra, c->side));
     return PSDR_OK;
 }
+// ... the PSK31 decoder, at the same reading point: it reads the listed clients' rows as the demodulator left them and writes the
+// frames' records and the clients' text
+static int launch_psk_decoder(psdr_ctx *c, const BatchPlan &b, int nframes) {
+    PskArgs pa{};
+    pa.list = c->psk.tab.dev(b.ring), pa.nlist = b.psk.n;
+    pa.tab = c->psk.plan;
+    pa.audio = c->d_audio, pa.nan_flags = c->d_nan;
+    pa.state = c->psk.state, pa.text = c->psk.text, pa.rec = c->psk.rec;
+    pa.nframes = nframes, pa.max_batch = c->max_batch, pa.h = c->n / 2;
+    ProfScope ps(c, K_AUDIO_PSK, c->side);
+    HIPCHK(audio_psk_launch(pa, c->side));
+    return PSDR_OK;
+}
 // ... the audio blanker, in front of the noise reduction, the audio filter and the chain: it works on the listed clients' rows in
 // place
 static int launch_audio_blanker(psdr_ctx *c, const BatchPlan &b, int nframes) {
@@ -1002,6 +1049,7 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     if (b.tone.any()) PSDRCHK(launch_tone_decoder(c, b, nframes, &chain_drop));
     if (b.cw.any()) PSDRCHK(launch_cw_decoder(c, b, nframes));
     if (b.rtty.any()) PSDRCHK(launch_rtty_decoder(c, b, nframes));
+    if (b.psk.any()) PSDRCHK(launch_psk_decoder(c, b, nframes));
     if (b.anb.any()) PSDRCHK(launch_audio_blanker(c, b, nframes));
     if (b.nr.any()) PSDRCHK(launch_noise_reduction(c, b, nframes));
     if (b.af.any()) PSDRCHK(launch_audio_filter(c, b, nframes));

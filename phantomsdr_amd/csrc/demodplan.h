@@ -114,6 +114,18 @@ struct AudioSlot {
     float rtty_rot[32][2] = {};
     bool b_rtty_on = false, rtty_fresh = false;
     int rtty_mode = PSDR_USB, rtty_l = 0, rtty_r = 0, rtty_m = 0;
+    // psdr_client_set_psk_decoder (pskplan.h): the parameters as the table holds them - the symbol window in hops, the symbol
+    // length in 1/16 hop, the candidate lanes, the coherence asked for, the level's scale, the lane spacing, the 16 lanes'
+    // increments and rotations; b_psk_on: the last batch ran with it (psdr_read_psk); psk_fresh, psk_mode, psk_l, psk_r, psk_m: as
+    // the tone decoder's
+    int psk_on = 0;
+    int psk_wn = 24, psk_u = 384;
+    uint32_t psk_cand = 0;
+    float psk_quality = 1.f, psk_lscale = 0.f, psk_df = 0.f;
+    uint32_t psk_inc[16] = {};
+    float psk_rot[16][2] = {};
+    bool b_psk_on = false, psk_fresh = false;
+    int psk_mode = PSDR_USB, psk_l = 0, psk_r = 0, psk_m = 0;
 };
 
 // The client parameter ring's slot.  [ClientParams x S][int x S]: the batch's list and, for the post chain, the list index of

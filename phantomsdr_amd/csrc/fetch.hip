@@ -536,6 +536,62 @@ extern "C" int psdr_read_rtty_text(psdr_ctx *c, int id, uint64_t from, char *out
     if (total_out) *total_out = total;
     return PSDR_OK;
 }
+// the PSK decoder's records of the last batch; any of the six arrays may be null
+extern "C" int psdr_read_psk(psdr_ctx *c, int id, int nframes, uint32_t *nchars, uint32_t *errors, float *offset_hz, float *level, float *quality, int32_t *present,
+                              int *nframes_out) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    size_t F = 0;
+    bool on = false;
+    PSDRCHK(read_begin(c, id, false, nframes, nframes_out, ROWS_AUDIO, false, &F, [&](const AudioSlot &s) { on = s.b_psk_on && (bool)c->psk; }));
+    if (!on) return fail(PSDR_ERR_NO_DATA, "client %d had no PSK decoder in the last demodulation batch", id);
+    HIPCHK(hipSetDevice(c->device));
+    PSDRCHK(drain(c));
+    std::vector<PskRec> rec(F);
+    HIPCHK(hipMemcpy(rec.data(), c->psk.rec + fetch_row(id, (size_t)c->max_batch, 0), F * sizeof(PskRec), hipMemcpyDeviceToHost));
+    for (size_t f = 0; f < F; f++) {
+        if (nchars) nchars[f] = rec[f].nchars;
+        if (errors) errors[f] = rec[f].errors;
+        if (offset_hz) offset_hz[f] = rec[f].offset_hz;
+        if (level) level[f] = rec[f].level;
+        if (quality) quality[f] = rec[f].quality;
+        if (present) present[f] = rec[f].present;
+    }
+    return PSDR_OK;
+}
+// the PSK decoder's text since the state last started, from the slot's ring
+extern "C" int psdr_read_psk_text(psdr_ctx *c, int id, uint64_t from, char *out, size_t cap, size_t *n_out, uint64_t *total_out) {
+    if (!c || (!out && cap)) return fail(PSDR_ERR_INVALID, "null argument");
+    bool pending = false;
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);
+        if (id < 0 || (size_t)id >= c->aslots.size()) return fail(PSDR_ERR_INVALID, "PSK text: id %d outside 0..%d", id, (int)c->aslots.size() - 1);
+        const AudioSlot &s = c->aslots[id];
+        if (!s.active) return fail(PSDR_ERR_INVALID, "no audio client with id %d", id);
+        if (!s.psk_on || !c->psk) return fail(PSDR_ERR_NO_DATA, "client %d has no PSK decoder", id);
+        pending = s.psk_fresh;
+    }
+    uint64_t total = 0;
+    std::vector<uint8_t> ring;
+    if (!pending) {
+        HIPCHK(hipSetDevice(c->device));
+        PSDRCHK(drain(c));
+        std::vector<PskState> st(1);
+        HIPCHK(hipMemcpy(st.data(), c->psk.state + (size_t)id, sizeof(PskState), hipMemcpyDeviceToHost));
+        total = st[0].nchars;
+        if (from < total && total - from <= (uint64_t)PSK_TEXT) {
+            ring.resize(PSK_TEXT);
+            HIPCHK(hipMemcpy(ring.data(), c->psk.text + (size_t)id * PSK_TEXT, PSK_TEXT, hipMemcpyDeviceToHost));
+        }
+    }
+    if (from > total) return fail(PSDR_ERR_INVALID, "PSK text: from %llu is beyond the text's %llu characters", (unsigned long long)from, (unsigned long long)total);
+    if (total - from > (uint64_t)PSK_TEXT)
+        return fail(PSDR_ERR_NO_DATA, "PSK text: from %llu is older than the last %d of %llu characters", (unsigned long long)from, PSK_TEXT, (unsigned long long)total);
+    const size_t n = std::min((size_t)(total - from), cap);
+    for (size_t j = 0; j < n; j++) out[j] = (char)ring[(from + j) % PSK_TEXT];
+    if (n_out) *n_out = n;
+    if (total_out) *total_out = total;
+    return PSDR_OK;
+}
 extern "C" int psdr_read_noise(psdr_ctx *c, int id, int nframes, float *w, int *nframes_out) {
     if (!c || !w) return fail(PSDR_ERR_INVALID, "null argument");
     size_t F = 0;
