@@ -930,6 +930,104 @@ int psdr_client_set_psk_decoder(psdr_ctx *ctx, int id, const psdr_psk_config *cf
 int psdr_read_psk(psdr_ctx *ctx, int id, int nframes, uint32_t *nchars, uint32_t *errors, float *offset_hz, float *level, float *quality,
                   int32_t *present, int *nframes_out);
 int psdr_read_psk_text(psdr_ctx *ctx, int id, uint64_t from, char *out, size_t cap, size_t *n_out, uint64_t *total_out);
+/* Radiofax (WEFAX) decoder: the image lines of the HF facsimile a client's audio carries - black 1500 Hz, white 2300 Hz in USB
+ * audio, 120 lines per minute as the weather services send it -, per client on the audio rows.  It READS the rows as the
+ * demodulator wrote them - the tone, CW, RTTY and PSK decoders' reading point: behind the squelch, in front of the audio blanker,
+ * the noise reduction and the audio filter - and never writes them: every other output of the client is that of a client without it.
+ *   Stream, hop.  The other decoders': the client's rows in frame order, a NaN-flagged frame entering as zeros, sample t counting
+ *     from the state's start; H = 8 samples below audio_rate 8000, 16 below 16000, 32 below 32000, else 64.
+ *   Discriminator, per sample.  z[t] = x[t] conj(w[t]); w turns at centre_hz = (black_hz + white_hz) / 2: phase increment
+ *     round(centre_hz / audio_rate * 2^32) in double, the seed from the two 4096-entry tables at the exact 32-bit phase of the hop's
+ *     first sample and one rotation per sample are the tone decoder's.  y[t] = sum_{i < K} z[t - i], i ascending from +0,
+ *     K = max(2, round(audio_rate / (2 centre_hz))), samples before the start counting as 0: the boxcar's first null sits on the
+ *     mixing image.  d[t] = y[t] conj(y[t - D]), D = max(1, floor(audio_rate / 3200)).  a[t] = fax_angle(d): ONE f32 division, of
+ *     the smaller of |Im d| and Re d by the larger (the quotient, in [-1, 1], clamped to it), an odd polynomial of degree 17 in fmaf
+ *     form with literal coefficients (Abramowitz and Stegun 4.4.49) and, where Im was the larger, +-pi/2 minus it; a d with
+ *     Re <= 0 or one that is not finite saturates at +-pi/2 by the sign of Im, a zero d reads 0.  (A clamped tangent Im / Re cannot
+ *     reach the +-pi/2 that a shift of 1600 Hz needs at a rate that is a multiple of 3200: DESIGN.md 3.24.)
+ *     v[t] = clamp(0.5 + a[t] s, 0, 1), s = audio_rate / (2 pi D (white_hz - black_hz)) in double, rounded once: 0 is black, 1 is
+ *     white, and a white_hz below black_hz inverts the picture.
+ *   Line and column, integers.  Lq = round(65536 * 60 audio_rate / lpm * (1 + slant_ppm 1e-6)) in double, held as 64 bits: the
+ *     line in 1/65536 sample.  Sample t lies in line floor((65536 t + Lq - origin) / Lq) - 1 and in column
+ *     floor(((65536 t + Lq - origin) mod Lq) width / Lq); origin, in [0, Lq), starts as phase_col Lq / width and is moved only by
+ *     the phasing, with the next line boundary.  The samples in front of the first origin and behind a move are a partial line,
+ *     which is never looked at.  A pixel is the sum of its samples' v (t ascending, one f32 accumulator) divided by their count
+ *     (one f32 division) as min(255, floor(255 p + 0.5)); the call makes sure that a pixel has 1 to 64 samples.  A line is
+ *     complete with the first sample of the next one.
+ *   Tones, on v, PSDR_FAX_AUTO only.  Per hop C_k = sum (v - 0.5) conj(w_k) for 300, 450 and 675 Hz (the tone decoder's seed,
+ *     rotation and single accumulator), Q = sum (v - 0.5)^2, M = sum (v - 0.5).  Blocks of NB = round(audio_rate / (8 H)) hops
+ *     (1/8 s) do not overlap; at a block's end rho_k = 2 |sum C_k|^2 / (NB H sum Q), 0 when not finite; tone k hits when it is
+ *     the (lowest) largest of the three and rho_k >= tone_ratio.  One counter per tone: + 1 in a block it hits, - 1 in any other,
+ *     held in [0, 2 start_blocks].
+ *   Machine.  IDLE -> PHASING when the 300 Hz counter (IOC 576) or the 675 Hz counter (IOC 288) reaches start_blocks: the image's
+ *     serial goes up by one, the IOC is noted, the counters are cleared.  Any state -> IDLE when the 450 Hz counter reaches
+ *     start_blocks (looked at first; the counters are cleared).  In PHASING every complete line is searched for the narrow pulse
+ *     of either polarity: a line whose pixels sum to 255 width / 2 or more has a dark pulse and is measured as 255 - pix, else as
+ *     pix; dev(c) = the sum over wp = max(1, width / 20) circular columns from c, c* the lowest column with the largest dev; the
+ *     line is valid when dev(c*) >= 192 wp and the rest of it sums to 64 (width - wp) at most.  A valid line within width / 64
+ *     columns, circularly, of the previous valid line's c* extends a run, any other starts it over; when the run reaches
+ *     phase_lines the origin moves on by ((c* + wp / 2) mod width) Lq / width - the pulse's middle becomes column 0 - and the
+ *     state is IMAGE; after 80 lines without that it is IMAGE with the origin as it stands.  In IMAGE every complete line is
+ *     kept; behind max_lines of them (0: no limit) the state is IDLE.  PSDR_FAX_FREE: no tones, no phasing, IMAGE from sample 0.
+ *   Kept lines.  A ring of R lines of width bytes per slot, each with 32 bits of meta: the image's serial << 8 | the state in
+ *     which it was taken.  R = max(64, 2 + the lines the context's largest batch can complete, floor(samples 65536 / Lq) + 1), fixed by the call.
+ *   Records.  Frame f's record is the state behind the last hop that is complete at the frame's last sample: nlines = the kept
+ *     lines modulo 2^32, state (0 IDLE, 1 PHASING, 2 IMAGE), image = the serial, ioc (0 before the first start tone),
+ *     offset_hz = (white_hz - black_hz) F with F <- F + (sum M / (NB H) - F) / 8 in the blocks with a hit - a start or stop tone
+ *     is symmetric about the centre, so this is the listener's mistuning; it is reported only -, tone_quality = the last block's
+ *     largest rho.  Any split of the same frames into batches gives the same bits in records, lines and meta.
+ *     phantomsdr_amd/csrc/faxplan.h is the one definition of all of it, for the device and a host program alike.
+ *   Who.  Every client of a batch whose kind writes audio rows; a PSDR_IQ client is refused, a client that becomes one keeps its
+ *     setting and is not listed.  The state is carried across batches and across dropped or flagged frames and stands still while
+ *     the client is paused.  It starts from zero when the call switches the decoder on (again, too), on a mode change and on a
+ *     retune.  Per client slot 3224 bytes of state, the ring (2048 bytes per line the context's largest batch can complete at 240
+ *     lines per minute, 64 lines at least), 24 bytes per frame of a batch for the records; 128 bytes per listed client in the
+ *     batch's table.
+ *   The default tone_ratio is the middle between two figures of the host model: the largest rho unit noise alone
+ *     reaches in 120 s, 0.0184, and the smallest a start tone keeps at the lowest signal-to-noise ratio, in 3 dB steps, at which
+ *     the test sequence still locks, 0.425 at 6 dB in 3 kHz: 0.22.  Nobody has tried it on off-air radiofax.
+ * psdr_client_set_fax_decoder: any thread; in force from the client's next batch; cfg = NULL switches it off.  PSDR_ERR_INVALID,
+ *   with nothing changed and a text of its own each, for an id outside the slots, a slot without a client, (cfg != NULL) a PSDR_IQ
+ *   client, then the fields in their order: a mode that is neither, black_hz or white_hz not finite or outside [300, 3400] or
+ *   |white_hz - black_hz| outside [200, 1600], an lpm that is none of 60, 90, 120, 240, width outside [256, 2048], slant_ppm not
+ *   finite or outside [-2000, 2000], phase_col outside [0, width), tone_ratio not finite or outside (0, 1), start_blocks outside
+ *   [2, 64], phase_lines outside [2, 32], max_lines below 0; then PSDR_ERR_STATE for a context whose audio_rate is outside
+ *   [4000, 48000]; then PSDR_ERR_STATE when the higher tone plus 300 Hz lies above 0.45 audio_rate; then PSDR_ERR_STATE when a
+ *   pixel would hold fewer than 1 or more than 64 samples - in this order.  The device state is allocated with the context's first
+ *   such client, all or none: PSDR_ERR_NOMEM and the setting unchanged if that fails.  A context without such a client allocates
+ *   nothing, a batch without one launches nothing.
+ * psdr_fax_defaults: needs no context; the values in the struct's comments.  PSDR_ERR_INVALID for a null pointer or an audio_rate
+ *   outside [4000, 48000].  (Below 5778 Hz the default tones do not fit: the call says so.)
+ * psdr_read_fax: psdr_read_psk's contract - the records of the last demodulation batch, nframes the room of the arrays (any of
+ *   which may be null), synchronises; a client whose last batch ran without the decoder reads PSDR_ERR_NO_DATA, as does one that
+ *   was not part of the batch or was demodulated as PSDR_IQ.
+ * psdr_read_fax_lines: psdr_read_psk_text's contract with a line in place of a character: the kept lines from .. total - 1 since
+ *   the state last started, cap_lines at most, width bytes each into pix and one meta word each into meta (either may be null when
+ *   cap_lines is 0); a from beyond total is PSDR_ERR_INVALID, one older than the ring's R lines PSDR_ERR_NO_DATA; total_out counts
+ *   every kept line, width_out is the client's width.
+ * Nothing of it goes through psdr_fetch_* yet, and there is no psdr_group_* call: a group's clients have no fax decoder.  Out of
+ * scope: applying offset_hz (AFC), automatic slant correction, colour fax and SSTV. */
+#define PSDR_FAX_AUTO 0
+#define PSDR_FAX_FREE 1
+#define PSDR_FAX_TONE_RATIO_DEFAULT 0.22
+typedef struct {
+    int    mode;         /* PSDR_FAX_AUTO (default) | PSDR_FAX_FREE */
+    double black_hz, white_hz;   /* each in [300, 3400], |white-black| in [200, 1600]; 1500 / 2300 */
+    double lpm;          /* 60, 90, 120 (default) or 240 */
+    int    width;        /* pixels per line, [256, 2048], default 1024 */
+    double slant_ppm;    /* [-2000, 2000], default 0 */
+    int    phase_col;    /* [0, width), default 0 */
+    double tone_ratio;   /* (0, 1), default PSDR_FAX_TONE_RATIO_DEFAULT (measured, above) */
+    int    start_blocks; /* [2, 64], default 8 (1 s) */
+    int    phase_lines;  /* [2, 32], default 4 */
+    int    max_lines;    /* >= 0, default 0 */
+} psdr_fax_config;
+int psdr_fax_defaults(double audio_rate, psdr_fax_config *out);               /* needs no context */
+int psdr_client_set_fax_decoder(psdr_ctx *ctx, int id, const psdr_fax_config *cfg);   /* NULL: off */
+int psdr_read_fax(psdr_ctx *ctx, int id, int nframes, uint32_t *nlines, int32_t *state, uint32_t *image, int32_t *ioc,
+                  float *offset_hz, float *tone_quality, int *nframes_out);
+int psdr_read_fax_lines(psdr_ctx *ctx, int id, uint64_t from, uint8_t *pix, uint32_t *meta, size_t cap_lines,
+                        size_t *n_out, uint64_t *total_out, int *width_out);
 /* AGC profile: speed, target, gain cap and manual gain per client.  The context's AGC is the reference's - target 0.2, attack
  * 50 ms, release 300 ms (psdr_set_post_chain) - for every client; a profile replaces these numbers for one client: a fast AGC for
  * CW, a slow one for broadcast, a bound on the gain a quiet channel is pumped up by, or no AGC at all and a fixed gain, which is

@@ -16,6 +16,7 @@ from .core import TONE_ANY, tone_defaults, tone_table  # noqa: F401
 from .core import cw_defaults  # noqa: F401
 from .core import rtty_defaults  # noqa: F401
 from .core import psk_defaults  # noqa: F401
+from .core import FAX_AUTO, FAX_FREE, fax_defaults  # noqa: F401
 from .core import AGC_FAST, AGC_PRESETS, AGC_REFERENCE, AGC_SLOW, agc_preset  # noqa: F401
 from .core import (AM, FM, IQ, LSB, MODES, SAM, SAM_BOTH, SAM_LOWER, SAM_SIDEBANDS, SAM_UPPER, USB, WF_DETECTORS, WF_MEAN, WF_PEAK,  # noqa: F401
                    WF_SAMPLE, AudioClient, Context, Group, HipFFT, SpectrumEngine, WaterfallClient, derived_params)

@@ -58,6 +58,13 @@ class psdr_psk_config(C.Structure):
     _fields_ = [("carrier_hz", C.c_double), ("baud", C.c_double), ("search_hz", C.c_double), ("quality", C.c_double)]
 
 
+class psdr_fax_config(C.Structure):
+    """psdr_client_set_fax_decoder: mode, black_hz, white_hz, lpm, width, slant_ppm, phase_col, tone_ratio, start_blocks, phase_lines,
+    max_lines"""
+    _fields_ = [("mode", C.c_int), ("black_hz", C.c_double), ("white_hz", C.c_double), ("lpm", C.c_double), ("width", C.c_int), ("slant_ppm", C.c_double),
+                ("phase_col", C.c_int), ("tone_ratio", C.c_double), ("start_blocks", C.c_int), ("phase_lines", C.c_int), ("max_lines", C.c_int)]
+
+
 class psdr_scan_config(C.Structure):
     """psdr_scan_set: scan level, trace shift 0..8, threshold in counts 1..255, gap in bins 0..64"""
     _fields_ = [(n, C.c_int) for n in ("level", "avg_shift", "threshold", "gap")]
@@ -142,6 +149,10 @@ SYMBOLS = [
     ("psdr_psk_defaults", _i, [C.c_double, C.POINTER(psdr_psk_config)]),
     ("psdr_read_psk", _i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i)]),
     ("psdr_read_psk_text", _i, [_vp, _i, C.c_uint64, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
+    ("psdr_client_set_fax_decoder", _i, [_vp, _i, C.POINTER(psdr_fax_config)]),
+    ("psdr_fax_defaults", _i, [C.c_double, C.POINTER(psdr_fax_config)]),
+    ("psdr_read_fax", _i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i)]),
+    ("psdr_read_fax_lines", _i, [_vp, _i, C.c_uint64, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(_i)]),
     ("psdr_client_set_agc_profile", _i, [_vp, _i, C.POINTER(psdr_agc_profile)]),
     ("psdr_agc_preset", _i, [_i, C.POINTER(psdr_agc_profile)]),
     ("psdr_read_agc_gain", _i, [_vp, _i, C.POINTER(C.c_float)]),

@@ -10,7 +10,7 @@ CSRC = os.path.join(_HERE, "csrc")
 # context: lifetime / Level 1 / ingest / instrumentation; pass1, pass2: the FFT pass launchers; forward: the frame loop,
 # read-back, band layout, waterfall; demod: audio clients; fetch: the served end, results to host memory; postchain: DC blocker /
 # AGC / int16; audiofilter: the per-client biquad cascade behind the detector; group: n GPUs from one process over RCCL; wire: packet formats; blanker: the impulse blanker on the ingest ring
-UNITS = ["context", "pass1", "pass2", "forward", "demod", "fetch", "postchain", "group", "wire", "blanker", "audiofilter", "nr", "anb", "scan", "tone", "cw", "rtty", "psk"]  # psk: the per-client PSK31 decoder at the same reading point; rtty: the per-client RTTY decoder at the same reading point; cw: the per-client CW decoder at the tone decoder's reading point; tone: the per-client tone decoder on the rows as the demodulator wrote them; scan: the band scan behind a batch (trace, segment floors, list of signals); nr: the per-client noise reduction in front of the audio filter; anb: the per-client audio blanker in front of it
+UNITS = ["context", "pass1", "pass2", "forward", "demod", "fetch", "postchain", "group", "wire", "blanker", "audiofilter", "nr", "anb", "scan", "tone", "cw", "rtty", "psk", "fax"]  # fax: the per-client radiofax decoder at the same reading point; psk: the per-client PSK31 decoder at the same reading point; rtty: the per-client RTTY decoder at the same reading point; cw: the per-client CW decoder at the tone decoder's reading point; tone: the per-client tone decoder on the rows as the demodulator wrote them; scan: the band scan behind a batch (trace, segment floors, list of signals); nr: the per-client noise reduction in front of the audio filter; anb: the per-client audio blanker in front of it
 OUT = os.path.join(_HERE, "libpsdr_hip.so")
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-value", "-fPIC"]

@@ -120,6 +120,19 @@ def psk_defaults(audio_rate):
     return {k: getattr(p, k) for k in PSK_FIELDS}
 
 
+FAX_AUTO, FAX_FREE = 0, 1
+FAX_FIELDS = ("mode", "black_hz", "white_hz", "lpm", "width", "slant_ppm", "phase_col", "tone_ratio", "start_blocks", "phase_lines", "max_lines")
+FAX_INT_FIELDS = ("mode", "width", "phase_col", "start_blocks", "phase_lines", "max_lines")
+
+
+def fax_defaults(audio_rate):
+    """the radiofax decoder's defaults at `audio_rate` as a dict for AudioClient.set_fax_decoder(**...) (psdr_fax_defaults; needs no
+    context): PSDR_FAX_AUTO, black 1500 Hz, white 2300 Hz, 120 lines per minute, 1024 pixels, the measured tone_ratio"""
+    p = _lib.psdr_fax_config()
+    check(_lib.load().psdr_fax_defaults(float(audio_rate), C.byref(p)))
+    return {k: getattr(p, k) for k in FAX_FIELDS}
+
+
 def noise_reduction_preset(kind):
     """(depth_db, beta) of a noise reduction preset for AudioClient.set_noise_reduction (psdr_noise_reduction_preset; needs no
     context): "light" (8 dB, 1), "normal" (14 dB, 1.5) or "strong" (22 dB, 2), or an NR_* constant"""
@@ -872,6 +885,49 @@ class AudioClient:
         n, total = C.c_size_t(0), C.c_uint64(0)
         check(self.ctx.lib.psdr_read_psk_text(self.ctx.h, self.id, int(since), buf, 1024, C.byref(n), C.byref(total)))
         return buf.raw[:n.value].decode("ascii"), total.value
+
+    def set_fax_decoder(self, on=True, **fields):
+        """the image lines of the HF radiofax in the client's audio rows as the demodulator wrote them
+        (psdr_client_set_fax_decoder).  on false or None: off.  Keyword arguments replace single fields of fax_defaults(): mode
+        (FAX_AUTO, FAX_FREE), black_hz, white_hz, lpm, width, slant_ppm, phase_col, tone_ratio, start_blocks, phase_lines,
+        max_lines.  The state and the lines start from zero with every call that switches it on."""
+        if not on:
+            check(self.ctx.lib.psdr_client_set_fax_decoder(self.ctx.h, self.id, None))
+            return
+        p = _lib.psdr_fax_config()
+        # (a rate outside the decoder's range is the call's refusal to make, not the defaults')
+        if self.ctx.lib.psdr_fax_defaults(float(self.ctx.cfg.audio_rate), C.byref(p)) != 0:
+            self.ctx.lib.psdr_fax_defaults(12000.0, C.byref(p))
+        for k, v in fields.items():
+            if k not in FAX_FIELDS:
+                raise TypeError("set_fax_decoder: unknown field %r" % k)
+            setattr(p, k, int(v) if k in FAX_INT_FIELDS else float(v))
+        check(self.ctx.lib.psdr_client_set_fax_decoder(self.ctx.h, self.id, C.byref(p)))
+
+    def read_fax(self, nframes=None):
+        """(nlines[F] uint32, state[F] int32, image[F] uint32, ioc[F] int32, offset_hz[F] float32, tone_quality[F] float32) of the
+        last demod batch (psdr.h: psdr_read_fax): per frame the kept lines so far, the machine's state (0 idle, 1 phasing, 2
+        image), the image's serial, its index of cooperation, the mistuning read off the start and stop tones, the last tone
+        block's largest rho"""
+        F = nframes or self.ctx.last_demod_frames or self.ctx.last_nframes
+        n, s, im = np.empty(F, np.uint32), np.empty(F, np.int32), np.empty(F, np.uint32)
+        io, o, q = np.empty(F, np.int32), np.empty(F, np.float32), np.empty(F, np.float32)
+        got = C.c_int(0)
+        check(self.ctx.lib.psdr_read_fax(self.ctx.h, self.id, F, _ptr(n), _ptr(s), _ptr(im), _ptr(io), _ptr(o), _ptr(q), C.byref(got)))
+        g = got.value
+        return n[:g], s[:g], im[:g], io[:g], o[:g], q[:g]
+
+    def read_fax_lines(self, from_=0):
+        """(lines uint8 [n, width], meta uint32 [n], total): the kept lines from_ .. total - 1 since the decoder's state last started
+        (psdr_read_fax_lines); the device keeps the last 64 at least.  meta: the image's serial << 8 | the state the line was
+        taken in"""
+        n, total, width = C.c_size_t(0), C.c_uint64(0), C.c_int(0)
+        check(self.ctx.lib.psdr_read_fax_lines(self.ctx.h, self.id, int(from_), None, None, 0, C.byref(n), C.byref(total), C.byref(width)))
+        cap = max(0, total.value - int(from_))
+        pix, meta = np.empty((cap, max(width.value, 1)), np.uint8), np.empty(cap, np.uint32)
+        if cap:
+            check(self.ctx.lib.psdr_read_fax_lines(self.ctx.h, self.id, int(from_), _ptr(pix), _ptr(meta), cap, C.byref(n), C.byref(total), C.byref(width)))
+        return pix[:n.value], meta[:n.value], total.value
 
     def set_agc_profile(self, profile, **fields):
         """the client's own AGC numbers in the post chain (psdr_client_set_agc_profile).  `profile`: None - back to the context's

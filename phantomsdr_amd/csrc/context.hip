@@ -27,7 +27,7 @@ const char *kKernelNames[K_COUNT] = {"fft_pass1",  "fft_pass2", "untangle_real",
                                      "demod_idft", "demod_ola", "waterfall_gather", "post_chain",
                                      "real_seam",  "band_pack",  "waterfall_hold", "waterfall_carry",
                                      "squelch",    "blanker_scan", "blanker_apply",  "audio_filter", "audio_nr", "audio_nb",
-                                     "scan_trace", "scan_floor",   "scan_hot",       "scan_mark",    "scan_emit", "audio_tone", "audio_cw", "audio_rtty", "audio_psk"};
+                                     "scan_trace", "scan_floor",   "scan_hot",       "scan_mark",    "scan_emit", "audio_tone", "audio_cw", "audio_rtty", "audio_psk", "audio_fax"};
 
 void resolve_pending(psdr_ctx *c) {
     if (c->pending.empty()) return;

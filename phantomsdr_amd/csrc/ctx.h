@@ -31,6 +31,7 @@
 #include "cwplan.h"
 #include "rttyplan.h"
 #include "pskplan.h"
+#include "faxplan.h"
 #include "demodplan.h"
 #include "fetchplan.h"
 #include "forwardplan.h"
@@ -76,7 +77,7 @@ inline const char *psdr_tuning_env(const char *name) {
 
 namespace psdr {
 
-enum KernelId { K_PASS1, K_PASS2, K_UNTANGLE, K_TAIL, K_IDFT, K_OLA, K_WFALL, K_POST, K_SEAM, K_BAND, K_WFHOLD, K_WFCARRY, K_SQUELCH, K_NB_SCAN, K_NB_APPLY, K_AUDIO_FILTER, K_AUDIO_NR, K_AUDIO_NB, K_SCAN_TRACE, K_SCAN_FLOOR, K_SCAN_HOT, K_SCAN_MARK, K_SCAN_EMIT, K_AUDIO_TONE, K_AUDIO_CW, K_AUDIO_RTTY, K_AUDIO_PSK, K_COUNT };
+enum KernelId { K_PASS1, K_PASS2, K_UNTANGLE, K_TAIL, K_IDFT, K_OLA, K_WFALL, K_POST, K_SEAM, K_BAND, K_WFHOLD, K_WFCARRY, K_SQUELCH, K_NB_SCAN, K_NB_APPLY, K_AUDIO_FILTER, K_AUDIO_NR, K_AUDIO_NB, K_SCAN_TRACE, K_SCAN_FLOOR, K_SCAN_HOT, K_SCAN_MARK, K_SCAN_EMIT, K_AUDIO_TONE, K_AUDIO_CW, K_AUDIO_RTTY, K_AUDIO_PSK, K_AUDIO_FAX, K_COUNT };
 extern const char *kKernelNames[K_COUNT];
 
 struct PendingEvent {
@@ -529,6 +530,36 @@ struct psdr_ctx {
         }
         explicit operator bool() const { return (bool)tab; }
     } psk;
+    // Radiofax decoder (fax.h: k_audio_fax): the clients' carried state [slots], the line rings [slots][rmax][2048] and their meta
+    // [slots][rmax] - rmax the lines the context's largest batch can complete at 240 lines per minute, 64 at least -, the seed
+    // tables for the context's audio_rate, the frames' records [slots][max_batch] (written and read on `side` within one batch or
+    // behind a drain: one set), and the batch's table (faxplan.h), a RingTable beside client_ring
+    struct FaxDecoder {
+        DevBuf<FaxState> state;
+        DevBuf<uint8_t> ring;
+        DevBuf<uint32_t> meta;
+        DevBuf<FaxTables> plan;
+        DevBuf<FaxRec> rec;
+        RingTable<FaxEntry> tab;
+        int rmax = 0;
+        static uint64_t max_samples(const psdr_ctx &c) { return (uint64_t)c.max_batch * (uint64_t)(c.n / 2); }
+        static size_t bytes(const psdr_ctx &c) {
+            const size_t S = c.aslots.size(), R = (size_t)fax_ring_max((double)c.cfg.audio_rate, max_samples(c));
+            return S * (sizeof(FaxState) + R * (FAX_WIDTH_MAX + sizeof(uint32_t)) + (size_t)c.max_batch * sizeof(FaxRec)) + sizeof(FaxTables) + RingTable<FaxEntry>::bytes(S);
+        }
+        int alloc(const psdr_ctx &c) {
+            const size_t S = c.aslots.size();
+            rmax = fax_ring_max((double)c.cfg.audio_rate, max_samples(c));
+            if (state.alloc(S, true) || ring.alloc(S * (size_t)rmax * FAX_WIDTH_MAX, true) || meta.alloc(S * (size_t)rmax, true) || plan.alloc(1) ||
+                rec.alloc(S * (size_t)c.max_batch, true) || tab.alloc(S))
+                return 1;
+            std::vector<FaxTables> t(1);
+            fax_tables(t[0], (double)c.cfg.audio_rate);
+            const hipError_t e = hipMemcpy(plan.get(), t.data(), sizeof(FaxTables), hipMemcpyHostToDevice);
+            return e == hipSuccess ? 0 : psdr_fail(PSDR_ERR_HIP, "fax decoder tables: %s", hipGetErrorString(e));
+        }
+        explicit operator bool() const { return (bool)tab; }
+    } fax;
     // AGC profiles (agcplan.h; postchain.h: k_pc_want_prof and the PcWithProfiles kernels): the batch's table, a RingTable beside
     // client_ring.  The chain's carried state is the context's own: a profile adds none
     struct AgcProfiles {

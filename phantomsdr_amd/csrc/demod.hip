@@ -12,6 +12,7 @@
 #include "cw.h"
 #include "rtty.h"
 #include "psk.h"
+#include "fax.h"
 
 // The context's first client of an optional feature (ctx.h: the structs behind `iq`): what the feature allocates is built whole
 // and only then moved in, so a failed call leaves the context as it was.  msg: the failure's text, with the bytes and the
@@ -37,6 +38,7 @@ static int first_tone_decoder(psdr_ctx *c) { return first_use(c, c->tone, "tone 
 static int first_cw_decoder(psdr_ctx *c) { return first_use(c, c->cw, "CW decoder state, text, records and tables (%zu bytes): %s"); }
 static int first_rtty_decoder(psdr_ctx *c) { return first_use(c, c->rtty, "RTTY decoder state, text, records and tables (%zu bytes): %s"); }
 static int first_psk_decoder(psdr_ctx *c) { return first_use(c, c->psk, "PSK decoder state, text, records and tables (%zu bytes): %s"); }
+static int first_fax_decoder(psdr_ctx *c) { return first_use(c, c->fax, "fax decoder state, line rings, records and tables (%zu bytes): %s"); }
 // the detector's state of one slot back to zero: sums, counter, both automatic entries (stream-ordered on `side`)
 static int notch_zero(psdr_ctx *c, size_t slot) {
     HIPCHK(hipMemsetAsync(c->notch.acc + slot * (size_t)c->n, 0, (size_t)c->n * sizeof(float), c->side));
@@ -456,6 +458,37 @@ extern "C" int psdr_psk_defaults(double audio_rate, psdr_psk_config *out) {
     if (!psk_defaults(audio_rate, out)) return fail(PSDR_ERR_INVALID, "PSK decoder defaults: audio_rate %g outside [%d, %d]", audio_rate, PSK_RATE_MIN, PSK_RATE_MAX);
     return PSDR_OK;
 }
+extern "C" int psdr_client_set_fax_decoder(psdr_ctx *c, int id, const psdr_fax_config *cfg) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(c->mtx);
+    switch (fax_check(c->aslots.data(), c->aslots.size(), id, cfg, c->cfg.audio_rate)) {
+    case FAX_OK: break;
+    case FAX_BAD_ID: return fail(PSDR_ERR_INVALID, "fax decoder: id %d outside 0..%d", id, (int)c->aslots.size() - 1);
+    case FAX_INACTIVE: return fail(PSDR_ERR_INVALID, "no audio client with id %d", id);
+    case FAX_IQ: return fail(PSDR_ERR_INVALID, "fax decoder: client %d is a PSDR_IQ client, which has no audio rows", id);
+    case FAX_BAD_MODE: return fail(PSDR_ERR_INVALID, "fax decoder: mode %d is neither PSDR_FAX_AUTO nor PSDR_FAX_FREE", cfg->mode);
+    case FAX_BAD_TONES: return fail(PSDR_ERR_INVALID, "fax decoder: black_hz %g and white_hz %g are not finite numbers inside [%g, %g] that lie %g to %g apart", cfg->black_hz, cfg->white_hz, FAX_TONE_MIN, FAX_TONE_MAX, FAX_SHIFT_MIN, FAX_SHIFT_MAX);
+    case FAX_BAD_LPM: return fail(PSDR_ERR_INVALID, "fax decoder: lpm %g is none of 60, 90, 120 and 240", cfg->lpm);
+    case FAX_BAD_WIDTH: return fail(PSDR_ERR_INVALID, "fax decoder: width %d outside [%d, %d]", cfg->width, FAX_WIDTH_MIN, FAX_WIDTH_MAX);
+    case FAX_BAD_SLANT: return fail(PSDR_ERR_INVALID, "fax decoder: slant_ppm %g is not a finite number inside [%g, %g]", cfg->slant_ppm, -FAX_SLANT_MAX, FAX_SLANT_MAX);
+    case FAX_BAD_PHASE_COL: return fail(PSDR_ERR_INVALID, "fax decoder: phase_col %d outside [0, width %d)", cfg->phase_col, cfg->width);
+    case FAX_BAD_RATIO: return fail(PSDR_ERR_INVALID, "fax decoder: tone_ratio %g is not a finite number inside (0, 1)", cfg->tone_ratio);
+    case FAX_BAD_START: return fail(PSDR_ERR_INVALID, "fax decoder: start_blocks %d outside [2, 64]", cfg->start_blocks);
+    case FAX_BAD_PHASE_LINES: return fail(PSDR_ERR_INVALID, "fax decoder: phase_lines %d outside [2, 32]", cfg->phase_lines);
+    case FAX_BAD_MAX_LINES: return fail(PSDR_ERR_INVALID, "fax decoder: max_lines %d is negative", cfg->max_lines);
+    case FAX_BAD_RATE: return fail(PSDR_ERR_STATE, "fax decoder: the context's audio_rate %d is outside [%d, %d]", c->cfg.audio_rate, FAX_RATE_MIN, FAX_RATE_MAX);
+    case FAX_BAD_BAND: return fail(PSDR_ERR_STATE, "fax decoder: the higher tone %g Hz plus %g does not lie under %g of the audio_rate %d", std::max(cfg->black_hz, cfg->white_hz), FAX_GUARD, FAX_TOP, c->cfg.audio_rate);
+    case FAX_BAD_PIXEL: return fail(PSDR_ERR_STATE, "fax decoder: at lpm %g and audio_rate %d a pixel of width %d would not hold 1 to %d samples", cfg->lpm, c->cfg.audio_rate, cfg->width, FAX_PIXEL_MAX);
+    }
+    if (cfg) PSDRCHK(first_fax_decoder(c));
+    fax_apply(c->aslots[id], cfg, c->cfg.audio_rate, psdr_ctx::FaxDecoder::max_samples(*c));
+    return PSDR_OK;
+}
+extern "C" int psdr_fax_defaults(double audio_rate, psdr_fax_config *out) {
+    if (!out) return fail(PSDR_ERR_INVALID, "null argument");
+    if (!fax_defaults(audio_rate, out)) return fail(PSDR_ERR_INVALID, "fax decoder defaults: audio_rate %g outside [%d, %d]", audio_rate, FAX_RATE_MIN, FAX_RATE_MAX);
+    return PSDR_OK;
+}
 extern "C" int psdr_client_set_agc_profile(psdr_ctx *c, int id, const psdr_agc_profile *p) {
     if (!c) return fail(PSDR_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(c->mtx);
@@ -642,6 +675,7 @@ struct BatchPlan {
     CwPlan cw;
     RttyPlan rtty;
     PskPlan psk;
+    FaxPlan fax;
     AgcPlan ag;
     bool chain = false;  // the post chain follows: it is on, and somebody is in it
     // of the optional features: the rows of the result set this batch writes and the detector's table - null where the context has
@@ -680,6 +714,7 @@ static int batch_plan(psdr_ctx *c, int nframes, const uint32_t *band, BatchPlan 
     if (c->cw) b.cw = cw_plan(slots, S, c->demod_seq, c->cw.tab.host(b.ring));
     if (c->rtty) b.rtty = rtty_plan(slots, S, c->demod_seq, c->rtty.tab.host(b.ring));
     if (c->psk) b.psk = psk_plan(slots, S, c->demod_seq, c->psk.tab.host(b.ring));
+    if (c->fax) b.fax = fax_plan(slots, S, c->demod_seq, c->fax.tab.host(b.ring));
     if (c->agc_prof && b.chain) b.ag = agc_profile_plan(slots, S, c->demod_seq, c->agc_prof.tab.host(b.ring));
     return PSDR_OK;
 }
@@ -717,6 +752,8 @@ static int batch_begin(psdr_ctx *c, const BatchPlan &b) {
         HIPCHK(hipMemsetAsync(c->psk.state + slot, 0, sizeof(PskState), c->side));
         HIPCHK(hipMemsetAsync(c->psk.text + slot * (size_t)PSK_TEXT, 0, PSK_TEXT, c->side));
     }
+    // ... and the fax decoders: the state (the ring's lines are counted from it: fax_plan has taken fax_fresh off these slots)
+    for (size_t slot : b.fax.zero) HIPCHK(hipMemsetAsync(c->fax.state + slot, 0, sizeof(FaxState), c->side));
     // ... and the noise floors that start from zero: sums and record (noise_plan has taken nf_fresh off these slots)
     for (size_t slot : b.nf.zero) {
         HIPCHK(hipMemsetAsync(c->noise.acc + slot * (size_t)c->n, 0, (size_t)c->n * sizeof(float), c->side));
@@ -753,6 +790,7 @@ static int batch_begin(psdr_ctx *c, const BatchPlan &b) {
     if (b.cw.any()) HIPCHK(c->cw.tab.upload(b.ring, (size_t)b.cw.n, c->side));
     if (b.rtty.any()) HIPCHK(c->rtty.tab.upload(b.ring, (size_t)b.rtty.n, c->side));
     if (b.psk.any()) HIPCHK(c->psk.tab.upload(b.ring, (size_t)b.psk.n, c->side));
+    if (b.fax.any()) HIPCHK(c->fax.tab.upload(b.ring, (size_t)b.fax.n, c->side));
     return PSDR_OK;
 }
 
@@ -975,6 +1013,19 @@ static int launch_psk_decoder(psdr_ctx *c, const BatchPlan &b, int nframes) {
     HIPCHK(audio_psk_launch(pa, c->side));
     return PSDR_OK;
 }
+// ... the radiofax decoder, at the same reading point: it reads the listed clients' rows as the demodulator left them and writes the
+// frames' records and the clients' kept lines
+static int launch_fax_decoder(psdr_ctx *c, const BatchPlan &b, int nframes) {
+    FaxArgs fa{};
+    fa.list = c->fax.tab.dev(b.ring), fa.nlist = b.fax.n;
+    fa.tab = c->fax.plan;
+    fa.audio = c->d_audio, fa.nan_flags = c->d_nan;
+    fa.state = c->fax.state, fa.ring = c->fax.ring, fa.meta = c->fax.meta, fa.rec = c->fax.rec;
+    fa.nframes = nframes, fa.max_batch = c->max_batch, fa.h = c->n / 2, fa.rmax = c->fax.rmax;
+    ProfScope ps(c, K_AUDIO_FAX, c->side);
+    HIPCHK(audio_fax_launch(fa, c->side));
+    return PSDR_OK;
+}
 // ... the audio blanker, in front of the noise reduction, the audio filter and the chain: it works on the listed clients' rows in
 // place
 static int launch_audio_blanker(psdr_ctx *c, const BatchPlan &b, int nframes) {
@@ -1050,6 +1101,7 @@ static int demod_impl(psdr_ctx *c, const cf *spec, size_t spec_stride, int nfram
     if (b.cw.any()) PSDRCHK(launch_cw_decoder(c, b, nframes));
     if (b.rtty.any()) PSDRCHK(launch_rtty_decoder(c, b, nframes));
     if (b.psk.any()) PSDRCHK(launch_psk_decoder(c, b, nframes));
+    if (b.fax.any()) PSDRCHK(launch_fax_decoder(c, b, nframes));
     if (b.anb.any()) PSDRCHK(launch_audio_blanker(c, b, nframes));
     if (b.nr.any()) PSDRCHK(launch_noise_reduction(c, b, nframes));
     if (b.af.any()) PSDRCHK(launch_audio_filter(c, b, nframes));

@@ -23,6 +23,15 @@ struct AfSection {
 };
 static_assert(sizeof(AfSection) == 128, "the device table's layout");
 
+// One entry of the fax decoder's batch table (faxplan.h), which an audio slot keeps whole
+struct FaxEntry {
+    int slot, mode, width, K, D, NB, start_blocks, phase_lines, max_lines, wp, R, pad;
+    uint64_t Lq, origin0;    // the line in 1/65536 sample; phase_col Lq / width
+    uint32_t inc, tinc[3];   // the centre's increment, the three tones'
+    float rot[2], trot[3][2];
+    float s, ratio, shift, nbh;  // v = 0.5 + a s; tone_ratio; white - black; NB H
+};
+
 struct AudioSlot {
     bool active = false;
     int l = 0, r = 0;
@@ -126,6 +135,12 @@ struct AudioSlot {
     float psk_rot[16][2] = {};
     bool b_psk_on = false, psk_fresh = false;
     int psk_mode = PSDR_USB, psk_l = 0, psk_r = 0, psk_m = 0;
+    // psdr_client_set_fax_decoder (faxplan.h): the parameters as the table holds them; b_fax_on: the last batch ran with it
+    // (psdr_read_fax); fax_fresh, fax_mode, fax_l, fax_r, fax_m: as the tone decoder's
+    int fax_on = 0;
+    FaxEntry fax = {};
+    bool b_fax_on = false, fax_fresh = false;
+    int fax_mode = PSDR_USB, fax_l = 0, fax_r = 0, fax_m = 0;
 };
 
 // The client parameter ring's slot.  [ClientParams x S][int x S]: the batch's list and, for the post chain, the list index of

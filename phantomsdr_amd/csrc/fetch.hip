@@ -592,6 +592,71 @@ extern "C" int psdr_read_psk_text(psdr_ctx *c, int id, uint64_t from, char *out,
     if (total_out) *total_out = total;
     return PSDR_OK;
 }
+// the fax decoder's records of the last batch; any of the six arrays may be null
+extern "C" int psdr_read_fax(psdr_ctx *c, int id, int nframes, uint32_t *nlines, int32_t *state, uint32_t *image, int32_t *ioc, float *offset_hz, float *tone_quality,
+                             int *nframes_out) {
+    if (!c) return fail(PSDR_ERR_INVALID, "null argument");
+    size_t F = 0;
+    bool on = false;
+    PSDRCHK(read_begin(c, id, false, nframes, nframes_out, ROWS_AUDIO, false, &F, [&](const AudioSlot &s) { on = s.b_fax_on && (bool)c->fax; }));
+    if (!on) return fail(PSDR_ERR_NO_DATA, "client %d had no fax decoder in the last demodulation batch", id);
+    HIPCHK(hipSetDevice(c->device));
+    PSDRCHK(drain(c));
+    std::vector<FaxRec> rec(F);
+    HIPCHK(hipMemcpy(rec.data(), c->fax.rec + fetch_row(id, (size_t)c->max_batch, 0), F * sizeof(FaxRec), hipMemcpyDeviceToHost));
+    for (size_t f = 0; f < F; f++) {
+        if (nlines) nlines[f] = rec[f].nlines;
+        if (state) state[f] = rec[f].state;
+        if (image) image[f] = rec[f].image;
+        if (ioc) ioc[f] = rec[f].ioc;
+        if (offset_hz) offset_hz[f] = rec[f].offset_hz;
+        if (tone_quality) tone_quality[f] = rec[f].tone_quality;
+    }
+    return PSDR_OK;
+}
+// the fax decoder's kept lines since the state last started, from the slot's ring
+extern "C" int psdr_read_fax_lines(psdr_ctx *c, int id, uint64_t from, uint8_t *pix, uint32_t *meta, size_t cap_lines, size_t *n_out, uint64_t *total_out, int *width_out) {
+    if (!c || ((!pix || !meta) && cap_lines)) return fail(PSDR_ERR_INVALID, "null argument");
+    bool pending = false;
+    int width = 0, R = 0;
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);
+        if (id < 0 || (size_t)id >= c->aslots.size()) return fail(PSDR_ERR_INVALID, "fax lines: id %d outside 0..%d", id, (int)c->aslots.size() - 1);
+        const AudioSlot &s = c->aslots[id];
+        if (!s.active) return fail(PSDR_ERR_INVALID, "no audio client with id %d", id);
+        if (!s.fax_on || !c->fax) return fail(PSDR_ERR_NO_DATA, "client %d has no fax decoder", id);
+        pending = s.fax_fresh;
+        width = s.fax.width, R = s.fax.R;
+    }
+    uint64_t total = 0;
+    std::vector<uint8_t> ring;
+    std::vector<uint32_t> rmeta;
+    if (!pending) {
+        HIPCHK(hipSetDevice(c->device));
+        PSDRCHK(drain(c));
+        std::vector<FaxState> st(1);
+        HIPCHK(hipMemcpy(st.data(), c->fax.state + (size_t)id, sizeof(FaxState), hipMemcpyDeviceToHost));
+        total = st[0].z.nlines;
+        if (from < total && total - from <= (uint64_t)R) {
+            ring.resize((size_t)R * width), rmeta.resize(R);
+            HIPCHK(hipMemcpy(ring.data(), c->fax.ring + (size_t)id * c->fax.rmax * FAX_WIDTH_MAX, ring.size(), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(rmeta.data(), c->fax.meta + (size_t)id * c->fax.rmax, rmeta.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        }
+    }
+    if (from > total) return fail(PSDR_ERR_INVALID, "fax lines: from %llu is beyond the image's %llu lines", (unsigned long long)from, (unsigned long long)total);
+    if (total - from > (uint64_t)R)
+        return fail(PSDR_ERR_NO_DATA, "fax lines: from %llu is older than the last %d of %llu lines", (unsigned long long)from, R, (unsigned long long)total);
+    const size_t n = std::min((size_t)(total - from), cap_lines);
+    for (size_t j = 0; j < n; j++) {
+        const size_t r = (size_t)((from + j) % (uint64_t)R);
+        memcpy(pix + j * width, ring.data() + r * width, width);
+        meta[j] = rmeta[r];
+    }
+    if (n_out) *n_out = n;
+    if (total_out) *total_out = total;
+    if (width_out) *width_out = width;
+    return PSDR_OK;
+}
 extern "C" int psdr_read_noise(psdr_ctx *c, int id, int nframes, float *w, int *nframes_out) {
     if (!c || !w) return fail(PSDR_ERR_INVALID, "null argument");
     size_t F = 0;
